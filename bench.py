@@ -13,7 +13,12 @@ Two families of workloads:
   * c3 / ecoli / c4s / c5s (one chunk per rank): N ranks = N index chunks + N overlap chunks over an N-times larger read set
     ("scaling": "weak"), the count tables / pair records exchanged between the stages over RCCL.
 
+A plain run sets up, warms up, times the steps, writes the last timed step's outputs if --dump-outputs DIR is given and prints the
+result line.  --full adds what the headline figure does not need (hashes and pins, the replay's kernel timing and the roofline, the
+reference CPU leg, the end-to-end leg).
+
   python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -34,6 +39,11 @@ SKETCH_BYTES_PER_BASE = 1.04     # 1 B seqdb + 16 B/408 L2 + MC 
 ALIGN_BYTES_PER_PAIR = 21664.0   # 2 x 10.8 kB read + 64 B written
 LEVELS = 2
 DEFAULT_WORKLOAD = "c4"
+BUDGET_S = 540                   # --full: seconds from the start the legs after the timed steps plan with (PGX_BENCH_BUDGET_S)
+DUMP_RECORDS = 1 << 18           # --dump-outputs: records sampled over the job's overlap chunks (18 float64 columns: 37.7 MB)
+DUMP_SEED = 20240917
+DUMP_COLUMNS = ("index", "y0_hi", "y0_lo", "y1_hi", "y1_lo", "rl0", "rl1", "strand0", "strand1", "ovlp_type",
+                "m_size", "dist", "q_bgn", "q_end", "t_bgn", "t_end", "t_m_end", "q_m_end")
 WORKLOAD_TEXT = {
     "c4": "BASELINE configs[3] at FULL size (the configuration the metric is quoted on): 3.1 Gb genome seeded with 207 families of 300 copies "
           "of a 6 kb unit at 1 % divergence, 31 k tandem arrays and 31 k homopolymer runs (CHM13 is not obtainable offline) x 30x",
@@ -89,13 +99,51 @@ def parse():
     ap.add_argument("--check-ref", action="store_true",
                     help="c4 family, small --genome-mb only: after the timed steps every rank compares the ovlp_t stream of each of its "
                          "chunks, field by field, with oracle/_ref/shmr_overlap -t CHUNKS -c c on files rank 0 writes")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the read set's hash, one more step whose streams are SHA-256'd and "
+                         "compared with the pins, the device replay's kernel-timing step and the roofline, the reference CPU leg and the "
+                         "end-to-end leg, within PGX_BENCH_BUDGET_S (default %d s).  --check-ref, --cpu-baseline and --end-to-end imply it" % BUDGET_S)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR: per overlap chunk, records_chunkCC_of_TT.npy "
+                         "(float64, one row per record of a seeded sample of at most %d records of the job, columns %s) and "
+                         "stream_chunkCC_of_TT.npy (float64: records in the chunk's whole stream, its 64-bit stream checksum as high and "
+                         "low 32 bits)" % (DUMP_RECORDS, ", ".join(DUMP_COLUMNS)))
     a = ap.parse_args()
+    if a.check_ref or a.cpu_baseline or a.end_to_end:
+        a.full = True
     big = a.workload in ("c4", "c5") and not a.genome_mb
     if a.steps is None:
         a.steps = 3 if big else 10
     if a.warmup is None:
         a.warmup = 1 if big else 2
     return a
+
+
+def budget_s():
+    """the command's time budget for the --full legs, from the process's start"""
+    return float(os.environ.get("PGX_BENCH_BUDGET_S", str(BUDGET_S)))
+
+
+def dump_sample(ov, c, n_chunks):
+    """--dump-outputs: a seeded sample of overlap chunk c's records (the same rows from run to run for the same stream length),
+    copied out of the library's array -> (positions in the stream, records)"""
+    n, k = len(ov), max(1, DUMP_RECORDS // n_chunks)
+    idx = np.arange(n) if n <= k else np.unique(np.random.default_rng([DUMP_SEED, c]).integers(0, n, k))
+    return idx, ov[idx]
+
+
+def write_dump(d, rows, checks, n_chunks):
+    """--dump-outputs: the sampled records as float64 columns (DUMP_COLUMNS; the 64-bit y0 / y1 split into exact 32-bit halves) and every
+    chunk's record count and stream checksum"""
+    os.makedirs(d, exist_ok=True)
+    lo32 = np.uint64(0xFFFFFFFF)
+    for c, (idx, rec) in sorted(rows.items()):
+        cols = [idx, rec["y0"] >> np.uint64(32), rec["y0"] & lo32, rec["y1"] >> np.uint64(32), rec["y1"] & lo32]
+        cols += [rec[f] for f in DUMP_COLUMNS[5:]]
+        tag = "chunk%02d_of_%02d" % (c, n_chunks)
+        np.save(os.path.join(d, f"records_{tag}.npy"), np.stack([np.asarray(x, np.float64) for x in cols], axis=1))
+        n, ck = checks[c]
+        np.save(os.path.join(d, f"stream_{tag}.npy"), np.array([n, ck >> 32, ck & 0xFFFFFFFF], np.float64))
 
 
 def _pair_keys(ov):
@@ -762,9 +810,10 @@ def main():
         seq_dev, total, rlen = simreads.make_workload_resident(a.workload, genome_mb=a.genome_mb or None)
         rid = np.arange(len(rlen), dtype=np.uint32)
         roff = np.concatenate([[0], np.cumsum(rlen.astype(np.uint64))[:-1]]).astype(np.uint64)
-        read_set_hash = device_read_set_hash(seq_dev, total)    # every byte, on the device
+        if a.full:
+            read_set_hash = device_read_set_hash(seq_dev, total)    # every byte, on the device
         read_set_hash_equal = None
-        if world > 1:    # same generator, same seeds, same device type: the ranks' copies must be the same bytes
+        if a.full and world > 1:    # same generator, same seeds, same device type: the ranks' copies must be the same bytes
             probe = [int(total), int(len(rlen)), int(read_set_hash[:15], 16), int(read_set_hash[15:30], 16), int(read_set_hash[30:], 16)]
             read_set_hash_equal = len({tuple(r) for r in allgather_ints(probe, world, device=home if backend == "nccl" else None)}) == 1
             assert read_set_hash_equal, "ranks generated different read sets"
@@ -825,6 +874,7 @@ def main():
     hash_jobs, hash_keep = {}, []
     import concurrent.futures as _cf
     hash_pool = _cf.ThreadPoolExecutor(8)
+    dump_rows = None    # --dump-outputs, the last timed step: {chunk: (positions, records)} sampled as each chunk's records arrive
 
     def index_my_chunks():
         """the rank's index chunks; the lists / count tables as device byte tensors (copies: the library reuses its buffers)"""
@@ -859,7 +909,7 @@ def main():
             (ov, st), info = exchange_overlap(eng, rank, world, tops[0], mcs[0], **ov_params)
             st["exchange"] = info
             st["chunk_checksums"] = {my_chunks[0]: (len(ov), st["stream_checksum"])}
-            if a.check_ref or hash_streams:
+            if a.check_ref or hash_streams or dump_rows is not None:
                 keep_streams[my_chunks[0]] = ov
             return ix, len(ov), st, s1 - s0
         if world > 1:       # several chunks per rank: the lists of ALL chunks, in chunk order, all-gathered round by round (round j = chunks j N + 1 .. j N + N)
@@ -880,13 +930,20 @@ def main():
         tot, nrec, cks = None, 0, {}
         was_async = _lib.results_async(os.environ.get("PGX_BENCH_SYNC_RESULTS") != "1")    # a chunk's records travel to the host beside the next chunk's main alignment launch
         prev = None                             # (the array of the chunk before: freeing it would wait for its copy)
+        prev_c = None
         for ci, c in enumerate(my_chunks):
             tc0 = time.perf_counter()
             ov, st = rdb.overlap_dev(mm_all.data_ptr(), mm_all.numel() // 16, mc_all.data_ptr(), mc_all.numel() // 16, total_chunk=CH, mychunk=c, **ov_params)
             if os.environ.get("PGX_BENCH_CHUNK_TIMES"):
                 log("chunk %d: call %.1f ms (library: gpu %.1f + host %.1f), %d records, attempts %d" % (c, (time.perf_counter() - tc0) * 1e3, st["gpu_ms"], st["host_ms"], len(ov), st["replay_attempts"]))
+            if dump_rows is not None and prev is not None:
+                # the chunk before's records: a device replay that emitted records has waited for their copy before starting its own
+                # (holding every chunk's array instead would take new pinned blocks in the middle of the step)
+                if not (st.get("device_replay") == 1 and len(ov)):
+                    _lib.results_wait()
+                dump_rows[prev_c] = dump_sample(prev, prev_c, CH)
             nrec += len(ov)
-            prev = ov
+            prev, prev_c = ov, c
             cks[c] = (len(ov), st["stream_checksum"])
             if a.check_ref:
                 keep_streams[c] = ov
@@ -904,6 +961,8 @@ def main():
             del ov
         _lib.results_wait()                     # the last chunk's records have arrived: the step is complete
         _lib.results_async(was_async)
+        if dump_rows is not None and prev is not None:
+            dump_rows[prev_c] = dump_sample(prev, prev_c, CH)
         del prev
         tot["chunks"] = len(my_chunks)
         tot["chunk_checksums"] = cks
@@ -968,7 +1027,9 @@ def main():
     fence()
     t0 = time.perf_counter()
     step_checksums = []
-    for _ in range(a.steps):
+    for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:
+            dump_rows = {}
         s0 = time.perf_counter()
         ix, nrec, st, ti = step()
         t_index += ti
@@ -977,6 +1038,14 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     log(f"{a.steps} timed step(s): {elapsed:.2f} s")
+    if dump_rows is not None:
+        _lib.results_wait()
+        for c in my_chunks:
+            if c not in dump_rows:     # (the one-chunk forms keep the last step's whole stream)
+                dump_rows[c] = dump_sample(np.asarray(keep_streams[c]), c, CH)
+        write_dump(a.dump_outputs, dump_rows, step_checksums[-1], CH)
+        dump_rows = None
+        log(f"outputs of the last timed step written to {a.dump_outputs}")
 
     tot = torch.tensor([elapsed, float(nrec), float(ix.bases), t_index, t_ovlp], dtype=torch.float64, device=xdev)
     if multi:
@@ -1003,7 +1072,7 @@ def main():
     # and SHA-256s it with the padding bytes (27, 60..63) zeroed; its per-chunk checksums must equal those of every timed step, so the hashed
     # streams ARE the timed ones.  tests/golden/c4_stream_pins.json holds the same hashes of oracle/_ref/shmr_overlap's streams.
     stream_report = None
-    if not os.environ.get("PGX_BENCH_NO_STREAM_HASH"):
+    if a.full and not os.environ.get("PGX_BENCH_NO_STREAM_HASH"):
         hash_streams = True
         hash_jobs.clear(), hash_keep.clear()
         _, _, st_h, _ = step()
@@ -1031,7 +1100,7 @@ def main():
     rank_rows = allgather_ints(rank_row, world, device=home if backend == "nccl" else None) if multi else [rank_row]
 
     if rank == 0:
-        if st.get("device_replay") and not multi and not os.environ.get("PGX_BENCH_NO_REPLAY_TIMING"):
+        if a.full and st.get("device_replay") and not multi and not os.environ.get("PGX_BENCH_NO_REPLAY_TIMING"):
             # the device replay's kernels (k_eval + k_update pairs) are timed in ONE EXTRA step, outside the timed region: a HIP
             # event pair around each of their ~40 launches per step would cost ~2 % of the step
             kern_timed = kern
@@ -1051,15 +1120,15 @@ def main():
                 kern["replay"] = {"ms_total": ms, "launches": launches, "units": int(st_x["n_evaluations"]), "avg_ms": ms / launches,
                                   "steps": 1, "by_kernel": rk, "max_kernel_ms": max(v["ms_total"] for v in rk.values()),
                                   "note": "one extra untimed step with PGX_REPLAY_TIMING=1; launches = evaluate/update rounds"}
-        cands = {}
-        if "sketch" in kern:
+        cands = {}     # (--full: the roofline takes the replay-timing step and the committed counter passes)
+        if a.full and "sketch" in kern:
             k = kern["sketch"]
             gbs = SKETCH_BYTES_PER_BASE * k["units"] / (k["ms_total"] * 1e-3) / 1e9
             cands["sketch"] = {"kernel": "k_sketch_blk (+ k_sketch_wave for the reads it flags)", "bound": "valu_issue", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                "frac": gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": k["avg_ms"],
                                "bytes_per_unit": SKETCH_BYTES_PER_BASE, "unit_name": "base",
                                "gbases_per_s": k["units"] / (k["ms_total"] * 1e-3) / 1e9}
-        if "align" in kern:
+        if a.full and "align" in kern:
             k = kern["align"]
             gbs = ALIGN_BYTES_PER_PAIR * k["units"] / (k["ms_total"] * 1e-3) / 1e9
             cands["align"] = {"kernel": "k_align_ph<8, u16, packed> (per-group phase machine over the 2-bit packs; + k_pack2 once per stage, k_align1_list for the candidates it hands on)", "bound": "valu_issue", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1069,14 +1138,14 @@ def main():
                               "bound_note": "instruction issue AND the wavefront's own dependent chain per d-step, at the hardware's 8 wavefronts per SIMD (DESIGN 4.4 round 4 (c): "
                                             "+10 % VALU = +16 % time, +46 % SALU = +8.5 %, 28 instead of 32 wavefronts per CU = +6 %); through round 4 the work counter's "
                                             "same-address atomic (12 ns per candidate) was the floor, not the instructions"}
-        if "align1" in kern:   # the one-candidate-per-wavefront form used for launches of at most 13 k alignments (tail rounds)
+        if a.full and "align1" in kern:   # the one-candidate-per-wavefront form used for launches of at most 13 k alignments (tail rounds)
             k = kern["align1"]
             gbs = ALIGN_BYTES_PER_PAIR * k["units"] / (k["ms_total"] * 1e-3) / 1e9
             cands["align1"] = {"kernel": "k_align1", "bound": "latency", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                "frac": gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": k["avg_ms"],
                                "bytes_per_unit": ALIGN_BYTES_PER_PAIR, "unit_name": "alignment",
                                "alignments_per_s": k["units"] / (k["ms_total"] * 1e-3)}
-        if "replay" in kern:   # the greedy walk on the GPU: dependent random probes of the pair / memo tables, latency-bound
+        if a.full and "replay" in kern:   # the greedy walk on the GPU: dependent random probes of the pair / memo tables, latency-bound
             k = kern["replay"]
             walk = 13 * st["n_pair_records"] + 16 * (st["n_seen_skip"] + st["n_align_needed"]) + 48 * st["n_align_needed"] + 16 * st["n_records"]
             per_eval = walk / max(1, st["n_buckets"])   # algorithmic bytes of one bucket evaluation
@@ -1123,13 +1192,16 @@ def main():
             "overlap_records_per_sec": records * a.steps / t_ovlp if t_ovlp else None,
             "records_per_step": records, "index_ms_per_step": t_index / a.steps * 1e3, "overlap_ms_per_step": t_ovlp / a.steps * 1e3,
             "overlap_stats_rank0": st, "reads_literal_rank0": ix.reads_literal,
-            "kernels": kern, "roofline": roof, "roofline_all": cands,
+            "kernels": kern,
         }
+        if a.full:
+            out["roofline"], out["roofline_all"] = roof, cands
         out["world_size"] = int(dist.get_world_size()) if multi else 1     # as the process group sees it
         out["per_rank"] = [{"rank": r, "hbm_bytes_in_use": row[0], "sent_records": row[1], "received_records": row[2], "records_last_step": row[3],
                             "chunks": row[4]} for r, row in enumerate(rank_rows)]
         if strong:
             out["hbm_bytes_in_use"] = int(rank_rows[0][0])
+        if strong and a.full:
             out["read_set_hash"] = read_set_hash
             out["read_set_hash_equal_on_all_ranks"] = True if world == 1 else read_set_hash_equal
         if stream_report is not None:
@@ -1161,7 +1233,7 @@ def main():
                                   "kernel trace give the busy / idle split kernel by kernel")
         # (the legs below run the reference on the host and shell out: whatever goes wrong there, the line of the timed steps still goes out)
         try:
-            if world == 1 and not a.no_cpu_baseline:
+            if a.full and world == 1 and not a.no_cpu_baseline:
                 if strong:
                     def gpu_index_files(prefix):     # the job's index chunk files, as bin/shmr_index writes them
                         for c in range(1, CH + 1):
@@ -1169,13 +1241,13 @@ def main():
                             formats.write_mmlist("%s-L%d-%02d-of-%02d.dat" % (prefix, sp["levels"], c, CH), p.top)
                             formats.write_mm_count("%s-L%d-MC-%02d-of-%02d.dat" % (prefix, sp["levels"], c, CH), p.top_mc)
                     # The honest leg is the WHOLE workload (24 processes over 24 + 24 chunks: ~12-14 min at full size); it is the default where the
-                    # command's time budget allows (PGX_BENCH_BUDGET_S, default 1,620 s of the driver's 1,800), else the bounded sample -- and the line says which
+                    # command's time budget allows (PGX_BENCH_BUDGET_S, default BUDGET_S), else the bounded sample -- and the line says which
                     mode = a.cpu_baseline
                     fallback_reason = None
                     if mode is None:
                         whole = "whole_chunks" if sp["levels"] == 1 else "full"
                         need = (1300.0 if whole == "whole_chunks" else 900.0) * (db.n_bases / 93.3e9) + 60
-                        left = float(os.environ.get("PGX_BENCH_BUDGET_S", "1620")) - (time.perf_counter() - _T0) - 150
+                        left = budget_s() - (time.perf_counter() - _T0) - 150
                         mode = whole if left >= need else "sample"
                         log(f"cpu baseline: {mode} (estimated {need:.0f} s for the {whole} leg, {left:.0f} s of the budget left)")
                         if mode == "sample":
@@ -1185,7 +1257,7 @@ def main():
                     # the end-to-end leg (default where the budget allows; it runs LAST -- this process gives its HBM to the server) reads the same seqdb files
                     # as the reference: written once, shared
                     cpu_est = {"full": 900.0, "whole_chunks": 1300.0, "sample": 330.0}[mode] * (db.n_bases / 93.3e9) + 60
-                    left_after = float(os.environ.get("PGX_BENCH_BUDGET_S", "1620")) - (time.perf_counter() - _T0) - cpu_est
+                    left_after = budget_s() - (time.perf_counter() - _T0) - cpu_est
                     if a.end_to_end is None:
                         a.end_to_end = bool(not a.genome_mb and a.workload == "c4" and left_after >= 200)
                         log(f"end to end leg: {'on' if a.end_to_end else 'off'} ({left_after:.0f} s of the budget expected to be left after the CPU leg)")

@@ -203,7 +203,7 @@ def test_rccl_exchange_as_one_rank_job(tmp_path):
 
 @pytest.mark.skipif(not U.have_ref(), reason="needs the prebuilt reference binaries (oracle/_ref)")
 @pytest.mark.parametrize("ranks,chunks", [(1, 4), (2, 2), (2, 4)])
-def test_bench_strong_scaling_form_of_configs3_against_the_reference(ranks, chunks):
+def test_bench_strong_scaling_form_of_configs3_against_the_reference(ranks, chunks, tmp_path):
     """bench.py's c4 family (BASELINE configs[3] AS STATED: one read set on every rank, the job's chunks dealt to the ranks, strong
     scaling) on a 12 Mb genome of the same recipe: one rank with 4 chunks; two ranks sharing the GPU under gloo with 2 chunks (one
     chunk per rank: count all-gather + pair-record all-to-all) and with 4 (two per rank: lists all-gathered round by round).
@@ -211,7 +211,8 @@ def test_bench_strong_scaling_form_of_configs3_against_the_reference(ranks, chun
     processes and the read simulator alone did not finish in five minutes -- (4, 8) passed in 313 s, (8, 8) not within 900.  The world-8 form is
     covered by test_scatter_and_records_path_equal_reference[8-...] here -- every kernel of the one-chunk-per-rank path, eight chunks, one
     process playing the ranks in turn -- and by tests/test_parallel_gloo.py at world 8 -- the real protocol code, eight processes, CPU.)  Every rank
-    compares the ovlp_t stream of each of its chunks with oracle/_ref/shmr_overlap -t C -c c on files (--check-ref)."""
+    compares the ovlp_t stream of each of its chunks with oracle/_ref/shmr_overlap -t C -c c on files (--check-ref, a leg of --full); the
+    last timed step's outputs (--dump-outputs) are every chunk's stream length and checksum and a sample of its records."""
     import json
     import subprocess
     cmd = [sys.executable]
@@ -219,8 +220,8 @@ def test_bench_strong_scaling_form_of_configs3_against_the_reference(ranks, chun
     if ranks > 1:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
         env["PGX_BENCH_BACKEND"] = "gloo"
-    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--workload", "c4", "--genome-mb", "12", "--chunks", str(chunks), "--check-ref",
-            "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+    cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--workload", "c4", "--genome-mb", "12", "--chunks", str(chunks), "--full", "--check-ref",
+            "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -232,6 +233,12 @@ def test_bench_strong_scaling_form_of_configs3_against_the_reference(ranks, chun
     if ranks > 1 and chunks == ranks:   # the all-to-all form: every record sent is received, and they are the records the overlap stages consumed
         sent, recv = sum(r["sent_records"] for r in line["per_rank"]), sum(r["received_records"] for r in line["per_rank"])
         assert sent == recv > 0
+    assert len(line["streams"]) == chunks
+    for c, row in enumerate(line["streams"], 1):     # the dump = the timed streams (each rank writes its own chunks)
+        n, hi, lo = np.load(tmp_path / "dump" / ("stream_chunk%02d_of_%02d.npy" % (c, chunks))).astype(np.int64).tolist()
+        assert row["chunk"] == "%d of %d" % (c, chunks) and n == row["records"] and (hi << 32 | lo) == row["stream_checksum"]
+        rec = np.load(tmp_path / "dump" / ("records_chunk%02d_of_%02d.npy" % (c, chunks)))
+        assert rec.dtype == np.float64 and 0 < len(rec) <= n and np.all(np.diff(rec[:, 0]) > 0) and rec[-1, 0] < n
 
 
 def test_shutdown_forgets_device_state():
