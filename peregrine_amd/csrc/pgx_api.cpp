@@ -905,17 +905,7 @@ int pgx_seqdb_release_bytes(pgx_seqdb *db) {
 }
 int pgx_seqdb_has_bytes(const pgx_seqdb *db) { return db && db->d_seq.p ? 1 : 0; }
 
-void pgx_seqdb_free(pgx_seqdb *db) {
-  if (db) {   // what the library kept for the chunks of a job on this database goes with it
-    try {
-      pgx::count_cache_drop();
-      pgx::replay_forget_sizes();
-      pgx::list_stash_clear();
-    } catch (...) {
-    }
-  }
-  delete db;
-}
+void pgx_seqdb_free(pgx_seqdb *db) { delete db; }   // (what the library kept for the job on this database goes with it: pgx_seqdb::caches)
 uint64_t pgx_seqdb_bases(const pgx_seqdb *db) { return db ? db->bases : 0; }
 uint32_t pgx_seqdb_reads(const pgx_seqdb *db) { return db ? (uint32_t)db->rid.size() : 0; }
 

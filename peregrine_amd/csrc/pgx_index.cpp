@@ -36,7 +36,7 @@ void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, 
   if (keep) keep->valid = false;
   const double t0 = now_ms();
   // read selection: rid % total == mychunk % total, in idx-file order (shmr_index.c:155-157); kept with the seqdb for the next call
-  static uint64_t next_serial = 0, use_clock = 0;
+  static uint64_t use_clock = 0;
   pgx_seqdb::IndexPlan *found = nullptr;
   for (auto &pl : db->plans)
     if (pl.total == p->total_chunk && pl.chunk == p->mychunk) found = &pl;
@@ -48,10 +48,10 @@ void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, 
       found = &db->plans[0];
       for (auto &pl : db->plans)
         if (pl.last_use < found->last_use) found = &pl;
+      sync();   // (its device buffers may still be read by what the last stage enqueued)
+      *found = pgx_seqdb::IndexPlan();
     }
     pgx_seqdb::IndexPlan &plan = *found;
-    plan.reads.clear();
-    plan.bases = 0;
     const uint32_t T = (uint32_t)p->total_chunk, c = (uint32_t)p->mychunk % T;
     for (size_t i = 0; i < db->rid.size(); ++i) {
       if (db->rid[i] % T != c) continue;
@@ -59,7 +59,7 @@ void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, 
       plan.reads.push_back(ReadDesc{db->roff[i], db->rlen[i], db->rid[i]});
       plan.bases += db->rlen[i];
     }
-    plan.total = p->total_chunk, plan.chunk = p->mychunk, plan.serial = ++next_serial;
+    plan.total = p->total_chunk, plan.chunk = p->mychunk;
   }
   pgx_seqdb::IndexPlan &plan = *found;
   plan.last_use = ++use_clock;
@@ -74,7 +74,7 @@ void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, 
   if (!p->want_l0) {
     const pgx_mm128 *d_top = nullptr;
     size_t ntop = 0;
-    if (dev_index_fused(db, reads, p->window, p->kmer, p->reduction, p->levels, &d_top, &ntop, plan.serial, &out->reads_literal)) {
+    if (dev_index_fused(db, reads, p->window, p->kmer, p->reduction, p->levels, &d_top, &ntop, &plan, &out->reads_literal)) {
       PGX_REQUIRE(ntop < (1ULL << 31), PGX_EARG, "chunk too large (use more index chunks)");
       DevBuf<pgx_mm_count> mc;
       size_t nmc = 0;
@@ -245,8 +245,8 @@ int pgx_index_chunk_db(pgx_seqdb *db, const char *out_prefix, const pgx_index_pa
       write_counted(level_path(out_prefix, lv, true, p->mychunk, p->total_chunk), res.top_mc, res.n_top_mc, sizeof(pgx_mm_count));
       // a resident database serves a JOB: the device copies stay for its overlap commands (pgx_served.cpp: list_stash)
       const bool d = dev.valid && dev.n_top == res.n_top && dev.n_mc == res.n_top_mc;
-      list_stash_put(level_path(out_prefix, lv, false, p->mychunk, p->total_chunk), d ? dev.d_top : nullptr, res.top, res.n_top * sizeof(pgx_mm128));
-      list_stash_put(level_path(out_prefix, lv, true, p->mychunk, p->total_chunk), d ? dev.mc.p : nullptr, res.top_mc, res.n_top_mc * sizeof(pgx_mm_count));
+      list_stash_put(db, level_path(out_prefix, lv, false, p->mychunk, p->total_chunk), d ? dev.d_top : nullptr, res.top, res.n_top * sizeof(pgx_mm128));
+      list_stash_put(db, level_path(out_prefix, lv, true, p->mychunk, p->total_chunk), d ? dev.mc.p : nullptr, res.top_mc, res.n_top_mc * sizeof(pgx_mm_count));
     }
   } catch (const Fail &f) {
     rc = f.code;

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -57,9 +58,11 @@ struct Context {
 };
 Context &ctx();
 void require_ready();
-// Device state that outlives a call (plan caches, buffers handed out as library-owned views) registers a reset function:
-// pgx_shutdown() runs them all BEFORE it returns the cached blocks to the driver, so nothing survives into the next pgx_init()
-// (which may choose another device).  Use: static pgx::ShutdownHook h_([] { ... });
+// Per-context device state that outlives a call (buffers handed out as library-owned views, side streams, pinned pools) registers a
+// reset function: pgx_shutdown() runs them all BEFORE it returns the cached blocks to the driver, so nothing survives into the next
+// pgx_init() (which may choose another device).  Use: static pgx::ShutdownHook h_([] { ... });
+// What belongs to a read database (its packs, index plans, DbCaches) goes with the database instead: a database stays on the device
+// it was made on.
 void on_shutdown(void (*fn)());
 struct ShutdownHook {
   explicit ShutdownHook(void (*fn)()) { on_shutdown(fn); }
@@ -151,6 +154,26 @@ struct ReadDesc {
   uint32_t len;
   uint32_t rid;
 };
+// What the library keeps between the stages of the job running on one read database: each part is built on first use by the file
+// that owns its type and released with the database (two live databases each hold their own).
+struct CountCache;    // the aggregated count table (pgx_pairs.hip)
+struct ReplayState;   // the device replay's learned table sizes and the tables it cleared ahead of time (pgx_replay.hip)
+struct ServedCache;   // device copies of the list / count files index commands wrote, the assembled lists of the last prefix (pgx_served.cpp)
+struct CacheFree {    // (each operator() is defined in the file that owns the type)
+  void operator()(CountCache *) const;
+  void operator()(ReplayState *) const;
+  void operator()(ServedCache *) const;
+};
+struct DbCaches {
+  std::unique_ptr<CountCache, CacheFree> counts;
+  std::unique_ptr<ReplayState, CacheFree> replay;
+  std::unique_ptr<ServedCache, CacheFree> served;
+};
+template <typename T>
+T &get_or_make(std::unique_ptr<T, CacheFree> &part) {   // the part, built on first use (where T is complete)
+  if (!part) part.reset(new T);
+  return *part;
+}
 }  // namespace pgx
 
 struct pgx_seqdb {
@@ -182,10 +205,18 @@ struct pgx_seqdb {
   // (76 ms of a full-size configs[3] step through round 4, when only the LAST selection was kept)
   struct IndexPlan {
     int total = -1, chunk = -1;
-    uint64_t serial = 0, bases = 0, last_use = 0;
+    uint64_t bases = 0, last_use = 0;
     std::vector<pgx::ReadDesc> reads;
+    // the fused index path's device half (dev_index_fused): the selection's descriptors and slab offsets, uploaded once per plan
+    pgx::DevBuf<pgx::ReadDesc> d_reads;
+    pgx::DevBuf<uint64_t> d_slab_off;
+    uint64_t slab_total = 0, plan_bases = 0;
+    int plan_w = 0, plan_k = 0;
+    uint64_t plan_div = 0;   // 0: the device half is not built
+    bool plan_ok = false;
   };
   std::vector<IndexPlan> plans;   // at most 32, least recently used replaced
+  mutable pgx::DbCaches caches;   // (built on first use, like the packs)
 };
 
 namespace pgx {
@@ -198,9 +229,9 @@ void dev_sketch(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, 
                 size_t &n_out, uint32_t *n_literal);
 // fused index path: sketch (wave kernel) -> per-read reduce x levels in LDS -> ordered gather.  Returns false (and
 // leaves the outputs untouched) when the chunk needs the general path (other w/k ...).
-// plan_serial != 0: identifies `reads` (same serial => same list as the last call: descriptors and slab offsets are still on the device)
+// plan: the database's selection of `reads`, whose descriptors and slab offsets stay on the device with it (nullptr: uploaded for this call only)
 bool dev_index_fused(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, int k, int rs, int levels,
-                     const pgx_mm128 **d_top, size_t *n_top, uint64_t plan_serial = 0, uint32_t *n_second = nullptr);   // n_second: reads sketched run by run (ambiguous bases)
+                     const pgx_mm128 **d_top, size_t *n_top, pgx_seqdb::IndexPlan *plan = nullptr, uint32_t *n_second = nullptr);   // n_second: reads sketched run by run (ambiguous bases)
 // one mm_reduce level over a device list
 void dev_reduce(const pgx_mm128 *d_in, size_t n, int rs, DevBuf<pgx_mm128> &out, size_t &n_out);
 // multiplicity of x>>8, sorted by mer
@@ -357,15 +388,16 @@ void dev_build_pairs(const uint32_t *d_rlen, const pgx_mm128 *mmers, size_t n_mm
                      const pgx_mm128 *d_mmers = nullptr, const pgx_mm_count *d_counts = nullptr,  // d_*: the same lists, already on the device
                      DevicePairs *keep = nullptr,   // keep: the sorted records stay on the device too
                      const EarlyFn &early = nullptr,
-                     const pgx_seqdb *locus_db = nullptr);   // locus_db: its packs' locus keys are gathered from the lists on the way (pgx_pack.hip)
+                     const pgx_seqdb *db = nullptr);   // db: keeps the count table for the job's next chunk, and its packs' locus keys are
+                                                       // gathered from the lists on the way (pgx_pack.hip); nullptr: the table is built uncached
 // ---- multi-GPU hand-over: counts all-gathered, pair records routed to their owner chunk -------------------------
 // prepare: aggregate ALL chunks' counts, flag the kept shimmers of THIS index chunk's list (both on the device); returns the index
 // of the first shimmer with lower <= count < upper (-1: none).  scatter: the records of every adjacent kept pair from `start` on
 // (the list position the global scan starts at, shmr_utils.c:311-320), grouped by destination chunk 1..T in scan order; *d_send
 // stays valid until the next prepare.  from_records: the join of one overlap chunk over the records it received, in arrival order
 // (= source chunk order, then scan order: the insertion order of build_map over the concatenated lists).
-int64_t dev_pairs_prepare(const uint32_t *d_rlen, uint32_t n_rid, const pgx_mm128 *d_mm, size_t n_mm, const pgx_mm_count *d_counts,
-                          size_t n_counts, uint32_t lower, uint32_t upper);
+int64_t dev_pairs_prepare(const pgx_seqdb *db, const pgx_mm128 *d_mm, size_t n_mm, const pgx_mm_count *d_counts, size_t n_counts,
+                          uint32_t lower, uint32_t upper);
 void dev_pairs_scatter(const uint32_t *d_rlen, uint32_t T, int64_t start, const pgx_pair_rec **d_send, uint64_t *counts);
 void dev_pairs_from_records(const pgx_pair_rec *d_rec, size_t n, PairTables &out, DevicePairs *keep_dev, unsigned flags = 0,
                             const EarlyFn &early = nullptr, const pgx_seqdb *locus_db = nullptr);
@@ -431,15 +463,13 @@ struct RecordSink {
   virtual ~RecordSink() {}
 };
 RecordSink *&record_sink();   // (one stage at a time per process: set around overlap_stage by the caller that owns the sink)
-// Served jobs: an index command leaves a device copy of every final-level list / count file it wrote (keyed by the file's absolute path,
-// size and mtime); the job's overlap commands assemble their input from those copies instead of reading the files back (pgx_served.cpp).
-// d_payload (device) or h_payload (host): the file's entries, without the 8-byte count header; call AFTER the file is closed.
-void list_stash_put(const std::string &path, const void *d_payload, const void *h_payload, size_t bytes);
-void list_stash_clear();
-void count_cache_drop();     // the aggregated count table kept across the chunks of a job (pgx_pairs.hip)
-void replay_forget_sizes();  // the device replay's learned table sizes (pgx_replay.hip): another database, another job
-void replay_drop_precleared();
-void replay_preclear();      // tables of the last stage's sizes, allocated and cleared ahead of the replay (while the GPU waits for the host's outer table)
+// Served jobs: an index command leaves with the database a device copy of every final-level list / count file it wrote (keyed by the
+// file's absolute path, size and mtime); the job's overlap commands assemble their input from those copies instead of reading the files
+// back (pgx_served.cpp).  d_payload (device) or h_payload (host): the file's entries, without the 8-byte count header; call AFTER the file
+// is closed.  A copy that cannot be made (no HBM, a HIP error) is skipped: the files are complete, the copies are only a cache.
+void list_stash_put(const pgx_seqdb *db, const std::string &path, const void *d_payload, const void *h_payload, size_t bytes);
+void replay_drop_precleared(const pgx_seqdb *db);
+void replay_preclear(const pgx_seqdb *db);   // tables of the last stage's sizes, allocated and cleared ahead of the replay (while the GPU waits for the host's outer table)
 
 // pgx_overlap_stats::stream_checksum: the sum over the records of a 64-bit mix of every field (padding bytes excluded) and the record's
 // position in the stream -- the same on the device (k_emit adds it up while it writes the records) and on the host

@@ -624,55 +624,16 @@ static double trace_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// the fused index path's plan cache: which read selection's descriptors and slab offsets the "ix.reads" / "ix.slab_off"
-// workspaces hold.  pgx_shutdown() frees the workspaces, so it must forget the plan too (a pgx_seqdb that outlives a
-// shutdown + init would otherwise run the sketch kernels on uninitialised descriptors).
-namespace {
-struct FusedPlan {
-  uint64_t dev_serial = 0, slab_total = 0, plan_bases = 0, last_use = 0;
-  int plan_w = 0, plan_k = 0;
-  uint64_t plan_div = 0;
-  bool plan_ok = false;
-  DevBuf<ReadDesc> d_reads;       // the selection's descriptors and slab offsets stay on the device with their plan (one pair per selection:
-  DevBuf<uint64_t> d_slab_off;    // a pipeline that cycles through a job's chunks uploads each once)
-};
-std::vector<FusedPlan> g_plans;   // at most 32, least recently used replaced
-uint64_t g_plan_clock = 0;
-ShutdownHook g_plan_reset([] { g_plans.clear(); });
-}  // namespace
-
 bool dev_index_fused(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, int k, int rs, int levels,
-                     const pgx_mm128 **d_top, size_t *n_top, uint64_t plan_serial, uint32_t *n_second) {
+                     const pgx_mm128 **d_top, size_t *n_top, pgx_seqdb::IndexPlan *plan, uint32_t *n_second) {
   if (n_second) *n_second = 0;
   const uint32_t n = (uint32_t)reads.size();
   if (n == 0 || levels < 1 || levels > 2 || rs < 1) return false;
   const bool trace = getenv("PGX_TRACE") != nullptr;
   const double tr0 = trace ? trace_ms() : 0;
-  // slab offsets and read descriptors: computed and uploaded once per plan (file-scope state above: reset by pgx_shutdown)
-  FusedPlan *fp = nullptr;
-  if (plan_serial)
-    for (auto &pl : g_plans)
-      if (pl.dev_serial == plan_serial) fp = &pl;
-  if (!fp)   // (a selection without a serial, or a new one: an entry that holds no plan first)
-    for (auto &pl : g_plans)
-      if (pl.dev_serial == 0) fp = &pl;
-  if (!fp) {
-    if (g_plans.size() < 32) {
-      g_plans.emplace_back();
-      fp = &g_plans.back();
-    } else {
-      fp = &g_plans[0];
-      for (auto &pl : g_plans)
-        if (pl.last_use < fp->last_use) fp = &pl;
-      sync();   // (its buffers may still be read by what the last stage enqueued)
-      *fp = FusedPlan();
-    }
-  }
-  FusedPlan &g_plan = *fp;
-  g_plan.last_use = ++g_plan_clock;
-  uint64_t &dev_serial = g_plan.dev_serial, &slab_total = g_plan.slab_total, &plan_bases = g_plan.plan_bases;
-  int &plan_w = g_plan.plan_w, &plan_k = g_plan.plan_k;
-  bool &plan_ok = g_plan.plan_ok;
+  // slab offsets and read descriptors: computed and uploaded once per plan (the device half of the database's read selection)
+  pgx_seqdb::IndexPlan own;   // (no plan: for this call only)
+  pgx_seqdb::IndexPlan &pl = plan ? *plan : own;
   static const char *mode_env = getenv("PGX_SKETCH");
   static const bool want_fuse = (getenv("PGX_FUSE") && atoi(getenv("PGX_FUSE")) != 0) || (mode_env && !strcmp(mode_env, "fuse"));
   static const bool want_wave = mode_env && !strcmp(mode_env, "wave");
@@ -684,39 +645,38 @@ bool dev_index_fused(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, in
   // (PGX_SLAB_DIV / PGX_SLAB_MIN: test knobs that make reads outgrow their slabs)
   const bool fused_out = !want_wave && (want_fuse ? sketch_fused_supported(w, rs, levels) : sketch_blk_supported(w, k, rs, levels));
   const uint64_t slab_div = getenv("PGX_SLAB_DIV") ? std::max(1ll, atoll(getenv("PGX_SLAB_DIV"))) : !fused_out ? 8 : levels >= 2 ? 48 : 24;
-  const bool cached = plan_serial != 0 && plan_serial == dev_serial && plan_w == w && plan_k == k && g_plan.plan_div == slab_div;
+  const bool cached = pl.plan_div == slab_div && pl.plan_w == w && pl.plan_k == k;
   hipStream_t st = ctx().stream;
   if (!cached) {
     MemTag plan_tag("index.plans");
-    g_plan.d_reads.alloc(n), g_plan.d_slab_off.alloc((size_t)n + 1);
+    pl.d_reads.alloc(n), pl.d_slab_off.alloc((size_t)n + 1);
   }
-  ReadDesc *d_reads = g_plan.d_reads.p;
-  uint64_t *d_slab_off = g_plan.d_slab_off.p;
+  ReadDesc *d_reads = pl.d_reads.p;
+  uint64_t *d_slab_off = pl.d_slab_off.p;
   if (!cached) {
-    dev_serial = 0;
+    pl.plan_div = 0;
     std::vector<uint64_t> slab_off(n + 1, 0);
     uint64_t bases = 0;
-    plan_ok = true;
+    pl.plan_ok = true;
     const uint64_t slab_min = getenv("PGX_SLAB_MIN") ? std::max(1ll, atoll(getenv("PGX_SLAB_MIN"))) : 64;
     for (uint32_t i = 0; i < n; ++i) {
-      if (!sketch_wave_eligible(reads[i], w, k)) plan_ok = false;
+      if (!sketch_wave_eligible(reads[i], w, k)) pl.plan_ok = false;
       slab_off[i + 1] = slab_off[i] + (uint64_t)reads[i].len / slab_div + slab_min;
       bases += reads[i].len;
     }
-    if (plan_ok) {
+    if (pl.plan_ok) {
       PGX_HIP(hipMemcpyAsync(d_reads, reads.data(), n * sizeof(ReadDesc), hipMemcpyHostToDevice, st));
       PGX_HIP(hipMemcpyAsync(d_slab_off, slab_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
       sync();  // (slab_off is a local)
     }
-    slab_total = slab_off[n], plan_bases = bases, plan_w = w, plan_k = k, g_plan.plan_div = slab_div;
-    dev_serial = plan_serial;
+    pl.slab_total = slab_off[n], pl.plan_bases = bases, pl.plan_w = w, pl.plan_k = k, pl.plan_div = slab_div;
   }
-  if (!plan_ok) return false;
-  const uint64_t bases = plan_bases;
+  if (!pl.plan_ok) return false;
+  const uint64_t bases = pl.plan_bases;
   uint32_t *d_cnt = ws<uint32_t>("ix.cnt", 3 * (size_t)n + 4);  // [counts0 | flags | counts_top | nbad]
   uint32_t *d_flags = d_cnt + n, *d_ctop = d_cnt + 2 * (size_t)n, *d_nbad = d_cnt + 3 * (size_t)n;
   uint64_t *d_offs = ws<uint64_t>("ix.offs", n + 1);
-  pgx_mm128 *slab = ws<pgx_mm128>("ix.slab", slab_total);
+  pgx_mm128 *slab = ws<pgx_mm128>("ix.slab", pl.slab_total);
   PGX_HIP(hipMemsetAsync(d_cnt, 0, (3 * (size_t)n + 4) * sizeof(uint32_t), st));
   if (trace) {
     sync();

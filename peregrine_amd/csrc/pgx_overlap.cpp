@@ -135,7 +135,7 @@ void overlap_front(pgx_seqdb *db, const pgx_mm128 *mmers, size_t n_mm, const pgx
         DevVisit dv;
         dev_visit_inner(dpairs, (uint32_t)p->ovlp_upper, dv);            // (enqueued: the GPU replays the inner tables ...
         if (pt.n_rec >= ((size_t)2 << 20)) dev_align_prepare(db);        //  ... and packs the reads for the alignments ...
-        if (pt.n_rec >= ((size_t)2 << 20)) replay_preclear();            //  ... and clears the replay's tables (round 6: 7-8 ms of a full-size chunk) ...
+        if (pt.n_rec >= ((size_t)2 << 20)) replay_preclear(db);          //  ... and clears the replay's tables (round 6: 7-8 ms of a full-size chunk) ...
         pre.join();                                                      //  ... while the outer table finishes here)
         const double tw = now_ms();
         for (size_t i = 0; ok && i < dpairs.key_sample.size(); ++i) ok = pre.eg.keys[i * KEY_SAMPLE_STRIDE] == dpairs.key_sample[i];
@@ -182,8 +182,9 @@ void run_overlap(pgx_seqdb *db, const pgx_mm128 *mmers, size_t n_mm, const pgx_m
   StageFront front;
   dev_cache_age();
   struct DropPre {   // (tables the front cleared ahead of time for a device replay that then did not run: an exception, the host path)
-    ~DropPre() { replay_drop_precleared(); }
-  } drop_pre;
+    const pgx_seqdb *db;
+    ~DropPre() { replay_drop_precleared(db); }
+  } drop_pre{db};
   overlap_front(db, mmers, n_mm, counts, n_counts, p, dev, d_recs, n_recs, front);
   pgx_overlap_stats s = front.s;
   const double t0 = front.t0, t1 = front.t1;
@@ -503,8 +504,7 @@ int pgx_pairs_prepare_dev(pgx_seqdb *db, const pgx_mm128 *d_top, size_t n_top, c
     require_ready();
     PGX_REQUIRE(db && first_strict && (n_top == 0 || d_top) && (n_counts_all == 0 || d_counts_all) && mc_lower >= 0 && mc_upper >= 0,
                 PGX_EARG, "pgx_pairs_prepare_dev: bad argument");
-    *first_strict = dev_pairs_prepare(db->d_rlen.p, (uint32_t)db->rlen_by_rid.size(), d_top, n_top, d_counts_all, n_counts_all,
-                                      (uint32_t)mc_lower, (uint32_t)mc_upper);
+    *first_strict = dev_pairs_prepare(db, d_top, n_top, d_counts_all, n_counts_all, (uint32_t)mc_lower, (uint32_t)mc_upper);
   } catch (const Fail &f) {
     return f.code;
   } catch (const std::bad_alloc &) {

@@ -397,7 +397,7 @@ static void aggregate_counts_now(const pgx_mm_count *cin, size_t n_counts, Count
 
 
 // Every overlap chunk of a job aggregates the SAME count files (shmr_overlap.c:359-384 globs them all), and a resident pipeline runs the
-// chunks one after the other in this process: the table of the last call is kept and handed out again when the entries are the same --
+// chunks one after the other on one database: the table of its last call is kept with it and handed out again when the entries are the same --
 // same number, same order-sensitive 64-bit checksum of (mer, count), one read-only pass over the entries (~1 ms per GB) instead of the
 // split + sort + reduce + insert (57 ms per full-size configs[3] chunk, profiles/r05a_chunk_timeline_c4.txt).
 __global__ __launch_bounds__(256) void k_counts_checksum(const pgx_mm_count *__restrict__ in, size_t n, unsigned long long *__restrict__ sum) {
@@ -429,18 +429,14 @@ __global__ __launch_bounds__(256) void k_counts_checksum(const pgx_mm_count *__r
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(sum, part[0] + part[1] + part[2] + part[3]), atomicAdd(sum + 1, part2[0] + part2[1] + part2[2] + part2[3]);
 }
-namespace {
-struct CountCache {
+struct CountCache {   // (DbCaches: the read database the job runs on keeps the table of its last chunk)
   size_t n = 0;
   unsigned long long sum[2] = {0, 0};
   CountTable ct;
   bool valid = false;
 };
-CountCache g_counts;
-ShutdownHook g_counts_reset([] { g_counts = CountCache(); });
-}  // namespace
-void count_cache_drop() { g_counts = CountCache(); }   // (pgx_seqdb_free: the job is over, its table's HBM goes back)
-static const CountTable &aggregate_counts(const pgx_mm_count *cin, size_t n_counts, Tmp &tmp) {
+void CacheFree::operator()(CountCache *c) const { delete c; }
+static const CountTable &aggregate_counts(CountCache &cc, const pgx_mm_count *cin, size_t n_counts, Tmp &tmp) {
   unsigned long long sum[2] = {0, 0};
   if (n_counts) {
     hipStream_t st = ctx().stream;
@@ -449,12 +445,12 @@ static const CountTable &aggregate_counts(const pgx_mm_count *cin, size_t n_coun
     hipLaunchKernelGGL(k_counts_checksum, dim3((unsigned)std::min<size_t>(cdiv(n_counts, 256), 8192)), dim3(256), 0, st, cin, n_counts, d_sum.p);
     d_sum.download(sum, 2);
     sync();
-    if (g_counts.valid && g_counts.n == n_counts && g_counts.sum[0] == sum[0] && g_counts.sum[1] == sum[1]) return g_counts.ct;
+    if (cc.valid && cc.n == n_counts && cc.sum[0] == sum[0] && cc.sum[1] == sum[1]) return cc.ct;
   }
-  g_counts.valid = false;
-  aggregate_counts_now(cin, n_counts, g_counts.ct, tmp);
-  g_counts.n = n_counts, g_counts.sum[0] = sum[0], g_counts.sum[1] = sum[1], g_counts.valid = n_counts != 0;
-  return g_counts.ct;
+  cc.valid = false;
+  aggregate_counts_now(cin, n_counts, cc.ct, tmp);
+  cc.n = n_counts, cc.sum[0] = sum[0], cc.sum[1] = sum[1], cc.valid = n_counts != 0;
+  return cc.ct;
 }
 
 // keep flags of a list against the table; returns the first strict index (0xFFFFFFFF: none)
@@ -494,7 +490,7 @@ static void early_groups(const PairRecs &R, Tmp &tmp, const EarlyFn &early);
 
 void dev_build_pairs(const uint32_t *d_rlen, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts, size_t n_counts,
                      const PairParams &pp, PairTables &out, unsigned flags, const pgx_mm128 *d_mmers, const pgx_mm_count *d_counts,
-                     DevicePairs *keep_dev, const EarlyFn &early, const pgx_seqdb *locus_db) {
+                     DevicePairs *keep_dev, const EarlyFn &early, const pgx_seqdb *db) {
   out = PairTables();
   if (keep_dev) *keep_dev = DevicePairs();
   if (n_mm == 0) return;
@@ -508,13 +504,14 @@ void dev_build_pairs(const uint32_t *d_rlen, const pgx_mm128 *mmers, size_t n_mm
   // ---- aggregated counts ----------------------------------------------------------------------------------
   DevBuf<pgx_mm_count> cin_own(d_counts ? 0 : n_counts);  // (lists that are already on the device are used in place)
   if (!d_counts) cin_own.upload(counts, n_counts);
-  const CountTable &ct = aggregate_counts(d_counts ? d_counts : cin_own.p, n_counts, tmp);
+  CountCache uncached;   // (no database: the table lives for this call)
+  const CountTable &ct = aggregate_counts(db ? get_or_make(db->caches.counts) : uncached, d_counts ? d_counts : cin_own.p, n_counts, tmp);
 
   // ---- keep flags, chain, records -------------------------------------------------------------------------
   DevBuf<pgx_mm128> mm_own(d_mmers ? 0 : n);
   if (!d_mmers) mm_own.upload(mmers, n);
   const pgx_mm128 *mm_dev = d_mmers ? d_mmers : mm_own.p;
-  if (locus_db) locus_key_add_mm(locus_db, mm_dev, n);   // (only before the database's packs exist)
+  if (db) locus_key_add_mm(db, mm_dev, n);   // (only before the database's packs exist)
   DevBuf<uint8_t> keep;
   DevBuf<uint32_t> d_misc;
   keep_flags(mm_dev, n, ct, pp, d_rlen, keep, d_misc);
@@ -562,18 +559,18 @@ ScatterState g_scatter;
 ShutdownHook g_scatter_reset([] { g_scatter = ScatterState(); });
 }  // namespace
 
-int64_t dev_pairs_prepare(const uint32_t *d_rlen, uint32_t n_rid, const pgx_mm128 *d_mm, size_t n_mm, const pgx_mm_count *d_counts,
-                          size_t n_counts, uint32_t lower, uint32_t upper) {
+int64_t dev_pairs_prepare(const pgx_seqdb *db, const pgx_mm128 *d_mm, size_t n_mm, const pgx_mm_count *d_counts, size_t n_counts,
+                          uint32_t lower, uint32_t upper) {
   PGX_REQUIRE(n_mm < (1ULL << 31) && n_counts < (1ULL << 31), PGX_EARG, "shimmer list too long for one chunk");
   g_scatter = ScatterState();
   g_scatter.mm = d_mm, g_scatter.n = (uint32_t)n_mm;
   g_scatter.ready = true, g_scatter.ix_gen = index_owns(d_mm) ? index_generation() : 0;
   if (n_mm == 0) return -1;
   Tmp tmp;
-  const CountTable &ct = aggregate_counts(d_counts, n_counts, tmp);
+  const CountTable &ct = aggregate_counts(get_or_make(db->caches.counts), d_counts, n_counts, tmp);
   DevBuf<uint32_t> d_misc;
-  PairParams pp{1, 1, lower, upper, n_rid};
-  const uint32_t first = keep_flags(d_mm, (uint32_t)n_mm, ct, pp, d_rlen, g_scatter.keep, d_misc);
+  PairParams pp{1, 1, lower, upper, (uint32_t)db->rlen_by_rid.size()};
+  const uint32_t first = keep_flags(d_mm, (uint32_t)n_mm, ct, pp, db->d_rlen.p, g_scatter.keep, d_misc);
   return first == 0xFFFFFFFFu ? -1 : (int64_t)first;
 }
 

@@ -42,6 +42,7 @@ uint32_t pow2_at_least(size_t x) {
   return (uint32_t)c;
 }
 unsigned cdiv256(size_t n) { return (unsigned)((n + 255) / 256); }
+}  // namespace
 
 // Round 6: the three hash tables of a stage (hot pair table, reader lists, memo: 38.6 GB at full-size configs[3]) must start all zero, and clearing them
 // takes 7-8 ms -- on a GPU that sits idle for ~18 ms of every chunk while the host finishes the outer khash table (pgx_overlap.cpp: overlap_front).
@@ -59,17 +60,24 @@ struct PreCleared {
     valid = false;
   }
 };
-PreCleared g_pre;
-uint32_t g_last_pcap = 0, g_last_mcap = 0;   // what the last successful stage of the process used
-size_t g_last_ccap = 0;
-ShutdownHook h_pre([] { g_pre.drop(), g_last_pcap = g_last_mcap = 0, g_last_ccap = 0; });
+// What the replay keeps between the stages of a job, with its read database (DbCaches): the chunks of a job are alike.
+struct ReplayState {
+  PreCleared pre;
+  uint32_t last_pcap = 0, last_mcap = 0;   // what the last successful stage on the database used
+  size_t last_ccap = 0;
+  double learned[4] = {0, 0, 0, 0};        // read pairs, requests, items, reader nodes per bucket entry (0: not known)
+};
+void CacheFree::operator()(ReplayState *r) const { delete r; }
 
+namespace {
 // one attempt with the given table sizes (multiples of the defaults); returns 0, or the OV_* bits of what overflowed
 uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visit_bids, const uint32_t *d_bids, size_t nb, size_t n_entries,
                         uint32_t bestn, int band, bool predict, const std::function<pgx_ovlp *(size_t)> &alloc_out,
                         size_t *n_out, pgx_overlap_stats *st, bool trace, const double *mult, double *usage) {
   const double t0 = now_ms();
   hipStream_t s = ctx().stream;
+  ReplayState &rs = get_or_make(db->caches.replay);
+  PreCleared &pre = rs.pre;
   const size_t ne = std::max<size_t>(n_entries, 1024);
   MemTag mem_tag("replay.other");
   R r;
@@ -83,10 +91,10 @@ uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32
   DevBuf<PCold> pc;
   DevBuf<MSlot> mt;
   // (what the pre-cleared tables hold was free memory when round 5 measured the rule below: counted as free here too)
-  const size_t pre_hold = g_pre.valid ? (size_t)g_pre.pcap * sizeof(PHot) + g_pre.ccap * sizeof(PCold) + (size_t)g_pre.mcap * sizeof(MSlot) : 0;
+  const size_t pre_hold = pre.valid ? (size_t)pre.pcap * sizeof(PHot) + pre.ccap * sizeof(PCold) + (size_t)pre.mcap * sizeof(MSlot) : 0;
   bool precleared = false;
-  if (g_pre.valid && g_pre.pcap == pcap && g_pre.mcap == mcap && !getenv("PGX_REPLAY_COLD_SHIFT")) {   // (its reader lists: checked below, once the shift is known)
-    ph = std::move(g_pre.ph), mt = std::move(g_pre.mt);
+  if (pre.valid && pre.pcap == pcap && pre.mcap == mcap && !getenv("PGX_REPLAY_COLD_SHIFT")) {   // (its reader lists: checked below, once the shift is known)
+    ph = std::move(pre.ph), mt = std::move(pre.mt);
     precleared = true;
   } else {
     MemTag t1("replay.pair_table_hot");
@@ -105,19 +113,19 @@ uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32
       while (r.cshift < 3 && ((size_t)pcap >> r.cshift) * sizeof(PCold) > (free_b + dev_cache_free_bytes() + pre_hold) / 3) ++r.cshift;   // (the last stage's tables are in the cache)
   }
   const size_t ccap = ((size_t)pcap >> r.cshift) + 1;
-  const bool pc_pre = precleared && g_pre.ccap == ccap;
+  const bool pc_pre = precleared && pre.ccap == ccap;
   if (pc_pre) {
-    pc = std::move(g_pre.pc);
+    pc = std::move(pre.pc);
   } else {
     MemTag t2("replay.pair_table_readers");
-    g_pre.pc.release();
+    pre.pc.release();
     pc.alloc(ccap);
   }
   if (!precleared) {
     MemTag t3("replay.memo_table");
     mt.alloc(mcap);
   }
-  g_pre.drop();   // (whatever was not taken over goes back to the block cache)
+  pre.drop();   // (whatever was not taken over goes back to the block cache)
   r.ph = ph.p, r.pc = pc.p, r.pmask = pcap - 1, r.mt = mt.p, r.mmask = mcap - 1;
   r.item_cap = (uint32_t)std::min<size_t>((size_t)(((size_t)(ne * 6) + nb * (size_t)64) * mult[0]) + (size_t)(nb / GPW + 2 + SPARSE_CAP + 8 + BIG_WG * BIG_NW) * ICH + (1u << 20), 0x7FFFFFF0u);
   r.rn_cap = (uint32_t)std::min<size_t>((size_t)(ne * 8 * mult[1]) + (1u << 20), 0x7FFFFFF0u);
@@ -494,7 +502,7 @@ uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32
     if (trace)
       fprintf(stderr, "[pgx]   tables: %llu read pairs in %u slots (load %.2f), %u alignments in %u memo slots (load %.2f), items %u of %u, reader nodes %u of %u, requests %u of %u\n",
               n_keys, pcap, (double)n_keys / pcap, hc->nreq, mcap, (double)hc->nreq / mcap, hc->item_top, r.item_cap, hc->rnode_top, r.rn_cap, hc->nreq, r.req_cap);
-    g_last_pcap = pcap, g_last_mcap = mcap, g_last_ccap = ccap;
+    rs.last_pcap = pcap, rs.last_mcap = mcap, rs.last_ccap = ccap;
     *n_out = nrec;
     if (st) {
       st->n_align_needed = hc->lookups, st->n_seen_skip = hc->skips, st->n_align_gpu = first_req;
@@ -540,45 +548,39 @@ void dev_place_bids(const uint32_t *ids_all, size_t n_ids, const uint32_t *psrc,
   sync();   // (the upload sources are the caller's host arrays; the temporaries go back to the block cache)
 }
 
-namespace {
-double g_learned[4] = {0, 0, 0, 0};
-ShutdownHook h_learn([] { replay_forget_sizes(); });
-}  // namespace
-void replay_forget_sizes() {
-  for (double &m : g_learned) m = 0;
-  g_pre.drop();
-  g_last_pcap = g_last_mcap = 0, g_last_ccap = 0;
+void replay_drop_precleared(const pgx_seqdb *db) {   // (a stage that ended without a device replay: nothing cleared ahead of time outlives it)
+  if (db->caches.replay) db->caches.replay->pre.drop();
 }
 
-void replay_drop_precleared() { g_pre.drop(); }   // (a stage that ended without a device replay: nothing cleared ahead of time outlives it)
-
 // called by the stage's front while the GPU would otherwise wait for the host's outer table: tables of the last stage's sizes, cleared, on ctx().stream
-void replay_preclear() {
-  if (!g_last_pcap || g_pre.valid || (getenv("PGX_REPLAY_PRECLEAR") && atoi(getenv("PGX_REPLAY_PRECLEAR")) == 0)) return;
+void replay_preclear(const pgx_seqdb *db) {
+  ReplayState &rs = get_or_make(db->caches.replay);
+  PreCleared &pre = rs.pre;
+  if (!rs.last_pcap || pre.valid || (getenv("PGX_REPLAY_PRECLEAR") && atoi(getenv("PGX_REPLAY_PRECLEAR")) == 0)) return;
   size_t free_b = 0, total_b = 0;
-  const size_t need = (size_t)g_last_pcap * sizeof(PHot) + g_last_ccap * sizeof(PCold) + (size_t)g_last_mcap * sizeof(MSlot);
+  const size_t need = (size_t)rs.last_pcap * sizeof(PHot) + rs.last_ccap * sizeof(PCold) + (size_t)rs.last_mcap * sizeof(MSlot);
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b + dev_cache_free_bytes()) return;   // (no room ahead of time: the attempt decides)
   try {
     hipStream_t s = ctx().stream;
     {
       MemTag t1("replay.pair_table_hot");
-      g_pre.ph.alloc(g_last_pcap);
+      pre.ph.alloc(rs.last_pcap);
     }
     {
       MemTag t2("replay.pair_table_readers");
-      g_pre.pc.alloc(g_last_ccap);
+      pre.pc.alloc(rs.last_ccap);
     }
     {
       MemTag t3("replay.memo_table");
-      g_pre.mt.alloc(g_last_mcap);
+      pre.mt.alloc(rs.last_mcap);
     }
-    PGX_HIP(hipMemsetAsync(g_pre.ph.p, 0, (size_t)g_last_pcap * sizeof(PHot), s));
-    PGX_HIP(hipMemsetAsync(g_pre.pc.p, 0, g_last_ccap * sizeof(PCold), s));
-    PGX_HIP(hipMemsetAsync(g_pre.mt.p, 0, (size_t)g_last_mcap * sizeof(MSlot), s));
-    g_pre.pcap = g_last_pcap, g_pre.mcap = g_last_mcap, g_pre.ccap = g_last_ccap, g_pre.valid = true;
+    PGX_HIP(hipMemsetAsync(pre.ph.p, 0, (size_t)rs.last_pcap * sizeof(PHot), s));
+    PGX_HIP(hipMemsetAsync(pre.pc.p, 0, rs.last_ccap * sizeof(PCold), s));
+    PGX_HIP(hipMemsetAsync(pre.mt.p, 0, (size_t)rs.last_mcap * sizeof(MSlot), s));
+    pre.pcap = rs.last_pcap, pre.mcap = rs.last_mcap, pre.ccap = rs.last_ccap, pre.valid = true;
   } catch (const Fail &) {
     (void)hipGetLastError();
-    g_pre.drop();
+    pre.drop();
   }
 }
 
@@ -586,9 +588,11 @@ bool dev_replay(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visi
                 uint32_t bestn, int band, bool predict, uint32_t ovlp_upper, const std::function<pgx_ovlp *(size_t)> &alloc_out,
                 size_t *n_out, pgx_overlap_stats *st, bool trace) {
   *n_out = 0;
+  ReplayState &rs = get_or_make(db->caches.replay);
   struct DropPre {   // (tables cleared ahead of time that no attempt took over do not outlive the stage)
-    ~DropPre() { g_pre.drop(); }
-  } drop_pre;
+    PreCleared &pre;
+    ~DropPre() { pre.drop(); }
+  } drop_pre{rs.pre};
   // what the encodings hold (anything else goes to the host replay)
   if (ovlp_upper > 128 || nb >= (1u << 29) - 2 || n_entries >= (1ULL << 31) || !dp.valid) return false;
   if (nb == 0) {
@@ -601,7 +605,7 @@ bool dev_replay(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visi
                         nb * (size_t)(64 * sizeof(Item) + 64) + (256u << 20);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
-      g_pre.drop();      // (tables cleared ahead of time are part of what `need` prices)
+      rs.pre.drop();     // (tables cleared ahead of time are part of what `need` prices)
       dev_cache_trim();  // (blocks the cache holds for re-use count as used)
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b) {
         fprintf(stderr, "[pgx] note: the device replay's tables (%.1f GB) do not fit the free device memory (%.1f GB); the host replay takes over\n",
@@ -616,10 +620,10 @@ bool dev_replay(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visi
   //    overflowing attempt costs a whole first sweep (the request / memo overflow is only seen when k_file runs): 205 of 1,103 ms;
   //  * the open-addressing tables want a LOW load: with the pair table at 0.75 (64 M slots for 50 M read pairs) and the memo table at 0.71
   //    the evaluations of a chunk took 73 ms longer than at 0.37 / 0.36 (linear probing: ~8 probes per miss instead of ~2).
-  // So a stage measures what it used per bucket entry -- read pairs, requests, items, reader nodes -- and the NEXT stage of the process (the
-  // chunks of a job are alike) sizes its tables by that: hash tables for a load of at most 0.4, arenas with 20 % to spare.  The first stage of
-  // a process starts from the defaults and, where they overflow, repeats with x 4 hash tables / x 2 arenas.
-  double *learned = g_learned;   // read pairs, requests, items, reader nodes per bucket entry (0: not known)
+  // So a stage measures what it used per bucket entry -- read pairs, requests, items, reader nodes -- and the NEXT stage on the database (the
+  // chunks of a job are alike) sizes its tables by that: hash tables for a load of at most 0.4, arenas with 20 % to spare.  The first stage on
+  // a database starts from the defaults and, where they overflow, repeats with x 4 hash tables / x 2 arenas.
+  double *learned = rs.learned;
   double mult[5] = {1, 1, 1, 1, 1};
   if (learned[0] > 0) {
     // (the arenas may also SHRINK to what the last stage used + 25-100 %: 8 reader nodes per entry are reserved by default and a c4 chunk links
@@ -641,7 +645,7 @@ bool dev_replay(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visi
       if (f.code != PGX_ENOMEM && !(f.code == PGX_EHIP && strstr(pgx_last_error(), "hipMalloc"))) throw;   // (only a failed allocation)
       (void)hipGetLastError();
       const bool had_learned = learned[0] > 0;
-      replay_forget_sizes();
+      rs = ReplayState();   // (the learned sizes and the tables cleared ahead of time)
       dev_cache_trim();
       if (!had_learned || attempt > 0) {
         fprintf(stderr, "[pgx] note: the device replay's tables could not be allocated (%s); the host replay takes over\n", pgx_last_error());

@@ -56,19 +56,14 @@ std::string absolute(const std::string &path) {
   return getcwd(cwd, sizeof(cwd)) ? std::string(cwd) + "/" + path : path;
 }
 
-// ---- device copies of the list / count files index commands of this process wrote ------------------------------------------------
+// ---- device copies of the list / count files index commands on a database wrote ------------------------------------------------
 struct Stashed {
   DevBuf<uint8_t> dev;    // the payload (entries only, without the 8-byte count header)
   size_t bytes = 0;
   long long size = 0, mtime_ns = 0;   // of the file as it was right after it was written
   uint64_t serial = 0;
 };
-std::mutex g_stash_mu;
-std::map<std::string, Stashed> g_stash;
-size_t g_stash_bytes = 0;
-uint64_t g_stash_serial = 0;
 constexpr size_t STASH_CAP = (size_t)24 << 30;   // (a full-size configs[4] job: 12.6 GB of L1 lists + counts)
-ShutdownHook g_stash_reset([] { list_stash_clear(); });
 
 // the payload of one counted file ("<uint64 n><n entries>", shmr_utils.c write_mmlist / shmr_index.c:165-233); a truncated file is an error
 template <typename T>
@@ -101,15 +96,16 @@ bool read_payload(const std::string &path, void *dst, size_t bytes) {
 // every file of a name-sorted group, one after the other, into ONE device array: from the stash where it holds a current copy
 // (device to device), else from the file (read by a few threads side by side, then uploaded)
 template <typename T>
-void assemble(const std::vector<FileId> &files, DevBuf<T> &out, size_t *n_out, size_t *from_stash) {
+void assemble(const std::vector<FileId> &files, std::mutex &stash_mu, const std::map<std::string, Stashed> &stash, DevBuf<T> &out, size_t *n_out,
+              size_t *from_stash) {
   std::vector<size_t> cnt(files.size()), off(files.size());
   std::vector<const uint8_t *> src(files.size(), nullptr);
   size_t total = 0;
   {
-    std::lock_guard<std::mutex> lk(g_stash_mu);
+    std::lock_guard<std::mutex> lk(stash_mu);
     for (size_t i = 0; i < files.size(); ++i) {
-      auto it = g_stash.find(files[i].first);
-      if (it != g_stash.end() && it->second.size == files[i].second.first && it->second.mtime_ns == files[i].second.second &&
+      auto it = stash.find(files[i].first);
+      if (it != stash.end() && it->second.size == files[i].second.first && it->second.mtime_ns == files[i].second.second &&
           it->second.bytes % sizeof(T) == 0 && (long long)it->second.bytes + 8 <= files[i].second.first) {
         src[i] = it->second.dev.p, cnt[i] = it->second.bytes / sizeof(T);
         ++*from_stash;
@@ -168,8 +164,6 @@ struct DevListCache {
     n_mm = n_mc = 0;
   }
 };
-DevListCache g_lists;
-ShutdownHook g_lists_reset([] { g_lists.clear(); });
 
 // ---- the records to out_path --------------------------------------------------------------------------------------------------------
 // From a host array (stand-alone commands, the host replay).  A regular file: several threads pwrite slices into the page cache.
@@ -372,38 +366,51 @@ void read_index_files(const char *shimmer_prefix, std::vector<pgx_mm128> &mm, st
 
 }  // namespace
 
-void list_stash_put(const std::string &path, const void *d_payload, const void *h_payload, size_t bytes) {
+// what a database keeps for the served commands of its job (DbCaches)
+struct ServedCache {
+  std::mutex stash_mu;
+  std::map<std::string, Stashed> stash;   // by absolute path
+  size_t stash_bytes = 0;
+  uint64_t stash_serial = 0;
+  DevListCache lists;
+};
+void CacheFree::operator()(ServedCache *c) const { delete c; }
+
+void list_stash_put(const pgx_seqdb *db, const std::string &path, const void *d_payload, const void *h_payload, size_t bytes) {
   const std::string abs = absolute(path);
   struct stat sb;
   if (stat(abs.c_str(), &sb) != 0 || (long long)sb.st_size != (long long)bytes + 8) return;
+  ServedCache &c = get_or_make(db->caches.served);
+  {
+    std::lock_guard<std::mutex> lk(c.stash_mu);   // (the file was rewritten: a copy of what it held before is gone whatever follows)
+    auto it = c.stash.find(abs);
+    if (it != c.stash.end()) c.stash_bytes -= it->second.bytes, c.stash.erase(it);
+  }
   Stashed e;
-  MemTag tag("served.list_stash");
-  e.dev.alloc(std::max<size_t>(bytes, 1));
-  if (bytes) {
-    if (d_payload) PGX_HIP(hipMemcpyAsync(e.dev.p, d_payload, bytes, hipMemcpyDeviceToDevice, ctx().stream));
-    else PGX_HIP(hipMemcpyAsync(e.dev.p, h_payload, bytes, hipMemcpyHostToDevice, ctx().stream));
-    sync();
+  try {
+    MemTag tag("served.list_stash");
+    e.dev.alloc(std::max<size_t>(bytes, 1));
+    if (bytes) {
+      if (d_payload) PGX_HIP(hipMemcpyAsync(e.dev.p, d_payload, bytes, hipMemcpyDeviceToDevice, ctx().stream));
+      else PGX_HIP(hipMemcpyAsync(e.dev.p, h_payload, bytes, hipMemcpyHostToDevice, ctx().stream));
+      sync();
+    }
+  } catch (const Fail &) {   // (no copy: the overlap commands read this file back)
+    (void)hipGetLastError();
+    return;
   }
   e.bytes = bytes, e.size = (long long)sb.st_size, e.mtime_ns = (long long)sb.st_mtim.tv_sec * 1000000000LL + sb.st_mtim.tv_nsec;
-  std::lock_guard<std::mutex> lk(g_stash_mu);
-  e.serial = ++g_stash_serial;
-  auto it = g_stash.find(abs);
-  if (it != g_stash.end()) g_stash_bytes -= it->second.bytes, g_stash.erase(it);
-  g_stash_bytes += bytes;
-  g_stash.emplace(abs, std::move(e));
-  while (g_stash_bytes > STASH_CAP && g_stash.size() > 1) {   // the oldest copies go first
-    auto old = g_stash.begin();
-    for (auto jt = g_stash.begin(); jt != g_stash.end(); ++jt)
+  std::lock_guard<std::mutex> lk(c.stash_mu);
+  e.serial = ++c.stash_serial;
+  c.stash_bytes += bytes;
+  c.stash.emplace(abs, std::move(e));
+  while (c.stash_bytes > STASH_CAP && c.stash.size() > 1) {   // the oldest copies go first
+    auto old = c.stash.begin();
+    for (auto jt = c.stash.begin(); jt != c.stash.end(); ++jt)
       if (jt->second.serial < old->second.serial) old = jt;
-    g_stash_bytes -= old->second.bytes;
-    g_stash.erase(old);
+    c.stash_bytes -= old->second.bytes;
+    c.stash.erase(old);
   }
-}
-void list_stash_clear() {   // (also the assembled lists of the last job: both belong to the database that is going away)
-  g_lists.clear();
-  std::lock_guard<std::mutex> lk(g_stash_mu);
-  g_stash.clear();
-  g_stash_bytes = 0;
 }
 
 }  // namespace pgx
@@ -459,12 +466,13 @@ int pgx_overlap_chunk_db_begin(pgx_seqdb *db, const char *shimmer_prefix, const 
     std::vector<FileId> mm_files, mc_files;
     identity(mm_files, mc_files);
     size_t from_stash = 0;
-    DevListCache &c = g_lists;
+    ServedCache &sc = get_or_make(db->caches.served);
+    DevListCache &c = sc.lists;
     if (c.prefix != abs_prefix || c.mm_files != mm_files || c.mc_files != mc_files || mm_files.empty()) {
       c.clear();   // (another prefix: the old lists' memory goes back first)
       MemTag tag("served.lists");
-      assemble(mm_files, c.mm, &c.n_mm, &from_stash);
-      assemble(mc_files, c.mc, &c.n_mc, &from_stash);
+      assemble(mm_files, sc.stash_mu, sc.stash, c.mm, &c.n_mm, &from_stash);
+      assemble(mc_files, sc.stash_mu, sc.stash, c.mc, &c.n_mc, &from_stash);
       std::vector<FileId> mm2, mc2;
       identity(mm2, mc2);
       if (mm2 == mm_files && mc2 == mc_files) c.prefix = abs_prefix, c.mm_files = mm_files, c.mc_files = mc_files;

@@ -109,6 +109,44 @@ def test_shimmer_list_of_another_seqdb_is_rejected():
     rb.close(), rs.close()
 
 
+def test_job_caches_belong_to_their_database(tmp_path, monkeypatch):
+    """What the library keeps between the chunks of a job (index plans, count table, the replay's learned sizes, the served list
+    copies) lives with its database: closing it gives all of that HBM back, and closing ANOTHER database leaves it alone."""
+    import ctypes as C
+    from peregrine_amd import _lib
+    monkeypatch.setenv("PGX_GPU_REPLAY", "1")
+    lib = _lib.load()
+
+    def served(rdb, name):   # an index command, then an overlap command on its files (pgx_cli serve's calls)
+        pre, out = str(tmp_path / name), str(tmp_path / (name + ".ovlp"))
+        _lib.check(lib.pgx_index_chunk_db(rdb.h, pre.encode(), C.byref(_lib.IndexParams(1, 1, 2, 6, 80, 16, 0)), C.byref(_lib.IndexResult())),
+                   "pgx_index_chunk_db")
+        st = _lib.OverlapStats()
+        _lib.check(lib.pgx_overlap_chunk_db(rdb.h, (pre + "-L2").encode(), out.encode(), C.byref(_lib.OverlapParams(1, 1, 4, 2, 240, 100, 120)),
+                                            C.byref(st)), "pgx_overlap_chunk_db")
+        return formats.read_ovlp(out), st.asdict()
+
+    small = simreads.make_workload("small")
+    live = []
+    for _ in range(2):   # create -> index + overlap -> close, twice: nothing of a freed database survives it
+        rdb = ResidentDB(small, 0)
+        ov, st = served(rdb, "job")
+        assert len(ov) > 1000 and st["device_replay"] == 1
+        rdb.close()
+        live.append(_lib.mem_ledger()["live_bytes"])
+    assert live[0] == live[1], live
+    a = ResidentDB(small, 0)
+    ix = a.index()
+    before, st0 = a.overlap(ix.top, ix.top_mc)
+    b = ResidentDB(simreads.make_workload("tiny"), 0)
+    served(b, "other")
+    b.close()
+    after, st1 = a.overlap(ix.top, ix.top_mc)
+    a.close()
+    assert len(before) > 1000 and formats.ovlp_fields_equal(after, before)
+    assert st0["device_replay"] == st1["device_replay"] == 1 and st0["replay_attempts"] == st1["replay_attempts"] == 1, (st0, st1)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
