@@ -1,18 +1,20 @@
 // pgx_align.hip -- banded O(ND) furthest-reaching confirmation (ovlp_match, /root/reference/src/DWmatch.c:66-204),
-// EIGHT (default) or four candidate alignments per wavefront.
+// EIGHT candidate alignments per wavefront.
 //
 // A candidate keeps on average 3.6 diagonals alive (<= 8 in 98.7 % of the steps, at most band+1 = 101), so one wavefront
 // per candidate leaves most lanes idle -- and the kernel is bound by VALU issue (profiles/r01_pmc_align.txt), so lane
-// utilisation is throughput.  Here a wavefront is eight independent 8-lane groups (GL = 8; or four 16-lane groups, the
-// description below uses 16); each group runs the reference's d-loop for its own
-// candidate, in lock-step with the other three, and pulls the next candidate from a device-wide counter the moment it
-// finishes (persistent groups: no tail inside the wave).  Lane j of a group owns diagonal k = min_k + 2*(base+j) of the
-// current step; wider bands take several rounds of 16.  V lives in a per-group LDS ring indexed by k (only the previous
-// step's values are ever read, so 2*band+8 slots never alias live data; only V[1] needs to start at 0).
-// Per step: start point from V[k-1], V[k+1]; an 8-code probe per lane (off-diagonal fronts stop there); long snakes are
-// extended by the whole group, 128 codes per iteration (8 per lane with 16 lanes, 16 per lane with 8), with coalesced loads; the order-dependent side results (first
-// diagonal reaching an end, first extension > 16, first occurrence of the strictly longest extension) are resolved
-// lowest-k-first with ballots restricted to the group; band update by ballot of U >= best - band.
+// utilisation is throughput.  Here a wavefront is eight independent 8-lane groups (GL); each group runs the reference's
+// d-loop for its own candidate and pulls the next one from a device-wide counter the moment it finishes (persistent groups:
+// no tail inside the wave).  Lane j of a group owns diagonal k = min_k + 2*(base+j) of the current step; wider bands take
+// several rounds of 8.  V lives in a per-group LDS ring indexed by k (only the previous step's values are ever read, so
+// 2*band+8 slots never alias live data; only V[1] needs to start at 0).
+// Per step: start point from V[k-1], V[k+1]; a probe per lane (off-diagonal fronts stop there); long snakes are extended
+// by the whole group with coalesced loads; the order-dependent side results (first diagonal reaching an end, first
+// extension > 16, first occurrence of the strictly longest extension) are resolved lowest-k-first with ballots restricted
+// to the group; band update by ballot of U >= best - band.
+//
+// Kernels: k_align_ph (the groups above, as per-group phase machines), k_align1 / k_align1_list (a wavefront per candidate);
+// each reads the seqdb bytes or the 2-bit packs (PACKED), as align_source() decides for the launch.
 #include <hipcub/hipcub.hpp>
 
 #include "pgx_internal.h"
@@ -43,17 +45,13 @@ template <int CTRL>
 __device__ __forceinline__ int dpp_max(int v) {
   return max(v, __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true));   // (bound_ctrl: folds into one v_max_i32_dpp)
 }
-// maximum over the GL (8 or 16) lanes of a group, result in every lane: xor-butterfly with quad_perm / row_half_mirror /
-// row_mirror
-template <int GL>
-__device__ __forceinline__ int group_max_i32(int v) {
+constexpr int GL = 8;   // lanes per candidate of the grouped kernel: half a DPP row, eight groups per wavefront
+// maximum over the 8 lanes of a group, result in every lane: xor-butterfly with quad_perm / row_half_mirror
+__device__ __forceinline__ int group_max8_i32(int v) {
   v = dpp_max<0xB1>(v);   // quad_perm [1,0,3,2]
   v = dpp_max<0x4E>(v);   // quad_perm [2,3,0,1]
-  if (GL >= 8) v = dpp_max<0x141>(v);  // row_half_mirror: lanes i <-> 7-i of every 8
-  if (GL == 16) v = dpp_max<0x140>(v);  // row_mirror: lanes i <-> 15-i
-  return v;
+  return dpp_max<0x141>(v);  // row_half_mirror: lanes i <-> 7-i of every 8
 }
-template <int GL>
 __device__ __forceinline__ uint32_t group_bits(uint64_t wave_mask, int gbase) {
   return (uint32_t)(wave_mask >> gbase) & ((1u << GL) - 1u);
 }
@@ -61,7 +59,7 @@ template <int CTRL>
 __device__ __forceinline__ int dpp_min(int v) {
   return min(v, __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true));   // (one v_min_i32_dpp)
 }
-// minimum over the 8 lanes of a group, result in every lane (same butterfly as group_max_i32<8>)
+// minimum over the 8 lanes of a group, result in every lane (same butterfly as group_max8_i32)
 __device__ __forceinline__ int group_min8_i32(int v) {
   v = dpp_min<0xB1>(v);
   v = dpp_min<0x4E>(v);
@@ -267,238 +265,21 @@ __global__ __launch_bounds__(64) void k_align1_list(const uint8_t *__restrict__ 
 }
 
 
-// GL = lanes per candidate: 16 (four candidates per wavefront) or 8 (eight).
-// VT = storage type of the V ring: uint16_t when no read is longer than 65,535 bases (x <= q_len fits), which halves the LDS of
-// a workgroup and lets 32 instead of 20 eight-candidate wavefronts share a CU; int32_t otherwise.
-template <int GL, typename VT>
-__global__ __launch_bounds__(64) void k_align4(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ roff,
-                                               const uint32_t *__restrict__ rlen,
-                                               const pgx_align_key *__restrict__ keys, uint32_t n, int band, int ring,
-                                               pgx_match *__restrict__ out, uint32_t *__restrict__ counter) {
-  extern __shared__ int32_t Vall[];
-  const int lane = threadIdx.x, gl = lane & (GL - 1), gbase = lane & ~(GL - 1);
-  VT *V = reinterpret_cast<VT *>(Vall) + (lane / GL) * ring;
-  const int mask = ring - 1, band_size = band * 2;
-
-  uint32_t c_next = 0, c_end = 0;   // the wavefront's chunk of the work counter
-  // per-candidate state, uniform within a 16-lane group
-  bool alive = false, exhausted = false;
-  uint32_t a = 0;
-  const uint8_t *q = seq, *t = seq;
-  int q_len = 0, t_len = 0, qs = 0, ts = 0, max_d = 0, d = 0;
-  int best_m = -1, min_k = 0, max_k = 0;
-  uint32_t longest = 0;
-  bool started = false, matched = false;
-  int q_bgn = 0, t_bgn = 0, q_m_end = 0, t_m_end = 0, q_end = 0, t_end = 0;
-
-  for (;;) {
-    // ---- idle groups pull the next candidate ---------------------------------------------------------------
-    // (the work counter in chunks of 8 per wavefront, as in k_align_ph below: one address, ~12 ns per same-address atomic)
-    const bool fetching = !alive && !exhausted;
-    const uint64_t fw = ballot64(fetching);
-    uint32_t na = 0;
-    if (fw) {
-      constexpr uint32_t CHUNK = 8;
-      uint64_t need = 0;
-      for (int g = 0; g < 64; g += GL) need |= 1ULL << g;   // the first lanes of the groups
-      need &= fw;
-      const uint32_t cnt = (uint32_t)__builtin_popcountll(need);
-      const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-      const uint32_t avail = __builtin_amdgcn_readfirstlane(c_end - c_next);
-      na = c_next + r;
-      if (avail < cnt) {
-        uint32_t got = 0;
-        if (lane == 0) got = atomicAdd(counter, CHUNK);
-        got = __builtin_amdgcn_readfirstlane(got);
-        if (r >= avail) na = got + (r - avail);
-        c_next = got + (cnt - avail), c_end = got + CHUNK;
-      } else {
-        c_next += cnt;
-      }
-    }
-    if (fetching) {
-      na = (uint32_t)__shfl((int)na, gbase, 64);
-      if (na >= n) {
-        exhausted = true;
-      } else {
-        a = na;
-        const pgx_align_key key = keys[a];
-        q = seq + roff[key.rid0] + key.q_off;
-        t = seq + roff[key.rid1];
-        q_len = (int)(rlen[key.rid0] - key.q_off);
-        t_len = (int)rlen[key.rid1];
-        qs = key.dir0 ? 4 : 0, ts = key.dir1 ? 4 : 0;
-        max_d = (int)(0.3 * (double)(q_len + t_len));  // DWmatch.c:96, one IEEE double multiply
-        d = 0, best_m = -1, min_k = 0, max_k = 0, longest = 0;
-        started = matched = false;
-        q_bgn = t_bgn = q_m_end = t_m_end = q_end = t_end = 0;
-        if (gl == 0) V[1 & mask] = (VT)0;  // the only slot read before it is written (d = 0 reads V[k+1] = V[1])
-        alive = true;
-      }
-    }
-    if (!ballot64(alive)) break;
-    __syncthreads();
-
-    // ---- end of the d-loop without a match (DWmatch.c:118-122,196-199) ---------------------------------------
-    bool stepping = alive;
-    if (alive && (d >= max_d || max_k - min_k > band_size)) {
-      if (gl == 0) {
-        pgx_match r;
-        r.m_size = 0, r.dist = 0, r.q_bgn = 0, r.q_end = 0, r.t_bgn = 0, r.t_end = 0;
-        r.t_m_end = t_m_end, r.q_m_end = q_m_end;
-        out[a] = r;
-      }
-      alive = false, stepping = false;
-    }
-
-    // ---- one step: all diagonals of the current band, 16 per round -------------------------------------------
-    const int nk = max_k >= min_k ? ((max_k - min_k) >> 1) + 1 : 0;
-    int x = 0, y = 0;
-    for (int base = 0;; base += GL) {
-      const bool inround = stepping && !matched && base < nk;
-      if (!ballot64(inround)) break;
-      const int j = base + gl;
-      const bool active = inround && j < nk;
-      const int k = min_k + 2 * j;
-      int x1 = 0, y1 = 0;
-      bool more = false;
-      if (inround) x = 0, y = 0;
-      if (active) {
-        const int va = (int)V[(k - 1) & mask], vb = (int)V[(k + 1) & mask];
-        x = (k == min_k || (k != max_k && va < vb)) ? vb : va + 1;
-        y = x - k;
-        x1 = x, y1 = y;
-        const int rem = min(q_len - x, t_len - y);
-        if (rem > 0) {  // probe: the first 8 codes
-          int m = match8(load_u64_unaligned(q + x), load_u64_unaligned(t + y), qs, ts);
-          m = min(m, rem);
-          x += m, y += m;
-          more = (m == 8) && (rem > 8);
-        }
-      }
-      // long snakes: the group extends one diagonal at a time, 128 codes per iteration
-      uint64_t mw = ballot64(more);
-      while (mw) {
-        const uint32_t gm = group_bits<GL>(mw, gbase);
-        const bool has = gm != 0;
-        const int L = has ? __builtin_ctz(gm) : 0;
-        const int xs = __shfl(x, gbase + L, 64), ys = __shfl(y, gbase + L, 64);
-        const int rem = min(q_len - xs, t_len - ys);
-        // codes per lane and iteration: 8 with 16-lane groups, 16 with 8-lane groups (128 per group either way)
-        constexpr int SL = GL == 16 ? 8 : 16;
-        const int off = gl * SL;
-        int m = SL;
-        if (has) {
-          m = 0;
-          if (off < rem) {
-            m = match8(load_u64_unaligned(q + xs + off), load_u64_unaligned(t + ys + off), qs, ts);
-            if (SL == 16 && m == 8 && off + 8 < rem)
-              m += match8(load_u64_unaligned(q + xs + off + 8), load_u64_unaligned(t + ys + off + 8), qs, ts);
-            m = min(m, rem - off);
-          }
-        }
-        const uint32_t sg = group_bits<GL>(ballot64(has && m < SL), gbase);
-        int ext = GL * SL;
-        if (sg) {
-          const int f = __builtin_ctz(sg);
-          ext = SL * f + __shfl(m, gbase + f, 64);
-        }
-        if (has && gl == L) {
-          x += ext, y += ext;
-          if (sg || ext >= rem) more = false;  // mismatch found or an end reached: this diagonal is done
-        }
-        mw = ballot64(more);
-      }
-      const int ext = x - x1;
-      const bool hit = active && (x >= q_len || y >= t_len);
-      const uint64_t hitw = ballot64(hit);  // rare (once per candidate): everything that depends on it sits behind the branch
-      int hl = GL;
-      if (hitw) {
-        const uint32_t hitm = group_bits<GL>(hitw, gbase);
-        if (hitm) hl = __builtin_ctz(hitm);
-      }
-      const bool valid = active && gl <= hl;
-      {  // first extension > 16 fixes q_bgn/t_bgn once (DWmatch.c:142-146)
-        const uint64_t sw = ballot64(valid && ext > 16 && !started);
-        if (sw) {
-          const uint32_t m = group_bits<GL>(sw, gbase);
-          const int l = m ? __builtin_ctz(m) : 0;
-          const int bx = __shfl(x1, gbase + l, 64), by = __shfl(y1, gbase + l, 64);
-          if (m) q_bgn = bx, t_bgn = by, started = true;
-        }
-      }
-      if (ballot64(valid && (uint32_t)ext > longest)) {  // strictly longer extension (DWmatch.c:148-152)
-        const int mx = group_max_i32<GL>(valid ? ext : -1);
-        const uint32_t m = group_bits<GL>(ballot64(valid && ext == mx), gbase);
-        const int l = m ? __builtin_ctz(m) : 0;
-        const int ex = __shfl(x, gbase + l, 64), ey = __shfl(y, gbase + l, 64);
-        if (inround && mx >= 0 && (uint32_t)mx > longest) longest = (uint32_t)mx, q_m_end = ex, t_m_end = ey;
-      }
-      if (valid) V[k & mask] = (VT)x;
-      {
-        const int s = group_max_i32<GL>(valid ? x + y : -1);
-        if (inround) best_m = max(best_m, s);
-      }
-      if (hitw) {
-        const uint32_t hitm = group_bits<GL>(hitw, gbase);
-        const int ex = __shfl(x, gbase + (hl & (GL - 1)), 64), ey = __shfl(y, gbase + (hl & (GL - 1)), 64);
-        if (inround && hitm) matched = true, q_end = ex, t_end = ey;
-      }
-    }
-    __syncthreads();
-
-    if (stepping && matched) {  // DWmatch.c:185-194
-      if (gl == 0) {
-        pgx_match r;
-        r.q_bgn = q_bgn, r.t_bgn = t_bgn, r.q_end = q_end, r.t_end = t_end, r.dist = d;
-        r.m_size = (q_end - q_bgn + t_end - t_bgn + 2 * d) / 2;
-        r.t_m_end = t_m_end, r.q_m_end = q_m_end;
-        out[a] = r;
-      }
-      alive = false, stepping = false;
-    }
-    // ---- band update (DWmatch.c:166-183) -------------------------------------------------------------------------
-    int new_min = max_k, new_max = min_k;
-    const int thr = best_m - band;
-    for (int base = 0;; base += GL) {
-      const bool inround = stepping && base < nk;
-      if (!ballot64(inround)) break;
-      const int j = base + gl;
-      const int k2 = min_k + 2 * j;
-      int u = 0;
-      if (inround && j < nk) u = (nk <= GL) ? x + y : 2 * (int)V[k2 & mask] - k2;
-      const uint32_t m = group_bits<GL>(ballot64(inround && j < nk && u >= thr), gbase);
-      if (m) {
-        new_min = min(new_min, min_k + 2 * (base + __builtin_ctz(m)));
-        new_max = max(new_max, min_k + 2 * (base + 31 - __builtin_clz(m)));
-      }
-    }
-    if (stepping) max_k = new_max + 1, min_k = new_min - 1, ++d;
-  }
-}
-
-
-// ---- the same d-loop as a per-group PHASE MACHINE (round 2) ------------------------------------------------------------------
-// k_align4 steps all groups of a wavefront through one d-step per iteration: a step takes as many rounds of GL diagonals, and
-// its snake loop as many iterations, as the NEEDIEST group of the wavefront -- which is why narrower groups did not pay there
-// (with sixteen 4-lane groups some group needs a second round in nearly every step).  Here every group carries its own phase
+// ---- the d-loop as a per-group PHASE MACHINE (round 2) --------------------------------------------------------------------------
+// Groups stepped in lock-step (one d-step of every group per iteration of the wavefront) take as many rounds of GL diagonals per
+// step, and as many snake iterations, as the NEEDIEST group of the wavefront.  Here every group carries its own phase
 //   FETCH -> STEP (loop conditions of DWmatch.c:118-122) -> ROUND (start points + 8-code probe of GL diagonals) -> SNAKE (one
-//   64- or 128-code extension of the group's lowest unfinished diagonal per iteration) -> END (the order-dependent side results
+//   128- or 256-code extension of the group's lowest unfinished diagonal per iteration) -> END (the order-dependent side results
 //   of the round, V, best_m, the first diagonal that reaches an end) -> next ROUND, or BAND (one round of the band scan per
 //   iteration, DWmatch.c:166-183) -> STEP of d + 1
 // and an iteration of the wavefront runs every phase body once, each under its groups' predicate; a group passes through
 // ROUND, SNAKE, END and BAND within ONE iteration when its step has a single round and a single extension (the common case),
-// and only the groups that need more take more iterations.  Lane utilisation is what the kernel is bound by (VALU issue):
-// sixteen 4-lane groups keep 3.6 live diagonals on 4 lanes instead of 8.
+// and only the groups that need more take more iterations.
 enum { PH_FETCH = 0, PH_STEP = 1, PH_ROUND = 2, PH_SNAKE = 3, PH_END = 4, PH_BAND = 5, PH_DONE = 6 };
 // The V rings are exchanged between the lanes of ONE wavefront (the block is a wavefront): its LDS instructions execute in program
 // order, so all the two exchange points of an iteration need is that the compiler keeps that order -- not __syncthreads()'s
-// s_waitcnt vmcnt(0) lgkmcnt(0), which also drains the sequence loads in flight.  -DPGX_PH_BARRIER: the round-2 form.
-#ifdef PGX_PH_BARRIER
-#define PH_SYNC() __syncthreads()
-#else
+// s_waitcnt vmcnt(0) lgkmcnt(0), which also drains the sequence loads in flight.
 #define PH_SYNC() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"), __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront")
-#endif
 // PACKED (round 3): the reads come from the 2-bit packs of the seqdb (pgx_pack.hip: k_pack2, one pass per read database, both
 // strands) instead of its bytes: the probe compares 16 bases with two funnel shifts, an XOR and a find-first-bit (8 codes, two
 // 64-bit shifts, XOR, AND and a 64-bit count before), an extension step 32 bases per lane = 256 per group with four funnel shifts
@@ -513,7 +294,9 @@ enum { PH_FETCH = 0, PH_STEP = 1, PH_ROUND = 2, PH_SNAKE = 3, PH_END = 4, PH_BAN
 // dozen translation ranges of the 47 GB of packs instead of 512 (pgx_pack.hip; rounds 2-5: a wavefront per workgroup, chunks of 8
 // straight from the device-wide counter: every wavefront of a CU at another locus).
 // PACKED: seq = the packs, roff = d_poff (dword index of a read's forward strand; its reverse complement follows at + ceil(len / 16)).
-template <int GL, typename VT, bool PACKED>
+// VT = storage type of the V ring: uint16_t when no read is longer than 65,535 bases (x <= q_len fits), which halves the LDS of a
+// group and lets 32 instead of 19 wavefronts share a CU; int32_t otherwise (the byte form only: such databases have no packs).
+template <typename VT, bool PACKED>
 __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ roff,
                                                       const uint32_t *__restrict__ rlen, const pgx_align_key *__restrict__ keys,
                                                       uint32_t n, int band, int ring, pgx_match *__restrict__ out,
@@ -527,13 +310,12 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
   extern __shared__ int32_t Vall[];
   __shared__ unsigned long long s_state;   // {start of the workgroup's segment : 32 | requests of it handed out : 32}
   __shared__ uint32_t s_lock;              // held by the wavefront that is claiming the next segment
-  static_assert(GL == 8, "the group operations below are written for 8-lane groups (half a DPP row)");
   const int lane = threadIdx.x & 63, gl = lane & (GL - 1), gbase = lane & ~(GL - 1), gb4 = gbase << 2;
   VT *V = reinterpret_cast<VT *>(Vall) + ((threadIdx.x >> 6) * (64 / GL) + lane / GL) * ring;
   if (threadIdx.x == 0) s_state = (unsigned long long)seg, s_lock = 0u;   // (an exhausted segment: the first fetch claims one)
   __syncthreads();
   const int mask = ring - 1, band_size = band * 2;
-  constexpr int SL = PACKED ? 32 : (GL == 16 ? 8 : 16);  // codes per lane and snake iteration
+  constexpr int SL = PACKED ? 32 : 16;                     // codes per lane and snake iteration
   constexpr int PROBE = PACKED ? 16 : 8;                   // codes of a probe
   if (redo_list) n = *redo_n;
   const uint32_t iter_budget = esc_list && iter_limit ? iter_limit : 0xFFFFFFFFu;
@@ -723,7 +505,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       // (a ballot of ONE integer compare is one v_cmp; of a bool the compiler materialises 0 / 1 and compares again.  Lanes outside
       //  ROUND hold 0.)  The group's mask is STATE from here on: SNAKE clears a bit per finished diagonal, no ballot of its own.
       asm volatile("" : "+v"(probe_full));   // (kept a VGPR value: as a bool the compiler carries it as a lane mask and the ballot costs a select + a compare on top)
-      const uint32_t g = group_bits<GL>(ballot64(probe_full >= PROBE), gbase);
+      const uint32_t g = group_bits(ballot64(probe_full >= PROBE), gbase);
       if (phase == PH_ROUND) gm = g, phase = g ? PH_SNAKE : PH_END;
     }
 
@@ -779,7 +561,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       int hl = GL;
       uint32_t hitm = 0;
       if (hitw) {   // (once per candidate)
-        hitm = group_bits<GL>(hitw, gbase);
+        hitm = group_bits(hitw, gbase);
         if (hitm) hl = __builtin_ctz(hitm);
         asm volatile("" : "+v"(hl));   // (keeps the branch: folded into selects the four instructions run in every iteration)
       }
@@ -788,7 +570,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
         const uint64_t sw = ballot64((valid && !started ? ext : 0) > 16);   // (a select + ONE compare: the compiler turns a ballot of
                                                                            // combined predicates into select 0/1 + compare on top of them)
         if (sw) {
-          const uint32_t m = group_bits<GL>(sw, gbase);
+          const uint32_t m = group_bits(sw, gbase);
           const int l = m ? __builtin_ctz(m) : 0;
           const int bx = group_lane(x1, gb4, l), by = group_lane(y1, gb4, l);
           if (m) q_bgn = bx, t_bgn = by, started = true;
@@ -796,8 +578,8 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       }
       const int ev = valid ? ext : -1;
       if (ballot64(ev > (int)longest)) {  // strictly longer extension (DWmatch.c:148-152)
-        const int mx = group_max_i32<GL>(ev);
-        const uint32_t m = group_bits<GL>(ballot64(valid && ext == mx), gbase);
+        const int mx = group_max8_i32(ev);
+        const uint32_t m = group_bits(ballot64(valid && ext == mx), gbase);
         const int l = m ? __builtin_ctz(m) : 0;
         const int ex = group_lane(x, gb4, l), ey = group_lane(y, gb4, l);
         if (e && mx >= 0 && (uint32_t)mx > longest) longest = (uint32_t)mx, q_m_end = ex, t_m_end = ey;
@@ -805,7 +587,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       if (valid) V[k & mask] = (VT)x;
       const int u = x + y;
       {
-        const int s = group_max_i32<GL>(valid ? u : -1);
+        const int s = group_max8_i32(valid ? u : -1);
         if (e) best_m = max(best_m, s);
       }
       bool matched = false;
@@ -825,7 +607,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       // The band update (DWmatch.c:166-183) of a step whose diagonals all sat in this one round -- 98.7 % of the steps -- right here, from
       // the registers: U = x + y of the group's lanes, the qualifying diagonals as a mask, its lowest and highest bit.  (hit lanes: the
       // candidate is finished, the update is not looked at.)  Wider bands go through BAND below, a round of GL diagonals per iteration.
-      const uint32_t qm = group_bits<GL>(ballot64((e && active ? u : INT32_MIN) >= best_m - band), gbase);
+      const uint32_t qm = group_bits(ballot64((e && active ? u : INT32_MIN) >= best_m - band), gbase);
       if (e) {
         if (matched) {
           phase = PH_FETCH;
@@ -850,7 +632,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
         const int k2 = min_k + 2 * j;
         int u = 0;
         if (bnd && j < nk) u = 2 * (int)V[k2 & mask] - k2;   // (nk > GL: U of the earlier rounds' diagonals is not in the registers)
-        const uint32_t m = group_bits<GL>(ballot64((bnd && j < nk ? u : INT32_MIN) >= thr), gbase);
+        const uint32_t m = group_bits(ballot64((bnd && j < nk ? u : INT32_MIN) >= thr), gbase);
         if (bnd) {
           if (m) {
             new_min = min(new_min, min_k + 2 * (bbase + __builtin_ctz(m)));
@@ -872,23 +654,60 @@ __global__ void k_order_keys(const pgx_align_key *__restrict__ keys, uint32_t n,
   if (i < n) k[i] = prank[keys[i].rid0], v[i] = i;
 }
 
+// ---- what a launch reads, and how each kernel family is launched on it ----------------------------------------------------------
+// A sequence source: the seqdb bytes (offsets d_roff) or the 2-bit packs (offsets d_poff; the PACKED forms of the kernels)
+struct SeqSource {
+  const uint8_t *seq;
+  const uint64_t *off;
+  bool packed;
+};
+static SeqSource seq_bytes(const pgx_seqdb *db) { return {db->d_seq.p, db->d_roff.p, false}; }
+static SeqSource seq_packed(const pgx_seqdb *db) { return {reinterpret_cast<const uint8_t *>(db->d_pack.p), db->d_poff.p, true}; }
+struct AlignSources {
+  SeqSource grouped;   // k_align_ph
+  SeqSource one;       // k_align1 / k_align1_list
+};
+// The one decision of what the kernels of a launch read.  grouped_n: the alignments of the launch's k_align_ph, which may build the
+// packs; < 0: the launch has none (k_align1 alone).  (The knobs are read per call: the parity tests walk every form inside one process.)
+//  - the packs are built by the first launch of at least PGX_ALIGN_PACKED_MIN alignments (default 100,000), or ahead of it by
+//    dev_align_prepare, and serve every later launch on this database; < 0: never.  A read beyond 65,535 bases: never (16-bit V rings only).
+//  - the one-candidate-per-wavefront kernels read the packs (round 6) where the database has them -- as it stands before this launch builds
+//    them -- and none of its reads lacks 2-bit codes (n_flagged_reads: such candidates compare nibbles, DWmatch.c:136-137);
+//    PGX_ALIGN1_PACKED=0 keeps them on the bytes.
+//  - seq_packs() == nullptr (no HBM for the packs): the bytes.
+//  - after pgx_seqdb_release_bytes the knobs that ask for the bytes are ignored; with neither bytes nor packs: PGX_ESTATE, so that no
+//    kernel is launched on a null sequence.
+static AlignSources align_source(const pgx_seqdb *db, long grouped_n) {
+  const bool has_bytes = db->d_seq.p != nullptr, short_reads = db->max_rlen <= 65535u;
+  const char *p1 = getenv("PGX_ALIGN1_PACKED");
+  const bool one_packed = seq_packs_valid(db) && db->n_flagged_reads == 0 && short_reads && (!has_bytes || !(p1 && atoi(p1) == 0));
+  const char *pm = getenv("PGX_ALIGN_PACKED_MIN");
+  const long packed_min = pm ? atol(pm) : 100000;
+  const bool grouped_packed = short_reads && grouped_n >= 0 &&
+                              (!has_bytes || (packed_min >= 0 && (grouped_n >= packed_min || seq_packs_valid(db)))) && seq_packs(db) != nullptr;
+  PGX_REQUIRE(has_bytes || (one_packed && (grouped_n < 0 || grouped_packed)), PGX_ESTATE,
+              "the seqdb's bytes were released (pgx_seqdb_release_bytes) and its packs are gone");
+  return {grouped_packed ? seq_packed(db) : seq_bytes(db), one_packed ? seq_packed(db) : seq_bytes(db)};
+}
+// the instance of a kernel that reads `s` (on_packs / on_bytes: its PACKED / byte form; the first two parameters: sequence, offsets)
+template <typename K, typename... A>
+void launch_on(const SeqSource &s, K on_packs, K on_bytes, dim3 grid, dim3 block, size_t lds, A... args) {
+  hipLaunchKernelGGL(s.packed ? on_packs : on_bytes, grid, block, lds, ctx().stream, s.seq, s.off, args...);
+}
+
 // The 2-bit packs ahead of the first large launch: run_overlap calls this while the GPU would otherwise wait for the host's outer
 // table, so the first stage's k_pack2 (1.6 ms at 4.5 Gbases) is off the critical path; later stages find the packs in place
-// (pgx_pack.hip: they are kept with the database).
-void dev_align_prepare(const pgx_seqdb *db) {
-  const char *pm = getenv("PGX_ALIGN_PACKED_MIN");
-  if (db->max_rlen > 65535u || (pm && atol(pm) < 0)) return;
-  (void)seq_packs(db);
-}
+// (pgx_pack.hip: they are kept with the database).  (As a grouped launch of any size would.)
+void dev_align_prepare(const pgx_seqdb *db) { (void)align_source(db, LONG_MAX); }
 
 // Dispatch (each form bit-exact against the oracle: tests/test_gpu_parity.py::test_align_variants_vs_oracle):
 //   n <= small     : k_align1, a wavefront per candidate -- the replay's tail rounds, where latency is everything
-//   large launches : k_align_ph<8, u16, packed> over the 2-bit packs + k_align1_list for what it hands on (reads with bytes that have no
+//   large launches : k_align_ph<u16, packed> over the 2-bit packs + k_align1_list for what it hands on (reads with bytes that have no
 //                    2-bit code, stragglers past the iteration budget); without packs (no HBM for them, PGX_ALIGN_PACKED_MIN < 0)
-//                    k_align_ph<8, u16> on the seqdb bytes; with a read beyond 65,535 bases (16-bit V ring too narrow) k_align4<8, int32>
+//                    k_align_ph<u16> on the seqdb bytes; with a read beyond 65,535 bases (16-bit V ring too narrow) k_align_ph<int32>
+//                    on the seqdb bytes
 void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int band, pgx_match *d_out, int tail_batch) {
   if (n == 0) return;
-  // (the knobs are read per call: the parity tests walk every kernel variant inside one process)
   // launches up to this many alignments take a wavefront per candidate (k_align1).  On uniform candidates the crossover is ~14 k
   // (tools/alignlat.py: 13,000) -- but the mid-size launches of a stage are its TAIL sweeps (tail_batch: every request batch of the
   // device replay after the first), and in repeat-rich sets those are mostly long, wide-band alignments that the 8-lane groups of
@@ -899,36 +718,24 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
   // candidates (wrong type guesses, not stragglers), loses 2 ms of 100 with them on k_align1: 250,000 from the third batch on, 60,000 for the
   // second.  PGX_ALIGN_SMALL overrides all three.
   const long small_max = getenv("PGX_ALIGN_SMALL") ? atol(getenv("PGX_ALIGN_SMALL")) : tail_batch >= 2 ? 250000 : tail_batch ? 60000 : 13000;
-  KernelTimer tm((long)n <= small_max ? "align1" : "align", n);
+  const bool small = (long)n <= small_max;
+  KernelTimer tm(small ? "align1" : "align", n);
   int ring = 64;
   while (ring < 2 * band + 8) ring <<= 1;
   hipStream_t st = ctx().stream;
-  // the one-candidate-per-wavefront kernels read the 2-bit packs too (round 6) where the database has them and none of its reads lacks 2-bit codes
-  // (n_flagged_reads: such candidates compare nibbles, DWmatch.c:136-137); PGX_ALIGN1_PACKED=0 keeps them on the bytes while those are there
-  const bool one_packed = seq_packs_valid(db) && db->n_flagged_reads == 0 && db->max_rlen <= 65535u &&
-                          (!db->d_seq.p || !(getenv("PGX_ALIGN1_PACKED") && atoi(getenv("PGX_ALIGN1_PACKED")) == 0));
-  PGX_REQUIRE(db->d_seq.p || one_packed, PGX_ESTATE, "the seqdb's bytes were released (pgx_seqdb_release_bytes) and its packs are gone");
-  if ((long)n <= small_max) {
-    if (one_packed)
-      hipLaunchKernelGGL(k_align1<true>, dim3((unsigned)n), dim3(64), ring * sizeof(int32_t), st, reinterpret_cast<const uint8_t *>(db->d_pack.p), db->d_poff.p,
-                         db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out);
-    else
-      hipLaunchKernelGGL(k_align1<false>, dim3((unsigned)n), dim3(64), ring * sizeof(int32_t), st, db->d_seq.p, db->d_roff.p, db->d_rlen.p, d_keys,
-                         (uint32_t)n, band, ring, d_out);
+  const AlignSources src = align_source(db, small ? -1 : (long)n);
+  if (small) {
+    launch_on(src.one, k_align1<true>, k_align1<false>, dim3((unsigned)n), dim3(64), ring * sizeof(int32_t), db->d_rlen.p, d_keys, (uint32_t)n, band,
+              ring, d_out);
     PGX_HIP(hipGetLastError());
     return;
   }
   uint32_t *counter = ws<uint32_t>("align.counter", 8);
   PGX_HIP(hipMemsetAsync(counter, 0, 8 * sizeof(uint32_t), st));
-  if (db->max_rlen > 65535u) {   // x <= read length must fit the V ring's element: 32-bit rings, 20 wavefronts per CU
-    const unsigned grid = (unsigned)std::min<size_t>((n + 7) / 8, (size_t)ctx().num_cu * 20);
-    hipLaunchKernelGGL((k_align4<8, int32_t>), dim3(grid), dim3(64), 8 * ring * sizeof(int32_t), st, db->d_seq.p, db->d_roff.p, db->d_rlen.p,
-                       d_keys, (uint32_t)n, band, ring, d_out, counter);
-    PGX_HIP(hipGetLastError());
-    return;
-  }
-  // k_align_ph: workgroups of NW wavefronts (a V ring of `ring` u16 per 8-lane group), as many as give a CU its 32 wavefronts
-  const size_t lds_wave = (size_t)8 * ring * sizeof(uint16_t);
+  // k_align_ph: workgroups of NW wavefronts (a V ring of `ring` elements per 8-lane group), as many as give a CU its 32 wavefronts.  x <= read
+  // length must fit the ring's element: 32-bit rings when a read is longer than 65,535 bases (19 wavefronts per CU at ring 256)
+  const bool wide = db->max_rlen > 65535u;
+  const size_t lds_wave = (size_t)8 * ring * (wide ? sizeof(int32_t) : sizeof(uint16_t));
   const unsigned waves_cu = (unsigned)std::min<size_t>(32, (158u << 10) / lds_wave);   // 32 = all the wavefronts a CU holds; alignment kernels per c3 step
                                                                                        // with the chunked work counter: 16 -> 65.3 ms, 20 -> 55.9, 24 -> 50.1, 28 -> 46.3, 32 -> 43.7
   const long nw_env = getenv("PGX_ALIGN_NW") ? atol(getenv("PGX_ALIGN_NW")) : 0;
@@ -939,11 +746,6 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
   if (nw_env >= 1 && nw_env <= 16 && (unsigned)nw_env <= waves_cu) NW = (unsigned)nw_env;
   const size_t lds = lds_wave * NW;
   const unsigned wg_cu = waves_cu / NW;
-  // the packs are built by the first launch of at least PGX_ALIGN_PACKED_MIN alignments (default 100,000) and serve every later launch
-  // on this database; < 0: never.
-  const char *pm = getenv("PGX_ALIGN_PACKED_MIN");
-  const long packed_min = pm ? atol(pm) : 100000;
-  const uint32_t *packs = (packed_min >= 0 && ((long)n >= packed_min || seq_packs_valid(db))) ? seq_packs(db) : nullptr;
   // segment = the run of requests a workgroup's wavefronts share (a multiple of the chunk of 8): long enough that the workgroup stays at
   // one place of the list, short enough that the last segments of a launch do not leave the other CUs idle
   const size_t n_wg = (size_t)ctx().num_cu * wg_cu;
@@ -954,16 +756,19 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
   };
   const uint32_t seg = segment(n);
   const unsigned grid = (unsigned)std::min<size_t>((n + seg - 1) / seg, n_wg);
-  if (packs) {
-    const uint32_t iter_limit = getenv("PGX_ALIGN_ITER_LIMIT") ? (uint32_t)atol(getenv("PGX_ALIGN_ITER_LIMIT")) : 2500u;   // (0: no hand-on of stragglers)
+  // the packed launch hands on (esc): stragglers past the iteration budget, and candidates on reads without 2-bit codes
+  uint32_t *esc = nullptr;
+  const uint32_t *order = nullptr;
+  uint32_t iter_limit = 0;
+  if (src.grouped.packed) {
+    iter_limit = getenv("PGX_ALIGN_ITER_LIMIT") ? (uint32_t)atol(getenv("PGX_ALIGN_ITER_LIMIT")) : 2500u;   // (0: no hand-on of stragglers)
     // escalation block: [0] stragglers handed on, [1] candidates that touch a read without 2-bit codes, [2] the byte-wise launch's work
     // counter, [3] the number of requests (for the order list), [4 .. 4 + n) the stragglers, [4 + n .. 4 + 2 n) the others
-    uint32_t *esc = ws<uint32_t>("align.esc", 2 * n + 4);
+    esc = ws<uint32_t>("align.esc", 2 * n + 4);
     PGX_HIP(hipMemsetAsync(esc, 0, 3 * sizeof(uint32_t), st));
     // The requests in the order of the packs' layout (round 6): sorted by the rank of the query read -- stable, so the requests of one read
     // stay in the walk's order -- when the layout follows the locus keys; results are addressed by request number, nothing downstream
     // sees the order.  15.7 M requests: ~1 ms of a 150-190 ms launch.
-    const uint32_t *order = nullptr;
     const long order_min = getenv("PGX_ALIGN_ORDER_MIN") ? atol(getenv("PGX_ALIGN_ORDER_MIN")) : 200000;
     if (db->locus_ordered && order_min >= 0 && (long)n >= order_min) {
       const uint32_t nn = (uint32_t)n;
@@ -978,30 +783,22 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
       PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, k_in, k_out, v_in, v_out, (int)nn, 0, bits, st));
       order = v_out;
     }
-    hipLaunchKernelGGL((k_align_ph<8, uint16_t, true>), dim3(grid), dim3(64 * NW), lds, st, reinterpret_cast<const uint8_t *>(packs), db->d_poff.p,
-                       db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out, counter, order ? esc + 3 : (const uint32_t *)nullptr, order, esc,
-                       esc + 4, db->d_nflag.p, seg, iter_limit);
+  }
+  const auto ph_bytes = wide ? k_align_ph<int32_t, false> : k_align_ph<uint16_t, false>;   // (the packs never serve a wide launch)
+  launch_on(src.grouped, k_align_ph<uint16_t, true>, ph_bytes, dim3(grid), dim3(64 * NW), lds, db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out,
+            counter, order ? esc + 3 : nullptr, order, esc, esc ? esc + 4 : nullptr, db->d_nflag.p, seg, iter_limit);
+  if (esc) {
     // candidates on reads with ambiguous bases: the same phase machine on the seqdb bytes, eight per wavefront, from their list (round 3 gave
     // each a wavefront of its own through k_align1_list: 5 % of the reads flagged = +64 % alignment time at c3).  Only when the database
     // holds such a read at all.
-    if (db->n_flagged_reads) {
-      const uint32_t seg2 = segment(n / 16 + 1);
-      hipLaunchKernelGGL((k_align_ph<8, uint16_t, false>), dim3((unsigned)std::min<size_t>(n / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds, st,
-                         db->d_seq.p, db->d_roff.p, db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out, esc + 2, esc + 1, esc + 4 + n, esc, esc + 4,
-                         (const uint32_t *)nullptr, seg2, iter_limit);
-    }
+    if (db->n_flagged_reads)
+      launch_on(seq_bytes(db), k_align_ph<uint16_t, true>, ph_bytes, dim3((unsigned)std::min<size_t>(n / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds,
+                db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out, esc + 2, esc + 1, esc + 4 + n, esc, esc + 4, nullptr, segment(n / 16 + 1),
+                iter_limit);
     // the stragglers of either launch, a wavefront per candidate, from the list
     const dim3 g1((unsigned)std::min<size_t>(std::max<size_t>(n / 256, 256), (size_t)ctx().num_cu * 32));
-    if (one_packed)
-      hipLaunchKernelGGL(k_align1_list<true>, g1, dim3(64), ring * sizeof(int32_t), st, reinterpret_cast<const uint8_t *>(packs), db->d_poff.p, db->d_rlen.p,
-                         d_keys, esc, esc + 4, band, ring, d_out);
-    else
-      hipLaunchKernelGGL(k_align1_list<false>, g1, dim3(64), ring * sizeof(int32_t), st, db->d_seq.p, db->d_roff.p, db->d_rlen.p, d_keys, esc, esc + 4, band,
-                         ring, d_out);
-  } else {
-    hipLaunchKernelGGL((k_align_ph<8, uint16_t, false>), dim3(grid), dim3(64 * NW), lds, st, db->d_seq.p, db->d_roff.p, db->d_rlen.p, d_keys,
-                       (uint32_t)n, band, ring, d_out, counter, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                       (uint32_t *)nullptr, (const uint32_t *)nullptr, seg, 0u);
+    launch_on(src.one, k_align1_list<true>, k_align1_list<false>, g1, dim3(64), ring * sizeof(int32_t), db->d_rlen.p, d_keys, esc, esc + 4, band,
+              ring, d_out);
   }
   PGX_HIP(hipGetLastError());
 }

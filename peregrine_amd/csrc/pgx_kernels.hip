@@ -7,7 +7,7 @@
 //   k_sketch_wave    : mm_sketch      closed form, one wavefront per read            (pgx_sketch_fast.hip)
 //   k_reduce_*       : mm_reduce      src/shmr_reduce.c:53-90
 //   count            : mm_count       src/shmr_utils.c:131-160  radix sort + run-length
-//   k_align4         : ovlp_match     src/DWmatch.c:66-204      four candidates per wavefront          (pgx_align.hip)
+//   k_align_ph       : ovlp_match     src/DWmatch.c:66-204      eight candidates per wavefront         (pgx_align.hip)
 #include <chrono>
 
 #include <hipcub/hipcub.hpp>

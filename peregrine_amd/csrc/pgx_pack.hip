@@ -1,4 +1,4 @@
-// pgx_pack.hip -- the 2-bit packs of a read database that the alignment kernels read (k_align_ph<8, u16, packed>, pgx_align.hip).
+// pgx_pack.hip -- the 2-bit packs of a read database that the alignment kernels read (k_align_ph<u16, packed>, pgx_align.hip).
 //
 // LAYOUT (round 6): read by read, both strands of a read next to each other, every strand starting at a dword:
 //   read r:  [ forward strand: nw(r) dwords | reverse complement, stored forward: nw(r) dwords ],  nw(r) = ceil(len(r) / 16),

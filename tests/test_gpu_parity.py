@@ -807,7 +807,7 @@ def test_overlap_argument_edges(small):
 # ---- every alignment kernel variant against the oracle ------------------------------------------------------------
 def _with_long_reads():
     """the `small` read set + two 100 kb reads of the same genome region: a read beyond 65,535 bases switches the whole stage to the
-    32-bit V rings (k_align4<8, int32_t>, pgx_align.hip)"""
+    32-bit V rings (k_align_ph<int32_t, false> on the seqdb bytes, pgx_align.hip)"""
     g = simreads.make_genome(400_000, 11)
     a = simreads.simulate_reads(g, coverage=12.0, seed=5, wrap=0)
     b = simreads.simulate_reads(g[100_000:260_000], n_reads=2, seed=6, mean_len=100_000, sd_len=0, wrap=0)
@@ -845,7 +845,7 @@ def _oracle_matches(db, keys, band):
 
 
 ALIGN_VARIANTS = [   # (id, environment, read set): every form dev_align dispatches to (pgx_align.hip)
-    ("ph8-packed", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0"), "small"),   # k_align_ph<8, u16, packed>: the default of large launches
+    ("ph8-packed", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0"), "small"),   # k_align_ph<u16, packed>: the default of large launches
     ("ph8-packed-ambiguous", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0"), "withN"),   # ... reads with N: handed on to the byte-wise launch
     ("ph8-packed-stragglers", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0", PGX_ALIGN_ITER_LIMIT="150"), "small"),   # most candidates outlast
                                                                                     # 150 iterations: handed on to k_align1_list, a wavefront each
@@ -856,12 +856,12 @@ ALIGN_VARIANTS = [   # (id, environment, read set): every form dev_align dispatc
     ("ph8-packed-nw1", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0", PGX_ALIGN_NW="1", PGX_ALIGN_SEG="8"), "small"),   # rounds 2-5's form: a wavefront per workgroup
     ("ph8-packed-file-order", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0", PGX_ALIGN_ORDER_MIN="0"), "small3"),   # a database that never saw an overlap stage:
                                                                                     # packs in the order of the seqdb file, no order list
-    ("ph8-bytes", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="-1"), "small2"),  # k_align_ph<8, u16> on the seqdb bytes (a database without packs)
+    ("ph8-bytes", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="-1"), "small2"),  # k_align_ph<u16> on the seqdb bytes (a database without packs)
     ("one-per-wave", dict(PGX_ALIGN_SMALL="1000000000"), "small"),                  # k_align1 on a LARGE launch (round 6: from the 2-bit packs -- this database has them by now)
     ("one-per-wave-bytes", dict(PGX_ALIGN_SMALL="1000000000", PGX_ALIGN1_PACKED="0"), "small"),   # ... on the seqdb bytes
     ("one-per-wave-ambiguous", dict(PGX_ALIGN_SMALL="1000000000"), "withN"),         # a database with reads that have no 2-bit codes: bytes
     ("ph8-packed-stragglers-bytes", dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0", PGX_ALIGN_ITER_LIMIT="150", PGX_ALIGN1_PACKED="0"), "small"),   # k_align1_list on the bytes
-    ("long-reads-int32", dict(PGX_ALIGN_SMALL="0"), "long"),                        # a 100 kb read in the set: k_align4<8, int32>
+    ("long-reads-int32", dict(PGX_ALIGN_SMALL="0"), "long"),                        # a 100 kb read in the set: k_align_ph<int32> on the bytes
 ]
 
 
@@ -910,7 +910,7 @@ def test_align_variants_vs_oracle(variant_sets, vid, env, which):
 
 
 @pytest.mark.parametrize("env,which", [(dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0"), "small"), (dict(PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0"), "withN"),
-                                       (dict(PGX_ALIGN_SMALL="0"), "long")], ids=["ph8", "ph8-ambiguous", "align4"])
+                                       (dict(PGX_ALIGN_SMALL="0"), "long")], ids=["ph8", "ph8-ambiguous", "long-reads-int32"])
 def test_grouped_alignment_launches_of_every_size(variant_sets, env, which):
     """The grouped kernels take the work counter in chunks of 8 per wavefront (round 4: the per-candidate add on one address was their
     floor): launches smaller than a chunk, one past a chunk, around a wavefront's 8 groups and around 64, each candidate exactly once."""
@@ -1059,7 +1059,10 @@ def test_index_and_overlap_from_the_packs_and_with_the_bytes_released():
 
     def check_streams(tag):
         for env in (dict(PGX_GPU_REPLAY="1"), dict(PGX_GPU_REPLAY="1", PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="0", PGX_ALIGN_ITER_LIMIT="300"),
-                    dict(PGX_GPU_REPLAY="0"), dict(PGX_GPU_REPLAY="1", PGX_ALIGN_SMALL="1000000000")):
+                    dict(PGX_GPU_REPLAY="0"), dict(PGX_GPU_REPLAY="1", PGX_ALIGN_SMALL="1000000000"),
+                    # the knobs that ask for the bytes: the byte forms while the bytes are there, the packs once they are released
+                    dict(PGX_GPU_REPLAY="1", PGX_ALIGN_SMALL="0", PGX_ALIGN_PACKED_MIN="-1"),
+                    dict(PGX_GPU_REPLAY="1", PGX_ALIGN_SMALL="1000000000", PGX_ALIGN1_PACKED="0")):
             with _env(**env):
                 for c in (1, 3):
                     got, _ = rdb.overlap(mm, mc, total_chunk=3, mychunk=c)
