@@ -237,6 +237,23 @@ int pgx_output_finish(pgx_output *pending);
  * recs: the concatenated ovlp_t streams (cat ovlp*.dat).  The first record of every read pair wins; *text receives the
  * FALCON-style overlap lines (malloc'd, release with pgx_free), byte-identical to the reference's stdout. */
 int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, uint64_t *n_unique);
+/* The same as a STREAM, for a job's worth of records in bounded memory: the concatenation of the texts of all feeds, in feed order, is byte
+ * for byte what pgx_dedup returns for the concatenation of the fed records (the first record of every unordered read pair in stream order
+ * wins; a feed returns the lines of the pairs first seen in that feed, in the order of their records).  The seen-pair set stays in HBM for
+ * the stream's life and grows as needed -- by the pairs a feed really adds, so a stream opened with its exact number of pairs never
+ * grows (expected_pairs sizes it up front; 0: start small and grow); first-wins, the coordinate
+ * transform and the text lines are computed on the GPU.
+ *   pgx_dedup_feed     : recs is a host array
+ *   pgx_dedup_feed_dev : d_recs is a device pointer (records another runtime holds in HBM: order its stream first, pgx_stream_wait)
+ * A feed takes n < 2^31 records, the stream as a whole has no limit.  *text is malloc'd (pgx_free), NUL-terminated, *text_len == 0 for a
+ * feed that adds nothing or has n == 0.  A stream that returned an error accepts only pgx_dedup_close, which frees it (always) and
+ * reports the records fed and the lines written.  A stream left open across pgx_shutdown loses its device state and accepts only
+ * pgx_dedup_close.  PGX_DEDUP_HOST_TEXT=1 (diagnostic) prints the lines with snprintf on the host instead. */
+typedef struct pgx_dedup_stream pgx_dedup_stream;
+int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out);
+int pgx_dedup_feed(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len);
+int pgx_dedup_feed_dev(pgx_dedup_stream *s, const pgx_ovlp *d_recs, size_t n, char **text, size_t *text_len);
+int pgx_dedup_close(pgx_dedup_stream *s, uint64_t *n_records, uint64_t *n_unique);
 
 /* ---- reads -> contigs mapping (replaces shmr_map, src/shmr_map.c:48-161,163-373) ----
  * The reads' shimmer-pair map is built exactly as in the overlap stage (build_map with -t/-c/-n/-M); the reference

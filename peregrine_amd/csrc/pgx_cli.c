@@ -367,33 +367,72 @@ static int run_overlap_args(int argc, char **argv, pgx_seqdb *db, const char *se
 }
 static int main_overlap(int argc, char **argv) { return run_overlap_args(argc, argv, NULL, NULL, NULL, 0, NULL); }
 
-static int main_dedup(int argc, char **argv) {
-  (void)argc, (void)argv;
-  size_t cap = 1 << 20, n = 0;
-  char *buf = (char *)malloc(cap);
-  if (!buf) return 1;
-  for (;;) { /* the whole ovlp_t stream from stdin (cat ovlp*.dat | shmr_dedup, pg_run.py:351-352) */
-    if (n == cap) {
-      char *nb = (char *)realloc(buf, cap *= 2);
-      if (!nb) {
-        free(buf);
-        return 1;
-      }
-      buf = nb;
-    }
-    const size_t got = fread(buf + n, 1, cap - n, stdin);
+/* shmr_dedup: the ovlp_t stream from stdin (cat ovlp*.dat | shmr_dedup, pg_run.py:351-352) goes through a pgx_dedup stream in pieces of
+ * PGX_DEDUP_PIECE records (default 16 Mi = 1 GiB; a test hook).  Two piece buffers: a reader thread fills one while the GPU works on the
+ * other, and each feed's text is written as it comes back -- host memory is two pieces and about two copies of one feed's text whatever
+ * the stream's length. */
+struct dedup_reader {
+  char *buf;
+  size_t cap, got;   /* bytes; cap is a whole number of records */
+};
+static void *dedup_read_piece(void *arg) {
+  struct dedup_reader *r = (struct dedup_reader *)arg;
+  size_t n = 0;
+  while (n < r->cap) {   /* (a pipe returns short counts: only the end of the stream leaves a piece short) */
+    const size_t got = fread(r->buf + n, 1, r->cap - n, stdin);
     if (got == 0) break;
     n += got;
   }
-  if (pgx_init(device_of_env())) return fail("shmr_dedup", "pgx_init");
-  char *text = NULL;
-  size_t len = 0;
-  uint64_t nu = 0;
-  if (pgx_dedup((const pgx_ovlp *)buf, n / sizeof(pgx_ovlp), &text, &len, &nu)) return fail("shmr_dedup", "pgx_dedup");
-  fwrite(text, 1, len, stdout);
-  pgx_free(text);
-  free(buf);
-  return 0;
+  r->got = n;
+  return NULL;
+}
+static int main_dedup(int argc, char **argv) {
+  (void)argc, (void)argv;
+  size_t piece = (size_t)16 << 20;
+  const char *pe = getenv("PGX_DEDUP_PIECE");
+  if (pe && atoll(pe) > 0) piece = (size_t)atoll(pe);
+  if (piece >= ((size_t)1 << 31)) piece = ((size_t)1 << 31) - 1;
+  char *bufs[2] = {(char *)malloc(piece * sizeof(pgx_ovlp)), (char *)malloc(piece * sizeof(pgx_ovlp))};
+  if (!bufs[0] || !bufs[1]) {
+    fprintf(stderr, "shmr_dedup: out of host memory\n");
+    return 1;
+  }
+  struct dedup_reader rd = {bufs[0], piece * sizeof(pgx_ovlp), 0};
+  pthread_t th;
+  if (pthread_create(&th, NULL, dedup_read_piece, &rd)) {   /* the first piece is read while the device context comes up */
+    fprintf(stderr, "shmr_dedup: cannot start the reader thread\n");
+    free(bufs[0]), free(bufs[1]);
+    return 1;
+  }
+  pgx_dedup_stream *ds = NULL;
+  int rc = 0, open_failed = 0;
+  if (pgx_init(device_of_env())) rc = fail("shmr_dedup", "pgx_init"), open_failed = 1;
+  else if (pgx_dedup_open(0, &ds)) rc = fail("shmr_dedup", "pgx_dedup_open"), open_failed = 1;
+  for (int k = 0;; k ^= 1) {
+    pthread_join(th, NULL);
+    const size_t got = rd.got;
+    if (got < sizeof(pgx_ovlp) || open_failed) break;
+    rd.buf = bufs[k ^ 1];
+    const int more = got == rd.cap;   /* a short piece was the last one (a trailing partial record is dropped, as today) */
+    if (more && pthread_create(&th, NULL, dedup_read_piece, &rd)) {
+      fprintf(stderr, "shmr_dedup: cannot start the reader thread\n");
+      rc = 1;
+      break;
+    }
+    char *text = NULL;
+    size_t len = 0;
+    if (pgx_dedup_feed(ds, (const pgx_ovlp *)bufs[k], got / sizeof(pgx_ovlp), &text, &len)) rc = fail("shmr_dedup", "pgx_dedup_feed");
+    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("shmr_dedup: stdout");
+    pgx_free(text);
+    if (rc) {
+      if (more) pthread_join(th, NULL);
+      break;
+    }
+    if (!more) break;
+  }
+  if (ds) pgx_dedup_close(ds, NULL, NULL);
+  free(bufs[0]), free(bufs[1]);
+  return rc;
 }
 
 static int main_map(int argc, char **argv) {

@@ -4,7 +4,14 @@
 // host: text formatting only ("%09d %09d %d %0.1f %u %d %d %u %u %d %d %u %s\n", shmr_dedup.c:91-99).
 // Note: on an EMPTY stream the reference formats one record from uninitialised stack memory (its while(!feof) loop runs
 // once); this implementation writes nothing.
+//
+// The STREAMING form (pgx_dedup_open / _feed / _feed_dev / _close) takes the job's records piece by piece in bounded memory: the
+// in-batch first-wins above makes a piece's pair keys distinct, a seen-pair set that lives in HBM for the stream's life (open
+// addressing, one 64-bit word per slot) says which of them are new, and the text lines are written on the device too (k_line_len ->
+// exclusive scan -> k_format) and leave through a pinned staging buffer.
 #include <hipcub/hipcub.hpp>
+
+#include <mutex>
 
 #include "pgx_internal.h"
 
@@ -66,6 +73,214 @@ __global__ void k_rows(const pgx_ovlp *__restrict__ in, const uint32_t *__restri
   r.b_bgn = b_bgn, r.b_end = b_end, r.rlen1 = rlen1, r.type = o.ovlp_type;
   out[j] = r;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// streaming form: the seen-pair set
+// ---------------------------------------------------------------------------------------------------------
+// One 64-bit word per slot: pair key + 1, 0 = empty; `mask + 1` slots, linear probing from a 64-bit mix of the key, load <= 1/2 (the
+// host grows the table BEFORE a feed could pass it, so a probe always ends at an empty slot).  The one key whose word would be 0 --
+// both read ids 2^32 - 1 -- has a word of its own behind the table (tab[mask + 1]).
+// Returns true when the key was absent (and is now present).  A feed's candidates are distinct, so no two lanes ever race for one key
+// and the answer does not depend on scheduling; they only race for SLOTS, which the compare-and-swap settles.
+__device__ inline bool seen_claim(unsigned long long *__restrict__ tab, uint64_t mask, uint64_t key) {
+  if (key == ~0ULL) return atomicExch(&tab[mask + 1], 1ULL) == 0;
+  const unsigned long long want = key + 1;
+  uint64_t s = checksum_mix(key) & mask;
+  for (;;) {
+    unsigned long long old = __atomic_load_n(&tab[s], __ATOMIC_RELAXED);
+    if (old == 0) old = atomicCAS(&tab[s], 0ULL, want);
+    if (old == 0) return true;
+    if (old == want) return false;
+    s = (s + 1) & mask;
+  }
+}
+// read-only probe: is the key in the set (no feed inserts while this runs)
+__device__ inline bool seen_has(const unsigned long long *__restrict__ tab, uint64_t mask, uint64_t key) {
+  if (key == ~0ULL) return tab[mask + 1] != 0;
+  const unsigned long long want = key + 1;
+  for (uint64_t s = checksum_mix(key) & mask;; s = (s + 1) & mask) {
+    const unsigned long long v = tab[s];
+    if (v == want) return true;
+    if (v == 0) return false;
+  }
+}
+// heads of the runs of equal keys in the sorted batch (stable sort: the head is the pair's earliest record of the batch) that the set
+// does not hold yet, and how many: EXACTLY the entries this feed adds, so the host grows the table only when it must
+__global__ void k_run_heads(const uint64_t *__restrict__ skey, uint32_t n, const unsigned long long *__restrict__ tab, uint64_t mask,
+                            uint8_t *__restrict__ head, uint32_t *__restrict__ n_new) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool h = i < n && (i == 0 || skey[i] != skey[i - 1]) && !seen_has(tab, mask, skey[i]);
+  if (i < n) head[i] = h;
+  const uint64_t b = __ballot(h);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_new, (uint32_t)__popcll(b));
+}
+// keep = run head AND the pair was not seen in an earlier feed (head[] already says so; the claim is what enters the key)
+__global__ void k_seen_insert(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ sidx, const uint8_t *__restrict__ head,
+                              uint32_t n, unsigned long long *__restrict__ tab, uint64_t mask, uint8_t *__restrict__ keep) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  keep[sidx[i]] = head[i] && seen_claim(tab, mask, skey[i]);
+}
+// every entry of the old table into the new (cleared) one
+__global__ void k_seen_rehash(const unsigned long long *__restrict__ old_tab, uint64_t old_cap, unsigned long long *__restrict__ tab,
+                              uint64_t mask) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > old_cap) return;
+  const unsigned long long v = old_tab[i];
+  if (i == old_cap) {
+    tab[mask + 1] = v;
+    return;
+  }
+  if (v) seen_claim(tab, mask, v - 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// streaming form: the text lines, "%09d %09d %d %0.1f %u %d %d %u %u %d %d %u %s\n" as glibc prints them
+// ---------------------------------------------------------------------------------------------------------
+__device__ inline uint32_t div10(uint32_t v) { return __umulhi(v, 0xCCCCCCCDu) >> 3; }
+__device__ inline uint64_t div10(uint64_t v) { return __umul64hi(v, 0xCCCCCCCCCCCCCCCDULL) >> 3; }
+__device__ inline uint32_t ndigits(uint32_t v) {
+  return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8
+         : v < 1000000000u ? 9 : 10;
+}
+// WRITE == false: only counts (k_line_len and k_format share one definition of a line)
+template <bool WRITE>
+struct LineOut {
+  char *p;
+  uint32_t n;
+  __device__ void ch(char c) {
+    if (WRITE) p[n] = c;
+    ++n;
+  }
+  __device__ void u32(uint32_t v, uint32_t min_digits = 1) {
+    const uint32_t nd = max(ndigits(v), min_digits);
+    if (WRITE)
+      for (uint32_t k = nd; k-- > 0;) {
+        const uint32_t q = div10(v);
+        p[n + k] = (char)('0' + (v - q * 10u));
+        v = q;
+      }
+    n += nd;
+  }
+  __device__ void u64(uint64_t v) {
+    uint32_t nd = 1;
+    for (uint64_t t = div10(v); t; t = div10(t)) ++nd;
+    if (WRITE)
+      for (uint32_t k = nd; k-- > 0;) {
+        const uint64_t q = div10(v);
+        p[n + k] = (char)('0' + (uint32_t)(v - q * 10u));
+        v = q;
+      }
+    n += nd;
+  }
+  __device__ void i32(int32_t v) {  // %d
+    if (v < 0) ch('-'), u32(0u - (uint32_t)v);
+    else u32((uint32_t)v);
+  }
+  __device__ void rid(int32_t v) {  // %09d: zero padding to width 9, the sign counts
+    if (v < 0) ch('-'), u32(0u - (uint32_t)v, 8);
+    else u32((uint32_t)v, 9);
+  }
+  // %0.1f of a finite double: the EXACT binary value M * 2^e rounded to one decimal, ties to even, in integer arithmetic
+  __device__ void f1(double x) {
+    const uint64_t bits = (uint64_t)__double_as_longlong(x);
+    if (bits >> 63) ch('-');  // also for a value that rounds to 0.0: "-0.0"
+    const uint32_t ex = (uint32_t)(bits >> 52) & 0x7FFu;
+    uint64_t M = bits & ((1ULL << 52) - 1);
+    int e = -1074;
+    if (ex) M |= 1ULL << 52, e = (int)ex - 1075;
+    const uint64_t m10 = M * 10u;  // < 2^57; tenths = m10 * 2^e
+    uint64_t t;
+    if (e >= 0) {
+      t = m10 << min(e, 6);  // (not reached: |err_est| < 2^38, so e <= -15)
+    } else if (-e >= 58) {
+      t = 0;  // m10 < 2^57 <= half a unit
+    } else {
+      const int s = -e;
+      t = m10 >> s;
+      const uint64_t rem = m10 & ((1ULL << s) - 1), half = 1ULL << (s - 1);
+      if (rem > half || (rem == half && (t & 1))) ++t;
+    }
+    const uint64_t whole = div10(t);
+    u64(whole);
+    ch('.');
+    ch((char)('0' + (uint32_t)(t - whole * 10u)));
+  }
+};
+// the three IEEE double operations of shmr_dedup.c:89-90 in that order, never contracted
+__device__ inline double err_est_of(int32_t dist, int32_t m_size) {
+#pragma clang fp contract(off)
+  const double p = 100.0 * (double)dist;
+  const double q = p / (double)m_size;
+  return 100.0 - q;
+}
+constexpr uint32_t FMT_MAXLINE = 148;  // longest line: 11 + 11 + 11 + 15 + 1 + 11 + 11 + 10 + 10 + 11 + 11 + 10 + 9 + 12 blanks + '\n' = 145
+template <bool WRITE>
+__device__ inline uint32_t format_row(const Row &r, char *dst) {  // m_size != 0
+  LineOut<WRITE> o{dst, 0};
+  o.rid((int32_t)r.rid0), o.ch(' ');
+  o.rid((int32_t)r.rid1), o.ch(' ');
+  o.i32((int32_t)(0u - (uint32_t)r.m_size)), o.ch(' ');
+  o.f1(err_est_of(r.dist, r.m_size)), o.ch(' ');
+  o.ch('0'), o.ch(' ');
+  o.i32((int32_t)r.a_bgn), o.ch(' ');
+  o.i32((int32_t)r.a_end), o.ch(' ');
+  o.u32(r.rlen0), o.ch(' ');
+  o.u32(r.strand), o.ch(' ');
+  o.i32((int32_t)r.b_bgn), o.ch(' ');
+  o.i32((int32_t)r.b_end), o.ch(' ');
+  o.u32(r.rlen1), o.ch(' ');
+  o.ch(r.type == 0 ? 'o' : 'c'), o.ch(r.type == 0 ? 'v' : 'o'), o.ch(r.type == 0 ? 'e' : 'n'), o.ch(r.type == 0 ? 'r' : 't');   // overlap / contains / contained
+  o.ch(r.type == 0 ? 'l' : 'a'), o.ch(r.type == 0 ? 'a' : 'i'), o.ch(r.type == 0 ? 'p' : 'n');
+  if (r.type != 0) o.ch(r.type == 1 ? 's' : 'e');
+  if (r.type > 1) o.ch('d');
+  o.ch('\n');
+  return o.n;
+}
+// len[j] = bytes of row j's line, len[m] = 0 (so that the exclusive scan's last entry is the total).  Rows with m_size == 0 get no
+// bytes here: their quotient is infinite or NaN, whose printed sign is the host FPU's -- the host formats and splices those in.
+__global__ void k_line_len(const Row *__restrict__ rows, uint32_t m, uint64_t *__restrict__ len, uint32_t *__restrict__ n_special) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > m) return;
+  uint32_t l = 0;
+  if (j < m) {
+    const Row r = rows[j];
+    if (r.m_size != 0) l = format_row<false>(r, nullptr);
+    else atomicAdd(n_special, 1u);
+  }
+  len[j] = l;
+}
+// A workgroup formats a tile of rows into LDS at the offsets the scan gives (a lane per row), then streams the tile out with 16-byte
+// stores.  The tile sits in LDS at the global address's offset within 16 bytes, so the aligned chunks line up on both sides; the head
+// and tail bytes that share a chunk with the neighbouring tiles go out byte by byte.
+constexpr uint32_t FMT_TILE = 256;
+__global__ __launch_bounds__(FMT_TILE) void k_format(const Row *__restrict__ rows, const uint64_t *__restrict__ off, uint32_t m,
+                                                     char *__restrict__ text) {
+  __shared__ __attribute__((aligned(16))) char tile[FMT_TILE * FMT_MAXLINE + 16];
+  const uint32_t j0 = blockIdx.x * FMT_TILE, j = j0 + threadIdx.x, j1 = min(m, j0 + FMT_TILE);
+  const uint64_t base = off[j0], end = off[j1];
+  const uint32_t pad = (uint32_t)((uintptr_t)(text + base) & 15u);
+  if (j < m) {
+    const Row r = rows[j];
+    if (r.m_size != 0) format_row<true>(r, tile + pad + (uint32_t)(off[j] - base));
+  }
+  __syncthreads();
+  char *g = text + base - pad;  // 16-byte aligned; g[k] <-> tile[k] for k in [lo, hi)
+  const uint32_t lo = pad, hi = pad + (uint32_t)(end - base);
+  const uint32_t body_lo = min(hi, (lo + 15u) & ~15u), body_hi = max(body_lo, hi & ~15u);
+  for (uint32_t k = lo + threadIdx.x; k < body_lo; k += FMT_TILE) g[k] = tile[k];
+  for (uint32_t k = body_lo + threadIdx.x * 16u; k < body_hi; k += FMT_TILE * 16u)
+    *reinterpret_cast<uint4 *>(g + k) = *reinterpret_cast<const uint4 *>(tile + k);
+  for (uint32_t k = body_hi + threadIdx.x; k < hi; k += FMT_TILE) g[k] = tile[k];
+}
+
+// one line on the host (what pgx_dedup prints, PGX_DEDUP_HOST_TEXT=1, and the rows with m_size == 0)
+static int host_line(const Row &r, char *line, size_t cap) {
+  const double err_est = 100.0 - 100.0 * (double)r.dist / (double)r.m_size;
+  return snprintf(line, cap, "%09d %09d %d %0.1f %u %d %d %u %u %d %d %u %s\n", (int)r.rid0, (int)r.rid1, -r.m_size, err_est, 0u,
+                  (int)r.a_bgn, (int)r.a_end, r.rlen0, r.strand, (int)r.b_bgn, (int)r.b_end, r.rlen1,
+                  r.type == 0 ? "overlap" : (r.type == 1 ? "contains" : "contained"));
+}
 }  // namespace
 }  // namespace pgx
 
@@ -109,13 +324,7 @@ extern "C" int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *te
       pgx::sync();
       out.reserve(m * 96);
       char line[256];
-      for (const Row &r : rows) {
-        const double err_est = 100.0 - 100.0 * (double)r.dist / (double)r.m_size;
-        const int len = snprintf(line, sizeof(line), "%09d %09d %d %0.1f %u %d %d %u %u %d %d %u %s\n", (int)r.rid0, (int)r.rid1,
-                                 -r.m_size, err_est, 0u, (int)r.a_bgn, (int)r.a_end, r.rlen0, r.strand, (int)r.b_bgn,
-                                 (int)r.b_end, r.rlen1, r.type == 0 ? "overlap" : (r.type == 1 ? "contains" : "contained"));
-        out.append(line, (size_t)len);
-      }
+      for (const Row &r : rows) out.append(line, (size_t)host_line(r, line, sizeof(line)));
     }
     *text = (char *)malloc(out.size() + 1);
     memcpy(*text, out.data(), out.size());
@@ -129,5 +338,285 @@ extern "C" int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *te
     set_error("out of host memory");
     return PGX_ENOMEM;
   }
+  return PGX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the streaming entry points
+// ---------------------------------------------------------------------------------------------------------
+struct pgx_dedup_stream {
+  DevBuf<unsigned long long> tab;   // the seen-pair set: cap slots + the word of the all-ones key; owned by the stream (MemTag "dedup")
+  uint64_t cap = 0;
+  uint64_t n_records = 0, n_unique = 0;
+  bool failed = false;              // an entry point returned an error: only pgx_dedup_close is accepted
+  bool shut = false;                // pgx_shutdown ran while the stream was open: its device state is gone
+  char *pin[2] = {nullptr, nullptr};   // text staging (pinned), made at the first feed that has text
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+namespace pgx {
+namespace {
+constexpr uint64_t SEEN_MIN_CAP = 1ULL << 16;
+constexpr size_t PIN_BYTES = (size_t)8 << 20;
+std::mutex g_streams_mu;
+std::vector<pgx_dedup_stream *> g_streams;   // the open ones
+
+void stream_drop_device_state(pgx_dedup_stream *s) {
+  s->tab.release();
+  for (int k = 0; k < 2; ++k) {
+    if (s->pin[k]) (void)hipHostFree(s->pin[k]);
+    if (s->ev[k]) (void)hipEventDestroy(s->ev[k]);
+    s->pin[k] = nullptr, s->ev[k] = nullptr;
+  }
+}
+ShutdownHook g_streams_hook([] {
+  std::lock_guard<std::mutex> lk(g_streams_mu);
+  for (pgx_dedup_stream *s : g_streams) stream_drop_device_state(s), s->shut = true;
+});
+
+void seen_alloc(DevBuf<unsigned long long> &tab, uint64_t cap) {
+  MemTag tag("dedup");
+  try {
+    tab.alloc(cap + 1);
+  } catch (const Fail &) {
+    (void)hipGetLastError();
+    set_error("pgx_dedup: no device memory for a pair set of %llu slots", (unsigned long long)cap);
+    throw Fail{PGX_ENOMEM};
+  }
+  PGX_HIP(hipMemsetAsync(tab.p, 0, (cap + 1) * sizeof(unsigned long long), ctx().stream));
+}
+// room for `more` new pairs at load <= 1/2
+void seen_reserve(pgx_dedup_stream *s, uint64_t more) {
+  uint64_t cap = s->cap;
+  while ((s->n_unique + more) * 2 > cap) cap *= 2;
+  if (cap == s->cap) return;
+  DevBuf<unsigned long long> bigger;
+  seen_alloc(bigger, cap);
+  hipLaunchKernelGGL(k_seen_rehash, dim3(cdiv(s->cap + 1, 256)), dim3(256), 0, ctx().stream, s->tab.p, s->cap, bigger.p, cap - 1);
+  PGX_HIP(hipGetLastError());
+  s->tab = std::move(bigger);   // (the old table goes back to the block cache: one stream, so its next user comes after the rehash)
+  s->cap = cap;
+}
+
+// `total` bytes of device text to host memory through the two pinned buffers: the copy of one piece runs while the host moves the last
+void text_download(pgx_dedup_stream *s, const char *d_text, size_t total, char *dst) {
+  hipStream_t st = ctx().stream;
+  for (int k = 0; k < 2; ++k)
+    if (!s->pin[k]) {
+      PGX_HIP(hipHostMalloc((void **)&s->pin[k], PIN_BYTES, hipHostMallocDefault));
+      PGX_HIP(hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming));
+    }
+  const size_t np = (total + PIN_BYTES - 1) / PIN_BYTES;
+  for (size_t i = 0; i <= np; ++i) {
+    if (i < np) {
+      PGX_HIP(hipMemcpyAsync(s->pin[i & 1], d_text + i * PIN_BYTES, std::min(PIN_BYTES, total - i * PIN_BYTES), hipMemcpyDeviceToHost, st));
+      PGX_HIP(hipEventRecord(s->ev[i & 1], st));
+    }
+    if (i > 0) {
+      const size_t j = i - 1;
+      PGX_HIP(hipEventSynchronize(s->ev[j & 1]));
+      memcpy(dst + j * PIN_BYTES, s->pin[j & 1], std::min(PIN_BYTES, total - j * PIN_BYTES));
+    }
+  }
+}
+
+char *empty_text() {
+  char *t = (char *)malloc(1);
+  if (!t) throw std::bad_alloc();
+  t[0] = 0;
+  return t;
+}
+
+// one feed over records that are on the device
+void feed_device(pgx_dedup_stream *s, const pgx_ovlp *d_in, size_t n, char **text, size_t *text_len) {
+  static const bool host_text = getenv("PGX_DEDUP_HOST_TEXT") && atoi(getenv("PGX_DEDUP_HOST_TEXT")) != 0;   // diagnostic (=1): the lines by snprintf on the host
+  hipStream_t st = ctx().stream;
+  KernelTimer tm("dedup", n);
+  uint64_t *key = ws<uint64_t>("dd.key", n), *skey = ws<uint64_t>("dd.skey", n);
+  uint32_t *idx = ws<uint32_t>("dd.idx", n), *sidx = ws<uint32_t>("dd.sidx", n), *sel = ws<uint32_t>("dd.sel", n);
+  uint8_t *keep = ws<uint8_t>("dd.keep", n), *head = ws<uint8_t>("dd.head", n);
+  uint32_t *d_m = ws<uint32_t>("dd.m", 2);   // [0]: a count; [1]: rows the host formats
+  PGX_HIP(hipMemsetAsync(d_m, 0, 2 * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_pair_keys, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, (uint32_t)n, key, idx);
+  size_t bytes = 0;
+  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
+  void *tmp = ws_raw("dd.tmp", bytes);
+  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
+  hipLaunchKernelGGL(k_run_heads, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, (uint32_t)n, s->tab.p, s->cap - 1, head, d_m);
+  uint32_t n_new = 0;
+  PGX_HIP(hipMemcpyAsync(&n_new, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  seen_reserve(s, n_new);
+  hipLaunchKernelGGL(k_seen_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, sidx, head, (uint32_t)n, s->tab.p, s->cap - 1, keep);
+  bytes = 0;
+  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> it(0);
+  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, it, keep, sel, d_m, (int)n, st));
+  tmp = ws_raw("dd.tmp", bytes);
+  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, it, keep, sel, d_m, (int)n, st));
+  uint32_t m = 0;
+  PGX_HIP(hipMemcpyAsync(&m, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  s->n_records += n, s->n_unique += m;   // (the set holds them from here on, whatever happens to the text)
+  if (m == 0) {
+    *text = empty_text(), *text_len = 0;
+    return;
+  }
+  Row *d_rows = ws<Row>("dd.rows", m);
+  hipLaunchKernelGGL(k_rows, dim3(cdiv(m, 256)), dim3(256), 0, st, d_in, sel, m, d_rows);
+  char line[256];
+  if (host_text) {
+    std::vector<Row> rows(m);
+    PGX_HIP(hipMemcpyAsync(rows.data(), d_rows, (size_t)m * sizeof(Row), hipMemcpyDeviceToHost, st));
+    pgx::sync();
+    std::string out;
+    out.reserve((size_t)m * 96);
+    for (const Row &r : rows) out.append(line, (size_t)host_line(r, line, sizeof(line)));
+    char *t = (char *)malloc(out.size() + 1);
+    if (!t) throw std::bad_alloc();
+    memcpy(t, out.data(), out.size());
+    t[out.size()] = 0;
+    *text = t, *text_len = out.size();
+    return;
+  }
+  uint64_t *d_off = ws<uint64_t>("dd.off", (size_t)m + 1);
+  {
+    uint64_t *d_len = ws<uint64_t>("dd.len", (size_t)m + 1);
+    hipLaunchKernelGGL(k_line_len, dim3(cdiv((size_t)m + 1, 256)), dim3(256), 0, st, d_rows, m, d_len, d_m + 1);
+    bytes = 0;
+    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_len, d_off, (int)(m + 1), st));
+    tmp = ws_raw("dd.tmp", bytes);
+    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_len, d_off, (int)(m + 1), st));
+  }
+  uint64_t total = 0;
+  uint32_t n_special = 0;
+  PGX_HIP(hipMemcpyAsync(&total, d_off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  PGX_HIP(hipMemcpyAsync(&n_special, d_m + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  char *d_text = ws<char>("dd.text", total);
+  hipLaunchKernelGGL(k_format, dim3(cdiv(m, FMT_TILE)), dim3(FMT_TILE), 0, st, d_rows, d_off, m, d_text);
+  PGX_HIP(hipGetLastError());
+  if (n_special == 0) {
+    char *t = (char *)malloc(total + 1);
+    if (!t) throw std::bad_alloc();
+    *text = t;   // (the caller's from here: released by its pgx_free also when the download fails)
+    t[total] = 0, *text_len = total;
+    text_download(s, d_text, total, t);
+    return;
+  }
+  // rows with m_size == 0 (no real overlap record has one): the host's snprintf prints them, spliced in at their place
+  std::vector<Row> rows(m);
+  std::vector<uint64_t> off((size_t)m + 1);
+  std::vector<char> dev_text(total);
+  PGX_HIP(hipMemcpyAsync(rows.data(), d_rows, (size_t)m * sizeof(Row), hipMemcpyDeviceToHost, st));
+  PGX_HIP(hipMemcpyAsync(off.data(), d_off, ((size_t)m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  text_download(s, d_text, total, dev_text.data());
+  pgx::sync();
+  std::string out;
+  out.reserve(total + (size_t)n_special * 64);
+  uint64_t done = 0;
+  for (uint32_t j = 0; j < m; ++j) {
+    if (rows[j].m_size != 0) continue;
+    if (off[j] > done) out.append(dev_text.data() + done, off[j] - done);
+    done = off[j];
+    out.append(line, (size_t)host_line(rows[j], line, sizeof(line)));
+  }
+  if (total > done) out.append(dev_text.data() + done, total - done);
+  char *t = (char *)malloc(out.size() + 1);
+  if (!t) throw std::bad_alloc();
+  memcpy(t, out.data(), out.size());
+  t[out.size()] = 0;
+  *text = t, *text_len = out.size();
+}
+
+// (*text was cleared before anything could throw: what it holds now is this call's own allocation)
+void feed_failed(pgx_dedup_stream *s, char **text, size_t *text_len) {
+  if (s) s->failed = true;
+  if (text && *text) free(*text), *text = nullptr;
+  if (text_len) *text_len = 0;
+}
+int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, bool on_device, const char *who) {
+  if (text) *text = nullptr;   // the outputs first: the caller's variables may hold anything, and the error paths free only what
+  if (text_len) *text_len = 0;  // this call put there
+  try {
+    PGX_REQUIRE(s && text && text_len && (n == 0 || recs), PGX_EARG, "%s: null argument", who);
+    PGX_REQUIRE(!s->shut, PGX_ESTATE, "%s: pgx_shutdown ran while the stream was open (close it)", who);
+    PGX_REQUIRE(!s->failed, PGX_ESTATE, "%s: the stream returned an error before (close it)", who);
+    require_ready();
+    PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many records for one feed");
+    if (n == 0) {
+      *text = empty_text();
+      return PGX_OK;
+    }
+    const pgx_ovlp *d_in = recs;
+    if (!on_device) {
+      pgx_ovlp *up = ws<pgx_ovlp>("dd.in", n);
+      PGX_HIP(hipMemcpyAsync(up, recs, n * sizeof(pgx_ovlp), hipMemcpyHostToDevice, ctx().stream));
+      d_in = up;
+    }
+    feed_device(s, d_in, n, text, text_len);
+    timing_flush();   // (synchronises: the caller's records are no longer read when the feed returns)
+  } catch (const Fail &f) {
+    feed_failed(s, text, text_len);
+    return f.code;
+  } catch (const std::bad_alloc &) {
+    feed_failed(s, text, text_len);
+    set_error("out of host memory");
+    return PGX_ENOMEM;
+  }
+  return PGX_OK;
+}
+}  // namespace
+}  // namespace pgx
+
+extern "C" int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out) {
+  pgx_dedup_stream *s = nullptr;
+  try {
+    PGX_REQUIRE(out, PGX_EARG, "pgx_dedup_open: null argument");
+    *out = nullptr;
+    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "pgx_dedup_open: no device context (pgx_init has not been called, or found no HIP device)");
+    PGX_REQUIRE(expected_pairs < (1ULL << 40), PGX_ENOMEM, "pgx_dedup_open: no device holds a set of %llu pairs", (unsigned long long)expected_pairs);
+    uint64_t cap = SEEN_MIN_CAP;
+    while (cap < 2 * expected_pairs) cap *= 2;
+    s = new pgx_dedup_stream;
+    seen_alloc(s->tab, cap);
+    s->cap = cap;
+    pgx::sync();
+    std::lock_guard<std::mutex> lk(g_streams_mu);
+    g_streams.push_back(s);
+    *out = s;
+  } catch (const Fail &f) {
+    delete s;
+    return f.code;
+  } catch (const std::bad_alloc &) {
+    delete s;
+    set_error("out of host memory");
+    return PGX_ENOMEM;
+  }
+  return PGX_OK;
+}
+
+extern "C" int pgx_dedup_feed(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len) {
+  return feed_any(s, recs, n, text, text_len, false, "pgx_dedup_feed");
+}
+
+extern "C" int pgx_dedup_feed_dev(pgx_dedup_stream *s, const pgx_ovlp *d_recs, size_t n, char **text, size_t *text_len) {
+  return feed_any(s, d_recs, n, text, text_len, true, "pgx_dedup_feed_dev");
+}
+
+extern "C" int pgx_dedup_close(pgx_dedup_stream *s, uint64_t *n_records, uint64_t *n_unique) {
+  if (!s) {
+    set_error("pgx_dedup_close: null argument");
+    return PGX_EARG;
+  }
+  if (n_records) *n_records = s->n_records;
+  if (n_unique) *n_unique = s->n_unique;
+  {
+    std::lock_guard<std::mutex> lk(g_streams_mu);
+    for (size_t i = 0; i < g_streams.size(); ++i)
+      if (g_streams[i] == s) g_streams.erase(g_streams.begin() + i), i = g_streams.size();
+    if (!s->shut && ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+    stream_drop_device_state(s);
+  }
+  delete s;
   return PGX_OK;
 }

@@ -253,21 +253,96 @@ def shmr_mkseqdb(seq_dataset_path: str = "seq_dataset.lst", seqdb_prefix: str = 
     return dict(reads=int(nr.value), bases=int(nb.value))
 
 
+def dedup_piece_records() -> int:
+    """records per feed of the file-level dedup (PGX_DEDUP_PIECE, a test hook; default 16 Mi records = 1 GiB)"""
+    import os
+    return min(max(int(os.environ.get("PGX_DEDUP_PIECE", 0)) or (16 << 20), 1), (1 << 31) - 1)
+
+
+class DedupStream:
+    """shmr_dedup as a stream (pgx_dedup_open / _feed / _close): feed the job's ovlp_t records piece by piece, in bounded memory;
+    every feed returns the text lines of the read pairs first seen in it, and the concatenation of the texts is the text of the
+    one-shot call on the concatenated records.  expected_pairs sizes the seen-pair set up front (0: it grows as needed)."""
+
+    def __init__(self, expected_pairs: int = 0, device=None):
+        _lib.init(device)
+        self._lib = _lib.load()
+        self.h = C.c_void_p()
+        _lib.check(self._lib.pgx_dedup_open(int(expected_pairs), C.byref(self.h)), "pgx_dedup_open")
+
+    def _feed(self, fn, name, ptr, n) -> bytes:
+        if not self.h:
+            raise _lib.PgxError(f"{name}: the stream is closed")
+        text, tl = C.c_void_p(), C.c_size_t(0)
+        _lib.check(fn(self.h, ptr, int(n), C.byref(text), C.byref(tl)), name)
+        data = C.string_at(text.value, tl.value)
+        self._lib.pgx_free(text)
+        return data
+
+    def feed(self, records: np.ndarray) -> bytes:
+        """records: ovlp_t records on the host (OVLP_DTYPE)"""
+        recs = np.ascontiguousarray(records, OVLP_DTYPE)
+        return self._feed(self._lib.pgx_dedup_feed, "pgx_dedup_feed", _ptr(recs), len(recs))
+
+    def feed_dev(self, d_ptr: int, n: int) -> bytes:
+        """n ovlp_t records at device pointer d_ptr (e.g. tensor.data_ptr()); what torch's current stream enqueued comes first"""
+        import sys
+        if "torch" in sys.modules:
+            _lib.stream_wait()
+        return self._feed(self._lib.pgx_dedup_feed_dev, "pgx_dedup_feed_dev", C.c_void_p(int(d_ptr)), n)
+
+    def close(self):
+        """frees the stream; returns (records fed, lines written)"""
+        if not self.h:
+            raise _lib.PgxError("pgx_dedup_close: the stream is closed")
+        nr, nu = C.c_uint64(0), C.c_uint64(0)
+        h, self.h = self.h, C.c_void_p()
+        _lib.check(self._lib.pgx_dedup_close(h, C.byref(nr), C.byref(nu)), "pgx_dedup_close")
+        return int(nr.value), int(nu.value)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.h:
+            self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.close()
+        except Exception:
+            pass
+
+
 def shmr_dedup(ovlp_paths, out_path: str | None = None, device=None):
-    """cat ovlp*.dat | shmr_dedup > preads.ovl (pg_run.py:351-352): returns the text (bytes) and the number of unique pairs."""
+    """cat ovlp*.dat | shmr_dedup > preads.ovl (pg_run.py:351-352): returns the text (bytes) and the number of unique pairs.
+    The files go through a DedupStream piece by piece; with out_path the text is written as it comes."""
     _lib.init(device)
     if isinstance(ovlp_paths, (str, bytes)):
         ovlp_paths = [ovlp_paths]
-    recs = np.concatenate([np.fromfile(p, dtype=OVLP_DTYPE) for p in ovlp_paths]) if ovlp_paths else np.zeros(0, OVLP_DTYPE)
-    recs = np.ascontiguousarray(recs)
-    text, tl, nu = C.c_void_p(), C.c_size_t(0), C.c_uint64(0)
-    _lib.check(_lib.load().pgx_dedup(_ptr(recs), len(recs), C.byref(text), C.byref(tl), C.byref(nu)), "pgx_dedup")
-    data = C.string_at(text.value, tl.value)
-    _lib.load().pgx_free(text)
-    if out_path:
-        with open(out_path, "wb") as f:
-            f.write(data)
-    return data, int(nu.value)
+    piece = dedup_piece_records()
+    parts = []
+    out = open(out_path, "wb") if out_path else None
+    try:
+        with DedupStream(device=device) as ds:
+            for p in ovlp_paths:
+                with open(p, "rb") as f:
+                    while True:
+                        recs = np.fromfile(f, dtype=OVLP_DTYPE, count=piece)
+                        if len(recs):
+                            text = ds.feed(recs)
+                            parts.append(text)
+                            if out:
+                                out.write(text)
+                        if len(recs) < piece:
+                            break
+            _, nu = ds.close()
+    finally:
+        if out:
+            out.close()
+    return b"".join(parts), nu
 
 
 def shmr_map(ref_shimmer_prefix: str = "ref-L2", seqdb_prefix: str = "seq_dataset", shimmer_prefix: str = "shimmer-L2",
