@@ -379,16 +379,16 @@ typedef struct {
 
 /* test hook (orc_pair_records): every insertion of build_map in the order it happens */
 typedef struct { size_t n, cap; orc_pair_rec_t *a; } recv_t;
-static recv_t *g_record_sink = NULL;
+static recv_t *g_pair_sink = NULL;
 
 static void pairmap_add(pairmap_t *pm, uint64_t k0, uint64_t k1, prec_t r) {
   int absent;
-  if (g_record_sink) {
+  if (g_pair_sink) {
     orc_pair_rec_t e;
     memset(&e, 0, sizeof(e));
     e.key0 = k0, e.key1 = k1, e.y0 = r.y0, e.dir = r.dir;
     e.npos = ~(uint32_t)((r.y0 & 0xFFFFFFFFu) >> 1);
-    VEC_PUSH(g_record_sink, orc_pair_rec_t, e);
+    VEC_PUSH(g_pair_sink, orc_pair_rec_t, e);
   }
   uint32_t s = otab_put(&pm->outer, k0, &absent);
   if (absent) {
@@ -543,9 +543,9 @@ orc_pair_rec_t *orc_pair_records(const orc_mm_t *mmers, size_t n_mm, const orc_m
     uint32_t s = otab_put(&mc, counts[i].mer, &absent);
     mc.vals[s] += counts[i].count;
   }
-  g_record_sink = &sink;
+  g_pair_sink = &sink;
   build_pairmap(&pm, mmers, n_mm, &mc, rlen, mychunk, total_chunk, mc_lower, mc_upper);
-  g_record_sink = NULL;
+  g_pair_sink = NULL;
   *n_out = sink.n;
   return sink.a ? sink.a : (orc_pair_rec_t *)malloc(1);
 }

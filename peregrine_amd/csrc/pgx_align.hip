@@ -695,7 +695,7 @@ void launch_on(const SeqSource &s, K on_packs, K on_bytes, dim3 grid, dim3 block
   hipLaunchKernelGGL(s.packed ? on_packs : on_bytes, grid, block, lds, ctx().stream, s.seq, s.off, args...);
 }
 
-// The 2-bit packs ahead of the first large launch: run_overlap calls this while the GPU would otherwise wait for the host's outer
+// The 2-bit packs ahead of the first large launch: the overlap stage's visit phase calls this while the GPU would otherwise wait for the host's outer
 // table, so the first stage's k_pack2 (1.6 ms at 4.5 Gbases) is off the critical path; later stages find the packs in place
 // (pgx_pack.hip: they are kept with the database).  (As a grouped launch of any size would.)
 void dev_align_prepare(const pgx_seqdb *db) { (void)align_source(db, LONG_MAX); }

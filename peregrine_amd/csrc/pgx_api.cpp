@@ -521,16 +521,6 @@ bool read_file(const std::string &path, std::vector<uint8_t> &out) {
 
 using namespace pgx;
 
-#define PGX_GUARD_BEGIN try {
-#define PGX_GUARD_END                          \
-  }                                            \
-  catch (const pgx::Fail &f) { return f.code; } \
-  catch (const std::bad_alloc &) {             \
-    pgx::set_error("out of host memory");      \
-    return PGX_ENOMEM;                         \
-  }                                            \
-  return PGX_OK;
-
 extern "C" {
 
 const char *pgx_last_error(void) { return pgx::g_err.c_str(); }
@@ -548,12 +538,7 @@ int pgx_results_async(int on) {
   return was;
 }
 int pgx_results_wait(void) {
-  try {
-    pgx::results_wait();
-  } catch (const pgx::Fail &f) {
-    return f.code;
-  }
-  return PGX_OK;
+  return guarded([] { pgx::results_wait(); });
 }
 
 int pgx_device_count(void) {
@@ -566,26 +551,27 @@ static double wall_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 int pgx_init(int device) {
-  PGX_GUARD_BEGIN
-  Context &c = ctx();
-  if (c.ready && c.device == device) return PGX_OK;
-  const double t_init = wall_ms();
-  // one context per process: workspaces, the block cache and every resident seqdb live on the device of the first call
-  PGX_REQUIRE(!c.ready, PGX_ESTATE, "pgx_init(%d): this process already runs on device %d (call pgx_shutdown first)", device, c.device);
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  PGX_REQUIRE(e == hipSuccess && n > 0, PGX_EHIP, "no HIP device visible (%s)", hipGetErrorString(e));
-  PGX_REQUIRE(device >= 0 && device < n, PGX_EARG, "device %d out of range (have %d)", device, n);
-  PGX_HIP(hipSetDevice(device));
-  if (c.stream) (void)hipStreamDestroy(c.stream);
-  PGX_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-  hipDeviceProp_t prop;
-  PGX_HIP(hipGetDeviceProperties(&prop, device));
-  c.num_cu = prop.multiProcessorCount;
-  c.device = device;
-  c.ready = true;
-  if (getenv("PGX_TRACE")) fprintf(stderr, "[pgx] init: device %d (HIP runtime + context + stream) in %.1f ms\n", device, wall_ms() - t_init);
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    Context &c = ctx();
+    if (c.ready && c.device == device) return PGX_OK;
+    const double t_init = wall_ms();
+    // one context per process: workspaces, the block cache and every resident seqdb live on the device of the first call
+    PGX_REQUIRE(!c.ready, PGX_ESTATE, "pgx_init(%d): this process already runs on device %d (call pgx_shutdown first)", device, c.device);
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    PGX_REQUIRE(e == hipSuccess && n > 0, PGX_EHIP, "no HIP device visible (%s)", hipGetErrorString(e));
+    PGX_REQUIRE(device >= 0 && device < n, PGX_EARG, "device %d out of range (have %d)", device, n);
+    PGX_HIP(hipSetDevice(device));
+    if (c.stream) (void)hipStreamDestroy(c.stream);
+    PGX_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    hipDeviceProp_t prop;
+    PGX_HIP(hipGetDeviceProperties(&prop, device));
+    c.num_cu = prop.multiProcessorCount;
+    c.device = device;
+    c.ready = true;
+    if (getenv("PGX_TRACE")) fprintf(stderr, "[pgx] init: device %d (HIP runtime + context + stream) in %.1f ms\n", device, wall_ms() - t_init);
+    return PGX_OK;
+  });
 }
 
 void pgx_shutdown(void) {
@@ -775,51 +761,52 @@ static void upload_file_pieces(const char *path, uint8_t *d_dst, size_t nbytes) 
 static int seqdb_upload_impl(const uint8_t *seqdb, size_t nbytes, const uint32_t *rid, const uint32_t *rlen,
                              const uint64_t *roff, uint32_t nreads, pgx_seqdb **out, bool from_device, const char *file = nullptr,
                              bool adopt = false) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE(out && (nreads == 0 || (rid && rlen && roff)), PGX_EARG, "pgx_seqdb_upload: null argument");
-  auto *db = new pgx_seqdb();
-  db->rid.assign(rid, rid + nreads);
-  db->rlen.assign(rlen, rlen + nreads);
-  db->roff.assign(roff, roff + nreads);
-  uint32_t max_rid = 0;
-  for (uint32_t i = 0; i < nreads; ++i) {
-    max_rid = std::max(max_rid, rid[i]);
-    db->bases += rlen[i];
-    if ((size_t)roff[i] + rlen[i] > nbytes) {
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(out && (nreads == 0 || (rid && rlen && roff)), PGX_EARG, "pgx_seqdb_upload: null argument");
+    auto *db = new pgx_seqdb();
+    db->rid.assign(rid, rid + nreads);
+    db->rlen.assign(rlen, rlen + nreads);
+    db->roff.assign(roff, roff + nreads);
+    uint32_t max_rid = 0;
+    for (uint32_t i = 0; i < nreads; ++i) {
+      max_rid = std::max(max_rid, rid[i]);
+      db->bases += rlen[i];
+      if ((size_t)roff[i] + rlen[i] > nbytes) {
+        delete db;
+        PGX_REQUIRE(false, PGX_EARG, "read %u exceeds the seqdb (%zu bytes)", rid[i], nbytes);
+      }
+    }
+    const size_t nr = nreads ? (size_t)max_rid + 1 : 0;
+    db->rlen_by_rid.assign(nr, 0);
+    db->roff_by_rid.assign(nr, 0);
+    for (uint32_t i = 0; i < nreads; ++i)
+      db->rlen_by_rid[rid[i]] = rlen[i], db->roff_by_rid[rid[i]] = roff[i], db->max_rlen = std::max(db->max_rlen, rlen[i]);
+    db->nbytes = nbytes;
+    try {
+      if (adopt) {
+        db->borrowed = true;
+        db->d_seq.p = const_cast<uint8_t *>(seqdb), db->d_seq.n = nbytes + 1024;
+      } else {
+        MemTag mem_tag("seqdb.bytes");
+        db->d_seq.alloc(nbytes + 1024);
+      }
+      PGX_HIP(hipMemsetAsync(db->d_seq.p + nbytes, 0, 1024, ctx().stream));
+      if (adopt) {
+      } else if (nbytes && file) upload_file_pieces(file, db->d_seq.p, nbytes);
+      else if (nbytes) PGX_HIP(hipMemcpyAsync(db->d_seq.p, seqdb, nbytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx().stream));
+      db->d_roff.alloc(nr ? nr : 1);
+      db->d_rlen.alloc(nr ? nr : 1);
+      db->d_roff.upload(db->roff_by_rid.data(), nr);
+      db->d_rlen.upload(db->rlen_by_rid.data(), nr);
+      pgx::sync();
+    } catch (...) {
       delete db;
-      PGX_REQUIRE(false, PGX_EARG, "read %u exceeds the seqdb (%zu bytes)", rid[i], nbytes);
+      throw;
     }
-  }
-  const size_t nr = nreads ? (size_t)max_rid + 1 : 0;
-  db->rlen_by_rid.assign(nr, 0);
-  db->roff_by_rid.assign(nr, 0);
-  for (uint32_t i = 0; i < nreads; ++i)
-    db->rlen_by_rid[rid[i]] = rlen[i], db->roff_by_rid[rid[i]] = roff[i], db->max_rlen = std::max(db->max_rlen, rlen[i]);
-  db->nbytes = nbytes;
-  try {
-    if (adopt) {
-      db->borrowed = true;
-      db->d_seq.p = const_cast<uint8_t *>(seqdb), db->d_seq.n = nbytes + 1024;
-    } else {
-      MemTag mem_tag("seqdb.bytes");
-      db->d_seq.alloc(nbytes + 1024);
-    }
-    PGX_HIP(hipMemsetAsync(db->d_seq.p + nbytes, 0, 1024, ctx().stream));
-    if (adopt) {
-    } else if (nbytes && file) upload_file_pieces(file, db->d_seq.p, nbytes);
-    else if (nbytes) PGX_HIP(hipMemcpyAsync(db->d_seq.p, seqdb, nbytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx().stream));
-    db->d_roff.alloc(nr ? nr : 1);
-    db->d_rlen.alloc(nr ? nr : 1);
-    db->d_roff.upload(db->roff_by_rid.data(), nr);
-    db->d_rlen.upload(db->rlen_by_rid.data(), nr);
-    pgx::sync();
-  } catch (...) {
-    delete db;
-    throw;
-  }
-  *out = db;
-  PGX_GUARD_END
+    *out = db;
+    return PGX_OK;
+  });
 }
 
 int pgx_seqdb_upload(const uint8_t *seqdb, size_t nbytes, const uint32_t *rid, const uint32_t *rlen,
@@ -841,46 +828,49 @@ int pgx_seqdb_adopt_dev(uint8_t *d_seqdb, size_t nbytes, size_t capacity, const 
 }
 // event hand-over between the library's stream and another runtime's
 static int stream_order(hipStream_t first, hipStream_t then) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  hipEvent_t ev;
-  PGX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev, first);
-  if (e == hipSuccess) e = hipStreamWaitEvent(then, ev, 0);
-  (void)hipEventDestroy(ev);   // (deferred by the runtime until the event has completed)
-  PGX_HIP(e);
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    hipEvent_t ev;
+    PGX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, first);
+    if (e == hipSuccess) e = hipStreamWaitEvent(then, ev, 0);
+    (void)hipEventDestroy(ev);   // (deferred by the runtime until the event has completed)
+    PGX_HIP(e);
+    return PGX_OK;
+  });
 }
 int pgx_stream_wait(void *other_stream) { return stream_order((hipStream_t)other_stream, ctx().stream); }
 int pgx_stream_signal(void *other_stream) { return stream_order(ctx().stream, (hipStream_t)other_stream); }
 int pgx_copy_dev(void *d_dst, const void *d_src, size_t nbytes) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE((d_dst && d_src) || nbytes == 0, PGX_EARG, "pgx_copy_dev: null argument");
-  if (nbytes) PGX_HIP(hipMemcpyAsync(d_dst, d_src, nbytes, hipMemcpyDeviceToDevice, ctx().stream));
-  pgx::sync();
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE((d_dst && d_src) || nbytes == 0, PGX_EARG, "pgx_copy_dev: null argument");
+    if (nbytes) PGX_HIP(hipMemcpyAsync(d_dst, d_src, nbytes, hipMemcpyDeviceToDevice, ctx().stream));
+    pgx::sync();
+    return PGX_OK;
+  });
 }
 
 int pgx_seqdb_load(const char *prefix, pgx_seqdb **out) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE(prefix && out, PGX_EARG, "pgx_seqdb_load: null argument");
-  std::vector<uint32_t> rid, rlen;
-  std::vector<uint64_t> roff;
-  std::string p(prefix);
-  const double t_load = wall_ms();
-  PGX_REQUIRE(load_idx((p + ".idx").c_str(), rid, rlen, roff) == 0, PGX_EIO, "cannot open %s.idx", prefix);
-  const double t_idx = wall_ms();
-  const std::string dbpath = p + ".seqdb";
-  struct stat sb;
-  PGX_REQUIRE(stat(dbpath.c_str(), &sb) == 0 && S_ISREG(sb.st_mode), PGX_EIO, "cannot read %s.seqdb", prefix);
-  int rc = seqdb_upload_impl(nullptr, (size_t)sb.st_size, rid.data(), rlen.data(), roff.data(), (uint32_t)rid.size(), out, false, dbpath.c_str());
-  if (rc) return rc;
-  if (getenv("PGX_TRACE"))
-    fprintf(stderr, "[pgx] seqdb load: idx file (%zu reads) %.1f ms, %.2f GB file -> HBM %.1f ms = %.1f GB/s\n", rid.size(), t_idx - t_load,
-            sb.st_size / 1e9, wall_ms() - t_idx, sb.st_size / 1e6 / (wall_ms() - t_idx));
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(prefix && out, PGX_EARG, "pgx_seqdb_load: null argument");
+    std::vector<uint32_t> rid, rlen;
+    std::vector<uint64_t> roff;
+    std::string p(prefix);
+    const double t_load = wall_ms();
+    PGX_REQUIRE(load_idx((p + ".idx").c_str(), rid, rlen, roff) == 0, PGX_EIO, "cannot open %s.idx", prefix);
+    const double t_idx = wall_ms();
+    const std::string dbpath = p + ".seqdb";
+    struct stat sb;
+    PGX_REQUIRE(stat(dbpath.c_str(), &sb) == 0 && S_ISREG(sb.st_mode), PGX_EIO, "cannot read %s.seqdb", prefix);
+    int rc = seqdb_upload_impl(nullptr, (size_t)sb.st_size, rid.data(), rlen.data(), roff.data(), (uint32_t)rid.size(), out, false, dbpath.c_str());
+    if (rc) return rc;
+    if (getenv("PGX_TRACE"))
+      fprintf(stderr, "[pgx] seqdb load: idx file (%zu reads) %.1f ms, %.2f GB file -> HBM %.1f ms = %.1f GB/s\n", rid.size(), t_idx - t_load,
+              sb.st_size / 1e9, wall_ms() - t_idx, sb.st_size / 1e6 / (wall_ms() - t_idx));
+    return PGX_OK;
+  });
 }
 
 // The byte seqdb out of HBM (round 6, VERDICT r5 task 5): once the 2-bit packs exist they carry the same information at a quarter of the
@@ -891,17 +881,18 @@ int pgx_seqdb_load(const char *prefix, pgx_seqdb **out) {
 // pgx_overlap_*, pgx_align_batch and the file-level forms over them work as before; entry points that need the bytes (other w / k, want_l0,
 // pgx_sketch_batch) fail with PGX_ESTATE.  A buffer the library adopted (pgx_seqdb_adopt_dev) is no longer referenced: the caller may free it.
 int pgx_seqdb_release_bytes(pgx_seqdb *db) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE(db, PGX_EARG, "pgx_seqdb_release_bytes: null argument");
-  if (!db->d_seq.p) return PGX_OK;   // (released already)
-  PGX_REQUIRE(db->max_rlen <= 65535u, PGX_ESTATE, "pgx_seqdb_release_bytes: a read of %u bases (> 65,535) needs the byte-wise alignment kernel: bytes kept", db->max_rlen);
-  PGX_REQUIRE(seq_packs(db) != nullptr, PGX_ESTATE, "pgx_seqdb_release_bytes: the 2-bit packs could not be built: bytes kept");
-  PGX_REQUIRE(db->n_flagged_reads == 0, PGX_ESTATE, "pgx_seqdb_release_bytes: %u reads hold an ambiguous base (no 2-bit code): bytes kept", db->n_flagged_reads);
-  pgx::sync();
-  if (db->borrowed) db->d_seq.p = nullptr, db->d_seq.n = 0;
-  else db->d_seq.release();
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(db, PGX_EARG, "pgx_seqdb_release_bytes: null argument");
+    if (!db->d_seq.p) return PGX_OK;   // (released already)
+    PGX_REQUIRE(db->max_rlen <= 65535u, PGX_ESTATE, "pgx_seqdb_release_bytes: a read of %u bases (> 65,535) needs the byte-wise alignment kernel: bytes kept", db->max_rlen);
+    PGX_REQUIRE(seq_packs(db) != nullptr, PGX_ESTATE, "pgx_seqdb_release_bytes: the 2-bit packs could not be built: bytes kept");
+    PGX_REQUIRE(db->n_flagged_reads == 0, PGX_ESTATE, "pgx_seqdb_release_bytes: %u reads hold an ambiguous base (no 2-bit code): bytes kept", db->n_flagged_reads);
+    pgx::sync();
+    if (db->borrowed) db->d_seq.p = nullptr, db->d_seq.n = 0;
+    else db->d_seq.release();
+    return PGX_OK;
+  });
 }
 int pgx_seqdb_has_bytes(const pgx_seqdb *db) { return db && db->d_seq.p ? 1 : 0; }
 
@@ -912,81 +903,85 @@ uint32_t pgx_seqdb_reads(const pgx_seqdb *db) { return db ? (uint32_t)db->rid.si
 // ---- batch level -----------------------------------------------------------------------------------------
 int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, pgx_mm128 **out,
                      size_t *n_out) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE(db && out && n_out, PGX_EARG, "pgx_sketch_batch: null argument");
-  PGX_REQUIRE(w > 0 && w < 256 && k > 0 && k <= 28, PGX_EARG, "need 0<w<256, 0<k<=28 (src/mm_sketch.c:77-78)");
-  std::vector<ReadDesc> reads(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    PGX_REQUIRE(read_slots[i] < db->rid.size(), PGX_EARG, "read slot %u out of range", read_slots[i]);
-    const uint32_t s = read_slots[i];
-    PGX_REQUIRE(db->rlen[s] > 0, PGX_EARG, "read slot %u is empty (mm_sketch asserts len > 0)", s);
-    reads[i] = ReadDesc{db->roff[s], db->rlen[s], db->rid[s]};
-  }
-  DevBuf<pgx_mm128> d;
-  size_t m = 0;
-  dev_sketch(db, reads, w, k, d, m, nullptr);
-  std::vector<pgx_mm128> h(m);
-  d.download(h.data(), m);
-  pgx::sync();
-  *out = host_copy(h);
-  *n_out = m;
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(db && out && n_out, PGX_EARG, "pgx_sketch_batch: null argument");
+    PGX_REQUIRE(w > 0 && w < 256 && k > 0 && k <= 28, PGX_EARG, "need 0<w<256, 0<k<=28 (src/mm_sketch.c:77-78)");
+    std::vector<ReadDesc> reads(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      PGX_REQUIRE(read_slots[i] < db->rid.size(), PGX_EARG, "read slot %u out of range", read_slots[i]);
+      const uint32_t s = read_slots[i];
+      PGX_REQUIRE(db->rlen[s] > 0, PGX_EARG, "read slot %u is empty (mm_sketch asserts len > 0)", s);
+      reads[i] = ReadDesc{db->roff[s], db->rlen[s], db->rid[s]};
+    }
+    DevBuf<pgx_mm128> d;
+    size_t m = 0;
+    dev_sketch(db, reads, w, k, d, m, nullptr);
+    std::vector<pgx_mm128> h(m);
+    d.download(h.data(), m);
+    pgx::sync();
+    *out = host_copy(h);
+    *n_out = m;
+    return PGX_OK;
+  });
 }
 
 int pgx_reduce_batch(const pgx_mm128 *in, size_t n, int rs, pgx_mm128 **out, size_t *n_out) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE(out && n_out && (n == 0 || in), PGX_EARG, "pgx_reduce_batch: null argument");
-  PGX_REQUIRE(rs > 0 && rs < 256, PGX_EARG, "reduction factor must be 1..255");
-  PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "list too long");
-  DevBuf<pgx_mm128> d_in(n), d_out;
-  d_in.upload(in, n);
-  size_t m = 0;
-  dev_reduce(d_in.p, n, rs, d_out, m);
-  std::vector<pgx_mm128> h(m);
-  d_out.download(h.data(), m);
-  pgx::sync();
-  *out = host_copy(h);
-  *n_out = m;
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(out && n_out && (n == 0 || in), PGX_EARG, "pgx_reduce_batch: null argument");
+    PGX_REQUIRE(rs > 0 && rs < 256, PGX_EARG, "reduction factor must be 1..255");
+    PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "list too long");
+    DevBuf<pgx_mm128> d_in(n), d_out;
+    d_in.upload(in, n);
+    size_t m = 0;
+    dev_reduce(d_in.p, n, rs, d_out, m);
+    std::vector<pgx_mm128> h(m);
+    d_out.download(h.data(), m);
+    pgx::sync();
+    *out = host_copy(h);
+    *n_out = m;
+    return PGX_OK;
+  });
 }
 
 int pgx_count_batch(const pgx_mm128 *in, size_t n, pgx_mm_count **out, size_t *n_out) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE(out && n_out && (n == 0 || in), PGX_EARG, "pgx_count_batch: null argument");
-  PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "list too long");
-  DevBuf<pgx_mm128> d_in(n);
-  DevBuf<pgx_mm_count> d_out;
-  d_in.upload(in, n);
-  size_t m = 0;
-  dev_count(d_in.p, n, 56, d_out, m);
-  std::vector<pgx_mm_count> h(m);
-  d_out.download(h.data(), m);
-  pgx::sync();
-  *out = host_copy(h);
-  *n_out = m;
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(out && n_out && (n == 0 || in), PGX_EARG, "pgx_count_batch: null argument");
+    PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "list too long");
+    DevBuf<pgx_mm128> d_in(n);
+    DevBuf<pgx_mm_count> d_out;
+    d_in.upload(in, n);
+    size_t m = 0;
+    dev_count(d_in.p, n, 56, d_out, m);
+    std::vector<pgx_mm_count> h(m);
+    d_out.download(h.data(), m);
+    pgx::sync();
+    *out = host_copy(h);
+    *n_out = m;
+    return PGX_OK;
+  });
 }
 
 int pgx_align_batch(pgx_seqdb *db, const pgx_align_key *keys, size_t n, int band, pgx_match *out) {
-  PGX_GUARD_BEGIN
-  require_ready();
-  PGX_REQUIRE(db && (n == 0 || (keys && out)), PGX_EARG, "pgx_align_batch: null argument");
-  PGX_REQUIRE(band > 0 && band < (1 << 20), PGX_EARG, "bad band");
-  for (size_t i = 0; i < n; ++i) {
-    const auto &k = keys[i];
-    PGX_REQUIRE(k.rid0 < db->rlen_by_rid.size() && k.rid1 < db->rlen_by_rid.size() && k.q_off <= db->rlen_by_rid[k.rid0],
-                PGX_EARG, "alignment key %zu out of range", i);
-  }
-  DevBuf<pgx_align_key> d_keys(n);
-  DevBuf<pgx_match> d_out(n);
-  d_keys.upload(keys, n);
-  dev_align(db, d_keys.p, n, band, d_out.p);
-  d_out.download(out, n);
-  pgx::sync();
-  PGX_GUARD_END
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(db && (n == 0 || (keys && out)), PGX_EARG, "pgx_align_batch: null argument");
+    PGX_REQUIRE(band > 0 && band < (1 << 20), PGX_EARG, "bad band");
+    for (size_t i = 0; i < n; ++i) {
+      const auto &k = keys[i];
+      PGX_REQUIRE(k.rid0 < db->rlen_by_rid.size() && k.rid1 < db->rlen_by_rid.size() && k.q_off <= db->rlen_by_rid[k.rid0],
+                  PGX_EARG, "alignment key %zu out of range", i);
+    }
+    DevBuf<pgx_align_key> d_keys(n);
+    DevBuf<pgx_match> d_out(n);
+    d_keys.upload(keys, n);
+    dev_align(db, d_keys.p, n, band, d_out.p);
+    d_out.download(out, n);
+    pgx::sync();
+    return PGX_OK;
+  });
 }
 
 }  // extern "C"

@@ -287,7 +287,7 @@ static int host_line(const Row &r, char *line, size_t cap) {
 using namespace pgx;
 
 extern "C" int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, uint64_t *n_unique) {
-  try {
+  return guarded([&] {
     require_ready();
     PGX_REQUIRE(text && text_len && (n == 0 || recs), PGX_EARG, "pgx_dedup: null argument");
     PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many records for one call");
@@ -332,13 +332,7 @@ extern "C" int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *te
     *text_len = out.size();
     if (n_unique) *n_unique = m;
     timing_flush();
-  } catch (const Fail &f) {
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
-  return PGX_OK;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -570,7 +564,7 @@ int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, s
 
 extern "C" int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out) {
   pgx_dedup_stream *s = nullptr;
-  try {
+  const int rc = guarded([&] {
     PGX_REQUIRE(out, PGX_EARG, "pgx_dedup_open: null argument");
     *out = nullptr;
     PGX_REQUIRE(ctx().ready, PGX_ESTATE, "pgx_dedup_open: no device context (pgx_init has not been called, or found no HIP device)");
@@ -584,15 +578,9 @@ extern "C" int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out) {
     std::lock_guard<std::mutex> lk(g_streams_mu);
     g_streams.push_back(s);
     *out = s;
-  } catch (const Fail &f) {
-    delete s;
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    delete s;
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
-  return PGX_OK;
+  });
+  if (rc) delete s;
+  return rc;
 }
 
 extern "C" int pgx_dedup_feed(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len) {

@@ -1,6 +1,7 @@
-// pgx_host_replay.h -- the greedy best-n walk (shimmer_to_overlap + the seen-pair table, /root/reference/src/shmr_overlap.c:52-228) on the HOST
-// (included by pgx_overlap.cpp only, inside its unnamed namespace, behind pgx_host_tables.h): Replay, the sequential fixed point, and ParReplay, the same
-// with a thread team over shared lock-free tables.  Sets below 200,000 pair records and the fall-back of the device replay (pgx_replay.hip) run here.
+// pgx_host_replay.h -- the greedy best-n walk (shimmer_to_overlap + the seen-pair table, src/shmr_overlap.c:52-228 of the reference) on the HOST
+// (included by pgx_overlap.cpp only, inside its unnamed namespace, behind pgx_host_tables.h and the stage's StageKnobs): Replay, the sequential
+// fixed point, ParReplay, the same with a thread team over shared lock-free tables, and HostWalk, which drives them for a stage.  Sets below
+// 200,000 pair records and the fall-back of the device replay (pgx_replay.hip) run here.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------------
@@ -31,7 +32,6 @@ struct Replay {
   const Visit &v;
   const std::vector<uint32_t> &rlen;
   uint32_t bestn;
-  bool predict = true;  // PGX_PREDICT=0: guess "plain overlap" always
 
   AKeyMap memo;                     // alignment key -> global request number (its result is pending while >= req_base)
   std::vector<pgx_match> results;   // indexed by global request number
@@ -164,7 +164,7 @@ struct Replay {
           // read0): if read1 fits inside the rest of read0, or read0 starts (almost) where read1 starts, a containment
           vd.accepted = true;
           vd.type = T_OVERLAP;
-          if (predict && (rlen1 <= rlen0 - q_off || q_off < (uint32_t)(END_FUZZ * 2 - 8)))
+          if (rlen1 <= rlen0 - q_off || q_off < (uint32_t)(END_FUZZ * 2 - 8))
             vd.type = rlen0 >= rlen1 ? T_CONTAINS : T_CONTAINED;
           guesses.push_back(Guess{b, *mv, (uint32_t)recs.size(), rlen0, rlen1, q_off, vd.type});
         } else {
@@ -298,7 +298,6 @@ struct ParReplay {
   const Visit &v;
   const std::vector<uint32_t> &rlen;
   uint32_t bestn;
-  bool predict = true;
   bool trace = false;
   unsigned nthr;
   size_t block = 64;  // buckets a worker takes at a time: neighbours in visit order share a key0 group, hence reads and
@@ -608,7 +607,7 @@ struct ParReplay {
         if (mval >= settled) {
           vd.accepted = true;
           vd.type = T_OVERLAP;
-          if (predict && (rlen1 <= rlen0 - q_off || q_off < (uint32_t)(END_FUZZ * 2 - 8)))
+          if (rlen1 <= rlen0 - q_off || q_off < (uint32_t)(END_FUZZ * 2 - 8))
             vd.type = rlen0 >= rlen1 ? T_CONTAINS : T_CONTAINED;
           guessed = true;
         } else {
@@ -822,3 +821,146 @@ struct ParReplay {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------
+// The host walk of a stage over its visit list: ParReplay where a thread team pays, Replay otherwise and as ParReplay's fall-back when
+// its tables overflow.  Alignments run on the GPU in batches; what they cost is added to the stage's gpu_ms.
+// ---------------------------------------------------------------------------------------------------------
+struct HostWalk {
+  const pgx_seqdb *db;
+  const Visit &visit;
+  const pgx_overlap_params *p;
+  const StageKnobs &k;
+  const double t0;            // the stage's start (trace lines)
+  OvOut &out;
+  pgx_overlap_stats &s;
+  double &gpu_ms;
+
+  // 24 threads measured best on a 64-core node at both ends (E. coli set: 8 -> 15.1 ms, 16 -> 12.3, 24 -> 10.3, 48 -> 10.0,
+  // 64 -> 16.6 per step; 4.5 Gbases: 16 -> 620 ms, 24 -> 539, 32 -> 571); the ranks of a multi-process job share the host
+  unsigned thread_count() const {
+    unsigned threads = std::max(1u, std::thread::hardware_concurrency());
+    cpu_set_t allowed;  // (a container may grant far fewer CPUs than the machine has)
+    if (sched_getaffinity(0, sizeof(allowed), &allowed) == 0 && CPU_COUNT(&allowed) > 0)
+      threads = std::min(threads, (unsigned)CPU_COUNT(&allowed));
+    if (k.local_world) threads = std::max(4u, threads / (2u * (unsigned)k.local_world));
+    threads = std::min(24u, threads);
+    if (k.threads) threads = (unsigned)k.threads;
+    // the shared-table protocol costs a locked operation per examination (plus one per insertion) and a thread team per round; measured against
+    // the sequential replay with 16 threads: 4.2 s -> 0.25 s for the first sweep at 4.5 Gbases, 11.9 -> 7 ms of sweeps at
+    // 75 Mbases (200 k entries); below ~50 k entries (StageKnobs::par_min) the team start-up dominates
+    if (visit.entries.size() < k.par_min) threads = 1;
+    return threads;
+  }
+
+  void run() {
+    const unsigned threads = thread_count();
+    if (threads > 1) {
+      try {
+        parallel(threads);
+        return;
+      } catch (const ParReplay::Overflow &) {
+        fprintf(stderr, "[pgx] note: parallel replay tables overflowed; falling back to the sequential replay\n");
+        s.rounds = 0, s.n_align_gpu = 0;
+      }
+    }
+    sequential();
+  }
+
+  void parallel(unsigned threads) {
+    const bool trace = k.trace;
+    const double c0 = now_ms();
+    ParReplay *rpp = new ParReplay(visit, db->rlen_by_rid, (uint32_t)(uint8_t)p->bestn, threads);
+    struct DeferReplay {   // (torn down on the housekeeping thread; ahead of the stage's tables, which it refers to)
+      ParReplay *r;
+      ~DeferReplay() {
+        ParReplay *z = r;
+        defer_destroy([z] { delete z; });
+      }
+    } defer_replay{rpp};
+    ParReplay &rp = *rpp;
+    rp.trace = trace;
+    if (k.block) rp.block = k.block;
+    if (trace) fprintf(stderr, "[pgx] parallel replay tables set up in %.2f ms; t = +%.2f ms\n", now_ms() - c0, now_ms() - t0);
+    size_t first_req = 0;
+    double settle_ms = 0;
+    // alignment batches go to the GPU while the sweep that files them is still running; the results come back once,
+    // after the sweep
+    struct Batch {
+      DevBuf<pgx_align_key> keys;
+      DevBuf<pgx_match> res;
+      size_t first, n;
+    };
+    std::vector<Batch> inflight;
+    rp.submit = [&](size_t first, size_t upto) {
+      const double g0 = now_ms();
+      Batch b{DevBuf<pgx_align_key>(upto - first), DevBuf<pgx_match>(upto - first), first, upto - first};
+      PGX_HIP(hipMemcpyAsync(b.keys.p, rp.requests.data() + first, b.n * sizeof(pgx_align_key), hipMemcpyHostToDevice,
+                             ctx().stream));
+      dev_align(db, b.keys.p, b.n, p->align_bandwidth, b.res.p);
+      inflight.push_back(std::move(b));
+      s.n_align_gpu += upto - first;
+      gpu_ms += now_ms() - g0;
+      if (trace) fprintf(stderr, "[pgx]   submitted %zu requests in %.2f ms at t = +%.2f ms\n", upto - first, now_ms() - g0, now_ms() - t0);
+    };
+    for (;;) {
+      const double p0 = now_ms();
+      uint64_t ev = 0;
+      unsigned rounds = 0;
+      rp.sweep_first = rp.submitted = first_req;
+      const size_t upto = rp.sweep(&ev, &rounds);
+      ++s.rounds;
+      s.n_evaluations = ev;
+      if (trace)
+        fprintf(stderr, "[pgx] parallel sweep %u (%u threads): %u rounds, %llu evaluations so far, %.2f ms, %zu requests (%zu already on the GPU)\n",
+                s.rounds, threads, rounds, (unsigned long long)ev, now_ms() - p0, upto - first_req, rp.submitted - first_req);
+      if (upto == first_req) break;
+      const double g0 = now_ms();
+      if (upto > rp.submitted) rp.submit(rp.submitted, upto);
+      for (Batch &b : inflight)
+        PGX_HIP(hipMemcpyAsync(rp.results.data() + b.first, b.res.p, b.n * sizeof(pgx_match), hipMemcpyDeviceToHost, ctx().stream));
+      pgx::sync();
+      inflight.clear();
+      gpu_ms += now_ms() - g0;
+      if (trace) fprintf(stderr, "[pgx]   waited %.2f ms for the GPU after the sweep\n", now_ms() - g0);
+      const double s0 = now_ms();
+      const bool any = rp.settle(first_req, upto);
+      settle_ms += now_ms() - s0;
+      first_req = upto;
+      if (!any) break;
+    }
+    const double k0 = now_ms();
+    rp.collect(out, s.n_align_needed, s.n_seen_skip);
+    if (trace) fprintf(stderr, "[pgx] settle %.2f ms total, collect %.2f ms; t = +%.2f ms\n", settle_ms, now_ms() - k0, now_ms() - t0);
+  }
+
+  // one batch of the sequential replay: the results land in the replay's table
+  void align_batch(const pgx_align_key *keys, size_t nreq, pgx_match *res) {
+    const double g0 = now_ms();
+    pgx_align_key *d_keys = ws<pgx_align_key>("ov.keys", nreq);
+    pgx_match *d_res = ws<pgx_match>("ov.res", nreq);
+    PGX_HIP(hipMemcpyAsync(d_keys, keys, nreq * sizeof(pgx_align_key), hipMemcpyHostToDevice, ctx().stream));
+    dev_align(db, d_keys, nreq, p->align_bandwidth, d_res);
+    PGX_HIP(hipMemcpyAsync(res, d_res, nreq * sizeof(pgx_match), hipMemcpyDeviceToHost, ctx().stream));
+    pgx::sync();
+    gpu_ms += now_ms() - g0;
+    s.n_align_gpu += nreq;
+  }
+
+  void sequential() {
+    Replay rp(visit, db->rlen_by_rid, (uint32_t)(uint8_t)p->bestn);  // bestn is a uint8_t in the reference (:245)
+    for (;;) {
+      const double p0 = now_ms();
+      const uint64_t ev0 = rp.n_eval;
+      const size_t nreq = rp.sweep();
+      ++s.rounds;
+      if (k.trace)
+        fprintf(stderr, "[pgx] replay sweep %u: %llu buckets evaluated in %.2f ms, %zu requests\n", s.rounds,
+                (unsigned long long)(rp.n_eval - ev0), now_ms() - p0, nreq);
+      if (nreq == 0) break;
+      align_batch(rp.requests.data(), nreq, rp.result_slots());
+      if (!rp.settle()) break;  // every guess was right: the replay is exact
+    }
+    rp.collect(out, s.n_align_needed, s.n_seen_skip);
+    s.n_evaluations = rp.n_eval;
+  }
+};

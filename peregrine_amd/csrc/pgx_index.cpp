@@ -177,18 +177,12 @@ void pgx_index_result_free(pgx_index_result *r) {
 }
 
 int pgx_index_resident(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out) {
-  try {
+  return guarded([&] {
     require_ready();
     PGX_REQUIRE(db && out, PGX_EARG, "pgx_index_resident: null argument");
     check_params(p);
     run_index(db, p, out);
-  } catch (const Fail &f) {
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
-  return PGX_OK;
+  });
 }
 
 // index stage of a multi-GPU rank: the final-level list and its counts stay in HBM for the exchange that follows
@@ -196,7 +190,7 @@ int pgx_index_resident_dev(pgx_seqdb *db, const pgx_index_params *p, pgx_index_r
                            size_t *n_top, const pgx_mm_count **d_mc, size_t *n_mc) {
   DeviceIndex &held = g_held.ix;             // one context per process: the previous call's buffers are released here
   DevBuf<pgx_mm128> &held_top = g_held.top;  // (only when the general index path produced host arrays)
-  try {
+  return guarded([&] {
     require_ready();
     PGX_REQUIRE(db && stats && d_top && n_top && d_mc && n_mc, PGX_EARG, "pgx_index_resident_dev: null argument");
     check_params(p);
@@ -215,20 +209,13 @@ int pgx_index_resident_dev(pgx_seqdb *db, const pgx_index_params *p, pgx_index_r
       stats->top = nullptr, stats->top_mc = nullptr;
     }
     *d_top = held.d_top, *n_top = held.n_top, *d_mc = held.mc.p, *n_mc = held.n_mc;
-  } catch (const Fail &f) {
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
-  return PGX_OK;
+  });
 }
 
 int pgx_index_chunk_db(pgx_seqdb *db, const char *out_prefix, const pgx_index_params *p, pgx_index_result *stats) {
   pgx_index_result res;
   memset(&res, 0, sizeof(res));
-  int rc = PGX_OK;
-  try {
+  const int rc = guarded([&] {
     require_ready();
     PGX_REQUIRE(db && out_prefix, PGX_EARG, "pgx_index_chunk_db: null argument");
     check_params(p);
@@ -248,12 +235,7 @@ int pgx_index_chunk_db(pgx_seqdb *db, const char *out_prefix, const pgx_index_pa
       list_stash_put(db, level_path(out_prefix, lv, false, p->mychunk, p->total_chunk), d ? dev.d_top : nullptr, res.top, res.n_top * sizeof(pgx_mm128));
       list_stash_put(db, level_path(out_prefix, lv, true, p->mychunk, p->total_chunk), d ? dev.mc.p : nullptr, res.top_mc, res.n_top_mc * sizeof(pgx_mm_count));
     }
-  } catch (const Fail &f) {
-    rc = f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    rc = PGX_ENOMEM;
-  }
+  });
   if (stats) {
     *stats = res;
     stats->l0 = stats->top = nullptr;
@@ -266,14 +248,12 @@ int pgx_index_chunk_db(pgx_seqdb *db, const char *out_prefix, const pgx_index_pa
 int pgx_index_chunk(const char *seqdb_prefix, const char *out_prefix, const pgx_index_params *p,
                     pgx_index_result *stats) {
   pgx_seqdb *db = nullptr;
-  try {
+  int rc = guarded([&] {
     require_ready();
     PGX_REQUIRE(seqdb_prefix && out_prefix, PGX_EARG, "pgx_index_chunk: null prefix");
     check_params(p);
-  } catch (const Fail &f) {
-    return f.code;
-  }
-  int rc = pgx_seqdb_load(seqdb_prefix, &db);
+  });
+  if (rc == PGX_OK) rc = pgx_seqdb_load(seqdb_prefix, &db);
   if (rc) return rc;
   rc = pgx_index_chunk_db(db, out_prefix, p, stats);
   pgx_seqdb_free(db);

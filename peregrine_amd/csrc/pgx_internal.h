@@ -9,7 +9,9 @@
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pgx.h"
@@ -46,6 +48,21 @@ struct Fail {
       throw pgx::Fail{code};         \
     }                                \
   } while (0)
+// The epilogue of a C entry point: runs body (which returns nothing -- PGX_OK is answered -- or the code to answer); a Fail becomes its
+// code, an allocation failure PGX_ENOMEM with a message.  No C++ exception of the library's own leaves an extern "C" function.
+template <class F>
+int guarded(F &&body) {
+  try {
+    if constexpr (std::is_void_v<decltype(body())>) body();
+    else return body();
+  } catch (const Fail &f) {
+    return f.code;
+  } catch (const std::bad_alloc &) {
+    set_error("out of host memory");
+    return PGX_ENOMEM;
+  }
+  return PGX_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // context: one device, one stream
@@ -382,10 +399,16 @@ struct EarlyGroups {
   uint32_t last_first = 0;   // record index of the last key's first occurrence
 };
 using EarlyFn = std::function<void(EarlyGroups &&)>;
+// the shimmer list and the count entries of a join, both as host arrays or both as device arrays (used in place)
+struct Lists {
+  const pgx_mm128 *mm = nullptr;
+  size_t n_mm = 0;
+  const pgx_mm_count *mc = nullptr;
+  size_t n_mc = 0;
+  bool on_device = false;
+};
 // d_rlen: read length by rid, on the device
-void dev_build_pairs(const uint32_t *d_rlen, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts,
-                     size_t n_counts, const PairParams &pp, PairTables &out, unsigned flags = 0,
-                     const pgx_mm128 *d_mmers = nullptr, const pgx_mm_count *d_counts = nullptr,  // d_*: the same lists, already on the device
+void dev_build_pairs(const uint32_t *d_rlen, const Lists &lists, const PairParams &pp, PairTables &out, unsigned flags = 0,
                      DevicePairs *keep = nullptr,   // keep: the sorted records stay on the device too
                      const EarlyFn &early = nullptr,
                      const pgx_seqdb *db = nullptr);   // db: keeps the count table for the job's next chunk, and its packs' locus keys are
@@ -404,12 +427,13 @@ void dev_pairs_from_records(const pgx_pair_rec *d_rec, size_t n, PairTables &out
 void pairs_fetch_records(const DevicePairs &dp, PairTables &out);  // the lazily kept records, to the host tables
 
 // The greedy walk over the visit list (visit_bids: the join's bucket ids in visit order) on the GPU; the records go to the
-// array alloc_out(n) returns.  false: the job does not fit the device tables' encodings or they overflowed -- nothing was
+// array alloc_out(n) returns, or -- sink != nullptr -- from the device to the sink, right behind k_emit.  false: the job does not fit the device tables' encodings or they overflowed -- nothing was
 // produced and the caller runs the host replay.
+struct RecordSink;
 void dev_place_bids(const uint32_t *ids_all, size_t n_ids, const uint32_t *psrc, const uint32_t *pcnt, const uint64_t *pdst,
                     size_t n_groups, size_t nb, DevBuf<uint32_t> &bid);   // the visit list assembled on the device
 bool dev_replay(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visit_bids, const uint32_t *d_bids, size_t nb, size_t n_entries,
-                uint32_t bestn, int band, bool predict, uint32_t ovlp_upper, const std::function<pgx_ovlp *(size_t)> &alloc_out,
+                uint32_t bestn, int band, uint32_t ovlp_upper, const std::function<pgx_ovlp *(size_t)> &alloc_out, RecordSink *sink,
                 size_t *n_out, pgx_overlap_stats *st, bool trace);
 
 // what the index stage leaves in HBM for a following overlap stage of the same process (pgx_index_overlap_resident)
@@ -448,13 +472,24 @@ struct OvOut {  // the stage's output: one malloc'd array handed to the caller a
   }
   ~OvOut() { out_free(a); }
 };
-struct DeviceLists {   // the lists as device arrays
-  const pgx_mm128 *d_top = nullptr;
-  const pgx_mm_count *d_mc = nullptr;
+// what a stage runs on: the lists (host or device arrays), or -- a rank of a multi-GPU job -- the pair records this chunk received from
+// all index chunks (device pointer, arrival order = insertion order; may be empty)
+struct StageInput {
+  bool records = false;
+  Lists lists;
+  const pgx_pair_rec *d_recs = nullptr;
+  size_t n_recs = 0;
+  static StageInput host_lists(const pgx_mm128 *mm, size_t n_mm, const pgx_mm_count *mc, size_t n_mc) {
+    return StageInput{false, Lists{mm, n_mm, mc, n_mc, false}, nullptr, 0};
+  }
+  static StageInput device_lists(const pgx_mm128 *d_mm, size_t n_mm, const pgx_mm_count *d_mc, size_t n_mc) {
+    return StageInput{false, Lists{d_mm, n_mm, d_mc, n_mc, true}, nullptr, 0};
+  }
+  static StageInput pair_records(const pgx_pair_rec *d_recs, size_t n) { return StageInput{true, Lists{}, d_recs, n}; }
 };
 void overlap_check_params(const pgx_overlap_params *p);
-void overlap_stage(pgx_seqdb *db, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts, size_t n_counts, const pgx_overlap_params *p,
-                   OvOut &out, pgx_overlap_stats *st, const DeviceLists *dev = nullptr);
+// the stage: the records go to `out`, or -- sink != nullptr and the walk ran on the device -- to the sink (out.a == nullptr, out.n set)
+void overlap_stage(pgx_seqdb *db, const StageInput &in, const pgx_overlap_params *p, OvOut &out, pgx_overlap_stats *st, RecordSink *sink = nullptr);
 // Where a stage's records go when they are not wanted as a host array (served commands: straight to the output file).  The device replay hands
 // its record buffer over right behind k_emit -- take() returns at once, the transfer runs on the sink's own threads and streams -- and
 // allocates no host array; the host replay (small sets, fall-back) delivers a host array that the caller writes itself.
@@ -462,7 +497,6 @@ struct RecordSink {
   virtual void take(DevBuf<pgx_ovlp> &&dev, size_t n) = 0;   // ordered behind what is enqueued on ctx().stream
   virtual ~RecordSink() {}
 };
-RecordSink *&record_sink();   // (one stage at a time per process: set around overlap_stage by the caller that owns the sink)
 // Served jobs: an index command leaves with the database a device copy of every final-level list / count file it wrote (keyed by the
 // file's absolute path, size and mtime); the job's overlap commands assemble their input from those copies instead of reading the files
 // back (pgx_served.cpp).  d_payload (device) or h_payload (host): the file's entries, without the 8-byte count header; call AFTER the file

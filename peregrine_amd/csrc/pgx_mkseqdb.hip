@@ -148,7 +148,7 @@ size_t parse_some(const uint8_t *b, size_t n, bool at_eof, ParseState &st, Recor
 using namespace pgx;
 
 extern "C" int pgx_mkseqdb(const char *seq_dataset_path, const char *seqdb_prefix, uint64_t *n_reads, uint64_t *n_bases) {
-  try {
+  return guarded([&]() -> int {
     require_ready();
     PGX_REQUIRE(seq_dataset_path && seqdb_prefix, PGX_EARG, "pgx_mkseqdb: null argument");
     FILE *lst = fopen(seq_dataset_path, "r");
@@ -234,10 +234,5 @@ extern "C" int pgx_mkseqdb(const char *seq_dataset_path, const char *seqdb_prefi
     if (n_reads) *n_reads = rid;
     if (n_bases) *n_bases = offset;
     return rc;
-  } catch (const Fail &f) {
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
+  });
 }

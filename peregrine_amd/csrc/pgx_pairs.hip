@@ -488,9 +488,9 @@ static void chain_scan(const DevBuf<uint8_t> &keep, uint32_t n, const uint32_t *
 static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs *keep_dev, Tmp &tmp);
 static void early_groups(const PairRecs &R, Tmp &tmp, const EarlyFn &early);
 
-void dev_build_pairs(const uint32_t *d_rlen, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts, size_t n_counts,
-                     const PairParams &pp, PairTables &out, unsigned flags, const pgx_mm128 *d_mmers, const pgx_mm_count *d_counts,
-                     DevicePairs *keep_dev, const EarlyFn &early, const pgx_seqdb *db) {
+void dev_build_pairs(const uint32_t *d_rlen, const Lists &lists, const PairParams &pp, PairTables &out, unsigned flags, DevicePairs *keep_dev,
+                     const EarlyFn &early, const pgx_seqdb *db) {
+  const size_t n_mm = lists.n_mm, n_counts = lists.n_mc;
   out = PairTables();
   if (keep_dev) *keep_dev = DevicePairs();
   if (n_mm == 0) return;
@@ -502,15 +502,15 @@ void dev_build_pairs(const uint32_t *d_rlen, const pgx_mm128 *mmers, size_t n_mm
   const uint32_t n = (uint32_t)n_mm;
 
   // ---- aggregated counts ----------------------------------------------------------------------------------
-  DevBuf<pgx_mm_count> cin_own(d_counts ? 0 : n_counts);  // (lists that are already on the device are used in place)
-  if (!d_counts) cin_own.upload(counts, n_counts);
+  DevBuf<pgx_mm_count> cin_own(lists.on_device ? 0 : n_counts);  // (lists that are already on the device are used in place)
+  if (!lists.on_device) cin_own.upload(lists.mc, n_counts);
   CountCache uncached;   // (no database: the table lives for this call)
-  const CountTable &ct = aggregate_counts(db ? get_or_make(db->caches.counts) : uncached, d_counts ? d_counts : cin_own.p, n_counts, tmp);
+  const CountTable &ct = aggregate_counts(db ? get_or_make(db->caches.counts) : uncached, lists.on_device ? lists.mc : cin_own.p, n_counts, tmp);
 
   // ---- keep flags, chain, records -------------------------------------------------------------------------
-  DevBuf<pgx_mm128> mm_own(d_mmers ? 0 : n);
-  if (!d_mmers) mm_own.upload(mmers, n);
-  const pgx_mm128 *mm_dev = d_mmers ? d_mmers : mm_own.p;
+  DevBuf<pgx_mm128> mm_own(lists.on_device ? 0 : n);
+  if (!lists.on_device) mm_own.upload(lists.mm, n);
+  const pgx_mm128 *mm_dev = lists.on_device ? lists.mm : mm_own.p;
   if (db) locus_key_add_mm(db, mm_dev, n);   // (only before the database's packs exist)
   DevBuf<uint8_t> keep;
   DevBuf<uint32_t> d_misc;

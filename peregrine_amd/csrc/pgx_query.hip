@@ -194,7 +194,7 @@ void run_map(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t 
   DevBuf<uint32_t> d_rlen(n_rid);
   d_rlen.upload(rlen_by_rid, n_rid);
   PairTables pt;
-  dev_build_pairs(d_rlen.p, mmers, n_mm, counts, n_counts,
+  dev_build_pairs(d_rlen.p, Lists{mmers, n_mm, counts, n_counts, false},
                   PairParams{(uint32_t)p->total_chunk, (uint32_t)p->mychunk, (uint32_t)p->mc_lower, (uint32_t)p->mc_upper}, pt,
                   PAIRS_Y1 | PAIRS_INSERTION_ORDER | PAIRS_COUNTS);
   if (pt.n_rec == 0) return;
@@ -262,7 +262,7 @@ extern "C" {
 int pgx_map(const pgx_mm128 *ref_mmers, size_t n_ref, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts,
             size_t n_counts, const uint32_t *rlen_by_rid, uint32_t n_rid, const pgx_map_params *p, char **text, size_t *text_len,
             uint64_t *n_lines) {
-  try {
+  return guarded([&] {
     require_ready();
     PGX_REQUIRE(text && text_len && (n_ref == 0 || ref_mmers) && (n_mm == 0 || mmers) && (n_counts == 0 || counts) &&
                     (n_rid == 0 || rlen_by_rid),
@@ -277,18 +277,12 @@ int pgx_map(const pgx_mm128 *ref_mmers, size_t n_ref, const pgx_mm128 *mmers, si
     out[s.size()] = 0;
     *text = out, *text_len = s.size();
     if (n_lines) *n_lines = nl;
-  } catch (const Fail &f) {
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
-  return PGX_OK;
+  });
 }
 
 int pgx_map_chunk(const char *refdb_prefix, const char *ref_shimmer_prefix, const char *seqdb_prefix, const char *shimmer_prefix,
                   const pgx_map_params *p, char **text, size_t *text_len, uint64_t *n_lines) {
-  try {
+  return guarded([&]() -> int {
     require_ready();
     PGX_REQUIRE(ref_shimmer_prefix && seqdb_prefix && shimmer_prefix, PGX_EARG, "pgx_map_chunk: null argument");
     (void)refdb_prefix;  // the reference maps the two seqdb files but never reads them (shmr_map.c:60-78)
@@ -301,12 +295,7 @@ int pgx_map_chunk(const char *refdb_prefix, const char *ref_shimmer_prefix, cons
     read_counted(std::string(shimmer_prefix) + "-MC-[0-9]*-of-[0-9]*.dat", mc);
     return pgx_map(ref.data(), ref.size(), mm.data(), mm.size(), mc.data(), mc.size(), rl.data(), (uint32_t)rl.size(), p, text,
                    text_len, n_lines);
-  } catch (const Fail &f) {
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
+  });
 }
 
 // ---- f4 ------------------------------------------------------------------------------------------------------
@@ -334,8 +323,8 @@ void build_shimmer_map4py(py_mmer_t *py_mmer, char *seqdb_prefix, char *shimmer_
     h = new Handle{MAGIC, {}};
     DevBuf<uint32_t> d_rlen(rl.size());
     d_rlen.upload(rl.data(), rl.size());
-    dev_build_pairs(d_rlen.p, mm.data(), mm.size(), mc.data(), mc.size(), PairParams{total_chunk, mychunk, lowerbound, upperbound},
-                    h->map.pt, PAIRS_Y1 | PAIRS_COUNTS);
+    dev_build_pairs(d_rlen.p, Lists{mm.data(), mm.size(), mc.data(), mc.size(), false},
+                    PairParams{total_chunk, mychunk, lowerbound, upperbound}, h->map.pt, PAIRS_Y1 | PAIRS_COUNTS);
     sync();
     timing_flush();
     // get_ridmm (shmr_utils.c:415-443): a read's list starts at its first occurrence and is as long as its occurrences

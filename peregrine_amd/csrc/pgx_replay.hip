@@ -45,8 +45,8 @@ unsigned cdiv256(size_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
 
 // Round 6: the three hash tables of a stage (hot pair table, reader lists, memo: 38.6 GB at full-size configs[3]) must start all zero, and clearing them
-// takes 7-8 ms -- on a GPU that sits idle for ~18 ms of every chunk while the host finishes the outer khash table (pgx_overlap.cpp: overlap_front).
-// So the front allocates and clears tables of the sizes the LAST stage used inside that window (replay_preclear); replay_attempt takes them over when
+// takes 7-8 ms -- on a GPU that sits idle for ~18 ms of every chunk while the host finishes the outer khash table (pgx_overlap.cpp: Stage::visit_order).
+// So the stage allocates and clears tables of the sizes the LAST stage used inside that window (replay_preclear); replay_attempt takes them over when
 // its own sizes come out the same (the chunks of a job are alike, the sizes are powers of two) and clears its own otherwise.
 struct PreCleared {
   DevBuf<PHot> ph;
@@ -72,7 +72,7 @@ void CacheFree::operator()(ReplayState *r) const { delete r; }
 namespace {
 // one attempt with the given table sizes (multiples of the defaults); returns 0, or the OV_* bits of what overflowed
 uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visit_bids, const uint32_t *d_bids, size_t nb, size_t n_entries,
-                        uint32_t bestn, int band, bool predict, const std::function<pgx_ovlp *(size_t)> &alloc_out,
+                        uint32_t bestn, int band, const std::function<pgx_ovlp *(size_t)> &alloc_out, RecordSink *sink,
                         size_t *n_out, pgx_overlap_stats *st, bool trace, const double *mult, double *usage) {
   const double t0 = now_ms();
   hipStream_t s = ctx().stream;
@@ -171,7 +171,7 @@ uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32
   PGX_HIP(hipMemsetAsync(spread.p, 0, SPREAD * 8 * sizeof(unsigned long long), s));
   {
     const int mq = END_FUZZ * 2 - 8, mt = END_FUZZ * 2 - 8;
-    r.predict = predict ? std::max(mq, 1) : 0, r.predict2 = mt;
+    r.predict = std::max(mq, 1), r.predict2 = mt;
   }
   r.bestn = bestn, r.settled = 0;
   const bool timed_misc = getenv("PGX_REPLAY_TIMING") && atoi(getenv("PGX_REPLAY_TIMING")) != 0;   // "replay_misc" / "replay_emit" in pgx_timing_get
@@ -490,7 +490,7 @@ uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32
       hipLaunchKernelGGL(k_emit, dim3(cdiv256(nb)), dim3(256), 0, s, r, off.p, d_out.p);
       // pgx_results_async: the copy runs on its own stream behind k_emit and this call returns without it -- the 2.9 GB of a human-scale
       // chunk (55 ms over PCIe) overlap the NEXT chunk's join and first sweep; the caller waits (pgx_results_wait) before it reads
-      if (nrec && record_sink()) record_sink()->take(std::move(d_out), nrec);   // (served commands: device -> output file, pgx_served.cpp)
+      if (nrec && sink) sink->take(std::move(d_out), nrec);   // (served commands: device -> output file, pgx_served.cpp)
       else if (nrec && results_async() && !timed_misc) results_copy_async(host, std::move(d_out), nrec);
       else if (nrec) PGX_HIP(hipMemcpyAsync(host, d_out.p, nrec * sizeof(pgx_ovlp), hipMemcpyDeviceToHost, s));
     }
@@ -552,7 +552,7 @@ void replay_drop_precleared(const pgx_seqdb *db) {   // (a stage that ended with
   if (db->caches.replay) db->caches.replay->pre.drop();
 }
 
-// called by the stage's front while the GPU would otherwise wait for the host's outer table: tables of the last stage's sizes, cleared, on ctx().stream
+// called by the stage's visit phase while the GPU would otherwise wait for the host's outer table: tables of the last stage's sizes, cleared, on ctx().stream
 void replay_preclear(const pgx_seqdb *db) {
   ReplayState &rs = get_or_make(db->caches.replay);
   PreCleared &pre = rs.pre;
@@ -585,7 +585,7 @@ void replay_preclear(const pgx_seqdb *db) {
 }
 
 bool dev_replay(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visit_bids, const uint32_t *d_bids, size_t nb, size_t n_entries,
-                uint32_t bestn, int band, bool predict, uint32_t ovlp_upper, const std::function<pgx_ovlp *(size_t)> &alloc_out,
+                uint32_t bestn, int band, uint32_t ovlp_upper, const std::function<pgx_ovlp *(size_t)> &alloc_out, RecordSink *sink,
                 size_t *n_out, pgx_overlap_stats *st, bool trace) {
   *n_out = 0;
   ReplayState &rs = get_or_make(db->caches.replay);
@@ -638,7 +638,7 @@ bool dev_replay(const pgx_seqdb *db, const DevicePairs &dp, const uint32_t *visi
     double usage[4] = {0, 0, 0, 0};
     uint32_t ov;
     try {
-      ov = replay_attempt(db, dp, visit_bids, d_bids, nb, n_entries, bestn, band, predict, alloc_out, n_out, st, trace, mult, usage);
+      ov = replay_attempt(db, dp, visit_bids, d_bids, nb, n_entries, bestn, band, alloc_out, sink, n_out, st, trace, mult, usage);
     } catch (const Fail &f) {
       //  tables sized by what an EARLIER stage used -- possibly another job's in a long-lived server -- may not fit where the
       // defaults would: once more with the defaults and the memory forgotten, else the host replay (which only needs host memory)

@@ -428,17 +428,13 @@ extern "C" {
 
 int pgx_output_finish(pgx_output *o) {
   if (!o) return PGX_OK;
-  int rc = PGX_OK;
-  try {
-    if (o->sink) {
-      o->sink->finish();
-      if (o->trace)
-        fprintf(stderr, "[pgx] overlap chunk (resident database): %zu records in their file %.1f ms after the stage (transfer %.1f ms)\n", o->n,
-                now_ms() - o->t_stage_done, o->sink->t_done - o->sink->t_take);
-    }
-  } catch (const Fail &f) {
-    rc = f.code;
-  }
+  const int rc = guarded([&] {
+    if (!o->sink) return;
+    o->sink->finish();
+    if (o->trace)
+      fprintf(stderr, "[pgx] overlap chunk (resident database): %zu records in their file %.1f ms after the stage (transfer %.1f ms)\n", o->n,
+              now_ms() - o->t_stage_done, o->sink->t_done - o->sink->t_take);
+  });
   delete o->sink;
   delete o;
   return rc;
@@ -446,10 +442,9 @@ int pgx_output_finish(pgx_output *o) {
 
 int pgx_overlap_chunk_db_begin(pgx_seqdb *db, const char *shimmer_prefix, const char *out_path, const pgx_overlap_params *p,
                                pgx_overlap_stats *stats, pgx_output **pending) {
-  int rc = PGX_OK;
   FileSink *sink = nullptr;
   if (pending) *pending = nullptr;
-  try {
+  const int rc = guarded([&] {
     require_ready();
     PGX_REQUIRE(db && shimmer_prefix && out_path && pending, PGX_EARG, "pgx_overlap_chunk_db_begin: null argument");
     overlap_check_params(p);
@@ -480,15 +475,7 @@ int pgx_overlap_chunk_db_begin(pgx_seqdb *db, const char *shimmer_prefix, const 
     const double t1 = now_ms();
     OvOut v;
     if (FileSink::usable(out_path)) sink = new FileSink(out_path);
-    const DeviceLists dl{c.mm.p, c.mc.p};
-    record_sink() = sink;
-    try {
-      overlap_stage(db, nullptr, c.n_mm, nullptr, c.n_mc, p, v, stats, &dl);
-    } catch (...) {
-      record_sink() = nullptr;
-      throw;
-    }
-    record_sink() = nullptr;
+    overlap_stage(db, StageInput::device_lists(c.mm.p, c.n_mm, c.mc.p, c.n_mc), p, v, stats, sink);
     if (c.prefix.empty()) c.clear();   // (lists that could not be tied to their files are not kept)
     const double t2 = now_ms();
     if (!sink || !sink->taken) {   // the host replay / an empty set / an output that cannot seek: the records are a host array
@@ -503,12 +490,7 @@ int pgx_overlap_chunk_db_begin(pgx_seqdb *db, const char *shimmer_prefix, const 
     o->sink = sink, o->trace = trace, o->t_stage_done = t2, o->n = v.n;
     sink = nullptr;
     *pending = o;
-  } catch (const Fail &f) {
-    rc = f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    rc = PGX_ENOMEM;
-  }
+  });
   delete sink;
   return rc;
 }
@@ -524,8 +506,7 @@ int pgx_overlap_chunk_db(pgx_seqdb *db, const char *shimmer_prefix, const char *
 int pgx_overlap_chunk(const char *seqdb_prefix, const char *shimmer_prefix, const char *out_path,
                       const pgx_overlap_params *p, pgx_overlap_stats *stats) {
   pgx_seqdb *db = nullptr;
-  int rc = PGX_OK;
-  try {
+  const int rc = guarded([&]() -> int {
     require_ready();
     PGX_REQUIRE(seqdb_prefix && shimmer_prefix && out_path, PGX_EARG, "pgx_overlap_chunk: null argument");
     overlap_check_params(p);
@@ -545,24 +526,20 @@ int pgx_overlap_chunk(const char *seqdb_prefix, const char *shimmer_prefix, cons
         rd_code = PGX_EIO, rd_err = "reading the shimmer files failed";
       }
     });
-    rc = pgx_seqdb_load(seqdb_prefix, &db);
-    const std::string load_err = rc ? pgx_last_error() : "";
+    const int load_rc = pgx_seqdb_load(seqdb_prefix, &db);
+    const std::string load_err = load_rc ? pgx_last_error() : "";
     reader.join();
-    if (rc) {
+    if (load_rc) {
       set_error("%s", load_err.c_str());
-      return rc;
+      return load_rc;
     }
     PGX_REQUIRE(rd_code == PGX_OK, rd_code, "%s", rd_err.c_str());
     OvOut v;
-    overlap_stage(db, mm.data(), mm.size(), mc.data(), mc.size(), p, v, stats);
+    overlap_stage(db, StageInput::host_lists(mm.data(), mm.size(), mc.data(), mc.size()), p, v, stats);
     results_wait();
     write_records(out_path, v.a, v.n);
-  } catch (const Fail &f) {
-    rc = f.code;
-  } catch (const std::bad_alloc &) {
-    set_error("out of host memory");
-    rc = PGX_ENOMEM;
-  }
+    return PGX_OK;
+  });
   pgx_seqdb_free(db);
   return rc;
 }
