@@ -27,7 +27,7 @@ extern "C" {
 #define PGX_EIO -2     /* file open/read/write failure (the reference would exit(1)) */
 #define PGX_EHIP -3    /* HIP runtime error / no device */
 #define PGX_ENOMEM -4
-#define PGX_ESTATE -5  /* pgx_init not called; or the call needs something the state no longer has (the seqdb bytes after pgx_seqdb_release_bytes) */
+#define PGX_ESTATE -5  /* pgx_init not called; or the call needs something the state no longer has (the seqdb bytes after pgx_seqdb_release_bytes / pgx_seqdb_compact_bytes) */
 
 /* ---- types shared with the on-disk formats (src/shimmer.h:24-30,61-64,97-110) ---- */
 typedef struct { uint64_t x, y; } pgx_mm128;                        /* x = hash<<8|span ; y = rid<<32|lastPos<<1|strand */
@@ -89,9 +89,24 @@ void pgx_seqdb_free(pgx_seqdb *db);
  * the database, or here): the index stage's closed-form kernels and every alignment kernel of the default path read the packs.  Refused --
  * PGX_ESTATE, bytes kept -- for a database with a read that holds an ambiguous base (sketched run by run / aligned nibble by nibble from the
  * bytes: src/mm_sketch.c:112-113, src/DWmatch.c:136-137) or a read longer than 65,535 bases.  Afterwards the entry points that need bytes (w / k
- * other than 80 / 16, want_l0, pgx_sketch_batch) return PGX_ESTATE; a buffer handed over with pgx_seqdb_adopt_dev is no longer referenced. */
+ * other than 80 / 16, want_l0, pgx_sketch_batch) return PGX_ESTATE; a buffer handed over with pgx_seqdb_adopt_dev is no longer referenced.
+ * A database with ambiguous bases gives its bytes back through pgx_seqdb_compact_bytes instead. */
 int pgx_seqdb_release_bytes(pgx_seqdb *db);
 int pgx_seqdb_has_bytes(const pgx_seqdb *db);
+/* The same for a database WITH ambiguous bases: the packs are built if need be, the bytes of the flagged reads alone (those that hold a byte without
+ * a 2-bit code) are copied into a side store, and the whole-seqdb bytes go (an adopted buffer is no longer referenced).  The packs then serve
+ * every kernel of the default path; a candidate alignment that touches a flagged read, and the run-by-run sketch of a flagged read, run the
+ * byte-wise kernels on the side store plus their unflagged partners' bytes, rebuilt from the packs for that call -- results stay bit-exact.
+ * Without a flagged read it is pgx_seqdb_release_bytes.  Idempotent.  PGX_ESTATE, bytes kept, nothing changed: a read longer than 65,535
+ * bases, packs that cannot be built, or bytes that are gone already without a side store.  Afterwards pgx_seqdb_has_bytes answers 0 and what
+ * needs the whole bytes (w / k other than 80 / 16, want_l0, pgx_sketch_batch) answers PGX_ESTATE as after a release. */
+int pgx_seqdb_compact_bytes(pgx_seqdb *db);
+/* HBM the side store of a compacted database holds (at most length + 64 bytes per flagged read, + 4 KiB); 0 before compaction and for a
+ * database without flagged reads. */
+uint64_t pgx_seqdb_side_bytes(const pgx_seqdb *db);
+/* One read's biseq bytes (rlen[rid] of them, cap >= that) as the seqdb file holds them, to host memory, in whatever state the database is:
+ * from the bytes, or -- compacted -- from the side store / rebuilt from the packs.  After pgx_seqdb_release_bytes: PGX_ESTATE. */
+int pgx_seqdb_read_bytes(pgx_seqdb *db, uint32_t rid, uint8_t *out, size_t cap);
 uint64_t pgx_seqdb_bases(const pgx_seqdb *db);
 uint32_t pgx_seqdb_reads(const pgx_seqdb *db);
 

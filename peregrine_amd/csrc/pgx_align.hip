@@ -248,6 +248,20 @@ __global__ __launch_bounds__(64) void k_align1(const uint8_t *__restrict__ seq, 
                                               int ring, pgx_match *__restrict__ out) {
   if (blockIdx.x < n) align_one_per_wave<PACKED>(seq, roff, rlen, keys, blockIdx.x, band, ring, out);
 }
+// k_align1 on the packs of a COMPACTED database (pgx_side.hip), the only one that pays for the look-up: a candidate that touches a read
+// without 2-bit codes is not aligned here but appended to hand_list (count at *hand_n) for k_align1_list on the byte view
+__global__ __launch_bounds__(64) void k_align1_handon(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ roff,
+                                                     const uint32_t *__restrict__ rlen, const pgx_align_key *__restrict__ keys, uint32_t n, int band,
+                                                     int ring, pgx_match *__restrict__ out, const uint32_t *__restrict__ nflag,
+                                                     uint32_t *__restrict__ hand_n, uint32_t *__restrict__ hand_list) {
+  if (blockIdx.x >= n) return;
+  const pgx_align_key key = keys[blockIdx.x];
+  if ((nflag[key.rid0] | nflag[key.rid1]) & 1u) {   // (uniform over the wavefront)
+    if (threadIdx.x == 0) hand_list[atomicAdd(hand_n, 1u)] = blockIdx.x;
+    return;
+  }
+  align_one_per_wave<true>(seq, roff, rlen, keys, blockIdx.x, band, ring, out);
+}
 // the same over a device-resident list of candidates (the ones a grouped launch handed on: reads with ambiguous bases, and the
 // STRAGGLERS -- round 3: at C4 scale ~600 of 9 M candidates of a launch run through low-complexity sequence with a band of up to 100
 // diagonals for thousands of steps; 8 lanes take 13 rounds per step for them, and the launch waited ~100 ms for them alone
@@ -666,6 +680,8 @@ static SeqSource seq_packed(const pgx_seqdb *db) { return {reinterpret_cast<cons
 struct AlignSources {
   SeqSource grouped;   // k_align_ph
   SeqSource one;       // k_align1 / k_align1_list
+  bool compacted;      // the packs serve both, except candidates on a read without 2-bit codes: those are handed on to the byte forms on a
+                       // byte view (the side store + partners unpacked on demand, pgx_side.hip) that dev_align builds once it knows them
 };
 // The one decision of what the kernels of a launch read.  grouped_n: the alignments of the launch's k_align_ph, which may build the
 // packs; < 0: the launch has none (k_align1 alone).  (The knobs are read per call: the parity tests walk every form inside one process.)
@@ -677,7 +693,13 @@ struct AlignSources {
 //  - seq_packs() == nullptr (no HBM for the packs): the bytes.
 //  - after pgx_seqdb_release_bytes the knobs that ask for the bytes are ignored; with neither bytes nor packs: PGX_ESTATE, so that no
 //    kernel is launched on a null sequence.
+//  - a compacted database (pgx_seqdb_compact_bytes: packs valid, no read beyond 65,535 bases, flagged reads in the side store): the packs
+//    for every kernel, whatever the knobs say, and `compacted` set.
 static AlignSources align_source(const pgx_seqdb *db, long grouped_n) {
+  if (seq_compacted(db)) {
+    PGX_REQUIRE(seq_packs_valid(db), PGX_ESTATE, "the seqdb's bytes were compacted (pgx_seqdb_compact_bytes) and its packs are gone");
+    return {seq_packed(db), seq_packed(db), true};
+  }
   const bool has_bytes = db->d_seq.p != nullptr, short_reads = db->max_rlen <= 65535u;
   const char *p1 = getenv("PGX_ALIGN1_PACKED");
   const bool one_packed = seq_packs_valid(db) && db->n_flagged_reads == 0 && short_reads && (!has_bytes || !(p1 && atoi(p1) == 0));
@@ -687,7 +709,7 @@ static AlignSources align_source(const pgx_seqdb *db, long grouped_n) {
                               (!has_bytes || (packed_min >= 0 && (grouped_n >= packed_min || seq_packs_valid(db)))) && seq_packs(db) != nullptr;
   PGX_REQUIRE(has_bytes || (one_packed && (grouped_n < 0 || grouped_packed)), PGX_ESTATE,
               "the seqdb's bytes were released (pgx_seqdb_release_bytes) and its packs are gone");
-  return {grouped_packed ? seq_packed(db) : seq_bytes(db), one_packed ? seq_packed(db) : seq_bytes(db)};
+  return {grouped_packed ? seq_packed(db) : seq_bytes(db), one_packed ? seq_packed(db) : seq_bytes(db), false};
 }
 // the instance of a kernel that reads `s` (on_packs / on_bytes: its PACKED / byte form; the first two parameters: sequence, offsets)
 template <typename K, typename... A>
@@ -724,6 +746,26 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
   while (ring < 2 * band + 8) ring <<= 1;
   hipStream_t st = ctx().stream;
   const AlignSources src = align_source(db, small ? -1 : (long)n);
+  if (small && src.compacted) {
+    // the packs for every candidate they can serve; the others (count and list in the hand-on block: [0] count, [4 ..) request numbers) on the
+    // byte view of their reads.  The count comes to the host to size the view's scratch: one small sync per launch of a compacted database.
+    uint32_t *hand = ws<uint32_t>("align.handon", n + 4);
+    PGX_HIP(hipMemsetAsync(hand, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_align1_handon, dim3((unsigned)n), dim3(64), ring * sizeof(int32_t), st, src.one.seq, src.one.off, db->d_rlen.p, d_keys, (uint32_t)n,
+                       band, ring, d_out, db->d_nflag.p, hand, hand + 4);
+    PGX_HIP(hipGetLastError());
+    uint32_t nh = 0;
+    PGX_HIP(hipMemcpyAsync(&nh, hand, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    sync();
+    if (nh) {
+      ByteView view;
+      side_view_of_keys(db, d_keys, hand + 4, nh, view);
+      hipLaunchKernelGGL(k_align1_list<false>, dim3(std::min<unsigned>(nh, (unsigned)ctx().num_cu * 32)), dim3(64), ring * sizeof(int32_t), st, view.seq,
+                         view.off, db->d_rlen.p, d_keys, hand, hand + 4, band, ring, d_out);
+      PGX_HIP(hipGetLastError());
+    }
+    return;
+  }
   if (small) {
     launch_on(src.one, k_align1<true>, k_align1<false>, dim3((unsigned)n), dim3(64), ring * sizeof(int32_t), db->d_rlen.p, d_keys, (uint32_t)n, band,
               ring, d_out);
@@ -791,7 +833,25 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
     // candidates on reads with ambiguous bases: the same phase machine on the seqdb bytes, eight per wavefront, from their list (round 3 gave
     // each a wavefront of its own through k_align1_list: 5 % of the reads flagged = +64 % alignment time at c3).  Only when the database
     // holds such a read at all.
-    if (db->n_flagged_reads)
+    if (src.compacted) {
+      // a compacted database: the candidates the packed launch handed on run the same byte-wise phase machine on the byte view of their reads
+      // (the side store + their unflagged partners, unpacked now); its stragglers go to a list of their own, for k_align1_list on that view.
+      // The number of such candidates comes to the host to size the view's scratch: one small sync per large launch of a compacted database.
+      uint32_t nf = 0;
+      PGX_HIP(hipMemcpyAsync(&nf, esc + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      sync();
+      if (nf) {
+        ByteView view;
+        side_view_of_keys(db, d_keys, esc + 4 + n, nf, view);
+        uint32_t *esc2 = ws<uint32_t>("align.esc_view", (size_t)nf + 4);
+        PGX_HIP(hipMemsetAsync(esc2, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL((k_align_ph<uint16_t, false>), dim3((unsigned)std::min<size_t>(nf / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds, st, view.seq, view.off,
+                           db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out, esc + 2, esc + 1, esc + 4 + n, esc2, esc2 + 4, (const uint32_t *)nullptr,
+                           segment(nf / 16 + 1), iter_limit);
+        hipLaunchKernelGGL(k_align1_list<false>, dim3(std::min<unsigned>(nf, (unsigned)ctx().num_cu * 32)), dim3(64), ring * sizeof(int32_t), st, view.seq,
+                           view.off, db->d_rlen.p, d_keys, esc2, esc2 + 4, band, ring, d_out);
+      }
+    } else if (db->n_flagged_reads)
       launch_on(seq_bytes(db), k_align_ph<uint16_t, true>, ph_bytes, dim3((unsigned)std::min<size_t>(n / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds,
                 db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out, esc + 2, esc + 1, esc + 4 + n, esc, esc + 4, nullptr, segment(n / 16 + 1),
                 iter_limit);

@@ -896,6 +896,60 @@ int pgx_seqdb_release_bytes(pgx_seqdb *db) {
 }
 int pgx_seqdb_has_bytes(const pgx_seqdb *db) { return db && db->d_seq.p ? 1 : 0; }
 
+// The bytes of a database WITH ambiguous bases out of HBM: compaction (pgx_side.hip).  The packs serve every read they can; the bytes of the
+// flagged reads alone stay, in a side store; the byte-wise kernels (run-by-run sketch, nibble-wise alignment) read a byte view of the
+// reads a call touches -- the side store plus the unflagged partners' bytes rebuilt from the packs for that call.  Without a flagged read this is
+// pgx_seqdb_release_bytes.  Refused (PGX_ESTATE, bytes kept, nothing changed): a read beyond 65,535 bases, no packs, or bytes that are gone
+// already with no side store to show for them.
+int pgx_seqdb_compact_bytes(pgx_seqdb *db) {
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(db, PGX_EARG, "pgx_seqdb_compact_bytes: null argument");
+    if (seq_compacted(db)) return PGX_OK;   // (compacted already)
+    if (!db->d_seq.p) {
+      PGX_REQUIRE(db->n_flagged_reads == 0 && seq_packs_valid(db), PGX_ESTATE, "pgx_seqdb_compact_bytes: the bytes are gone and there is no side store: nothing to compact from");
+      return PGX_OK;   // (released: a database without flagged reads has nothing to keep)
+    }
+    PGX_REQUIRE(db->max_rlen <= 65535u, PGX_ESTATE, "pgx_seqdb_compact_bytes: a read of %u bases (> 65,535) needs the byte-wise alignment kernel for every candidate: bytes kept", db->max_rlen);
+    PGX_REQUIRE(seq_packs(db) != nullptr, PGX_ESTATE, "pgx_seqdb_compact_bytes: the 2-bit packs could not be built: bytes kept");
+    pgx::sync();
+    if (db->n_flagged_reads) side_build(db);
+    if (db->borrowed) db->d_seq.p = nullptr, db->d_seq.n = 0;
+    else db->d_seq.release();
+    return PGX_OK;
+  });
+}
+uint64_t pgx_seqdb_side_bytes(const pgx_seqdb *db) { return db ? side_store_bytes(db) : 0; }
+
+// One read's biseq bytes as the file holds them, whatever the database's state: from the seqdb bytes, or -- compacted -- from the byte view of
+// that read (the side store, or k_unpack_reads on its packs).  A released database (no bytes, no side store) answers PGX_ESTATE.
+int pgx_seqdb_read_bytes(pgx_seqdb *db, uint32_t rid, uint8_t *out, size_t cap) {
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(db && out, PGX_EARG, "pgx_seqdb_read_bytes: null argument");
+    PGX_REQUIRE(rid < db->rlen_by_rid.size() && cap >= db->rlen_by_rid[rid], PGX_EARG, "pgx_seqdb_read_bytes: rid %u out of range, or the buffer is shorter than the read", rid);
+    const uint32_t len = db->rlen_by_rid[rid];
+    if (!len) return PGX_OK;
+    if (db->d_seq.p) {
+      PGX_HIP(hipMemcpyAsync(out, db->d_seq.p + db->roff_by_rid[rid], len, hipMemcpyDeviceToHost, ctx().stream));
+      pgx::sync();
+      return PGX_OK;
+    }
+    PGX_REQUIRE(seq_compacted(db), PGX_ESTATE, "pgx_seqdb_read_bytes: the seqdb's bytes were released (pgx_seqdb_release_bytes)");
+    const ReadDesc rd{0, len, rid};
+    DevBuf<ReadDesc> d_rd(1);
+    d_rd.upload(&rd, 1);
+    ByteView view;
+    side_view_of_reads(db, d_rd.p, nullptr, 1, view);
+    uint64_t off = 0;
+    PGX_HIP(hipMemcpyAsync(&off, view.off + rid, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx().stream));
+    pgx::sync();
+    PGX_HIP(hipMemcpyAsync(out, view.seq + off, len, hipMemcpyDeviceToHost, ctx().stream));
+    pgx::sync();
+    return PGX_OK;
+  });
+}
+
 void pgx_seqdb_free(pgx_seqdb *db) { delete db; }   // (what the library kept for the job on this database goes with it: pgx_seqdb::caches)
 uint64_t pgx_seqdb_bases(const pgx_seqdb *db) { return db ? db->bases : 0; }
 uint32_t pgx_seqdb_reads(const pgx_seqdb *db) { return db ? (uint32_t)db->rid.size() : 0; }

@@ -208,6 +208,10 @@ struct pgx_seqdb {
   mutable bool locus_key_filled = false, locus_ordered = false;   // (ordered: the packs' reads are laid out by locus key, not in file order)
   mutable bool packs_built = false, packs_failed = false;   // (failed: no HBM for them -- the byte-wise kernels serve this database)
   mutable uint32_t n_flagged_reads = 0;                     // reads marked in d_nflag (known once the packs are built)
+  // the side store of a COMPACTED database (pgx_side.hip, pgx_seqdb_compact_bytes): the bytes of the flagged reads only, kept when d_seq goes
+  pgx::DevBuf<uint8_t> d_side;      // [16 zero bytes | a slot per flagged read, ascending rid | 1 KiB of zero padding]
+  pgx::DevBuf<uint32_t> d_side_rid; // the flagged rids, ascending
+  pgx::DevBuf<uint64_t> d_side_off; // byte offset in d_side of each one's first base (congruent mod 16 to its seqdb offset)
   pgx::DevBuf<uint64_t> d_roff;    // indexed by rid
   pgx::DevBuf<uint32_t> d_rlen;    // indexed by rid
   std::vector<uint32_t> rid, rlen; // idx-file order
@@ -265,6 +269,26 @@ bool seq_packs_valid(const pgx_seqdb *db);
 uint64_t *seq_locus_key_buffer(const pgx_seqdb *db);
 void locus_key_add_mm(const pgx_seqdb *db, const pgx_mm128 *d_mm, size_t n);
 void locus_key_add_records(const pgx_seqdb *db, const uint64_t *d_key0, const uint64_t *d_y0, size_t n);
+
+// ---- a compacted database (pgx_side.hip): the whole-seqdb bytes are gone, the packs serve what they can, and the byte-wise kernels read a
+// BYTE VIEW -- the side store (flagged reads, as in the file) plus a scratch region into which k_unpack_reads rebuilds the bytes of the
+// unflagged reads a call needs (shmr_utils.c:44-51 backwards).  seq + off[rid] is the read's first base, at an address congruent mod 16 to its
+// seqdb offset (the tile loads of the sketch kernels take the same path as on the seqdb); off[] counts from the side store and wraps modulo
+// 2^64 into the scratch region.  Only the entries of the reads the view was built for are valid.  The view's scratch goes back to the block
+// cache with it (stream-ordered: kernels enqueued before that still read it safely).
+inline bool seq_compacted(const pgx_seqdb *db) { return db->d_seq.p == nullptr && db->d_side.p != nullptr; }
+struct ByteView {
+  const uint8_t *seq = nullptr;
+  const uint64_t *off = nullptr;   // by rid
+  DevBuf<uint8_t> scratch;
+};
+void side_build(pgx_seqdb *db);    // the side store from the bytes (which must be there, the packs built, every read <= 65,535 bases)
+uint64_t side_store_bytes(const pgx_seqdb *db);
+// the view for both reads of the candidates keys[list[0 .. n)], and for the reads of the slots d_reads[list[0 .. n)]
+void side_view_of_keys(const pgx_seqdb *db, const pgx_align_key *d_keys, const uint32_t *d_list, uint32_t n, ByteView &v);
+void side_view_of_reads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n, ByteView &v);
+// tr[i] = d_reads[list[i]] with its offset in the view, iota[i] = i
+void side_translate_reads(const ByteView &v, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n, ReadDesc *tr, uint32_t *iota);
 
 // Large host arrays.  Never value-initialised (they are about to be overwritten); from 16 MiB up they are pooled anonymous
 // mappings advised to use transparent huge pages, which the allocator would not do for us (THP is in "madvise" mode on

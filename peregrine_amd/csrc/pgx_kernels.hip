@@ -176,7 +176,8 @@ void dev_count(const pgx_mm128 *d_in, size_t n, int kmer_bits, DevBuf<pgx_mm_cou
 // =========================================================================================================
 bool sketch_wave_eligible(const ReadDesc &rd, int w, int k);  // pgx_sketch_fast.hip
 void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int w,
-                        int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags);
+                        int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
+                        const uint8_t *bytes = nullptr);   // bytes: the byte view of a compacted database that d_reads' offsets count from
 bool sketch_fused_supported(int w, int rs, int levels);
 bool sketch_blk_supported(int w, int k, int rs, int levels);
 void launch_sketch_blk(const pgx_seqdb *db, const ReadDesc *d_reads, uint32_t n, int rs, int levels, pgx_mm128 *d_slab,
@@ -402,8 +403,10 @@ __global__ __launch_bounds__(64) void k_sketch_general(const uint8_t *__restrict
 // Entry scratch (hash, position|strand, window minimum, two running-extremum arrays: 36 B per base) in batches of at most
 // ~256 Mbases.
 void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list,
-                           int w, int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags) {
+                           int w, int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
+                           const uint8_t *bytes = nullptr) {   // bytes: the byte view of a compacted database that d_reads' offsets count from (nullptr: the seqdb)
   hipStream_t st = ctx().stream;
+  if (!bytes) bytes = db->d_seq.p;
   const uint64_t batch_bases = 256ull << 20;
   DevBuf<uint32_t> iota;
   if (!d_list) {   // the kernel walks a list: the identity
@@ -425,8 +428,8 @@ void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const s
     uint32_t *PY = ws<uint32_t>("sk.gen_py", acc);
     PGX_HIP(hipMemcpyAsync(d_so, so.data(), so.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     const unsigned grid = (unsigned)std::min<size_t>(b1 - b0, (size_t)ctx().num_cu * 16);
-    PGX_REQUIRE(db->d_seq.p, PGX_ESTATE, "the seqdb's bytes were released (pgx_seqdb_release_bytes): the general sketch kernel (other w / k, L0 output) needs them");
-    hipLaunchKernelGGL(k_sketch_general, dim3(grid), dim3(64), 0, st, db->d_seq.p, d_reads, d_list + b0, (uint32_t)(b1 - b0), w, k,
+    PGX_REQUIRE(bytes, PGX_ESTATE, "the seqdb's bytes were released (pgx_seqdb_release_bytes): the general sketch kernel (other w / k, L0 output) needs them");
+    hipLaunchKernelGGL(k_sketch_general, dim3(grid), dim3(64), 0, st, bytes, d_reads, d_list + b0, (uint32_t)(b1 - b0), w, k,
                        d_so, H, PY, WMv, T1, T2, d_slab, d_slab_off, d_counts, d_flags);
     PGX_HIP(hipGetLastError());
     sync();  // (so[] is reused by the next batch)

@@ -1032,7 +1032,12 @@ bool sketch_wave_eligible(const ReadDesc &rd, int w, int k) {
 template <bool FUSED, int A>
 static void launch_w(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n, pgx_mm128 *d_slab,
                      const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags, int rs, int levels, uint32_t *d_need = nullptr,
-                     int off_by_list = 0) {
+                     int off_by_list = 0, const uint8_t *bytes = nullptr) {   // bytes: the byte view d_reads' offsets count from (a compacted database)
+  if (!FUSED && bytes) {
+    hipLaunchKernelGGL((k_sketch_wave<FUSED, A>), dim3(n), dim3(64), 0, ctx().stream, bytes, d_reads, d_list, n, d_slab,
+                       d_slab_off, d_counts, d_flags, rs, levels, d_need, off_by_list, (const uint64_t *)nullptr, (const uint32_t *)nullptr);
+    return;
+  }
   if (FUSED && sketch_from_packs(db)) {   // (round 6: from the 2-bit packs once they exist)
     hipLaunchKernelGGL((k_sketch_wave<FUSED, A, true>), dim3(n), dim3(64), 0, ctx().stream, reinterpret_cast<const uint8_t *>(db->d_pack.p), d_reads, d_list, n,
                        d_slab, d_slab_off, d_counts, d_flags, rs, levels, d_need, off_by_list, db->d_poff.p, db->d_nflag.p);
@@ -1044,14 +1049,14 @@ static void launch_w(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_
 }
 
 void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int w,
-                        int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags) {
+                        int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags, const uint8_t *bytes) {
   (void)k;
   if (!n_list) return;
   switch (w) {
-    case 64: launch_w<false, 4>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0); break;
-    case 80: launch_w<false, 5>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0); break;
-    case 96: launch_w<false, 6>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0); break;
-    case 128: launch_w<false, 8>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0); break;
+    case 64: launch_w<false, 4>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0, nullptr, 0, bytes); break;
+    case 80: launch_w<false, 5>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0, nullptr, 0, bytes); break;
+    case 96: launch_w<false, 6>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0, nullptr, 0, bytes); break;
+    case 128: launch_w<false, 8>(db, d_reads, d_list, n_list, d_slab, d_slab_off, d_counts, d_flags, 0, 0, nullptr, 0, bytes); break;
     default: PGX_REQUIRE(false, PGX_EARG, "window %d has no closed-form kernel", w);
   }
   PGX_HIP(hipGetLastError());

@@ -37,10 +37,12 @@
 namespace pgx {
 
 void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int w, int k,
-                        pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags);   // pgx_sketch_fast.hip
+                        pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
+                        const uint8_t *bytes = nullptr);   // pgx_sketch_fast.hip; bytes: the byte view d_reads' offsets count from (nullptr: the seqdb)
 bool sketch_wave_eligible(const ReadDesc &rd, int w, int k);
 void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list,
-                           int w, int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags);   // pgx_kernels.hip
+                           int w, int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
+                           const uint8_t *bytes = nullptr);   // pgx_kernels.hip
 
 namespace {
 
@@ -364,8 +366,21 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
   nl0_off.alloc((size_t)nn + 1);
   if (nn == 0) return;
   hipStream_t st = ctx().stream;
-  PGX_REQUIRE(db->d_seq.p, PGX_ESTATE, "the seqdb's bytes were released (pgx_seqdb_release_bytes): reads with ambiguous bases are sketched from them");
-  const uint8_t *seq = db->d_seq.p;
+  // A compacted database (pgx_side.hip): the listed reads on the byte view -- the flagged ones in the side store, any other one (the universal
+  // fallback above) unpacked from the packs first --, through descriptors of their own whose offsets count from the view's base.  The
+  // kernels below are the same, on bytes equal to the file's at addresses congruent mod 16 to the file's.
+  ByteView view;
+  DevBuf<ReadDesc> tr;
+  DevBuf<uint32_t> tr_list;
+  const bool compacted = seq_compacted(db);
+  if (compacted) {
+    side_view_of_reads(db, d_reads, d_list, nn, view);
+    tr.alloc(nn), tr_list.alloc(nn);
+    side_translate_reads(view, d_reads, d_list, nn, tr.p, tr_list.p);
+    d_reads = tr.p, d_list = tr_list.p;
+  }
+  PGX_REQUIRE(compacted || db->d_seq.p, PGX_ESTATE, "the seqdb's bytes were released (pgx_seqdb_release_bytes): reads with ambiguous bases are sketched from them");
+  const uint8_t *seq = compacted ? view.seq : db->d_seq.p;
   // segments
   DevBuf<uint64_t> seg_off((size_t)nn + 1);
   hipLaunchKernelGGL(k_nseg_scan<false>, dim3(nn), dim3(64), 0, st, seq, d_reads, d_list, nn, seg_off.p, (const uint64_t *)nullptr,
@@ -395,7 +410,7 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
       PGX_HIP(hipMemsetAsync(vcnt.p, 0, ns * sizeof(uint32_t), st));
       PGX_HIP(hipMemsetAsync(vflag.p, 0, ns * sizeof(uint32_t), st));
       if (wave) {
-        launch_sketch_wave(db, vdesc.p, nullptr, (uint32_t)ns, w, k, vslab.p, vslab_off.p, vcnt.p, vflag.p);
+        launch_sketch_wave(db, vdesc.p, nullptr, (uint32_t)ns, w, k, vslab.p, vslab_off.p, vcnt.p, vflag.p, compacted ? seq : nullptr);
       } else {
         if (hdesc.empty()) {
           hdesc.resize(ns);
@@ -404,7 +419,7 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
           lens.resize(ns);
           for (uint64_t i = 0; i < ns; ++i) lens[i] = hdesc[i].len;
         }
-        launch_sketch_general(db, vdesc.p, lens, nullptr, w, k, vslab.p, vslab_off.p, vcnt.p, vflag.p);
+        launch_sketch_general(db, vdesc.p, lens, nullptr, w, k, vslab.p, vslab_off.p, vcnt.p, vflag.p, compacted ? seq : nullptr);
       }
       uint32_t *d_nbad = ws<uint32_t>("nsk.nbad", 1);
       PGX_HIP(hipMemsetAsync(d_nbad, 0, sizeof(uint32_t), st));

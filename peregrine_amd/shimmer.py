@@ -134,9 +134,33 @@ class ResidentDB:
         self._adopted = None
         return True
 
+    def compact_bytes(self) -> bool:
+        """release_bytes for a database WITH ambiguous bases (pgx_seqdb_compact_bytes): the bytes of the flagged reads alone stay in HBM (a side
+        store), the packs serve everything else, and the byte-wise kernels read those reads' partners from bytes rebuilt out of the packs for
+        the call.  Without a flagged read it is release_bytes.  Returns False -- bytes kept, nothing changed -- for a database with a read beyond
+        65,535 bases; True: an adopted device buffer is no longer referenced (this object drops its hold on it)."""
+        rc = self._lib.pgx_seqdb_compact_bytes(self.h)
+        if rc == _lib.PGX_ESTATE:
+            return False
+        _lib.check(rc, "pgx_seqdb_compact_bytes")
+        self._adopted = None
+        return True
+
     @property
     def has_bytes(self) -> bool:
         return bool(self._lib.pgx_seqdb_has_bytes(self.h))
+
+    @property
+    def side_bytes(self) -> int:
+        """HBM the side store of a compacted database holds (0 before compact_bytes, and without flagged reads)"""
+        return int(self._lib.pgx_seqdb_side_bytes(self.h))
+
+    def read_bytes(self, rid: int, length: int) -> np.ndarray:
+        """the `length` biseq bytes of read `rid` as the seqdb file holds them (pgx_seqdb_read_bytes): from the bytes, or -- compacted -- from
+        the side store / rebuilt from the packs"""
+        out = np.zeros(int(length), np.uint8)
+        _lib.check(self._lib.pgx_seqdb_read_bytes(self.h, int(rid), _ptr(out), len(out)), "pgx_seqdb_read_bytes")
+        return out
 
     def close(self):
         if self.h:
