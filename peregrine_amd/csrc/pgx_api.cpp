@@ -547,9 +547,6 @@ int pgx_device_count(void) {
   return n;
 }
 
-static double wall_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 int pgx_init(int device) {
   return guarded([&]() -> int {
     Context &c = ctx();

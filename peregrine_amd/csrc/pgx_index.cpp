@@ -1,17 +1,10 @@
 // pgx_index.cpp -- the index stage: what main() of /root/reference/src/shmr_index.c:37-245 does for one chunk,
 // with sketch / reduce / count on the GPU.  Host work here is read selection, file naming and file IO only.
-#include <chrono>
-
 #include "pgx_internal.h"
 
 using namespace pgx;
 
 namespace {
-
-double now_ms() {
-  using namespace std::chrono;
-  return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 void check_params(const pgx_index_params *p) {
   PGX_REQUIRE(p, PGX_EARG, "null params");
@@ -34,7 +27,7 @@ void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, 
   ++index_generation();   // every index-stage call rewrites the "ix.*" workspaces: views of them handed out earlier are stale now
   memset(out, 0, sizeof(*out));
   if (keep) keep->valid = false;
-  const double t0 = now_ms();
+  const double t0 = wall_ms();
   // read selection: rid % total == mychunk % total, in idx-file order (shmr_index.c:155-157); kept with the seqdb for the next call
   static uint64_t use_clock = 0;
   pgx_seqdb::IndexPlan *found = nullptr;
@@ -68,63 +61,54 @@ void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, 
   out->reads = (uint32_t)reads.size();
   const int kbits = 2 * p->kmer;
   const bool trace = getenv("PGX_TRACE") != nullptr;
-  if (trace) fprintf(stderr, "[pgx] index: read selection %.2f ms\n", now_ms() - t0);
+  if (trace) fprintf(stderr, "[pgx] index: read selection %.2f ms\n", wall_ms() - t0);
 
-  // fast path: everything of the chunk goes through the wave kernel and the in-LDS reduce (pg_run.py's defaults)
-  if (!p->want_l0) {
-    const pgx_mm128 *d_top = nullptr;
-    size_t ntop = 0;
-    if (dev_index_fused(db, reads, p->window, p->kmer, p->reduction, p->levels, &d_top, &ntop, &plan, &out->reads_literal)) {
-      PGX_REQUIRE(ntop < (1ULL << 31), PGX_EARG, "chunk too large (use more index chunks)");
+  // The final-level list on the device: the fused path (closed-form kernels fused with the per-read reduce: pg_run.py's defaults) where it
+  // takes the chunk, else -- other (w, k), or the level-0 list is wanted too -- sketch, then one list-wide reduce per level.
+  const pgx_mm128 *d_top = nullptr;
+  size_t ntop = 0;
+  DevBuf<pgx_mm128> l0, l1, l2;
+  const bool fused = !p->want_l0 && dev_index_fused(db, reads, p->window, p->kmer, p->reduction, p->levels, &d_top, &ntop, &plan, &out->reads_literal);
+  if (!fused) {
+    size_t n0 = 0, n1 = 0, n2 = 0;
+    dev_sketch(db, reads, p->window, p->kmer, l0, n0, &out->reads_literal);
+    PGX_REQUIRE(n0 < (1ULL << 31), PGX_EARG, "chunk too large: %zu L0 minimizers (use more index chunks)", n0);
+    if (p->want_l0) {
       DevBuf<pgx_mm_count> mc;
       size_t nmc = 0;
-      dev_count(d_top, ntop, kbits, mc, nmc);
-      out->n_top = ntop, out->n_top_mc = nmc;
-      if (host_arrays) {
-        out->top = (pgx_mm128 *)out_alloc(ntop ? ntop * sizeof(pgx_mm128) : 1);
-        if (ntop) PGX_HIP(hipMemcpyAsync(out->top, d_top, ntop * sizeof(pgx_mm128), hipMemcpyDeviceToHost, ctx().stream));
-        out->top_mc = download_list(mc, nmc);
-      }
+      dev_count(l0.p, n0, kbits, mc, nmc);
+      out->l0 = download_list(l0, n0), out->n_l0 = n0;
+      out->l0_mc = download_list(mc, nmc), out->n_l0_mc = nmc;
       sync();
-      if (trace) fprintf(stderr, "[pgx] index: counts (+ downloads) done at +%.2f ms\n", now_ms() - t0);
-      if (keep) keep->d_top = d_top, keep->n_top = ntop, keep->mc = std::move(mc), keep->n_mc = nmc, keep->valid = true;
-      timing_flush();
-      out->gpu_ms = now_ms() - t0;
-      if (trace) fprintf(stderr, "[pgx] index: stage total %.2f ms\n", out->gpu_ms);
-      return;
+    }
+    dev_reduce(l0.p, n0, p->reduction, l1, n1);
+    l0.release();
+    d_top = l1.p, ntop = n1;
+    if (p->levels > 1) {
+      dev_reduce(l1.p, n1, p->reduction, l2, n2);
+      l1.release();
+      d_top = l2.p, ntop = n2;
     }
   }
-  DevBuf<pgx_mm128> l0, l1, l2;
-  size_t n0 = 0, n1 = 0, n2 = 0;
-  dev_sketch(db, reads, p->window, p->kmer, l0, n0, &out->reads_literal);
-  PGX_REQUIRE(n0 < (1ULL << 31), PGX_EARG, "chunk too large: %zu L0 minimizers (use more index chunks)", n0);
-  if (p->want_l0) {
-    DevBuf<pgx_mm_count> mc;
-    size_t nmc = 0;
-    dev_count(l0.p, n0, kbits, mc, nmc);
-    out->l0 = download_list(l0, n0), out->n_l0 = n0;
-    out->l0_mc = download_list(mc, nmc), out->n_l0_mc = nmc;
-    sync();
-  }
-  dev_reduce(l0.p, n0, p->reduction, l1, n1);
-  l0.release();
-  const DevBuf<pgx_mm128> *top = &l1;
-  size_t ntop = n1;
-  if (p->levels > 1) {
-    dev_reduce(l1.p, n1, p->reduction, l2, n2);
-    l1.release();
-    top = &l2, ntop = n2;
-  }
+  // count -> download -> timing.  (The fused path's list lives in the index workspace: `keep` hands it on as it is.)
   if (p->levels >= 1) {
+    PGX_REQUIRE(ntop < (1ULL << 31), PGX_EARG, "chunk too large (use more index chunks)");
     DevBuf<pgx_mm_count> mc;
     size_t nmc = 0;
-    dev_count(top->p, ntop, kbits, mc, nmc);
-    out->top = download_list(*top, ntop), out->n_top = ntop;
-    out->top_mc = download_list(mc, nmc), out->n_top_mc = nmc;
+    dev_count(d_top, ntop, kbits, mc, nmc);
+    out->n_top = ntop, out->n_top_mc = nmc;
+    if (host_arrays || !fused) {
+      out->top = (pgx_mm128 *)out_alloc(ntop ? ntop * sizeof(pgx_mm128) : 1);
+      if (ntop) PGX_HIP(hipMemcpyAsync(out->top, d_top, ntop * sizeof(pgx_mm128), hipMemcpyDeviceToHost, ctx().stream));
+      out->top_mc = download_list(mc, nmc);
+    }
     sync();
+    if (trace) fprintf(stderr, "[pgx] index: counts (+ downloads) done at +%.2f ms\n", wall_ms() - t0);
+    if (keep && fused) keep->d_top = d_top, keep->n_top = ntop, keep->mc = std::move(mc), keep->n_mc = nmc, keep->valid = true;
   }
   timing_flush();
-  out->gpu_ms = now_ms() - t0;
+  out->gpu_ms = wall_ms() - t0;
+  if (trace) fprintf(stderr, "[pgx] index: stage total %.2f ms\n", out->gpu_ms);
 }
 
 void write_counted(const std::string &path, const void *data, size_t n, size_t elem) {

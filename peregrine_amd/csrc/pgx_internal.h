@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -143,6 +144,7 @@ struct DevBuf {
   }
 };
 inline void sync() { PGX_HIP(hipStreamSynchronize(ctx().stream)); }
+inline double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // grow-only named device buffers that persist across calls (hipMalloc/hipFree are synchronous and slow)
 void *ws_raw(const char *name, size_t bytes);
@@ -248,8 +250,8 @@ namespace pgx {
 // L0 minimizers of the given reads (device array of ReadDesc, in output order). Returns device list.
 void dev_sketch(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, int k, DevBuf<pgx_mm128> &out,
                 size_t &n_out, uint32_t *n_literal);
-// fused index path: sketch (wave kernel) -> per-read reduce x levels in LDS -> ordered gather.  Returns false (and
-// leaves the outputs untouched) when the chunk needs the general path (other w/k ...).
+// fused index path: k_sketch_blk, or k_sketch_wave -> per-read reduce x levels in LDS; redo passes for the reads they flag; ordered
+// gather.  Returns false (and leaves the outputs untouched) when the chunk needs the general path (other w/k ...).
 // plan: the database's selection of `reads`, whose descriptors and slab offsets stay on the device with it (nullptr: uploaded for this call only)
 bool dev_index_fused(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, int k, int rs, int levels,
                      const pgx_mm128 **d_top, size_t *n_top, pgx_seqdb::IndexPlan *plan = nullptr, uint32_t *n_second = nullptr);   // n_second: reads sketched run by run (ambiguous bases)
@@ -257,6 +259,34 @@ bool dev_index_fused(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, in
 void dev_reduce(const pgx_mm128 *d_in, size_t n, int rs, DevBuf<pgx_mm128> &out, size_t &n_out);
 // multiplicity of x>>8, sorted by mer
 void dev_count(const pgx_mm128 *d_in, size_t n, int kmer_bits, DevBuf<pgx_mm_count> &out, size_t &n_out);
+// ---- the index stage's launchers and helpers, shared by pgx_kernels.hip, pgx_sketch_fast.hip and pgx_sketch_n.hip -----------------------
+// bytes: the byte view of a compacted database that d_reads' offsets count from (nullptr: the seqdb)
+bool sketch_wave_eligible(const ReadDesc &rd, int w, int k);
+void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int w, int k,
+                        pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags, const uint8_t *bytes = nullptr);
+void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list, int w,
+                           int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
+                           const uint8_t *bytes = nullptr);
+bool sketch_blk_supported(int w, int k, int rs, int levels);
+void launch_sketch_blk(const pgx_seqdb *db, const ReadDesc *d_reads, uint32_t n, int rs, int levels, pgx_mm128 *d_slab,
+                       const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags);
+void launch_sketch_fused_list(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int rs, int levels,
+                              pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
+                              uint32_t *d_need = nullptr, int off_by_list = 0);
+// the listed reads (slots of d_reads, ascending) cut into runs of unambiguous bases (pgx_sketch_n.hip): their level-0 lists packed in
+// list order, nl0[nl0_off[i] .. nl0_off[i+1]); reduced `levels` times per read: top[nl0_off[i] .. + cnt[i])
+void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t nn, int w, int k,
+                       DevBuf<pgx_mm128> &nl0, DevBuf<uint64_t> &nl0_off, uint64_t *n_total);
+void dev_reduce_nreads(const DevBuf<pgx_mm128> &nl0, const DevBuf<uint64_t> &nl0_off, uint32_t nn, uint64_t total, int rs, int levels,
+                       DevBuf<pgx_mm128> &top, DevBuf<uint32_t> &cnt);
+void dev_scatter_counts(uint32_t *d_counts_by_slot, const uint32_t *d_list, uint32_t nn, const uint64_t *d_off, const uint32_t *d_cnt);
+void dev_mark_slots(uint32_t *d_by_slot, const uint32_t *d_list, uint32_t nn, uint32_t v);
+// hipcub's two-call idiom, once each (size query, workspace, run, one number back, sync):
+// list = the i < n, ascending, with flags[i] != 0 and none of skip_bits set in it; returns how many
+uint32_t select_flagged(const uint32_t *d_flags, uint32_t n, uint32_t *d_list, uint32_t skip_bits = 0);
+// offs[0] = 0, offs[i + 1] = vals[0] + .. + vals[i] (n + 1 entries; vals == offs + 1 scans in place); returns offs[n]
+uint64_t scan_to_total(const uint32_t *d_vals, uint64_t *d_offs, size_t n);
+uint64_t scan_to_total(const uint64_t *d_vals, uint64_t *d_offs, size_t n);
 // banded O(ND) confirmation of n candidate alignments (keys on device)
 void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int band, pgx_match *d_out,
                int tail_batch = 0);   // tail_batch: 1 = the second request batch of a stage, 2 = a later one (mostly hard candidates: pgx_align.hip)

@@ -8,8 +8,6 @@
 //   k_reduce_*       : mm_reduce      src/shmr_reduce.c:53-90
 //   count            : mm_count       src/shmr_utils.c:131-160  radix sort + run-length
 //   k_align_ph       : ovlp_match     src/DWmatch.c:66-204      eight candidates per wavefront         (pgx_align.hip)
-#include <chrono>
-
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -174,37 +172,77 @@ void dev_count(const pgx_mm128 *d_in, size_t n, int kmer_bits, DevBuf<pgx_mm_cou
 // =========================================================================================================
 // sketch driver
 // =========================================================================================================
-bool sketch_wave_eligible(const ReadDesc &rd, int w, int k);  // pgx_sketch_fast.hip
-void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int w,
-                        int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
-                        const uint8_t *bytes = nullptr);   // bytes: the byte view of a compacted database that d_reads' offsets count from
-bool sketch_fused_supported(int w, int rs, int levels);
-bool sketch_blk_supported(int w, int k, int rs, int levels);
-void launch_sketch_blk(const pgx_seqdb *db, const ReadDesc *d_reads, uint32_t n, int rs, int levels, pgx_mm128 *d_slab,
-                       const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags);
-void launch_sketch_fused_list(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int rs,
-                              int levels, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
-                              uint32_t *d_need = nullptr, int off_by_list = 0);
-void launch_sketch_fused(const pgx_seqdb *db, const ReadDesc *d_reads, uint32_t n, int rs, int levels, pgx_mm128 *d_slab,
-                         const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags);
+// The flags of the reads (uint32 per read; non-zero: the read is unfinished, the bits say why) as hipcub select flags
+struct FlaggedFor {
+  uint32_t skip_bits;
+  __host__ __device__ bool operator()(uint32_t f) const { return f != 0 && !(f & skip_bits); }
+};
+uint32_t select_flagged(const uint32_t *d_flags, uint32_t n, uint32_t *d_list, uint32_t skip_bits) {
+  hipStream_t st = ctx().stream;
+  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> iota(0);
+  hipcub::TransformInputIterator<bool, FlaggedFor, const uint32_t *> flagged(d_flags, FlaggedFor{skip_bits});
+  uint32_t *d_num = ws<uint32_t>("ix.sel_n", 1);
+  size_t bytes = 0;
+  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flagged, d_list, d_num, (int)n, st));
+  void *tmp = ws_raw("ix.sel_tmp", bytes);
+  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, iota, flagged, d_list, d_num, (int)n, st));
+  uint32_t num = 0;
+  PGX_HIP(hipMemcpyAsync(&num, d_num, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  sync();
+  return num;
+}
 
+template <typename T>
+static uint64_t scan_to_total_of(const T *d_vals, uint64_t *d_offs, size_t n) {
+  hipStream_t st = ctx().stream;
+  PGX_HIP(hipMemsetAsync(d_offs, 0, sizeof(uint64_t), st));
+  if (n == 0) return 0;
+  size_t bytes = 0;
+  PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, d_vals, d_offs + 1, (int)n, st));
+  void *tmp = ws_raw("ix.scan_tmp", bytes);
+  PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_vals, d_offs + 1, (int)n, st));
+  uint64_t total = 0;
+  PGX_HIP(hipMemcpyAsync(&total, d_offs + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  sync();
+  return total;
+}
+uint64_t scan_to_total(const uint32_t *d_vals, uint64_t *d_offs, size_t n) { return scan_to_total_of(d_vals, d_offs, n); }
+uint64_t scan_to_total(const uint64_t *d_vals, uint64_t *d_offs, size_t n) { return scan_to_total_of(d_vals, d_offs, n); }
+
+// slab of read i: len / slab_div + slab_min elements from off[i] on (off: n + 1 entries); returns the bases of the reads
+static uint64_t slab_offsets(const std::vector<ReadDesc> &reads, uint64_t slab_div, uint64_t slab_min, std::vector<uint64_t> &off) {
+  off.assign(reads.size() + 1, 0);
+  uint64_t bases = 0;
+  for (size_t i = 0; i < reads.size(); ++i) {
+    off[i + 1] = off[i] + (uint64_t)reads[i].len / slab_div + slab_min;
+    bases += reads[i].len;
+  }
+  return bases;
+}
+
+// Where a read's final list lives: in its own slab (slab + slab_off[slot]) unless the pass that finished it wrote elsewhere -- exact
+// slabs, the run-by-run path's lists -- and said so in src_of[slot] (nullptr: own slab; a later pass overwrites an earlier one's entry).
+__global__ void k_set_sources(const pgx_mm128 **__restrict__ src_of, const uint32_t *__restrict__ list, uint32_t n_list,
+                              const pgx_mm128 *__restrict__ base, const uint64_t *__restrict__ off) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_list) src_of[list[i]] = base + off[i];
+}
+static void set_sources(const pgx_mm128 **d_src_of, const uint32_t *d_list, uint32_t n_list, const pgx_mm128 *base, const uint64_t *d_off) {
+  if (n_list) hipLaunchKernelGGL(k_set_sources, dim3(cdiv(n_list, 256)), dim3(256), 0, ctx().stream, d_src_of, d_list, n_list, base, d_off);
+}
+__global__ void k_gather_slabs(const pgx_mm128 *__restrict__ slab, const uint64_t *__restrict__ slab_off,
+                               const pgx_mm128 *const *__restrict__ src_of, uint32_t n, const uint32_t *__restrict__ counts,
+                               const uint64_t *__restrict__ out_off, pgx_mm128 *__restrict__ out) {
+  const uint32_t slot = blockIdx.x;
+  if (slot >= n) return;
+  const pgx_mm128 *src = src_of[slot] ? src_of[slot] : slab + slab_off[slot];
+  pgx_mm128 *dst = out + out_off[slot];
+  const uint32_t c = counts[slot];
+  for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) dst[i] = src[i];
+}
 __global__ void k_need_of_list(const uint32_t *__restrict__ need, const uint32_t *__restrict__ list, uint32_t n, uint64_t *__restrict__ out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = need[list[i]];
-}
-// skip (optional): reads whose elements live elsewhere (the exact-size slabs of the second redo pass); off_by_list: slab_off is
-// indexed by the position in `list`
-__global__ void k_gather_slabs(const pgx_mm128 *__restrict__ slab, const uint64_t *__restrict__ slab_off,
-                               const uint32_t *__restrict__ list, uint32_t n_list, const uint32_t *__restrict__ counts,
-                               const uint64_t *__restrict__ out_off, pgx_mm128 *__restrict__ out,
-                               const uint32_t *__restrict__ skip = nullptr, int off_by_list = 0) {
-  if (blockIdx.x >= n_list) return;
-  const uint32_t slot = list ? list[blockIdx.x] : blockIdx.x;
-  if (skip && skip[slot]) return;
-  const pgx_mm128 *src = slab + slab_off[off_by_list ? blockIdx.x : slot];
-  pgx_mm128 *dst = out + out_off[slot];
-  const uint32_t n = counts[slot];
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 
 // Running extremum within blocks of w consecutive elements (block b = [b w, (b+1) w)), the whole wavefront walking the array 64
@@ -404,7 +442,7 @@ __global__ __launch_bounds__(64) void k_sketch_general(const uint8_t *__restrict
 // ~256 Mbases.
 void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list,
                            int w, int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
-                           const uint8_t *bytes = nullptr) {   // bytes: the byte view of a compacted database that d_reads' offsets count from (nullptr: the seqdb)
+                           const uint8_t *bytes) {
   hipStream_t st = ctx().stream;
   if (!bytes) bytes = db->d_seq.p;
   const uint64_t batch_bases = 256ull << 20;
@@ -437,13 +475,6 @@ void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const s
   }
 }
 
-void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t nn, int w, int k,
-                       DevBuf<pgx_mm128> &nl0, DevBuf<uint64_t> &nl0_off, uint64_t *n_total);   // pgx_sketch_n.hip
-void dev_reduce_nreads(const DevBuf<pgx_mm128> &nl0, const DevBuf<uint64_t> &nl0_off, uint32_t nn, uint64_t total, int rs, int levels,
-                       DevBuf<pgx_mm128> &top, DevBuf<uint32_t> &cnt);
-void dev_scatter_counts(uint32_t *d_counts_by_slot, const uint32_t *d_list, uint32_t nn, const uint64_t *d_off, const uint32_t *d_cnt);
-void dev_mark_slots(uint32_t *d_by_slot, const uint32_t *d_list, uint32_t nn, uint32_t v);
-
 // Level-0 minimizers of `reads`, one contiguous list in `reads` order.  Every read goes through the closed-form kernel of the
 // (w, k) -- k_sketch_wave for k = 16 and w in {64, 80, 96, 128}, k_sketch_general otherwise -- single pass into per-read slabs, then
 // an ordered gather; the reads it flags (an ambiguous base, a slab outgrown by low-complexity sequence) are cut into runs of
@@ -456,75 +487,50 @@ void dev_sketch(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, 
   const uint32_t n = (uint32_t)reads.size();
   if (n == 0) { out.alloc(0); return; }
   hipStream_t st = ctx().stream;
-  DevBuf<ReadDesc> d_reads(n);
-  d_reads.upload(reads.data(), n);
-  DevBuf<uint32_t> counts(n), d_flag(n);
-  DevBuf<uint64_t> offs(n + 1);
-  PGX_HIP(hipMemsetAsync(counts.p, 0, n * sizeof(uint32_t), st));
-  PGX_HIP(hipMemsetAsync(d_flag.p, 0, n * sizeof(uint32_t), st));
-
-  std::vector<uint64_t> slab_off(n + 1, 0);
   std::vector<uint32_t> lens(n);
-  uint64_t bases = 0;
-  // (w, k) outside the specialised kernel's set: the general closed-form kernel takes the wave kernel's place
-  const bool general = !(k == 16 && (w == 64 || w == 80 || w == 96 || w == 128));
   for (uint32_t i = 0; i < n; ++i) {
     PGX_REQUIRE(reads[i].len < (1u << 30), PGX_EARG, "read %u is longer than 2^30 bases", reads[i].rid);
-    // slab capacity: 5x the expected density 2/(w+1); a read that outgrows it (low complexity) takes the second path
-    slab_off[i + 1] = slab_off[i] + (uint64_t)reads[i].len / 8 + 64;
-    lens[i] = reads[i].len, bases += reads[i].len;
+    lens[i] = reads[i].len;
   }
-  DevBuf<uint64_t> d_slab_off(n + 1);
-  d_slab_off.upload(slab_off.data(), n + 1);
+  // slab capacity: 5x the expected density 2/(w+1); a read that outgrows it (low complexity) takes the second path
+  std::vector<uint64_t> slab_off;
+  const uint64_t bases = slab_offsets(reads, 8, 64, slab_off);
+  DevBuf<ReadDesc> d_reads(n);
+  DevBuf<uint64_t> d_slab_off(n + 1), offs(n + 1);
+  DevBuf<uint32_t> counts(n), d_flags(n), d_list(n);
+  DevBuf<const pgx_mm128 *> d_src_of(n);
   DevBuf<pgx_mm128> slab(slab_off[n]);
-  if (!general) {
+  d_reads.upload(reads.data(), n);
+  d_slab_off.upload(slab_off.data(), n + 1);
+  PGX_HIP(hipMemsetAsync(counts.p, 0, n * sizeof(uint32_t), st));
+  PGX_HIP(hipMemsetAsync(d_flags.p, 0, n * sizeof(uint32_t), st));
+  PGX_HIP(hipMemsetAsync(d_src_of.p, 0, n * sizeof(pgx_mm128 *), st));
+  // (w, k) outside the specialised kernel's set: the general closed-form kernel takes the wave kernel's place
+  if (k == 16 && (w == 64 || w == 80 || w == 96 || w == 128)) {
     KernelTimer tm("sketch", bases);
-    launch_sketch_wave(db, d_reads.p, nullptr, n, w, k, slab.p, d_slab_off.p, counts.p, d_flag.p);
+    launch_sketch_wave(db, d_reads.p, nullptr, n, w, k, slab.p, d_slab_off.p, counts.p, d_flags.p);
   } else {
     KernelTimer tm("sketch_general", bases);
-    launch_sketch_general(db, d_reads.p, lens, nullptr, w, k, slab.p, d_slab_off.p, counts.p, d_flag.p);
+    launch_sketch_general(db, d_reads.p, lens, nullptr, w, k, slab.p, d_slab_off.p, counts.p, d_flags.p);
   }
-  std::vector<uint32_t> flag(n);
-  d_flag.download(flag.data(), n);
-  sync();
-  std::vector<uint32_t> second;
-  for (uint32_t i = 0; i < n; ++i)
-    if (flag[i]) second.push_back(i);
   // the flagged reads: segments of unambiguous bases through the same kernels, exact slabs on demand
-  DevBuf<uint32_t> d_second(second.size()), d_skip;
+  const uint32_t n_second = select_flagged(d_flags.p, n, d_list.p);
   DevBuf<pgx_mm128> nl0;
   DevBuf<uint64_t> nl0_off;
-  if (!second.empty()) {
+  if (n_second) {
     KernelTimer tm("sketch_nreads", 0);
-    d_second.upload(second.data(), second.size());
     uint64_t tot2 = 0;
-    dev_sketch_nreads(db, d_reads.p, d_second.p, (uint32_t)second.size(), w, k, nl0, nl0_off, &tot2);
-    dev_scatter_counts(counts.p, d_second.p, (uint32_t)second.size(), nl0_off.p, nullptr);
-    d_skip.alloc(n);
-    PGX_HIP(hipMemsetAsync(d_skip.p, 0, n * sizeof(uint32_t), st));
-    dev_mark_slots(d_skip.p, d_second.p, (uint32_t)second.size(), 1u);
+    dev_sketch_nreads(db, d_reads.p, d_list.p, n_second, w, k, nl0, nl0_off, &tot2);
+    dev_scatter_counts(counts.p, d_list.p, n_second, nl0_off.p, nullptr);
+    set_sources(d_src_of.p, d_list.p, n_second, nl0.p, nl0_off.p);
   }
-  if (n_literal) *n_literal = (uint32_t)second.size();
-  {
-    CubTemp tmp;
-    size_t bytes = 0;
-    PGX_HIP(hipMemsetAsync(offs.p, 0, sizeof(uint64_t), st));
-    PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, counts.p, offs.p + 1, (int)n, st));
-    PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp.get(bytes), bytes, counts.p, offs.p + 1, (int)n, st));
-    uint64_t total = 0;
-    PGX_HIP(hipMemcpyAsync(&total, offs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    sync();
-    n_out = (size_t)total;
-  }
+  if (n_literal) *n_literal = n_second;
+  n_out = (size_t)scan_to_total(counts.p, offs.p, n);
   out.alloc(n_out);
   if (n_out == 0) return;
   {
     KernelTimer tm("sketch_gather", bases);
-    hipLaunchKernelGGL(k_gather_slabs, dim3(n), dim3(64), 0, st, slab.p, d_slab_off.p, (const uint32_t *)nullptr, n, counts.p, offs.p, out.p,
-                       (const uint32_t *)d_skip.p, 0);
-    if (!second.empty())
-      hipLaunchKernelGGL(k_gather_slabs, dim3((unsigned)second.size()), dim3(64), 0, st, nl0.p, nl0_off.p, (const uint32_t *)d_second.p,
-                         (uint32_t)second.size(), counts.p, offs.p, out.p, (const uint32_t *)nullptr, 1);
+    hipLaunchKernelGGL(k_gather_slabs, dim3(n), dim3(64), 0, st, slab.p, d_slab_off.p, d_src_of.p, n, counts.p, offs.p, out.p);
   }
   sync();
 }
@@ -533,22 +539,27 @@ void dev_sketch(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, 
 // k_reduce_read: mm_reduce (src/shmr_reduce.c:53-90) applied `levels` times to ONE read's minimizers, in LDS, in place
 // in the read's slab.  Same restatement as k_reduce_flag (winner = smallest x>>8, ties to the lowest ring slot
 // offset % rs; emitted iff its y differs from the previous window's winner; the first window always emits).
+// A read the sketch kernel flagged is left alone; one whose list is longer than RMAX gets flag bit 256: the run-by-run path, which
+// reduces lists of any length (k_reduce_long), takes both.
 // =========================================================================================================
 constexpr int RMAX = 1024;  // minimizers per read handled in LDS (a 15 kb read has ~375 at w = 80)
 
 __global__ __launch_bounds__(64) void k_reduce_read(pgx_mm128 *__restrict__ slab, const uint64_t *__restrict__ slab_off,
                                                     const ReadDesc *__restrict__ reads,
-                                                    const uint32_t *__restrict__ counts0,
-                                                    const uint32_t *__restrict__ flags, uint32_t n, int rs, int levels,
-                                                    uint32_t *__restrict__ counts_top, uint32_t *__restrict__ nbad) {
+                                                    const uint32_t *__restrict__ counts0, uint32_t *__restrict__ flags,
+                                                    uint32_t n, int rs, int levels, uint32_t *__restrict__ counts_top) {
   __shared__ uint64_t sx[RMAX];
   __shared__ uint32_t sy[RMAX];
   const int lane = threadIdx.x;
   const uint32_t slot = blockIdx.x;
   if (slot >= n) return;
   const uint32_t c0 = counts0[slot];
-  if (flags[slot] || c0 > (uint32_t)RMAX) {
-    if (lane == 0) atomicAdd(nbad, 1u), counts_top[slot] = 0;
+  const uint32_t flagged = flags[slot];
+  if (flagged || c0 > (uint32_t)RMAX) {
+    if (lane == 0) {
+      counts_top[slot] = 0;
+      if (!flagged) flags[slot] = 256u;
+    }
     return;
   }
   pgx_mm128 *p = slab + slab_off[slot];
@@ -607,245 +618,193 @@ __global__ __launch_bounds__(64) void k_reduce_read(pgx_mm128 *__restrict__ slab
   if (lane == 0) counts_top[slot] = (uint32_t)ncur;
 }
 
-__global__ void k_set_aside_ambiguous(uint32_t *__restrict__ flags, uint32_t n, uint32_t *__restrict__ mark) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t f = flags[i];
-  mark[i] = (f & 2u) ? 1u : 0u;   // k_sketch_blk's "ambiguous base" bit
-  if (f & 2u) flags[i] = 0;
-}
-__global__ void k_restore_marks(uint32_t *__restrict__ flags, uint32_t n, const uint32_t *__restrict__ mark) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && mark[i]) flags[i] |= 2u;
-}
-__global__ void k_count_flags(const uint32_t *__restrict__ flags, uint32_t n, uint32_t *__restrict__ nbad) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && flags[i]) atomicAdd(nbad, 1u);
+// =========================================================================================================
+// the fused index path's driver: one decision, then a function per pass over an IndexRun
+// =========================================================================================================
+// Which first pass a (w, k, rs, levels) gets, and the slab divisor that goes with it (slab of a read: len / slab_div + slab_min elements).
+//   blk:  k_sketch_blk -- block-per-lane closed form fused with the streaming reduce, L0 never leaves the CU, HBM traffic == the
+//         algorithmic 1.04 B/base.  Only the TOP-level list reaches the slab (1 element per 408 bases at l = 2, per 142 at l = 1), so
+//         the slabs are len / 48 resp. len / 24: six and three times the expected list.  (Rounds 1-4 reserved len / 8 for every path: 27 GB
+//         of workspace for one index chunk of full-size configs[3], resident through the overlap stages too.)
+//   else: k_sketch_wave + k_reduce_read (w = 64 / 96 / 128, or a reduction factor above RCARRY + 1): L0 goes through the slab, len / 8.
+// (PGX_SLAB_DIV / PGX_SLAB_MIN: test knobs that make reads outgrow their slabs)
+struct FirstPass {
+  bool blk;
+  uint64_t slab_div, slab_min;
+};
+static FirstPass choose_first_pass(int w, int k, int rs, int levels) {
+  FirstPass fp;
+  fp.blk = sketch_blk_supported(w, k, rs, levels);
+  fp.slab_div = getenv("PGX_SLAB_DIV") ? std::max(1ll, atoll(getenv("PGX_SLAB_DIV"))) : !fp.blk ? 8 : levels >= 2 ? 48 : 24;
+  fp.slab_min = getenv("PGX_SLAB_MIN") ? std::max(1ll, atoll(getenv("PGX_SLAB_MIN"))) : 64;
+  return fp;
 }
 
-static double trace_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+// What the passes of one call share.  A read is UNFINISHED iff its flag word is non-zero (the bits say why: flag_histogram); a pass takes
+// the list of the reads flagged for it, clears their flags, and the kernels it runs flag again what they could not finish.
+struct IndexRun {
+  const pgx_seqdb *db;
+  int w, k, rs, levels;
+  uint32_t n;
+  uint64_t bases;
+  const ReadDesc *d_reads;
+  const uint64_t *d_slab_off;
+  pgx_mm128 *slab;
+  const pgx_mm128 **d_src_of;               // per read: k_gather_slabs' rule
+  uint32_t *d_cnt0, *d_flags, *d_ctop;      // per read: level-0 elements (k_sketch_wave -> k_reduce_read only), flag word, final elements
+  uint64_t *d_offs;                         // n + 1: the reads' offsets in the final list
+  uint32_t *d_list, *d_need;                // the current pass's reads; elements a read needs when it outgrew its slab
+  DevBuf<pgx_mm128> run_lists;              // the run-by-run path's final lists (read by the gather)
+  bool trace;
+};
+
+static void flag_histogram(const IndexRun &r, uint32_t n_listed, const char *what) {
+  std::vector<uint32_t> hf(r.n);
+  PGX_HIP(hipMemcpy(hf.data(), r.d_flags, (size_t)r.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  unsigned why[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (uint32_t f : hf)
+    for (int b = 0; b < 9; ++b) why[b] += (f >> b) & 1u;
+  fprintf(stderr, "[pgx] index: %u of %u reads %s (short %u, ambiguous base %u, two drops in a tile %u, drop in the first window %u, close drops %u, "
+          "tie burst %u / %u, slab %u, list longer than the in-LDS reduce holds %u)\n", n_listed, r.n, what, why[0], why[1], why[2], why[3], why[4],
+          why[5], why[6], why[7], why[8]);
+}
+
+// The plan: read descriptors and slab offsets, computed and uploaded once per (plan, w, k, slab_div) -- the device half of the database's
+// read selection.  false: some read is not for the closed-form kernels (the caller runs the general path).
+static bool index_plan(pgx_seqdb::IndexPlan &pl, const std::vector<ReadDesc> &reads, int w, int k, const FirstPass &fp) {
+  if (pl.plan_div == fp.slab_div && pl.plan_w == w && pl.plan_k == k) return pl.plan_ok;
+  const size_t n = reads.size();
+  {
+    MemTag plan_tag("index.plans");
+    pl.d_reads.alloc(n), pl.d_slab_off.alloc(n + 1);
+  }
+  pl.plan_div = 0;
+  std::vector<uint64_t> slab_off;
+  pl.plan_bases = slab_offsets(reads, fp.slab_div, fp.slab_min, slab_off);
+  pl.plan_ok = std::all_of(reads.begin(), reads.end(), [&](const ReadDesc &rd) { return sketch_wave_eligible(rd, w, k); });
+  if (pl.plan_ok) {
+    pl.d_reads.upload(reads.data(), n);
+    pl.d_slab_off.upload(slab_off.data(), n + 1);
+    sync();  // (slab_off is a local)
+  }
+  pl.slab_total = slab_off[n], pl.plan_w = w, pl.plan_k = k, pl.plan_div = fp.slab_div;
+  return pl.plan_ok;
+}
+
+static void index_workspaces(IndexRun &r, const pgx_seqdb::IndexPlan &pl) {
+  const size_t n = r.n;
+  r.bases = pl.plan_bases, r.d_reads = pl.d_reads.p, r.d_slab_off = pl.d_slab_off.p;
+  const size_t per_read = sizeof(pgx_mm128 *) + 3 * sizeof(uint32_t);   // [src_of | counts0 | flags | counts_top], cleared together
+  r.d_src_of = (const pgx_mm128 **)ws_raw("ix.cnt", n * per_read);
+  r.d_cnt0 = (uint32_t *)(r.d_src_of + n), r.d_flags = r.d_cnt0 + n, r.d_ctop = r.d_flags + n;
+  r.d_offs = ws<uint64_t>("ix.offs", n + 1);
+  r.d_list = ws<uint32_t>("ix.redo", n);
+  r.d_need = ws<uint32_t>("ix.need", n);
+  r.slab = ws<pgx_mm128>("ix.slab", pl.slab_total);
+  PGX_HIP(hipMemsetAsync(r.d_src_of, 0, n * per_read, ctx().stream));
+}
+
+static void first_pass(const IndexRun &r, const FirstPass &fp) {
+  if (fp.blk) {
+    KernelTimer tm("sketch", r.bases);
+    launch_sketch_blk(r.db, r.d_reads, r.n, r.rs, r.levels, r.slab, r.d_slab_off, r.d_ctop, r.d_flags);
+    return;
+  }
+  {
+    KernelTimer tm("sketch", r.bases);
+    launch_sketch_wave(r.db, r.d_reads, nullptr, r.n, r.w, r.k, r.slab, r.d_slab_off, r.d_cnt0, r.d_flags);
+  }
+  KernelTimer tm("reduce", r.bases);
+  hipLaunchKernelGGL(k_reduce_read, dim3(r.n), dim3(64), 0, ctx().stream, r.slab, r.d_slab_off, r.d_reads, r.d_cnt0, r.d_flags, r.n, r.rs,
+                     r.levels, r.d_ctop);
+}
+
+// What k_sketch_blk flagged (two drops close together, bursts of ties, very short reads ...), once more on k_sketch_wave in its fused
+// form, into the same slabs.  It flags the reads that outgrow their slab and reports how many elements each has (d_need).
+static void redo_on_wave(const IndexRun &r, uint32_t n_list) {
+  dev_mark_slots(r.d_flags, r.d_list, n_list, 0u);
+  launch_sketch_fused_list(r.db, r.d_reads, r.d_list, n_list, r.rs, r.levels, r.slab, r.d_slab_off, r.d_ctop, r.d_flags, r.d_need, 0);
+}
+
+// Low-complexity reads (a homopolymer or a short-period tandem array makes every position a tied minimum, on every level) can
+// outgrow their slab: exactly those reads are redone into slabs of exactly the size the wave kernel reported.  (Round 1 redid the
+// WHOLE chunk on the slow general path when a single read was left over: 0.4 s instead of 15 ms at 9 Gbases with 1 % low-complexity
+// sequence.)  Reads with an ambiguous base are not listed: the kernel would walk them whole only to flag them again.
+static void redo_into_exact_slabs(const IndexRun &r) {
+  const uint32_t n_list = select_flagged(r.d_flags, r.n, r.d_list, 2u);
+  if (!n_list) return;
+  uint64_t *d_off = ws<uint64_t>("ix.off2", (size_t)n_list + 1);
+  hipLaunchKernelGGL(k_need_of_list, dim3(cdiv(n_list, 256)), dim3(256), 0, ctx().stream, r.d_need, r.d_list, n_list, d_off + 1);
+  const uint64_t total = scan_to_total(d_off + 1, d_off, n_list);
+  pgx_mm128 *exact = ws<pgx_mm128>("ix.slab2", total);
+  dev_mark_slots(r.d_flags, r.d_list, n_list, 0u);
+  launch_sketch_fused_list(r.db, r.d_reads, r.d_list, n_list, r.rs, r.levels, exact, d_off, r.d_ctop, r.d_flags, nullptr, 1);
+  set_sources(r.d_src_of, r.d_list, n_list, exact, d_off);
+  if (r.trace) fprintf(stderr, "[pgx] index: %u reads outgrew their slabs and were redone into exact ones (%llu elements)\n", n_list, (unsigned long long)total);
+}
+
+// Every read still flagged -- an ambiguous base (mm_sketch.c:112-113), a list k_reduce_read cannot hold, whatever else the passes above
+// left -- is cut into runs of unambiguous bases, every run sketched by the unfused closed-form kernel, the read's list assembled and
+// reduced per read (pgx_sketch_n.hip).  That path takes any read: nothing is flagged after it.
+static void run_by_run(IndexRun &r, uint32_t n_list) {
+  DevBuf<pgx_mm128> l0;
+  DevBuf<uint64_t> off;
+  DevBuf<uint32_t> cnt;
+  uint64_t total = 0;
+  dev_sketch_nreads(r.db, r.d_reads, r.d_list, n_list, r.w, r.k, l0, off, &total);
+  dev_reduce_nreads(l0, off, n_list, total, r.rs, r.levels, r.run_lists, cnt);
+  dev_scatter_counts(r.d_ctop, r.d_list, n_list, nullptr, cnt.p);
+  set_sources(r.d_src_of, r.d_list, n_list, r.run_lists.p, off.p);
+  dev_mark_slots(r.d_flags, r.d_list, n_list, 0u);
+  if (r.trace) fprintf(stderr, "[pgx] index: %u reads sketched run by run (%llu level-0 minimizers)\n", n_list, (unsigned long long)total);
+}
+
+static void gather(const IndexRun &r, const pgx_mm128 **d_top, size_t *n_top) {
+  const uint64_t total = scan_to_total(r.d_ctop, r.d_offs, r.n);
+  pgx_mm128 *top = ws<pgx_mm128>("ix.top", total);
+  if (total) {
+    KernelTimer tm("sketch_gather", r.bases);
+    hipLaunchKernelGGL(k_gather_slabs, dim3(r.n), dim3(64), 0, ctx().stream, r.slab, r.d_slab_off, r.d_src_of, r.n, r.d_ctop, r.d_offs, top);
+    if (r.run_lists.p) sync();   // (run_lists goes back to the block cache with the IndexRun)
+  }
+  *d_top = top, *n_top = (size_t)total;
 }
 
 bool dev_index_fused(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, int k, int rs, int levels,
                      const pgx_mm128 **d_top, size_t *n_top, pgx_seqdb::IndexPlan *plan, uint32_t *n_second) {
   if (n_second) *n_second = 0;
-  const uint32_t n = (uint32_t)reads.size();
-  if (n == 0 || levels < 1 || levels > 2 || rs < 1) return false;
-  const bool trace = getenv("PGX_TRACE") != nullptr;
-  const double tr0 = trace ? trace_ms() : 0;
-  // slab offsets and read descriptors: computed and uploaded once per plan (the device half of the database's read selection)
+  if (reads.empty() || levels < 1 || levels > 2 || rs < 1) return false;
+  IndexRun r{};
+  r.db = db, r.w = w, r.k = k, r.rs = rs, r.levels = levels, r.n = (uint32_t)reads.size(), r.trace = getenv("PGX_TRACE") != nullptr;
+  const double t0 = wall_ms();
+  const FirstPass fp = choose_first_pass(w, k, rs, levels);
   pgx_seqdb::IndexPlan own;   // (no plan: for this call only)
   pgx_seqdb::IndexPlan &pl = plan ? *plan : own;
-  static const char *mode_env = getenv("PGX_SKETCH");
-  static const bool want_fuse = (getenv("PGX_FUSE") && atoi(getenv("PGX_FUSE")) != 0) || (mode_env && !strcmp(mode_env, "fuse"));
-  static const bool want_wave = mode_env && !strcmp(mode_env, "wave");
-  // slab of a read: len / slab_div + 64 elements.  The fused kernels only ever write the TOP-level list there (1 element per 408 bases at
-  // l = 2, per 142 at l = 1: L0 never leaves the CU), so their slabs are len / 48 resp. len / 24 -- six and three times the expected list; a
-  // read that outgrows its slab (low-complexity sequence) is flagged and redone into an exact one below, as ever.  Round 1-4 reserved
-  // len / 8 for every path: 27 GB of workspace for one index chunk of full-size configs[3], resident through the overlap stages too (round 5:
-  // the HBM ledger).  The unfused path (k_sketch_wave + k_reduce_read: L0 goes through the slab) keeps len / 8.
-  // (PGX_SLAB_DIV / PGX_SLAB_MIN: test knobs that make reads outgrow their slabs)
-  const bool fused_out = !want_wave && (want_fuse ? sketch_fused_supported(w, rs, levels) : sketch_blk_supported(w, k, rs, levels));
-  const uint64_t slab_div = getenv("PGX_SLAB_DIV") ? std::max(1ll, atoll(getenv("PGX_SLAB_DIV"))) : !fused_out ? 8 : levels >= 2 ? 48 : 24;
-  const bool cached = pl.plan_div == slab_div && pl.plan_w == w && pl.plan_k == k;
-  hipStream_t st = ctx().stream;
-  if (!cached) {
-    MemTag plan_tag("index.plans");
-    pl.d_reads.alloc(n), pl.d_slab_off.alloc((size_t)n + 1);
-  }
-  ReadDesc *d_reads = pl.d_reads.p;
-  uint64_t *d_slab_off = pl.d_slab_off.p;
-  if (!cached) {
-    pl.plan_div = 0;
-    std::vector<uint64_t> slab_off(n + 1, 0);
-    uint64_t bases = 0;
-    pl.plan_ok = true;
-    const uint64_t slab_min = getenv("PGX_SLAB_MIN") ? std::max(1ll, atoll(getenv("PGX_SLAB_MIN"))) : 64;
-    for (uint32_t i = 0; i < n; ++i) {
-      if (!sketch_wave_eligible(reads[i], w, k)) pl.plan_ok = false;
-      slab_off[i + 1] = slab_off[i] + (uint64_t)reads[i].len / slab_div + slab_min;
-      bases += reads[i].len;
-    }
-    if (pl.plan_ok) {
-      PGX_HIP(hipMemcpyAsync(d_reads, reads.data(), n * sizeof(ReadDesc), hipMemcpyHostToDevice, st));
-      PGX_HIP(hipMemcpyAsync(d_slab_off, slab_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-      sync();  // (slab_off is a local)
-    }
-    pl.slab_total = slab_off[n], pl.plan_bases = bases, pl.plan_w = w, pl.plan_k = k, pl.plan_div = slab_div;
-  }
-  if (!pl.plan_ok) return false;
-  const uint64_t bases = pl.plan_bases;
-  uint32_t *d_cnt = ws<uint32_t>("ix.cnt", 3 * (size_t)n + 4);  // [counts0 | flags | counts_top | nbad]
-  uint32_t *d_flags = d_cnt + n, *d_ctop = d_cnt + 2 * (size_t)n, *d_nbad = d_cnt + 3 * (size_t)n;
-  uint64_t *d_offs = ws<uint64_t>("ix.offs", n + 1);
-  pgx_mm128 *slab = ws<pgx_mm128>("ix.slab", pl.slab_total);
-  PGX_HIP(hipMemsetAsync(d_cnt, 0, (3 * (size_t)n + 4) * sizeof(uint32_t), st));
-  if (trace) {
+  if (!index_plan(pl, reads, w, k, fp)) return false;
+  index_workspaces(r, pl);
+  if (r.trace) {
     sync();
-    fprintf(stderr, "[pgx] index: plan (slab offsets, descriptors, workspaces, uploads) %.2f ms\n", trace_ms() - tr0);
+    fprintf(stderr, "[pgx] index: plan (slab offsets, descriptors, workspaces, uploads) %.2f ms\n", wall_ms() - t0);
   }
-  // Default (round 2): k_sketch_blk -- block-per-lane closed form fused with the streaming reduce, L0 never leaves the CU, HBM
-  // traffic == the algorithmic 1.04 B/base -- and k_sketch_wave (fused form) for the reads it flags (two drops close together,
-  // bursts of ties, very short reads).  PGX_SKETCH=wave: k_sketch_wave + k_reduce_read (round 1's default); PGX_SKETCH=fuse (or
-  // PGX_FUSE=1): k_sketch_wave in its fused form for every read.
-  uint32_t n_redo2 = 0;               // reads redone into exact-size slabs (slab2, offsets by list position)
-  pgx_mm128 *slab2 = nullptr;
-  uint64_t *d_off2_keep = nullptr;
-  uint32_t *d_list2_keep = nullptr, *d_in2 = nullptr;
-  if (!want_fuse && !want_wave && sketch_blk_supported(w, k, rs, levels)) {
-    {
-      KernelTimer tm("sketch", bases);
-      launch_sketch_blk(db, d_reads, n, rs, levels, slab, d_slab_off, d_ctop, d_flags);
-    }
-    // reads with an ambiguous base (flag bit 2) skip the two redo passes below -- the fused wave kernel would walk them whole only to flag
-    // them again -- and go straight to the run-by-run path at the end (their mark is put back once the passes are through)
-    uint32_t *d_nmark = ws<uint32_t>("ix.nmark", n);
-    hipLaunchKernelGGL(k_set_aside_ambiguous, dim3(cdiv(n, 256)), dim3(256), 0, st, d_flags, n, d_nmark);
-    // the flagged reads, once more on the general closed-form kernel
-    uint32_t *d_list = ws<uint32_t>("ix.redo", (size_t)n + 1);
-    size_t sbytes = 0;
-    hipcub::CountingInputIterator<uint32_t, ptrdiff_t> iota(0);
-    PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, sbytes, iota, d_flags, d_list, d_list + n, (int)n, st));
-    void *stmp = ws_raw("ix.sel_tmp", sbytes);
-    PGX_HIP(hipcub::DeviceSelect::Flagged(stmp, sbytes, iota, d_flags, d_list, d_list + n, (int)n, st));
-    uint32_t nredo = 0;
-    PGX_HIP(hipMemcpyAsync(&nredo, d_list + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    sync();
-    if (getenv("PGX_TRACE")) {
-      std::vector<uint32_t> hf(n);
-      PGX_HIP(hipMemcpy(hf.data(), d_flags, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      unsigned why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (uint32_t f : hf)
-        for (int b = 0; b < 8; ++b) why[b] += (f >> b) & 1u;
-      fprintf(stderr, "[pgx] index: %u of %u reads redone by the general closed-form kernel (short %u, ambiguous base %u, two drops in a tile %u, "
-              "drop in the first window %u, close drops %u, tie burst %u / %u, slab %u)\n", nredo, n, why[0], why[1], why[2], why[3], why[4],
-              why[5], why[6], why[7]);
-    }
-    if (nredo) {
+  first_pass(r, fp);
+  if (fp.blk) {   // (k_sketch_wave + k_reduce_read have no second closed form: what they flag goes straight to the run-by-run path)
+    const uint32_t n_redo = select_flagged(r.d_flags, r.n, r.d_list, 2u);
+    if (r.trace) flag_histogram(r, n_redo, "redone by the fused wave kernel");
+    if (n_redo) {
       KernelTimer tm("sketch_redo", 0);
-      uint32_t *d_need = ws<uint32_t>("ix.need", n);
-      PGX_HIP(hipMemsetAsync(d_flags, 0, (size_t)n * sizeof(uint32_t), st));
-      launch_sketch_fused_list(db, d_reads, d_list, nredo, rs, levels, slab, d_slab_off, d_ctop, d_flags, d_need, 0);
-      // Low-complexity reads (a homopolymer or a short-period tandem array makes every position a tied minimum, on every level)
-      // can outgrow their slab; the kernel reports how many elements each such read has, and a second launch redoes exactly
-      // those reads into slabs of exactly that size.  (Round 1 redid the WHOLE chunk on the slow general path when a single
-      // read was left over: 0.4 s instead of 15 ms at 9 Gbases with 1 % low-complexity sequence.)
-      uint32_t *d_list2 = ws<uint32_t>("ix.redo2", (size_t)n + 1);
-      PGX_HIP(hipcub::DeviceSelect::Flagged(stmp, sbytes, iota, d_flags, d_list2, d_list2 + n, (int)n, st));
-      PGX_HIP(hipMemcpyAsync(&n_redo2, d_list2 + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      sync();
-      if (n_redo2) {
-        uint64_t *d_off2 = ws<uint64_t>("ix.off2", (size_t)n_redo2 + 1);
-        hipLaunchKernelGGL(k_need_of_list, dim3(cdiv(n_redo2, 256)), dim3(256), 0, st, d_need, d_list2, n_redo2, d_off2 + 1);
-        PGX_HIP(hipMemsetAsync(d_off2, 0, sizeof(uint64_t), st));
-        size_t b2 = 0;
-        PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, b2, d_off2 + 1, d_off2 + 1, (int)n_redo2, st));
-        void *t2 = ws_raw("ix.scan2_tmp", b2);
-        PGX_HIP(hipcub::DeviceScan::InclusiveSum(t2, b2, d_off2 + 1, d_off2 + 1, (int)n_redo2, st));
-        uint64_t total2 = 0;
-        PGX_HIP(hipMemcpyAsync(&total2, d_off2 + n_redo2, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        sync();
-        slab2 = ws<pgx_mm128>("ix.slab2", std::max<uint64_t>(total2, 1));
-        d_off2_keep = d_off2, d_list2_keep = d_list2;
-        d_in2 = ws<uint32_t>("ix.in2", n);
-        PGX_HIP(hipMemcpyAsync(d_in2, d_flags, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));   // (1 for the reads of list 2)
-        PGX_HIP(hipMemsetAsync(d_flags, 0, (size_t)n * sizeof(uint32_t), st));
-        launch_sketch_fused_list(db, d_reads, d_list2, n_redo2, rs, levels, slab2, d_off2, d_ctop, d_flags, nullptr, 1);
-        if (trace) fprintf(stderr, "[pgx] index: %u reads outgrew their slabs and were redone into exact ones (%llu elements)\n", n_redo2, (unsigned long long)total2);
-      }
-    }
-    hipLaunchKernelGGL(k_restore_marks, dim3(cdiv(n, 256)), dim3(256), 0, st, d_flags, n, d_nmark);
-    hipLaunchKernelGGL(k_count_flags, dim3(cdiv(n, 256)), dim3(256), 0, st, d_flags, n, d_nbad);
-  } else if (want_fuse && sketch_fused_supported(w, rs, levels)) {
-    KernelTimer tm("sketch", bases);
-    launch_sketch_fused(db, d_reads, n, rs, levels, slab, d_slab_off, d_ctop, d_flags);
-    hipLaunchKernelGGL(k_count_flags, dim3(cdiv(n, 256)), dim3(256), 0, st, d_flags, n, d_nbad);
-  } else {
-    {
-      KernelTimer tm("sketch", bases);
-      launch_sketch_wave(db, d_reads, nullptr, n, w, k, slab, d_slab_off, d_cnt, d_flags);
-    }
-    KernelTimer tm("reduce", bases);
-    hipLaunchKernelGGL(k_reduce_read, dim3(n), dim3(64), 0, st, slab, d_slab_off, d_reads, d_cnt, d_flags, n, rs, levels,
-                       d_ctop, d_nbad);
-  }
-  // Reads still flagged here hold an ambiguous base (mm_sketch.c:112-113): they are cut into runs of unambiguous bases, every run
-  // sketched by the unfused closed-form kernel, the read's list assembled and reduced per read (pgx_sketch_n.hip)
-  DevBuf<pgx_mm128> n_l0, n_toplist;
-  DevBuf<uint64_t> n_off;
-  DevBuf<uint32_t> n_cnt;
-  uint32_t n3 = 0;
-  uint32_t *d_list3 = nullptr;
-  uint32_t *d_skip = d_in2, *d_skip3 = nullptr;
-  {
-    uint32_t nb = 0;
-    PGX_HIP(hipMemcpyAsync(&nb, d_nbad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    sync();
-    if (nb && !want_wave) {
-      KernelTimer tm("sketch_nreads", 0);
-      d_list3 = ws<uint32_t>("ix.redo3", (size_t)n + 1);
-      size_t sb = 0;
-      hipcub::CountingInputIterator<uint32_t, ptrdiff_t> iota(0);
-      PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, sb, iota, d_flags, d_list3, d_list3 + n, (int)n, st));
-      void *stmp = ws_raw("ix.sel_tmp", sb);
-      PGX_HIP(hipcub::DeviceSelect::Flagged(stmp, sb, iota, d_flags, d_list3, d_list3 + n, (int)n, st));
-      PGX_HIP(hipMemcpyAsync(&n3, d_list3 + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      sync();
-      uint64_t tot3 = 0;
-      dev_sketch_nreads(db, d_reads, d_list3, n3, w, k, n_l0, n_off, &tot3);
-      dev_reduce_nreads(n_l0, n_off, n3, tot3, rs, levels, n_toplist, n_cnt);
-      dev_scatter_counts(d_ctop, d_list3, n3, nullptr, n_cnt.p);
-      if (!d_skip) {
-        d_skip = ws<uint32_t>("ix.in2", n);
-        PGX_HIP(hipMemsetAsync(d_skip, 0, (size_t)n * sizeof(uint32_t), st));
-      }
-      dev_mark_slots(d_skip, d_list3, n3, 1u);
-      d_skip3 = ws<uint32_t>("ix.in3", n);   // (the exact-slab gather below must step over them too: a read can be in both lists)
-      PGX_HIP(hipMemsetAsync(d_skip3, 0, (size_t)n * sizeof(uint32_t), st));
-      dev_mark_slots(d_skip3, d_list3, n3, 1u);
-      dev_mark_slots(d_flags, d_list3, n3, 0u);
-      PGX_HIP(hipMemsetAsync(d_nbad, 0, sizeof(uint32_t), st));
-      if (n_second) *n_second = n3;
-      if (trace) fprintf(stderr, "[pgx] index: %u reads with ambiguous bases sketched run by run (%llu level-0 minimizers)\n", n3, (unsigned long long)tot3);
+      redo_on_wave(r, n_redo);
+      redo_into_exact_slabs(r);
     }
   }
-  size_t bytes = 0;
-  PGX_HIP(hipMemsetAsync(d_offs, 0, sizeof(uint64_t), st));
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, d_ctop, d_offs + 1, (int)n, st));
-  void *tmp = ws_raw("ix.scan_tmp", bytes);
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_ctop, d_offs + 1, (int)n, st));
-  uint64_t total = 0;
-  uint32_t nbad = 0;
-  PGX_HIP(hipMemcpyAsync(&total, d_offs + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  PGX_HIP(hipMemcpyAsync(&nbad, d_nbad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  sync();
-  if (trace) fprintf(stderr, "[pgx] index: sketch + reduce done at +%.2f ms\n", trace_ms() - tr0);
-  if (trace && nbad) {
-    std::vector<uint32_t> hf(n);
-    PGX_HIP(hipMemcpy(hf.data(), d_flags, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    unsigned why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t f : hf)
-      for (int b = 0; b < 8; ++b) why[b] += (f >> b) & 1u;
-    fprintf(stderr, "[pgx] index: %u reads still flagged after the general closed-form kernel (bits 0..7: %u %u %u %u %u %u %u %u)\n", nbad, why[0], why[1], why[2],
-            why[3], why[4], why[5], why[6], why[7]);
+  const uint32_t n_runs = select_flagged(r.d_flags, r.n, r.d_list);
+  if (r.trace && n_runs) flag_histogram(r, n_runs, "left for the run-by-run path");
+  if (n_runs) {
+    KernelTimer tm("sketch_nreads", 0);
+    run_by_run(r, n_runs);
   }
-  if (nbad) return false;  // some read needs the general path; the caller redoes the chunk there
-  pgx_mm128 *top = ws<pgx_mm128>("ix.top", total);
-  if (total) {
-    KernelTimer tm("sketch_gather", bases);
-    hipLaunchKernelGGL(k_gather_slabs, dim3(n), dim3(64), 0, st, slab, d_slab_off, (const uint32_t *)nullptr, n, d_ctop, d_offs,
-                       top, (const uint32_t *)d_skip, 0);
-    if (n_redo2)
-      hipLaunchKernelGGL(k_gather_slabs, dim3(n_redo2), dim3(64), 0, st, slab2, d_off2_keep, (const uint32_t *)d_list2_keep, n_redo2, d_ctop,
-                         d_offs, top, (const uint32_t *)d_skip3, 1);
-    if (n3)
-      hipLaunchKernelGGL(k_gather_slabs, dim3(n3), dim3(64), 0, st, n_toplist.p, n_off.p, (const uint32_t *)d_list3, n3, d_ctop, d_offs, top,
-                         (const uint32_t *)nullptr, 1);
-    if (n3) sync();   // (n_toplist goes back to the block cache when this function returns)
-  }
-  *d_top = top;
-  *n_top = (size_t)total;
+  if (n_second) *n_second = n_runs;
+  gather(r, d_top, n_top);
+  if (r.trace) fprintf(stderr, "[pgx] index: sketch + reduce done at +%.2f ms\n", wall_ms() - t0);
   return true;
 }
 

@@ -1062,20 +1062,11 @@ void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint
   PGX_HIP(hipGetLastError());
 }
 
-// fused sketch + reduce x levels (w = 80 only); requires rs <= RCARRY + 1 and levels in {1, 2}
-bool sketch_fused_supported(int w, int rs, int levels) {
-  return w == 80 && rs >= 1 && rs <= RCARRY + 1 && (levels == 1 || levels == 2);
+// round 2: the block-per-lane closed form, fused with the streaming reduce x levels (w = 80 only; rs <= RCARRY + 1, levels in {1, 2}).
+// Reads it flags are redone by launch_sketch_fused_list (k_sketch_wave in its fused form on the listed slots: same limits).
+bool sketch_blk_supported(int w, int k, int rs, int levels) {
+  return k == K && w == 80 && rs >= 1 && rs <= RCARRY + 1 && (levels == 1 || levels == 2);
 }
-void launch_sketch_fused(const pgx_seqdb *db, const ReadDesc *d_reads, uint32_t n, int rs, int levels, pgx_mm128 *d_slab,
-                         const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags) {
-  if (!n) return;
-  launch_w<true, 5>(db, d_reads, nullptr, n, d_slab, d_slab_off, d_counts, d_flags, rs, levels);
-  PGX_HIP(hipGetLastError());
-}
-
-// round 2: the block-per-lane closed form (fused with the streaming reduce).  Reads it flags are redone by
-// launch_sketch_fused_list (k_sketch_wave on the listed slots).
-bool sketch_blk_supported(int w, int k, int rs, int levels) { return k == K && sketch_fused_supported(w, rs, levels); }
 void launch_sketch_blk(const pgx_seqdb *db, const ReadDesc *d_reads, uint32_t n, int rs, int levels, pgx_mm128 *d_slab,
                        const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags) {
   if (!n) return;

@@ -36,14 +36,6 @@
 
 namespace pgx {
 
-void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int w, int k,
-                        pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
-                        const uint8_t *bytes = nullptr);   // pgx_sketch_fast.hip; bytes: the byte view d_reads' offsets count from (nullptr: the seqdb)
-bool sketch_wave_eligible(const ReadDesc &rd, int w, int k);
-void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list,
-                           int w, int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
-                           const uint8_t *bytes = nullptr);   // pgx_kernels.hip
-
 namespace {
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
@@ -343,23 +335,8 @@ __global__ void k_scatter_cnt32(uint32_t *__restrict__ dst, const uint32_t *__re
   if (i < nn) dst[list[i]] = cnt[i];
 }
 
-uint64_t exclusive_offsets(uint64_t *d_vals_then_offs, uint64_t n) {
-  // d[0..n) = values on entry; on exit d[0..n] = exclusive prefix sums (n + 1 entries); returns the total
-  hipStream_t st = ctx().stream;
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_vals_then_offs, d_vals_then_offs, (int)(n + 1), st));
-  void *tmp = ws_raw("nsk.scan_tmp", bytes);
-  PGX_HIP(hipMemsetAsync(d_vals_then_offs + n, 0, sizeof(uint64_t), st));
-  PGX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_vals_then_offs, d_vals_then_offs, (int)(n + 1), st));
-  uint64_t total = 0;
-  PGX_HIP(hipMemcpyAsync(&total, d_vals_then_offs + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  sync();
-  return total;
-}
-
 }  // namespace
 
-// The level-0 minimizers of the listed reads (slots of d_reads, ascending), packed in list order: nl0[nl0_off[i] .. nl0_off[i+1]).
 void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t nn, int w, int k,
                        DevBuf<pgx_mm128> &nl0, DevBuf<uint64_t> &nl0_off, uint64_t *n_total) {
   *n_total = 0;
@@ -383,9 +360,9 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
   const uint8_t *seq = compacted ? view.seq : db->d_seq.p;
   // segments
   DevBuf<uint64_t> seg_off((size_t)nn + 1);
-  hipLaunchKernelGGL(k_nseg_scan<false>, dim3(nn), dim3(64), 0, st, seq, d_reads, d_list, nn, seg_off.p, (const uint64_t *)nullptr,
+  hipLaunchKernelGGL(k_nseg_scan<false>, dim3(nn), dim3(64), 0, st, seq, d_reads, d_list, nn, seg_off.p + 1, (const uint64_t *)nullptr,
                      (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr);
-  const uint64_t ns = exclusive_offsets(seg_off.p, nn);
+  const uint64_t ns = scan_to_total(seg_off.p + 1, seg_off.p, nn);   // (counts at [1, nn], scanned in place)
   PGX_REQUIRE(ns < (1ULL << 31), PGX_EARG, "too many runs of unambiguous bases in one chunk (%llu)", (unsigned long long)ns);
   DevBuf<pgx_mm128> end_el(nn);
   DevBuf<uint32_t> end_has(nn);
@@ -404,8 +381,8 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
     // batch through once more with one element per position, which always fits
     for (int attempt = 0; attempt < 2; ++attempt) {
       hipLaunchKernelGGL(k_nseg_virtual, dim3(cdiv(ns, 256)), dim3(256), 0, st, seq, d_reads, d_list, seg_s.p, seg_e.p, seg_read.p, ns, k,
-                         attempt ? 0u : 8u, 64u, vdesc.p, vpos0.p, vslab_off.p);
-      const uint64_t cap = exclusive_offsets(vslab_off.p, ns);
+                         attempt ? 0u : 8u, 64u, vdesc.p, vpos0.p, vslab_off.p + 1);
+      const uint64_t cap = scan_to_total(vslab_off.p + 1, vslab_off.p, ns);
       vslab.alloc(cap ? cap : 1);
       PGX_HIP(hipMemsetAsync(vcnt.p, 0, ns * sizeof(uint32_t), st));
       PGX_HIP(hipMemsetAsync(vflag.p, 0, ns * sizeof(uint32_t), st));
@@ -421,22 +398,22 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
         }
         launch_sketch_general(db, vdesc.p, lens, nullptr, w, k, vslab.p, vslab_off.p, vcnt.p, vflag.p, compacted ? seq : nullptr);
       }
-      uint32_t *d_nbad = ws<uint32_t>("nsk.nbad", 1);
-      PGX_HIP(hipMemsetAsync(d_nbad, 0, sizeof(uint32_t), st));
+      uint32_t *d_anybad = ws<uint32_t>("nsk.nbad", 1);
+      PGX_HIP(hipMemsetAsync(d_anybad, 0, sizeof(uint32_t), st));
       size_t rb = 0;
-      PGX_HIP(hipcub::DeviceReduce::Max(nullptr, rb, vflag.p, d_nbad, (int)ns, st));
+      PGX_HIP(hipcub::DeviceReduce::Max(nullptr, rb, vflag.p, d_anybad, (int)ns, st));
       void *rt = ws_raw("nsk.red_tmp", rb);
-      PGX_HIP(hipcub::DeviceReduce::Max(rt, rb, vflag.p, d_nbad, (int)ns, st));
+      PGX_HIP(hipcub::DeviceReduce::Max(rt, rb, vflag.p, d_anybad, (int)ns, st));
       uint32_t anybad = 0;
-      PGX_HIP(hipMemcpyAsync(&anybad, d_nbad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      PGX_HIP(hipMemcpyAsync(&anybad, d_anybad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       sync();
       if (!anybad) break;
       PGX_REQUIRE(attempt == 0, PGX_EARG, "a run of unambiguous bases was flagged by the closed-form kernel although its slab holds an element per position");
     }
   }
   // totals, offsets, assembly
-  hipLaunchKernelGGL(k_nread_total, dim3(cdiv(nn, 256)), dim3(256), 0, st, seg_off.p, vcnt.p, end_has.p, nn, nl0_off.p);
-  const uint64_t total = exclusive_offsets(nl0_off.p, nn);
+  hipLaunchKernelGGL(k_nread_total, dim3(cdiv(nn, 256)), dim3(256), 0, st, seg_off.p, vcnt.p, end_has.p, nn, nl0_off.p + 1);
+  const uint64_t total = scan_to_total(nl0_off.p + 1, nl0_off.p, nn);
   nl0.alloc(total ? total : 1);
   hipLaunchKernelGGL(k_nread_assemble, dim3(nn), dim3(64), 0, st, seg_off.p, vcnt.p, vpos0.p, vslab.p, vslab_off.p, end_el.p, end_has.p, nn,
                      nl0_off.p, nl0.p);
@@ -445,7 +422,7 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
   *n_total = total;
 }
 
-// the listed reads' minimizers reduced `levels` times per read (any list length): top[off[i] .. off[i] + cnt[i]) -- off = nl0_off
+// the listed reads' minimizers reduced `levels` times per read (any list length)
 void dev_reduce_nreads(const DevBuf<pgx_mm128> &nl0, const DevBuf<uint64_t> &nl0_off, uint32_t nn, uint64_t total, int rs, int levels,
                        DevBuf<pgx_mm128> &top, DevBuf<uint32_t> &cnt) {
   cnt.alloc(nn ? nn : 1);

@@ -303,12 +303,6 @@ def test_adversarial_reads_all_paths():
     assert np.array_equal(rdb.index(levels=1).top, l1)
     assert np.array_equal(rdb.index(total_chunk=3, mychunk=1).top,
                           U.orc_reduce(U.orc_reduce(np.concatenate([U.orc_sketch_seqdb(e, 80, 16, i) for i, e in enumerate(enc) if i % 3 == 1]), 6), 6))
-    import os
-    os.environ["PGX_FUSE"] = "1"   # read when the fused path is first consulted in this process; harmless if already cached
-    try:
-        assert np.array_equal(rdb.index().top, l2)
-    finally:
-        del os.environ["PGX_FUSE"]
     ov, _ = rdb.overlap(a.top, a.top_mc)
     want, _ = U.orc_overlap(db, l2, U.orc_count(l2))
     assert formats.ovlp_fields_equal(ov, want)
@@ -492,14 +486,38 @@ def test_low_complexity_reads_stay_on_the_fused_index_path(monkeypatch, tiny_sla
     l2 = U.orc_reduce(l1, 6)
     a = rdb.index()
     assert np.array_equal(a.top, l2)
-    import os
-    default_path = not (os.environ.get("PGX_SKETCH") or os.environ.get("PGX_FUSE"))   # (the round-1 kernels do fall back)
-    assert a.reads_literal == 0 or not default_path                                 # nothing fell back to the general path
+    assert a.reads_literal == 0                                                     # nothing left the closed-form passes
     b = rdb.index(levels=1)
-    assert np.array_equal(b.top, l1) and (b.reads_literal == 0 or not default_path)
+    assert np.array_equal(b.top, l1) and b.reads_literal == 0
     assert np.array_equal(rdb.index(total_chunk=2, mychunk=2).top,
                           U.orc_reduce(U.orc_reduce(np.concatenate([U.orc_sketch_seqdb(e, 80, 16, i) for i, e in enumerate(enc) if i % 2 == 0]), 6), 6))
     rdb.close()
+
+
+def test_reads_longer_than_the_in_lds_reduce_holds():
+    """k_sketch_wave + k_reduce_read (every window but 80, or a reduction factor above 17) reduce a read's level-0 list in LDS, 1,024
+    elements at most: a longer list marks its read (flag bit 256) and the run-by-run path, which reduces lists of any length, takes it.
+    Once alone among ordinary reads, once next to a read with an ambiguous base (the chunk then runs that path anyway)."""
+    from peregrine_amd.formats import SeqDB
+    rng = np.random.default_rng(4242)
+    rnd = lambda n: rng.integers(0, 4, n).astype(np.uint8)
+    for with_ambiguous in (False, True):
+        for long_len, kw, w, rs in ((60_000, dict(window=64), 64, 6), (600_000, dict(reduction=24), 80, 24)):
+            enc = [_enc(rnd(int(n))) for n in rng.integers(3000, 20000, 6)]
+            if with_ambiguous:
+                enc[1] = _with_ambiguous(rnd(9000), [4000])
+            enc.insert(3, _enc(rnd(long_len)))
+            rlen = np.array([len(e) for e in enc], np.uint32)
+            roff = np.concatenate([[0], np.cumsum(rlen.astype(np.uint64))[:-1]]).astype(np.uint64)
+            db = SeqDB(np.concatenate(enc), np.arange(len(enc), dtype=np.uint32), rlen, roff, None)
+            per = [U.orc_sketch_seqdb(e, w, 16, i) for i, e in enumerate(enc)]
+            assert len(per[3]) > 1024, len(per[3])                     # the precondition: more than k_reduce_read's RMAX
+            l1 = U.orc_reduce(np.concatenate(per), rs)
+            l2 = U.orc_reduce(l1, rs)
+            rdb = ResidentDB(db, 0)
+            assert np.array_equal(rdb.index(**kw).top, l2), (with_ambiguous, kw)
+            assert np.array_equal(rdb.index(levels=1, **kw).top, l1), (with_ambiguous, kw)
+            rdb.close()
 
 
 def _write_query_files(tmp_path):

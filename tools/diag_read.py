@@ -27,7 +27,7 @@ if len(sys.argv) > 2 and sys.argv[2] == "child":
         p = int(pos(l1)[i]); j = int(np.searchsorted(pos(l0[:len(l0) // 3]), p))
         print("   L0 index of that position in the read:", j, " L0 positions around", pos(l0)[j - 8:j + 4])
     sys.exit(0)
-for env in ({}, {"PGX_SKETCH": "wave"}, {"PGX_SKETCH": "fuse"}, {"PGX_TRACE": "1"}):
+for env in ({}, {"PGX_TRACE": "1"}):
     print("env", env, flush=True)
     r = subprocess.run([sys.executable, __file__, sys.argv[1], "child"], env=dict(os.environ, **env), capture_output=True, text=True)
     print(r.stdout, end="")

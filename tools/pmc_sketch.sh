@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ counters of the sketch kernel of the index stage (default: k_sketch_blk; PGX_SKETCH=wave for round 1's k_sketch_wave):
+# SQ counters of the sketch kernel of the index stage (default: k_sketch_blk; an index call with window=64, or with want_l0, reaches k_sketch_wave):
 #   tools/pmc_sketch.sh [tag]      4 x the E. coli-size set = 299 Mbases, 19,936 waves per launch, one wave per read
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 T=${1:-blk}
