@@ -61,7 +61,7 @@ void pgx_free(void *p);              /* releases any host array returned by this
 
 /* per-kernel device time (HIP events on the library's stream), accumulated since the last reset.
  * names: "sketch", "sketch_general", "sketch_redo", "sketch_nreads", "sketch_gather", "pack", "reduce", "count", "pairs", "replay_dense" / "replay_rows" / "replay_update" (k_eval, k_eval_rows, k_update of the device replay; only with PGX_REPLAY_TIMING=1), "align" (k_align_ph), "align1" (k_align1: launches of
- * at most 13 k alignments), "encode", "dedup", "map". */
+ * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map". */
 int pgx_timing_get(const char *kernel, double *total_ms, uint64_t *launches, uint64_t *units);
 void pgx_timing_reset(void);
 /* HBM ledger: JSON text of the library's device memory -- live bytes, bytes held in the block cache, and the live bytes BY OWNER (seqdb,
@@ -292,6 +292,31 @@ int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int 
 int pgx_reduce_batch(const pgx_mm128 *in, size_t n, int rs, pgx_mm128 **out, size_t *n_out);
 int pgx_count_batch(const pgx_mm128 *in, size_t n, pgx_mm_count **out, size_t *n_out);
 int pgx_align_batch(pgx_seqdb *db, const pgx_align_key *keys, size_t n, int band, pgx_match *out);
+/* pgx_align_key plus an offset into the TARGET: target = read rid1 from byte t_off to its end (the arguments path_to_contig.py passes to
+ * ovlp_match, py/scripts/path_to_contig.py:80-84).  Runs nibble by nibble on the reads' bytes in every state of the database: after
+ * pgx_seqdb_release_bytes / _compact_bytes on a byte view of the reads the keys name, rebuilt from the packs for the call. */
+typedef struct { uint32_t rid0, rid1, q_off, t_off; uint8_t dir0, dir1, pad[2]; } pgx_align_key2; /* 20 bytes */
+int pgx_align_batch2(pgx_seqdb *db, const pgx_align_key2 *keys, size_t n, int band, pgx_match *out);
+
+/* ---- contig layout (replaces py/scripts/path_to_contig.py, run twice by py/scripts/pg_run.py:356-362) ----
+ * One row of a tiling path: `ctg_id v w r s e olen idt _ _` with v = rid0:E|B, w = rid1:E|B (strand 0 for E, 1 otherwise) and s, e as the
+ * file gives them.  ctg numbers the contigs 0 .. n_ctg - 1 in order of first appearance; the rows of a contig are consecutive, in file
+ * order.  Per contig the first row's read v is laid down whole at 0; every row (the first included) aligns the last 500 bases of v to the
+ * last |e - s| + 500 of w (band 100) and appends seg = e - s + 500 - t_m_end bytes of w that end at e (s, e = rlen - s, rlen - e on
+ * strand 1) at ctg_len - 500 + q_m_end; later rows overwrite earlier ones, bytes no segment covers are 'N'.
+ *   pgx_contigs_resident : the contig bytes only, contig c at (*text)[ctg_off[c] .. ctg_off[c + 1]) (ctg_off: n_ctg + 1 entries, caller's);
+ *                          *text is malloc'd (pgx_free).  Any state of the database (bytes / released / compacted).
+ *   pgx_contigs_chunk    : the file level -- <seqdb_prefix>.idx / .seqdb and the tiling path in, FASTA (">ctg_id\n" contig "\n") to out_path
+ *                          (NULL: stdout), byte for byte the script's stdout.  Only the reads the path names are uploaded, in batches of
+ *                          whole contigs that fit HBM (PGX_CONTIGS_BATCH=<contigs per batch>: a test hook).
+ * PGX_EARG, a message that names the row (0-based, in file order), nothing written -- where the script raises or reads out of bounds: a
+ * row without 10 fields or with an unparsable s / e, a rid the idx lacks, len(v) < 500, |e - s| + 500 > len(w), e <= s after the strand
+ * transform, and -- known after the alignment, the first such row is reported -- e - seg < 0, a segment that starts before 0 or ends
+ * beyond the end of its contig. */
+typedef struct { uint32_t ctg, rid0, rid1; int32_t s, e; uint8_t strand0, strand1, pad[2]; } pgx_tile_row; /* 24 bytes */
+int pgx_contigs_resident(pgx_seqdb *db, const pgx_tile_row *rows, size_t n_rows, size_t n_ctg, char **text, uint64_t *ctg_off,
+                         uint64_t *text_len);
+int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const char *out_path, uint64_t *n_ctg, uint64_t *n_bases);
 
 /* host utility: the order in which klib khash (src/khash.h:232-336, integer hash :373) iterates n DISTINCT 64-bit keys
  * inserted in the given order -- the order shmr_overlap visits its tables in (src/shmr_overlap.c:206-215).  out receives

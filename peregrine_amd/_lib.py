@@ -14,7 +14,10 @@ LIB_PATH = os.environ.get("PGX_LIB", os.path.join(_HERE, "libpgx.so"))   # (PGX_
 
 MATCH_DTYPE = np.dtype([(f, "<i4") for f in ("m_size", "dist", "q_bgn", "q_end", "t_bgn", "t_end", "t_m_end", "q_m_end")])
 ALIGN_KEY_DTYPE = np.dtype([("rid0", "<u4"), ("rid1", "<u4"), ("q_off", "<u4"), ("dir0", "u1"), ("dir1", "u1"), ("pad", "u1", 2)])
-assert MATCH_DTYPE.itemsize == 32 and ALIGN_KEY_DTYPE.itemsize == 16
+ALIGN_KEY2_DTYPE = np.dtype([("rid0", "<u4"), ("rid1", "<u4"), ("q_off", "<u4"), ("t_off", "<u4"), ("dir0", "u1"), ("dir1", "u1"), ("pad", "u1", 2)])
+TILE_ROW_DTYPE = np.dtype([("ctg", "<u4"), ("rid0", "<u4"), ("rid1", "<u4"), ("s", "<i4"), ("e", "<i4"), ("strand0", "u1"), ("strand1", "u1"),
+                           ("pad", "u1", 2)])
+assert MATCH_DTYPE.itemsize == 32 and ALIGN_KEY_DTYPE.itemsize == 16 and ALIGN_KEY2_DTYPE.itemsize == 20 and TILE_ROW_DTYPE.itemsize == 24
 
 
 class PgxError(RuntimeError):
@@ -76,6 +79,7 @@ EXPORTS = [
     "pgx_map", "pgx_map_chunk", "pgx_khash_slot_order", "pgx_khash_slot_order_ex",
     "pgx_seqdb_upload_dev", "pgx_index_resident_dev", "pgx_pairs_prepare_dev", "pgx_pairs_scatter_dev", "pgx_overlap_records_dev",
     "pgx_overlap_resident_dev", "pgx_copy_dev", "pgx_seqdb_adopt_dev", "pgx_stream_wait", "pgx_stream_signal",
+    "pgx_align_batch2", "pgx_contigs_resident", "pgx_contigs_chunk",
     "build_shimmer_map4py", "get_shimmers_for_read", "get_mmer_count", "get_shimmer_hits", "pgx_shimmer_map_free",
 ]
 
@@ -144,6 +148,9 @@ def load():
         lib.pgx_reduce_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         lib.pgx_count_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.pgx_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        lib.pgx_align_batch2.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        lib.pgx_contigs_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_contigs_chunk.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
         lib.pgx_timing_get.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_khash_slot_order.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         lib.pgx_khash_slot_order_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -164,7 +171,7 @@ def load():
     return _lib
 
 
-PGX_ESTATE = -5   # include/pgx.h
+PGX_EARG, PGX_ESTATE = -1, -5   # include/pgx.h
 
 
 def check(rc: int, what: str = "pgx"):

@@ -107,20 +107,24 @@ __device__ __forceinline__ int match16p(const uint8_t *q, uint32_t xq, const uin
 // PACKED (round 6): seq = the 2-bit packs, roff = d_poff (dword index of a read's forward strand; its reverse complement follows): a probe
 // compares 16 codes, a snake iteration 64 x 16.  The run a diagonal is extended by is the same whatever the piece size, so the results are
 // those of the byte form; candidates on reads without 2-bit codes never come here (dev_align).
-template <bool PACKED>
+// KEY: pgx_align_key (the target is the whole read rid1), or pgx_align_key2 (the target starts at byte t_off of it: the byte form only)
+__device__ __forceinline__ uint32_t target_offset(const pgx_align_key &) { return 0u; }
+__device__ __forceinline__ uint32_t target_offset(const pgx_align_key2 &k) { return k.t_off; }
+template <bool PACKED, typename KEY = pgx_align_key>
 __device__ __forceinline__ void align_one_per_wave(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ roff,
-                                                   const uint32_t *__restrict__ rlen, const pgx_align_key *__restrict__ keys, uint32_t a, int band,
+                                                   const uint32_t *__restrict__ rlen, const KEY *__restrict__ keys, uint32_t a, int band,
                                                    int ring, pgx_match *__restrict__ out) {
+  static_assert(!PACKED || std::is_same_v<KEY, pgx_align_key>, "a target offset is honoured by the byte form only");
   extern __shared__ int32_t V[];
   constexpr int PB = PACKED ? 16 : 8;   // codes of a probe / of a lane's piece of a snake iteration
   const int lane = threadIdx.x;
-  const pgx_align_key key = keys[a];
+  const KEY key = keys[a];
   const uint32_t len0 = rlen[key.rid0], len1 = rlen[key.rid1];
   const uint8_t *q = PACKED ? seq + (roff[key.rid0] + (key.dir0 ? (len0 + 15u) >> 4 : 0u) + (key.q_off >> 4)) * 4 : seq + roff[key.rid0] + key.q_off;
-  const uint8_t *t = PACKED ? seq + (roff[key.rid1] + (key.dir1 ? (len1 + 15u) >> 4 : 0u)) * 4 : seq + roff[key.rid1];
+  const uint8_t *t = PACKED ? seq + (roff[key.rid1] + (key.dir1 ? (len1 + 15u) >> 4 : 0u)) * 4 : seq + roff[key.rid1] + target_offset(key);
   const uint32_t qo = PACKED ? key.q_off & 15u : 0u;
   const int q_len = (int)(len0 - key.q_off);
-  const int t_len = (int)len1;
+  const int t_len = (int)(len1 - target_offset(key));
   const int qs = key.dir0 ? 4 : 0, ts = key.dir1 ? 4 : 0;
   const int max_d = (int)(0.3 * (double)(q_len + t_len));  // DWmatch.c:96, one IEEE double multiply
   const int band_size = band * 2;
@@ -247,6 +251,11 @@ __global__ __launch_bounds__(64) void k_align1(const uint8_t *__restrict__ seq, 
                                               const pgx_align_key *__restrict__ keys, uint32_t n, int band,
                                               int ring, pgx_match *__restrict__ out) {
   if (blockIdx.x < n) align_one_per_wave<PACKED>(seq, roff, rlen, keys, blockIdx.x, band, ring, out);
+}
+// k_align1 for keys with a target offset (pgx_align_batch2, the contig layout's stitching alignments), on bytes: the seqdb, or a byte view
+__global__ __launch_bounds__(64) void k_align1t(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ roff, const uint32_t *__restrict__ rlen,
+                                               const pgx_align_key2 *__restrict__ keys, uint32_t n, int band, int ring, pgx_match *__restrict__ out) {
+  if (blockIdx.x < n) align_one_per_wave<false, pgx_align_key2>(seq, roff, rlen, keys, blockIdx.x, band, ring, out);
 }
 // k_align1 on the packs of a COMPACTED database (pgx_side.hip), the only one that pays for the look-up: a candidate that touches a read
 // without 2-bit codes is not aligned here but appended to hand_list (count at *hand_n) for k_align1_list on the byte view
@@ -860,6 +869,17 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
     launch_on(src.one, k_align1_list<true>, k_align1_list<false>, g1, dim3(64), ring * sizeof(int32_t), db->d_rlen.p, d_keys, esc, esc + 4, band,
               ring, d_out);
   }
+  PGX_HIP(hipGetLastError());
+}
+
+// n alignments with a target offset, a wavefront each, on the bytes seq + off[rid] (the seqdb, or a byte view of the reads the keys name)
+void dev_align2(const pgx_seqdb *db, const uint8_t *seq, const uint64_t *off, const pgx_align_key2 *d_keys, size_t n, int band, pgx_match *d_out) {
+  if (n == 0) return;
+  KernelTimer tm("align1t", n);
+  int ring = 64;
+  while (ring < 2 * band + 8) ring <<= 1;
+  hipLaunchKernelGGL(k_align1t, dim3((unsigned)n), dim3(64), ring * sizeof(int32_t), ctx().stream, seq, off, db->d_rlen.p, d_keys, (uint32_t)n, band, ring,
+                     d_out);
   PGX_HIP(hipGetLastError());
 }
 

@@ -1,6 +1,6 @@
 /*
  * pgx_cli.c -- native drop-ins for the reference's stage executables, one multi-call binary (the tool is chosen by the
- * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map.  Same getopt strings, defaults
+ * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map, path_to_contig.py.  Same getopt strings, defaults
  * and output files / streams as /root/reference/src/shmr_mkseqdb.c:14-128, shmr_index.c:37-245, shmr_overlap.c:233-419,
  * shmr_dedup.c:19-104, shmr_map.c:163-373; everything else happens behind the C-ABI of include/pgx.h on the GPU.
  * Plain C against libpgx.so: this is the cgo / FFI-free form of the boundary (the Python shims in bin/ do the same).
@@ -463,6 +463,18 @@ static int main_map(int argc, char **argv) {
   return 0;
 }
 
+/* path_to_contig.py <seqdb_prefix> <tiling_path> > contigs.fa (py/scripts/path_to_contig.py; pg_run.py:356-362 runs it for the primary and for
+ * the alternate contigs).  Always stand-alone: it uploads only the reads the path names, `pgx_cli serve` is not asked. */
+static int main_path_to_contig(int argc, char **argv) {
+  if (argc != 3) {
+    fprintf(stderr, "Usage: path_to_contig.py seqdb_prefix tiling_path > contigs.fa\n");
+    return 1;
+  }
+  if (pgx_init(device_of_env())) return fail("path_to_contig.py", "pgx_init");
+  if (pgx_contigs_chunk(argv[1], argv[2], NULL, NULL, NULL)) return fail("path_to_contig.py", "pgx_contigs_chunk");
+  return 0;
+}
+
 int main(int argc, char **argv) {
   char *self = strdup(argv[0]);
   const char *tool = basename(self);
@@ -476,9 +488,10 @@ int main(int argc, char **argv) {
   else if (strcmp(tool, "shmr_overlap") == 0) rc = main_overlap(argc, argv);
   else if (strcmp(tool, "shmr_dedup") == 0) rc = main_dedup(argc, argv);
   else if (strcmp(tool, "shmr_map") == 0) rc = main_map(argc, argv);
+  else if (strcmp(tool, "path_to_contig.py") == 0) rc = main_path_to_contig(argc, argv);
   else if (strcmp(tool, "serve") == 0) rc = main_serve(argc, argv);
   else {
-    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_map} [flags]   (or invoke through a link of that name)\n"
+    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_map|path_to_contig.py} [flags]   (or invoke through a link of that name)\n"
                     "       pgx_cli serve -p seqdb_prefix [-i idle_seconds]   (keeps the read database in HBM; the drop-ins attach to it)\n");
     rc = 2;
   }

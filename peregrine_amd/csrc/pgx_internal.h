@@ -290,6 +290,8 @@ uint64_t scan_to_total(const uint64_t *d_vals, uint64_t *d_offs, size_t n);
 // banded O(ND) confirmation of n candidate alignments (keys on device)
 void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int band, pgx_match *d_out,
                int tail_batch = 0);   // tail_batch: 1 = the second request batch of a stage, 2 = a later one (mostly hard candidates: pgx_align.hip)
+// alignments whose target starts at byte t_off of read rid1 (k_align1t), a wavefront each, on the bytes seq + off[rid]
+void dev_align2(const pgx_seqdb *db, const uint8_t *seq, const uint64_t *off, const pgx_align_key2 *d_keys, size_t n, int band, pgx_match *d_out);
 void dev_align_prepare(const pgx_seqdb *db);   // the database's 2-bit packs, ahead of the first large launch (no-op once they exist)
 // the 2-bit packs of a read database (pgx_pack.hip: read by read, [forward strand | reverse complement] at dword d_poff[rid]; d_nflag
 // marks the reads with bytes that have no 2-bit code): built on first use, kept with the database; nullptr: no HBM
@@ -317,6 +319,8 @@ uint64_t side_store_bytes(const pgx_seqdb *db);
 // the view for both reads of the candidates keys[list[0 .. n)], and for the reads of the slots d_reads[list[0 .. n)]
 void side_view_of_keys(const pgx_seqdb *db, const pgx_align_key *d_keys, const uint32_t *d_list, uint32_t n, ByteView &v);
 void side_view_of_reads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n, ByteView &v);
+// the view for the reads d_rids[0 .. n) names (duplicates allowed), also on a database whose bytes were RELEASED: all of them from the packs
+void side_view_of_rids(const pgx_seqdb *db, const uint32_t *d_rids, uint32_t n, ByteView &v);
 // tr[i] = d_reads[list[i]] with its offset in the view, iota[i] = i
 void side_translate_reads(const ByteView &v, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n, ReadDesc *tr, uint32_t *iota);
 

@@ -75,6 +75,12 @@ __global__ void k_claim_keys(const pgx_align_key *__restrict__ keys, const uint3
   claim(key.rid0, nflag, roff, rlen, mark, state, plist, prel);
   claim(key.rid1, nflag, roff, rlen, mark, state, plist, prel);
 }
+__global__ void k_claim_rids(const uint32_t *__restrict__ rids, uint32_t n, const uint32_t *__restrict__ nflag, const uint64_t *__restrict__ roff,
+                             const uint32_t *__restrict__ rlen, uint32_t *__restrict__ mark, unsigned long long *__restrict__ state,
+                             uint32_t *__restrict__ plist, uint64_t *__restrict__ prel) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) claim(rids[i], nflag, roff, rlen, mark, state, plist, prel);
+}
 __global__ void k_claim_reads(const ReadDesc *__restrict__ reads, const uint32_t *__restrict__ list, uint32_t n, const uint32_t *__restrict__ nflag,
                               const uint64_t *__restrict__ roff, const uint32_t *__restrict__ rlen, uint32_t *__restrict__ mark,
                               unsigned long long *__restrict__ state, uint32_t *__restrict__ plist, uint64_t *__restrict__ prel) {
@@ -132,10 +138,12 @@ __global__ void k_translate_reads(const ReadDesc *__restrict__ reads, const uint
   tr[i] = rd, iota[i] = i;
 }
 
-// the view for the reads a claim kernel names (at most max_claims distinct ones)
+// the view for the reads a claim kernel names (at most max_claims distinct ones).  released: also on a database whose bytes were RELEASED (no
+// flagged read, no side store): every read comes from the packs and the offsets count from the scratch region itself
 template <typename Claim>
-void view_build(const pgx_seqdb *db, size_t max_claims, ByteView &v, Claim &&launch_claim) {
-  PGX_REQUIRE(seq_compacted(db) && seq_packs_valid(db), PGX_ESTATE, "a byte view needs a compacted database (pgx_seqdb_compact_bytes)");
+void view_build(const pgx_seqdb *db, size_t max_claims, ByteView &v, Claim &&launch_claim, bool released = false) {
+  PGX_REQUIRE((seq_compacted(db) || (released && !db->d_seq.p)) && seq_packs_valid(db), PGX_ESTATE,
+              "a byte view needs a compacted database (pgx_seqdb_compact_bytes)");
   hipStream_t st = ctx().stream;
   const size_t nr = db->rlen_by_rid.size();
   max_claims = std::min(max_claims, nr);
@@ -162,8 +170,9 @@ void view_build(const pgx_seqdb *db, size_t max_claims, ByteView &v, Claim &&lau
     uint8_t *dst = v.scratch.p + 16;
     PGX_HIP(hipMemsetAsync(v.scratch.p, 0, 16, st));
     PGX_HIP(hipMemsetAsync(dst + bytes, 0, 1024, st));
+    if (!v.seq) v.seq = v.scratch.p;   // (a released database: no side store to count from)
     hipLaunchKernelGGL(k_unpack_reads, dim3(np), dim3(64), 0, st, db->d_pack.p, db->d_poff.p, db->d_roff.p, db->d_rlen.p, plist, prel, np, dst,
-                       (uint64_t)dst - (uint64_t)db->d_side.p, boff);
+                       (uint64_t)dst - (uint64_t)v.seq, boff);
   }
   PGX_HIP(hipGetLastError());
 }
@@ -226,6 +235,13 @@ void side_view_of_reads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint
       hipLaunchKernelGGL(k_claim_reads, dim3(cdiv(n, 256)), dim3(256), 0, ctx().stream, d_reads, d_list, n, db->d_nflag.p, db->d_roff.p, db->d_rlen.p, mark,
                          state, plist, prel);
   });
+}
+void side_view_of_rids(const pgx_seqdb *db, const uint32_t *d_rids, uint32_t n, ByteView &v) {
+  view_build(db, n, v, [&](uint32_t *mark, unsigned long long *state, uint32_t *plist, uint64_t *prel) {
+    if (n)
+      hipLaunchKernelGGL(k_claim_rids, dim3(cdiv(n, 256)), dim3(256), 0, ctx().stream, d_rids, n, db->d_nflag.p, db->d_roff.p, db->d_rlen.p, mark, state,
+                         plist, prel);
+  }, true);
 }
 void side_translate_reads(const ByteView &v, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n, ReadDesc *tr, uint32_t *iota) {
   if (n) hipLaunchKernelGGL(k_translate_reads, dim3(cdiv(n, 256)), dim3(256), 0, ctx().stream, d_reads, d_list, n, v.off, tr, iota);

@@ -224,6 +224,26 @@ class ResidentDB:
         _lib.check(self._lib.pgx_align_batch(self.h, _ptr(keys), len(keys), band, _ptr(out)), "pgx_align_batch")
         return out
 
+    def align2(self, keys: np.ndarray, band=100) -> np.ndarray:
+        """align() with a target offset (pgx_align_batch2): the target is read rid1 from byte t_off to its end"""
+        keys = np.ascontiguousarray(keys, _lib.ALIGN_KEY2_DTYPE)
+        out = np.zeros(len(keys), _lib.MATCH_DTYPE)
+        _lib.check(self._lib.pgx_align_batch2(self.h, _ptr(keys), len(keys), band, _ptr(out)), "pgx_align_batch2")
+        return out
+
+    def contigs(self, rows: np.ndarray):
+        """Contig layout of tiling-path rows (pgx_contigs_resident; _lib.TILE_ROW_DTYPE: contigs numbered 0 .. in order, a contig's rows
+        consecutive, s / e as the tiling path gives them).  Returns (bytes, offsets): contig c is bytes[offsets[c]:offsets[c + 1]]."""
+        rows = np.ascontiguousarray(rows, _lib.TILE_ROW_DTYPE)
+        n_ctg = int(rows["ctg"].max()) + 1 if len(rows) else 0
+        off = np.zeros(n_ctg + 1, np.uint64)
+        text, tl = C.c_void_p(), C.c_uint64(0)
+        _lib.check(self._lib.pgx_contigs_resident(self.h, _ptr(rows), len(rows), n_ctg, C.byref(text), _ptr(off), C.byref(tl)),
+                   "pgx_contigs_resident")
+        data = C.string_at(text.value, tl.value)
+        self._lib.pgx_free(text)
+        return data, off
+
 
 def mm_reduce(mm: np.ndarray, rs: int) -> np.ndarray:
     """GPU mm_reduce over an arbitrary multi-read list (src/shmr_reduce.c:53-90)."""
@@ -384,6 +404,19 @@ def shmr_map(ref_shimmer_prefix: str = "ref-L2", seqdb_prefix: str = "seq_datase
         with open(out_path, "wb") as f:
             f.write(data)
     return data, int(nl.value)
+
+
+def path_to_contig(seqdb_prefix: str, tiling_path: str, out: str | None = None, device=None) -> dict:
+    """path_to_contig.py seqdb_prefix tiling_path (pgx_contigs_chunk): the contigs of a tiling path as FASTA, byte for byte the script's
+    stdout, written to `out` (None: this process's stdout).  Only the reads the path names go to the GPU."""
+    _lib.init(device)
+    if out is None:
+        import sys
+        sys.stdout.flush()
+    nc, nb = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.load().pgx_contigs_chunk(seqdb_prefix.encode(), tiling_path.encode(), out.encode() if out is not None else None,
+                                             C.byref(nc), C.byref(nb)), "pgx_contigs_chunk")
+    return dict(contigs=int(nc.value), bases=int(nb.value))
 
 
 def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None):
