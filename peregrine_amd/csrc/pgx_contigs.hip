@@ -12,7 +12,11 @@
 //                the contig's offset in the output plus ctg_len before the row -- every segment's place in the concatenated output, every
 //                contig's offset and the total from one scan, nothing segmented
 //   k_tile_place per row: the segment's descriptor {output offset, source byte, length, strand}, and the checks that need the alignment
-//                (e - seg < 0; a segment that starts before its contig or ends beyond it): the smallest offending row goes to the host
+//                (a segment that starts before its contig or ends beyond it)
+//   the error row: k_tile_geom (e - seg < 0) and k_tile_place both run on every call, whatever the other finds, and atomicMin
+//                row << 2 | kind into ONE word: the host names the smallest offending row in contig order whatever its kind, and of two
+//                kinds on one row the smaller (BAD_SOURCE < BAD_START < BAD_END).  A row with e - seg < 0 keeps its seg and its step, so
+//                the places of all other rows are defined; its descriptor is stored and never read (no k_stitch after an offence)
 //   two running maxima: PM[k] = the furthest end of the segments 0 .. k, and the smallest start of the segments k .. (as a maximum of
 //                complements over the reversed order) -- both monotone in k whatever the rows do
 //   k_stitch     a workgroup per 4 KiB tile of the output: the segments that can touch the tile [a, b) are k in [first PM > a, first
@@ -265,16 +269,14 @@ void contigs_layout(pgx_seqdb *db, const std::vector<pgx_tile_row> &rows, const 
     hipLaunchKernelGGL(k_tile_geom, dim3(cdiv(n, 256)), dim3(256), 0, st, d_rows.p, d_match.p, (uint32_t)n, db->d_rlen.p, d_step.p, d_seglen.p, d_bad.p);
     exclusive_sum(d_step.p, d_before.p, n_seg + 1);   // (step[n_seg] = 0: before[n_seg] is the total)
   }
+  // the placement checks run whatever the geometry pass found: a row with e - seg < 0 still has its seg and its step, so every other row's
+  // place is defined, and k_tile_place only STORES the descriptor of such a row (nothing is read through it: k_stitch is not launched)
+  hipLaunchKernelGGL(k_tile_place, dim3(cdiv(n, 256)), dim3(256), 0, st, d_rows.p, d_match.p, d_seglen.p, (uint32_t)n, (uint32_t)n_seg, d_first.p, d_before.p,
+                     src.off, db->d_rlen.p, d_segs.p, d_end.p, d_rev.p, d_ctg_off.p, d_bad.p);
+  PGX_HIP(hipGetLastError());
   PGX_HIP(hipMemcpyAsync(&total, d_before.p + n_seg, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   PGX_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(bad), hipMemcpyDeviceToHost, st));
   sync();
-  if (bad == NO_BAD) {
-    hipLaunchKernelGGL(k_tile_place, dim3(cdiv(n, 256)), dim3(256), 0, st, d_rows.p, d_match.p, d_seglen.p, (uint32_t)n, (uint32_t)n_seg, d_first.p, d_before.p,
-                       src.off, db->d_rlen.p, d_segs.p, d_end.p, d_rev.p, d_ctg_off.p, d_bad.p);
-    PGX_HIP(hipGetLastError());
-    PGX_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(bad), hipMemcpyDeviceToHost, st));
-    sync();
-  }
   if (bad != NO_BAD) {
     const size_t i = (size_t)(bad >> 2);
     const unsigned kind = (unsigned)(bad & 3u);
