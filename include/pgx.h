@@ -269,6 +269,25 @@ int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out);
 int pgx_dedup_feed(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len);
 int pgx_dedup_feed_dev(pgx_dedup_stream *s, const pgx_ovlp *d_recs, size_t n, char **text, size_t *text_len);
 int pgx_dedup_close(pgx_dedup_stream *s, uint64_t *n_records, uint64_t *n_unique);
+/* GRAPH MODE of the stream: only the lines the string graph's loader can use (ovlp_to_graph.py:677-770 reads every line, keeps the
+ * `overlap` lines, and then skips those with a read in contained_reads).  A printed line with rid0 != rid1 marks a read contained: rid0 if
+ * its type is `contained` (every ovlp_type but 0 and 1), rid1 if it is `contains`; a self pair marks nothing and a record that lost
+ * first-wins prints -- and marks -- nothing.  The stream hands out, in stream order, exactly the lines of type `overlap` with
+ * rid0 != rid1 and neither read marked by ANY line of the whole stream; the loader makes the same add_edge calls from them as from the full
+ * text, for every --min_len / --min_idt (neither is applied here).  Read ids are compared as 32-bit numbers.
+ *   pgx_dedup_open_graph : as pgx_dedup_open.  pgx_dedup_feed / _feed_dev return *text_len == 0: the lines wait in HBM as 48-byte rows
+ *                          (rows whose read is marked already are not even stored), beside a bitmap of the marked reads (one bit per id up
+ *                          to the largest marked one, 512 MiB at most).  No host spill: PGX_ENOMEM fails the stream.
+ *   pgx_dedup_drain      : after the last feed, the kept lines in order, at most max_lines (> 0) and 2^24 per call;
+ *                          *text as from a feed, *done != 0 with the last of them (at once on a stream that keeps nothing).  The
+ *                          first call compacts the rows against the final bitmap; from then on feeds are refused with PGX_ESTATE (which
+ *                          does not fail the stream).
+ *   pgx_dedup_graph_stats: reads marked so far, lines kept (final once a drain has run; before, the rows held -- an upper bound), lines
+ *                          a plain stream would have written so far (pgx_dedup_close's n_unique).  Any of the three may be NULL.
+ * Both refuse a plain stream, a failed one and a missing device context with PGX_ESTATE.  pgx_dedup_close as above. */
+int pgx_dedup_open_graph(uint64_t expected_pairs, pgx_dedup_stream **out);
+int pgx_dedup_drain(pgx_dedup_stream *s, uint64_t max_lines, char **text, size_t *text_len, int *done);
+int pgx_dedup_graph_stats(pgx_dedup_stream *s, uint64_t *n_contained_reads, uint64_t *n_lines_kept, uint64_t *n_lines_total);
 
 /* ---- reads -> contigs mapping (replaces shmr_map, src/shmr_map.c:48-161,163-373) ----
  * The reads' shimmer-pair map is built exactly as in the overlap stage (build_map with -t/-c/-n/-M); the reference

@@ -370,7 +370,9 @@ static int main_overlap(int argc, char **argv) { return run_overlap_args(argc, a
 /* shmr_dedup: the ovlp_t stream from stdin (cat ovlp*.dat | shmr_dedup, pg_run.py:351-352) goes through a pgx_dedup stream in pieces of
  * PGX_DEDUP_PIECE records (default 16 Mi = 1 GiB; a test hook).  Two piece buffers: a reader thread fills one while the GPU works on the
  * other, and each feed's text is written as it comes back -- host memory is two pieces and about two copies of one feed's text whatever
- * the stream's length. */
+ * the stream's length.
+ * -g (the reference's tool takes no flags): a graph-mode stream -- nothing is written until the end of stdin, then the lines the string
+ * graph's loader uses are drained in pieces of PGX_DEDUP_PIECE lines. */
 struct dedup_reader {
   char *buf;
   size_t cap, got;   /* bytes; cap is a whole number of records */
@@ -387,7 +389,8 @@ static void *dedup_read_piece(void *arg) {
   return NULL;
 }
 static int main_dedup(int argc, char **argv) {
-  (void)argc, (void)argv;
+  int graph = 0;
+  for (int i = 1; i < argc; ++i) graph |= strcmp(argv[i], "-g") == 0;   /* (other arguments are ignored, as ever) */
   size_t piece = (size_t)16 << 20;
   const char *pe = getenv("PGX_DEDUP_PIECE");
   if (pe && atoll(pe) > 0) piece = (size_t)atoll(pe);
@@ -407,7 +410,7 @@ static int main_dedup(int argc, char **argv) {
   pgx_dedup_stream *ds = NULL;
   int rc = 0, open_failed = 0;
   if (pgx_init(device_of_env())) rc = fail("shmr_dedup", "pgx_init"), open_failed = 1;
-  else if (pgx_dedup_open(0, &ds)) rc = fail("shmr_dedup", "pgx_dedup_open"), open_failed = 1;
+  else if (graph ? pgx_dedup_open_graph(0, &ds) : pgx_dedup_open(0, &ds)) rc = fail("shmr_dedup", "pgx_dedup_open"), open_failed = 1;
   for (int k = 0;; k ^= 1) {
     pthread_join(th, NULL);
     const size_t got = rd.got;
@@ -429,6 +432,14 @@ static int main_dedup(int argc, char **argv) {
       break;
     }
     if (!more) break;
+  }
+  for (int done = !graph || !ds || rc; !done;) {
+    char *text = NULL;
+    size_t len = 0;
+    if (pgx_dedup_drain(ds, piece, &text, &len, &done)) rc = fail("shmr_dedup", "pgx_dedup_drain");
+    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("shmr_dedup: stdout");
+    pgx_free(text);
+    if (rc) break;
   }
   if (ds) pgx_dedup_close(ds, NULL, NULL);
   free(bufs[0]), free(bufs[1]);

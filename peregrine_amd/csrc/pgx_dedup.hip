@@ -274,6 +274,60 @@ __global__ __launch_bounds__(FMT_TILE) void k_format(const Row *__restrict__ row
   for (uint32_t k = body_hi + threadIdx.x; k < hi; k += FMT_TILE) g[k] = tile[k];
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// graph mode: the reads the string graph's loader would call contained, and the lines it would keep
+// ---------------------------------------------------------------------------------------------------------
+// the read a printed line marks (ovlp_to_graph.py:683-698): none for a self pair or an `overlap` line, rid1 for `contains`, rid0 for
+// `contained` -- every other type value, as the formatter prints it
+__device__ inline bool row_marks(const Row &r, uint32_t *rid) {
+  if (r.rid0 == r.rid1 || r.type == 0) return false;
+  *rid = r.type == 1 ? r.rid1 : r.rid0;
+  return true;
+}
+// one bit per read id; ids beyond the bitmap are unmarked (it is sized by the largest id that WAS marked)
+__device__ inline bool bit_marked(const uint32_t *__restrict__ bits, uint32_t n_words, uint32_t rid) {
+  const uint32_t w = rid >> 5;
+  return w < n_words && ((bits[w] >> (rid & 31u)) & 1u);
+}
+__device__ inline bool row_kept(const Row &r, const uint32_t *__restrict__ bits, uint32_t n_words) {
+  return r.type == 0 && r.rid0 != r.rid1 && !bit_marked(bits, n_words, r.rid0) && !bit_marked(bits, n_words, r.rid1);
+}
+// out[0] += rows that mark a read, out[1] = max(out[1], the largest id they mark): a wavefront reduces first, one atomic pair per wavefront
+__global__ void k_mark_extent(const Row *__restrict__ rows, uint32_t m, uint32_t *__restrict__ out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t rid = 0;
+  const bool mk = j < m && row_marks(rows[j], &rid);
+  uint32_t v = mk ? rid : 0u;
+  for (int d = 32; d; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
+  const uint64_t b = __ballot(mk);
+  if ((threadIdx.x & 63) == 0 && b) {
+    atomicAdd(&out[0], (uint32_t)__popcll(b));
+    atomicMax(&out[1], v);
+  }
+}
+__global__ void k_mark(const Row *__restrict__ rows, uint32_t m, uint32_t *__restrict__ bits, uint32_t n_words) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t rid;
+  if (j >= m || !row_marks(rows[j], &rid)) return;
+  const uint32_t w = rid >> 5;
+  if (w < n_words) atomicOr(&bits[w], 1u << (rid & 31u));   // (the host sized the bitmap for this feed's largest id before the launch)
+}
+__global__ void k_kept_flags(const Row *__restrict__ rows, uint32_t m, const uint32_t *__restrict__ bits, uint32_t n_words,
+                             uint8_t *__restrict__ flag) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < m) flag[j] = row_kept(rows[j], bits, n_words);
+}
+__global__ void k_gather_rows(const Row *__restrict__ rows, const uint32_t *__restrict__ sel, uint32_t m, Row *__restrict__ out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < m) out[j] = rows[sel[j]];
+}
+__global__ void k_count_bits(const uint32_t *__restrict__ bits, uint32_t n_words, unsigned long long *__restrict__ total) {
+  uint32_t c = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += gridDim.x * blockDim.x) c += (uint32_t)__popc(bits[i]);
+  for (int d = 32; d; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(total, (unsigned long long)c);
+}
+
 // one line on the host (what pgx_dedup prints, PGX_DEDUP_HOST_TEXT=1, and the rows with m_size == 0)
 static int host_line(const Row &r, char *line, size_t cap) {
   const double err_est = 100.0 - 100.0 * (double)r.dist / (double)r.m_size;
@@ -346,6 +400,12 @@ struct pgx_dedup_stream {
   bool shut = false;                // pgx_shutdown ran while the stream was open: its device state is gone
   char *pin[2] = {nullptr, nullptr};   // text staging (pinned), made at the first feed that has text
   hipEvent_t ev[2] = {nullptr, nullptr};
+  // graph mode (pgx_dedup_open_graph): the lines wait in HBM as rows until the end of the stream says which reads are contained
+  bool graph = false;
+  bool draining = false;            // the first pgx_dedup_drain ran: the store holds exactly the kept lines' rows, no feed is accepted
+  DevBuf<uint32_t> bits;            // contained reads, one bit per read id (MemTag "dedup"); bits.n words, a power of two
+  DevBuf<pgx::Row> store;           // rows of the `overlap` lines between two unmarked reads, in stream order; store.n is the capacity
+  uint64_t store_n = 0, drained = 0;   // rows held; rows handed out as text
 };
 
 namespace pgx {
@@ -357,6 +417,7 @@ std::vector<pgx_dedup_stream *> g_streams;   // the open ones
 
 void stream_drop_device_state(pgx_dedup_stream *s) {
   s->tab.release();
+  s->bits.release(), s->store.release();
   for (int k = 0; k < 2; ++k) {
     if (s->pin[k]) (void)hipHostFree(s->pin[k]);
     if (s->ev[k]) (void)hipEventDestroy(s->ev[k]);
@@ -421,42 +482,12 @@ char *empty_text() {
   return t;
 }
 
-// one feed over records that are on the device
-void feed_device(pgx_dedup_stream *s, const pgx_ovlp *d_in, size_t n, char **text, size_t *text_len) {
+// the text of m rows on the device (m > 0; d_m[1] is zero: it counts the rows the host formats)
+void rows_to_text(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *d_m, char **text, size_t *text_len) {
   static const bool host_text = getenv("PGX_DEDUP_HOST_TEXT") && atoi(getenv("PGX_DEDUP_HOST_TEXT")) != 0;   // diagnostic (=1): the lines by snprintf on the host
   hipStream_t st = ctx().stream;
-  KernelTimer tm("dedup", n);
-  uint64_t *key = ws<uint64_t>("dd.key", n), *skey = ws<uint64_t>("dd.skey", n);
-  uint32_t *idx = ws<uint32_t>("dd.idx", n), *sidx = ws<uint32_t>("dd.sidx", n), *sel = ws<uint32_t>("dd.sel", n);
-  uint8_t *keep = ws<uint8_t>("dd.keep", n), *head = ws<uint8_t>("dd.head", n);
-  uint32_t *d_m = ws<uint32_t>("dd.m", 2);   // [0]: a count; [1]: rows the host formats
-  PGX_HIP(hipMemsetAsync(d_m, 0, 2 * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_pair_keys, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, (uint32_t)n, key, idx);
   size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
-  void *tmp = ws_raw("dd.tmp", bytes);
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
-  hipLaunchKernelGGL(k_run_heads, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, (uint32_t)n, s->tab.p, s->cap - 1, head, d_m);
-  uint32_t n_new = 0;
-  PGX_HIP(hipMemcpyAsync(&n_new, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  pgx::sync();
-  seen_reserve(s, n_new);
-  hipLaunchKernelGGL(k_seen_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, sidx, head, (uint32_t)n, s->tab.p, s->cap - 1, keep);
-  bytes = 0;
-  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> it(0);
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, it, keep, sel, d_m, (int)n, st));
-  tmp = ws_raw("dd.tmp", bytes);
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, it, keep, sel, d_m, (int)n, st));
-  uint32_t m = 0;
-  PGX_HIP(hipMemcpyAsync(&m, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  pgx::sync();
-  s->n_records += n, s->n_unique += m;   // (the set holds them from here on, whatever happens to the text)
-  if (m == 0) {
-    *text = empty_text(), *text_len = 0;
-    return;
-  }
-  Row *d_rows = ws<Row>("dd.rows", m);
-  hipLaunchKernelGGL(k_rows, dim3(cdiv(m, 256)), dim3(256), 0, st, d_in, sel, m, d_rows);
+  void *tmp = nullptr;
   char line[256];
   if (host_text) {
     std::vector<Row> rows(m);
@@ -522,6 +553,164 @@ void feed_device(pgx_dedup_stream *s, const pgx_ovlp *d_in, size_t n, char **tex
   *text = t, *text_len = out.size();
 }
 
+// ---- graph mode -----------------------------------------------------------------------------------------------------------------------
+constexpr uint64_t BITS_MIN_WORDS = 2;   // doubled up to the word of the largest marked id: 2^27 words = 512 MiB at most
+constexpr uint64_t STORE_MIN_ROWS = 1ULL << 16;
+constexpr uint32_t COMPACT_ROWS = 1u << 22;    // rows per piece of the final compaction (its scratch: 192 MiB)
+constexpr uint64_t DRAIN_MAX_LINES = 1ULL << 24;   // lines per drain call at most (their text: < 2.4 GB)
+
+template <typename T>
+void graph_alloc(DevBuf<T> &buf, uint64_t count, const char *what) {
+  MemTag tag("dedup");
+  try {
+    buf.alloc(count);
+  } catch (const Fail &) {
+    (void)hipGetLastError();
+    set_error("pgx_dedup: no device memory for %s of %llu bytes", what, (unsigned long long)(count * sizeof(T)));
+    throw Fail{PGX_ENOMEM};
+  }
+}
+// the bitmap covers read id max_rid
+void bits_reserve(pgx_dedup_stream *s, uint32_t max_rid) {
+  uint64_t words = s->bits.n ? s->bits.n : BITS_MIN_WORDS;
+  while (words * 32 <= (uint64_t)max_rid) words *= 2;
+  if (words == s->bits.n) return;
+  DevBuf<uint32_t> bigger;
+  graph_alloc(bigger, words, "a read bitmap");
+  hipStream_t st = ctx().stream;
+  if (s->bits.n) PGX_HIP(hipMemcpyAsync(bigger.p, s->bits.p, s->bits.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  PGX_HIP(hipMemsetAsync(bigger.p + s->bits.n, 0, (words - s->bits.n) * sizeof(uint32_t), st));
+  s->bits = std::move(bigger);   // (one stream: the old words' next user comes after the copy)
+}
+// room for `more` rows behind the store's store_n
+void store_reserve(pgx_dedup_stream *s, uint64_t more) {
+  uint64_t cap = s->store.n ? s->store.n : STORE_MIN_ROWS;
+  while (s->store_n + more > cap) cap *= 2;
+  if (cap == s->store.n) return;
+  DevBuf<Row> bigger;
+  graph_alloc(bigger, cap, "a row store");
+  if (s->store_n) PGX_HIP(hipMemcpyAsync(bigger.p, s->store.p, s->store_n * sizeof(Row), hipMemcpyDeviceToDevice, ctx().stream));
+  s->store = std::move(bigger);
+}
+// sel[0 .. returned) = the j < m, ascending, whose row the graph's loader would keep under the bitmap as it is now
+uint32_t select_kept(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *sel, uint32_t *d_cnt) {
+  hipStream_t st = ctx().stream;
+  uint8_t *flag = ws<uint8_t>("dd.gflag", m);
+  hipLaunchKernelGGL(k_kept_flags, dim3(cdiv(m, 256)), dim3(256), 0, st, d_rows, m, s->bits.p, (uint32_t)s->bits.n, flag);
+  size_t bytes = 0;
+  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> it(0);
+  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag, sel, d_cnt, (int)m, st));
+  void *tmp = ws_raw("dd.tmp", bytes);
+  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, it, flag, sel, d_cnt, (int)m, st));
+  uint32_t k = 0;
+  PGX_HIP(hipMemcpyAsync(&k, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  return k;
+}
+// a feed's winner rows: their marks into the bitmap, then the rows that may still become lines behind the store.  A row whose read is
+// marked ALREADY is dropped here, which only bounds the store: a mark that arrives later is seen by the final pass (graph_compact).
+void graph_take(pgx_dedup_stream *s, const Row *d_rows, uint32_t m) {
+  hipStream_t st = ctx().stream;
+  uint32_t *d_g = ws<uint32_t>("dd.g", 3);   // [0]: rows that mark, [1]: the largest id they mark, [2]: a count
+  PGX_HIP(hipMemsetAsync(d_g, 0, 3 * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_mark_extent, dim3(cdiv(m, 256)), dim3(256), 0, st, d_rows, m, d_g);
+  uint32_t ext[2] = {0, 0};
+  PGX_HIP(hipMemcpyAsync(ext, d_g, sizeof(ext), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  if (ext[0]) {
+    bits_reserve(s, ext[1]);
+    hipLaunchKernelGGL(k_mark, dim3(cdiv(m, 256)), dim3(256), 0, st, d_rows, m, s->bits.p, (uint32_t)s->bits.n);
+  }
+  uint32_t *sel = ws<uint32_t>("dd.gsel", m);
+  const uint32_t k = select_kept(s, d_rows, m, sel, d_g + 2);
+  if (k == 0) return;
+  store_reserve(s, k);
+  hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(k, 256)), dim3(256), 0, st, d_rows, sel, k, s->store.p + s->store_n);
+  PGX_HIP(hipGetLastError());
+  s->store_n += k;
+}
+// the end of the stream: one stable pass over the store against the FINAL bitmap, piece by piece and in place (a piece's kept rows go
+// to a scratch buffer and from there to the store's front, which the pass has read already)
+void graph_compact(pgx_dedup_stream *s) {
+  hipStream_t st = ctx().stream;
+  const uint64_t n = s->store_n;
+  uint64_t kept = 0;
+  if (n) {
+    const uint32_t piece = (uint32_t)std::min<uint64_t>(n, COMPACT_ROWS);
+    DevBuf<Row> scratch;
+    graph_alloc(scratch, piece, "the compaction's scratch");
+    uint32_t *sel = ws<uint32_t>("dd.gsel", piece), *d_g = ws<uint32_t>("dd.g", 3);
+    for (uint64_t at = 0; at < n; at += piece) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
+      const uint32_t k = select_kept(s, s->store.p + at, m, sel, d_g + 2);
+      if (k == 0) continue;
+      if (kept == at && k == m) {   // nothing dropped so far: the rows are in place
+        kept += k;
+        continue;
+      }
+      hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(k, 256)), dim3(256), 0, st, s->store.p + at, sel, k, scratch.p);
+      PGX_HIP(hipMemcpyAsync(s->store.p + kept, scratch.p, (size_t)k * sizeof(Row), hipMemcpyDeviceToDevice, st));
+      kept += k;
+    }
+    PGX_HIP(hipGetLastError());
+  }
+  s->store_n = kept;
+  s->draining = true;
+}
+uint64_t graph_count_marked(pgx_dedup_stream *s) {
+  if (!s->bits.n) return 0;
+  hipStream_t st = ctx().stream;
+  unsigned long long *d_total = ws<unsigned long long>("dd.gtotal", 1), total = 0;
+  PGX_HIP(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_count_bits, dim3(std::min<unsigned>(cdiv(s->bits.n, 256), 4096)), dim3(256), 0, st, s->bits.p, (uint32_t)s->bits.n, d_total);
+  PGX_HIP(hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  return total;
+}
+
+// one feed over records that are on the device
+void feed_device(pgx_dedup_stream *s, const pgx_ovlp *d_in, size_t n, char **text, size_t *text_len) {
+  hipStream_t st = ctx().stream;
+  KernelTimer tm("dedup", n);
+  uint64_t *key = ws<uint64_t>("dd.key", n), *skey = ws<uint64_t>("dd.skey", n);
+  uint32_t *idx = ws<uint32_t>("dd.idx", n), *sidx = ws<uint32_t>("dd.sidx", n), *sel = ws<uint32_t>("dd.sel", n);
+  uint8_t *keep = ws<uint8_t>("dd.keep", n), *head = ws<uint8_t>("dd.head", n);
+  uint32_t *d_m = ws<uint32_t>("dd.m", 2);   // [0]: a count; [1]: rows the host formats
+  PGX_HIP(hipMemsetAsync(d_m, 0, 2 * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_pair_keys, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, (uint32_t)n, key, idx);
+  size_t bytes = 0;
+  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
+  void *tmp = ws_raw("dd.tmp", bytes);
+  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
+  hipLaunchKernelGGL(k_run_heads, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, (uint32_t)n, s->tab.p, s->cap - 1, head, d_m);
+  uint32_t n_new = 0;
+  PGX_HIP(hipMemcpyAsync(&n_new, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  seen_reserve(s, n_new);
+  hipLaunchKernelGGL(k_seen_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, sidx, head, (uint32_t)n, s->tab.p, s->cap - 1, keep);
+  bytes = 0;
+  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> it(0);
+  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, it, keep, sel, d_m, (int)n, st));
+  tmp = ws_raw("dd.tmp", bytes);
+  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, it, keep, sel, d_m, (int)n, st));
+  uint32_t m = 0;
+  PGX_HIP(hipMemcpyAsync(&m, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  s->n_records += n, s->n_unique += m;   // (the set holds them from here on, whatever happens to the text)
+  if (m == 0) {
+    *text = empty_text(), *text_len = 0;
+    return;
+  }
+  Row *d_rows = ws<Row>("dd.rows", m);
+  hipLaunchKernelGGL(k_rows, dim3(cdiv(m, 256)), dim3(256), 0, st, d_in, sel, m, d_rows);
+  if (s->graph) {   // the lines wait for the end of the stream (pgx_dedup_drain)
+    graph_take(s, d_rows, m);
+    *text = empty_text(), *text_len = 0;
+    return;
+  }
+  rows_to_text(s, d_rows, m, d_m, text, text_len);
+}
+
 // (*text was cleared before anything could throw: what it holds now is this call's own allocation)
 void feed_failed(pgx_dedup_stream *s, char **text, size_t *text_len) {
   if (s) s->failed = true;
@@ -535,6 +724,10 @@ int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, s
     PGX_REQUIRE(s && text && text_len && (n == 0 || recs), PGX_EARG, "%s: null argument", who);
     PGX_REQUIRE(!s->shut, PGX_ESTATE, "%s: pgx_shutdown ran while the stream was open (close it)", who);
     PGX_REQUIRE(!s->failed, PGX_ESTATE, "%s: the stream returned an error before (close it)", who);
+    if (s->draining) {   // (refused, not an error of the stream: the drain goes on)
+      set_error("%s: the stream is being drained (pgx_dedup_drain ran)", who);
+      return PGX_ESTATE;
+    }
     require_ready();
     PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many records for one feed");
     if (n == 0) {
@@ -562,16 +755,17 @@ int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, s
 }  // namespace
 }  // namespace pgx
 
-extern "C" int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out) {
+static int open_any(uint64_t expected_pairs, pgx_dedup_stream **out, bool graph, const char *who) {
   pgx_dedup_stream *s = nullptr;
   const int rc = guarded([&] {
-    PGX_REQUIRE(out, PGX_EARG, "pgx_dedup_open: null argument");
+    PGX_REQUIRE(out, PGX_EARG, "%s: null argument", who);
     *out = nullptr;
-    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "pgx_dedup_open: no device context (pgx_init has not been called, or found no HIP device)");
-    PGX_REQUIRE(expected_pairs < (1ULL << 40), PGX_ENOMEM, "pgx_dedup_open: no device holds a set of %llu pairs", (unsigned long long)expected_pairs);
+    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "%s: no device context (pgx_init has not been called, or found no HIP device)", who);
+    PGX_REQUIRE(expected_pairs < (1ULL << 40), PGX_ENOMEM, "%s: no device holds a set of %llu pairs", who, (unsigned long long)expected_pairs);
     uint64_t cap = SEEN_MIN_CAP;
     while (cap < 2 * expected_pairs) cap *= 2;
     s = new pgx_dedup_stream;
+    s->graph = graph;
     seen_alloc(s->tab, cap);
     s->cap = cap;
     pgx::sync();
@@ -583,12 +777,76 @@ extern "C" int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out) {
   return rc;
 }
 
+extern "C" int pgx_dedup_open(uint64_t expected_pairs, pgx_dedup_stream **out) { return open_any(expected_pairs, out, false, "pgx_dedup_open"); }
+
+extern "C" int pgx_dedup_open_graph(uint64_t expected_pairs, pgx_dedup_stream **out) {
+  return open_any(expected_pairs, out, true, "pgx_dedup_open_graph");
+}
+
 extern "C" int pgx_dedup_feed(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len) {
   return feed_any(s, recs, n, text, text_len, false, "pgx_dedup_feed");
 }
 
 extern "C" int pgx_dedup_feed_dev(pgx_dedup_stream *s, const pgx_ovlp *d_recs, size_t n, char **text, size_t *text_len) {
   return feed_any(s, d_recs, n, text, text_len, true, "pgx_dedup_feed_dev");
+}
+
+// what both graph-mode calls ask of their stream (the device context first: without one no stream can exist)
+static void require_graph_stream(const pgx_dedup_stream *s, const char *who) {
+  PGX_REQUIRE(ctx().ready, PGX_ESTATE, "%s: no device context (pgx_init has not been called, or found no HIP device)", who);
+  PGX_REQUIRE(s, PGX_EARG, "%s: null argument", who);
+  PGX_REQUIRE(!s->shut, PGX_ESTATE, "%s: pgx_shutdown ran while the stream was open (close it)", who);
+  PGX_REQUIRE(!s->failed, PGX_ESTATE, "%s: the stream returned an error before (close it)", who);
+  PGX_REQUIRE(s->graph, PGX_ESTATE, "%s: not a graph-mode stream (pgx_dedup_open_graph)", who);
+}
+
+// the next lines of a graph-mode stream, at most max_lines of them; the first call settles which lines there are
+static void drain_lines(pgx_dedup_stream *s, uint64_t max_lines, char **text, size_t *text_len, int *done) {
+  KernelTimer tm("dedup", std::min<uint64_t>(max_lines, s->store_n - s->drained));
+  if (!s->draining) graph_compact(s);
+  const uint32_t m = (uint32_t)std::min<uint64_t>({max_lines, s->store_n - s->drained, DRAIN_MAX_LINES});
+  if (m == 0) *text = empty_text();
+  else {
+    uint32_t *d_m = ws<uint32_t>("dd.m", 2);
+    PGX_HIP(hipMemsetAsync(d_m, 0, 2 * sizeof(uint32_t), ctx().stream));
+    rows_to_text(s, s->store.p + s->drained, m, d_m, text, text_len);
+  }
+  s->drained += m;
+  if (s->drained == s->store_n) {
+    *done = 1;
+    s->store.release();   // (the counters stay for pgx_dedup_graph_stats)
+  }
+}
+
+extern "C" int pgx_dedup_drain(pgx_dedup_stream *s, uint64_t max_lines, char **text, size_t *text_len, int *done) {
+  if (text) *text = nullptr;
+  if (text_len) *text_len = 0;
+  if (done) *done = 0;
+  bool mine = false;   // the checks passed: an error from here on is the stream's
+  try {
+    require_graph_stream(s, "pgx_dedup_drain");
+    PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_dedup_drain: null argument or max_lines == 0");
+    mine = true;
+    drain_lines(s, max_lines, text, text_len, done);
+    timing_flush();
+  } catch (const Fail &f) {
+    feed_failed(mine ? s : nullptr, text, text_len);
+    return f.code;
+  } catch (const std::bad_alloc &) {
+    feed_failed(mine ? s : nullptr, text, text_len);
+    set_error("out of host memory");
+    return PGX_ENOMEM;
+  }
+  return PGX_OK;
+}
+
+extern "C" int pgx_dedup_graph_stats(pgx_dedup_stream *s, uint64_t *n_contained_reads, uint64_t *n_lines_kept, uint64_t *n_lines_total) {
+  return guarded([&] {
+    require_graph_stream(s, "pgx_dedup_graph_stats");
+    if (n_contained_reads) *n_contained_reads = graph_count_marked(s);
+    if (n_lines_kept) *n_lines_kept = s->store_n;
+    if (n_lines_total) *n_lines_total = s->n_unique;
+  });
 }
 
 extern "C" int pgx_dedup_close(pgx_dedup_stream *s, uint64_t *n_records, uint64_t *n_unique) {

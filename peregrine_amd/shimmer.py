@@ -306,13 +306,17 @@ def dedup_piece_records() -> int:
 class DedupStream:
     """shmr_dedup as a stream (pgx_dedup_open / _feed / _close): feed the job's ovlp_t records piece by piece, in bounded memory;
     every feed returns the text lines of the read pairs first seen in it, and the concatenation of the texts is the text of the
-    one-shot call on the concatenated records.  expected_pairs sizes the seen-pair set up front (0: it grows as needed)."""
+    one-shot call on the concatenated records.  expected_pairs sizes the seen-pair set up front (0: it grows as needed).
+    graph_ready=True (pgx_dedup_open_graph): every feed returns b"", and after the last one drain() yields only the lines the string
+    graph's loader would use -- type `overlap`, two different reads, neither contained by any line of the stream -- in stream order."""
 
-    def __init__(self, expected_pairs: int = 0, device=None):
+    def __init__(self, expected_pairs: int = 0, device=None, graph_ready: bool = False):
         _lib.init(device)
         self._lib = _lib.load()
         self.h = C.c_void_p()
-        _lib.check(self._lib.pgx_dedup_open(int(expected_pairs), C.byref(self.h)), "pgx_dedup_open")
+        self.graph_ready = bool(graph_ready)
+        name = "pgx_dedup_open_graph" if graph_ready else "pgx_dedup_open"
+        _lib.check(getattr(self._lib, name)(int(expected_pairs), C.byref(self.h)), name)
 
     def _feed(self, fn, name, ptr, n) -> bytes:
         if not self.h:
@@ -335,8 +339,30 @@ class DedupStream:
             _lib.stream_wait()
         return self._feed(self._lib.pgx_dedup_feed_dev, "pgx_dedup_feed_dev", C.c_void_p(int(d_ptr)), n)
 
+    def drain(self, max_lines: int = 1 << 20):
+        """graph_ready streams, after the last feed: the kept lines in order, as bytes of at most max_lines lines each"""
+        done = C.c_int(0)
+        while not done.value:
+            if not self.h:
+                raise _lib.PgxError("pgx_dedup_drain: the stream is closed")
+            text, tl = C.c_void_p(), C.c_size_t(0)
+            _lib.check(self._lib.pgx_dedup_drain(self.h, int(max_lines), C.byref(text), C.byref(tl), C.byref(done)), "pgx_dedup_drain")
+            data = C.string_at(text.value, tl.value)
+            self._lib.pgx_free(text)
+            if data:
+                yield data
+
+    @property
+    def stats(self) -> dict:
+        """graph_ready streams: reads marked contained, lines kept (final once drain() has started), lines a plain stream writes"""
+        if not self.h:
+            raise _lib.PgxError("pgx_dedup_graph_stats: the stream is closed")
+        nc, nk, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _lib.check(self._lib.pgx_dedup_graph_stats(self.h, C.byref(nc), C.byref(nk), C.byref(nt)), "pgx_dedup_graph_stats")
+        return dict(contained_reads=int(nc.value), lines_kept=int(nk.value), lines_total=int(nt.value))
+
     def close(self):
-        """frees the stream; returns (records fed, lines written)"""
+        """frees the stream; returns (records fed, lines written -- by a plain stream: a graph_ready one reports its kept lines in stats)"""
         if not self.h:
             raise _lib.PgxError("pgx_dedup_close: the stream is closed")
         nr, nu = C.c_uint64(0), C.c_uint64(0)
@@ -387,6 +413,13 @@ def shmr_dedup(ovlp_paths, out_path: str | None = None, device=None):
         if out:
             out.close()
     return b"".join(parts), nu
+
+
+def dedup_graph_ready(records, device=None) -> bytes:
+    """shmr_dedup -g in one call: of the text of `records` (OVLP_DTYPE), the lines the string graph's loader would use"""
+    with DedupStream(device=device, graph_ready=True) as ds:
+        ds.feed(records)
+        return b"".join(ds.drain())
 
 
 def shmr_map(ref_shimmer_prefix: str = "ref-L2", seqdb_prefix: str = "seq_dataset", shimmer_prefix: str = "shimmer-L2",
