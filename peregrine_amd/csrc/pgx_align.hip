@@ -15,7 +15,6 @@
 //
 // Kernels: k_align_ph (the groups above, as per-group phase machines), k_align1 / k_align1_list (a wavefront per candidate);
 // each reads the seqdb bytes or the 2-bit packs (PACKED), as align_source() decides for the launch.
-#include <hipcub/hipcub.hpp>
 
 #include "pgx_internal.h"
 
@@ -828,10 +827,7 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
       hipLaunchKernelGGL(k_order_keys, dim3((nn + 255) / 256), dim3(256), 0, st, d_keys, nn, db->d_prank.p, k_in, v_in, esc + 3);
       int bits = 1;
       while (bits < 32 && (db->rlen_by_rid.size() >> bits)) ++bits;
-      size_t tb = 0;
-      PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k_in, k_out, v_in, v_out, (int)nn, 0, bits, st));
-      void *tmp = ws_raw("align.ord_tmp", tb + 256);
-      PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, k_in, k_out, v_in, v_out, (int)nn, 0, bits, st));
+      sort_pairs(k_in, k_out, v_in, v_out, nn, 0, bits);
       order = v_out;
     }
   }

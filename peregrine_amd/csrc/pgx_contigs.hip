@@ -25,7 +25,6 @@
 //                than 500 - q_m_end); the image, 'N' where nothing wrote, leaves with 16-byte stores.
 // HBM of a call, booked under "contigs": 132 bytes per row, the output bytes, and -- without the seqdb's bytes -- one byte per base of the
 // reads the rows name.
-#include <hipcub/hipcub.hpp>
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -167,19 +166,6 @@ __global__ __launch_bounds__(STITCH_THREADS) void k_stitch(const uint8_t *__rest
 __global__ void k_key_rids(const pgx_align_key2 *__restrict__ keys, uint32_t n, uint32_t *__restrict__ rids) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) rids[2 * i] = keys[i].rid0, rids[2 * i + 1] = keys[i].rid1;
-}
-
-void running_max(const uint64_t *d_in, uint64_t *d_out, size_t n) {
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, bytes, d_in, d_out, hipcub::Max(), (int)n, ctx().stream));
-  DevBuf<uint8_t> tmp(bytes + 256);
-  PGX_HIP(hipcub::DeviceScan::InclusiveScan(tmp.p, bytes, d_in, d_out, hipcub::Max(), (int)n, ctx().stream));
-}
-void exclusive_sum(const uint64_t *d_in, uint64_t *d_out, size_t n) {
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_in, d_out, (int)n, ctx().stream));
-  DevBuf<uint8_t> tmp(bytes + 256);
-  PGX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, d_in, d_out, (int)n, ctx().stream));
 }
 
 // The bytes the byte-wise kernels of a call read: the seqdb's, or -- released / compacted -- a view of the reads d_rids names

@@ -9,7 +9,6 @@
 // in-batch first-wins above makes a piece's pair keys distinct, a seen-pair set that lives in HBM for the stream's life (open
 // addressing, one 64-bit word per slot) says which of them are new, and the text lines are written on the device too (k_line_len ->
 // exclusive scan -> k_format) and leave through a pinned staging buffer.
-#include <hipcub/hipcub.hpp>
 
 #include <mutex>
 
@@ -340,55 +339,6 @@ static int host_line(const Row &r, char *line, size_t cap) {
 
 using namespace pgx;
 
-extern "C" int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, uint64_t *n_unique) {
-  return guarded([&] {
-    require_ready();
-    PGX_REQUIRE(text && text_len && (n == 0 || recs), PGX_EARG, "pgx_dedup: null argument");
-    PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many records for one call");
-    std::string out;
-    uint64_t m = 0;
-    if (n) {
-      hipStream_t st = ctx().stream;
-      KernelTimer tm("dedup", n);
-      pgx_ovlp *d_in = ws<pgx_ovlp>("dd.in", n);
-      uint64_t *key = ws<uint64_t>("dd.key", n), *skey = ws<uint64_t>("dd.skey", n);
-      uint32_t *idx = ws<uint32_t>("dd.idx", n), *sidx = ws<uint32_t>("dd.sidx", n), *sel = ws<uint32_t>("dd.sel", n);
-      uint8_t *keep = ws<uint8_t>("dd.keep", n);
-      uint32_t *d_m = ws<uint32_t>("dd.m", 1);
-      PGX_HIP(hipMemcpyAsync(d_in, recs, n * sizeof(pgx_ovlp), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_pair_keys, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, (uint32_t)n, key, idx);
-      size_t bytes = 0;
-      PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
-      void *tmp = ws_raw("dd.tmp", bytes);
-      PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
-      hipLaunchKernelGGL(k_first_flags, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, sidx, (uint32_t)n, keep);
-      bytes = 0;
-      hipcub::CountingInputIterator<uint32_t, ptrdiff_t> it(0);
-      PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, it, keep, sel, d_m, (int)n, st));
-      tmp = ws_raw("dd.tmp", bytes);
-      PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, it, keep, sel, d_m, (int)n, st));
-      uint32_t mm = 0;
-      PGX_HIP(hipMemcpyAsync(&mm, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      pgx::sync();
-      m = mm;
-      Row *d_rows = ws<Row>("dd.rows", m);
-      hipLaunchKernelGGL(k_rows, dim3(cdiv(m, 256)), dim3(256), 0, st, d_in, sel, (uint32_t)m, d_rows);
-      std::vector<Row> rows(m);
-      PGX_HIP(hipMemcpyAsync(rows.data(), d_rows, m * sizeof(Row), hipMemcpyDeviceToHost, st));
-      pgx::sync();
-      out.reserve(m * 96);
-      char line[256];
-      for (const Row &r : rows) out.append(line, (size_t)host_line(r, line, sizeof(line)));
-    }
-    *text = (char *)malloc(out.size() + 1);
-    memcpy(*text, out.data(), out.size());
-    (*text)[out.size()] = 0;
-    *text_len = out.size();
-    if (n_unique) *n_unique = m;
-    timing_flush();
-  });
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // the streaming entry points
 // ---------------------------------------------------------------------------------------------------------
@@ -475,42 +425,56 @@ void text_download(pgx_dedup_stream *s, const char *d_text, size_t total, char *
   }
 }
 
-char *empty_text() {
-  char *t = (char *)malloc(1);
-  if (!t) throw std::bad_alloc();
-  t[0] = 0;
-  return t;
+char *empty_text() { return caller_text("", 0); }
+
+// The text the device wrote for m rows: `total` bytes, row j's line at off[j] -- none for the n_special rows with m_size == 0
+struct DeviceLines {
+  pgx_dedup_stream *s;
+  const uint64_t *d_off;
+  const char *d_text;
+  uint64_t total;
+  uint32_t n_special;
+};
+// The lines of m rows (m > 0) as the host's snprintf prints them; dev != nullptr: only those of the rows with m_size == 0, spliced into the
+// device's text at their place.
+std::string rows_to_host_text(const Row *d_rows, size_t m, const DeviceLines *dev = nullptr) {
+  hipStream_t st = ctx().stream;
+  std::vector<Row> rows(m);
+  std::vector<uint64_t> off(dev ? m + 1 : 0);
+  std::vector<char> dev_text(dev ? dev->total : 0);
+  PGX_HIP(hipMemcpyAsync(rows.data(), d_rows, m * sizeof(Row), hipMemcpyDeviceToHost, st));
+  if (dev) {
+    PGX_HIP(hipMemcpyAsync(off.data(), dev->d_off, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    text_download(dev->s, dev->d_text, dev->total, dev_text.data());
+  }
+  pgx::sync();
+  std::string out;
+  out.reserve(dev ? dev->total + (size_t)dev->n_special * 64 : m * 96);
+  char line[256];
+  uint64_t done = 0;   // bytes of the device's text taken so far
+  for (size_t j = 0; j < m; ++j) {
+    if (dev && rows[j].m_size != 0) continue;
+    if (dev) out.append(dev_text.data() + done, off[j] - done), done = off[j];
+    out.append(line, (size_t)host_line(rows[j], line, sizeof(line)));
+  }
+  if (dev && dev->total > done) out.append(dev_text.data() + done, dev->total - done);
+  return out;
 }
 
 // the text of m rows on the device (m > 0; d_m[1] is zero: it counts the rows the host formats)
 void rows_to_text(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *d_m, char **text, size_t *text_len) {
   static const bool host_text = getenv("PGX_DEDUP_HOST_TEXT") && atoi(getenv("PGX_DEDUP_HOST_TEXT")) != 0;   // diagnostic (=1): the lines by snprintf on the host
   hipStream_t st = ctx().stream;
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  char line[256];
   if (host_text) {
-    std::vector<Row> rows(m);
-    PGX_HIP(hipMemcpyAsync(rows.data(), d_rows, (size_t)m * sizeof(Row), hipMemcpyDeviceToHost, st));
-    pgx::sync();
-    std::string out;
-    out.reserve((size_t)m * 96);
-    for (const Row &r : rows) out.append(line, (size_t)host_line(r, line, sizeof(line)));
-    char *t = (char *)malloc(out.size() + 1);
-    if (!t) throw std::bad_alloc();
-    memcpy(t, out.data(), out.size());
-    t[out.size()] = 0;
-    *text = t, *text_len = out.size();
+    const std::string out = rows_to_host_text(d_rows, m);
+    *text = caller_text(out.data(), out.size()), *text_len = out.size();
     return;
   }
   uint64_t *d_off = ws<uint64_t>("dd.off", (size_t)m + 1);
   {
     uint64_t *d_len = ws<uint64_t>("dd.len", (size_t)m + 1);
     hipLaunchKernelGGL(k_line_len, dim3(cdiv((size_t)m + 1, 256)), dim3(256), 0, st, d_rows, m, d_len, d_m + 1);
-    bytes = 0;
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_len, d_off, (int)(m + 1), st));
-    tmp = ws_raw("dd.tmp", bytes);
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_len, d_off, (int)(m + 1), st));
+    exclusive_sum(d_len, d_off, (size_t)m + 1);
   }
   uint64_t total = 0;
   uint32_t n_special = 0;
@@ -521,36 +485,15 @@ void rows_to_text(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *
   hipLaunchKernelGGL(k_format, dim3(cdiv(m, FMT_TILE)), dim3(FMT_TILE), 0, st, d_rows, d_off, m, d_text);
   PGX_HIP(hipGetLastError());
   if (n_special == 0) {
-    char *t = (char *)malloc(total + 1);
-    if (!t) throw std::bad_alloc();
-    *text = t;   // (the caller's from here: released by its pgx_free also when the download fails)
-    t[total] = 0, *text_len = total;
-    text_download(s, d_text, total, t);
+    *text = caller_text(nullptr, total);   // (the caller's from here: released by its pgx_free also when the download fails)
+    *text_len = total;
+    text_download(s, d_text, total, *text);
     return;
   }
   // rows with m_size == 0 (no real overlap record has one): the host's snprintf prints them, spliced in at their place
-  std::vector<Row> rows(m);
-  std::vector<uint64_t> off((size_t)m + 1);
-  std::vector<char> dev_text(total);
-  PGX_HIP(hipMemcpyAsync(rows.data(), d_rows, (size_t)m * sizeof(Row), hipMemcpyDeviceToHost, st));
-  PGX_HIP(hipMemcpyAsync(off.data(), d_off, ((size_t)m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  text_download(s, d_text, total, dev_text.data());
-  pgx::sync();
-  std::string out;
-  out.reserve(total + (size_t)n_special * 64);
-  uint64_t done = 0;
-  for (uint32_t j = 0; j < m; ++j) {
-    if (rows[j].m_size != 0) continue;
-    if (off[j] > done) out.append(dev_text.data() + done, off[j] - done);
-    done = off[j];
-    out.append(line, (size_t)host_line(rows[j], line, sizeof(line)));
-  }
-  if (total > done) out.append(dev_text.data() + done, total - done);
-  char *t = (char *)malloc(out.size() + 1);
-  if (!t) throw std::bad_alloc();
-  memcpy(t, out.data(), out.size());
-  t[out.size()] = 0;
-  *text = t, *text_len = out.size();
+  const DeviceLines dev{s, d_off, d_text, total, n_special};
+  const std::string out = rows_to_host_text(d_rows, m, &dev);
+  *text = caller_text(out.data(), out.size()), *text_len = out.size();
 }
 
 // ---- graph mode -----------------------------------------------------------------------------------------------------------------------
@@ -593,26 +536,18 @@ void store_reserve(pgx_dedup_stream *s, uint64_t more) {
   s->store = std::move(bigger);
 }
 // sel[0 .. returned) = the j < m, ascending, whose row the graph's loader would keep under the bitmap as it is now
-uint32_t select_kept(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *sel, uint32_t *d_cnt) {
+uint32_t select_kept(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *sel) {
   hipStream_t st = ctx().stream;
   uint8_t *flag = ws<uint8_t>("dd.gflag", m);
   hipLaunchKernelGGL(k_kept_flags, dim3(cdiv(m, 256)), dim3(256), 0, st, d_rows, m, s->bits.p, (uint32_t)s->bits.n, flag);
-  size_t bytes = 0;
-  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> it(0);
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, it, flag, sel, d_cnt, (int)m, st));
-  void *tmp = ws_raw("dd.tmp", bytes);
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, it, flag, sel, d_cnt, (int)m, st));
-  uint32_t k = 0;
-  PGX_HIP(hipMemcpyAsync(&k, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  pgx::sync();
-  return k;
+  return select_indices(flag, m, sel);
 }
 // a feed's winner rows: their marks into the bitmap, then the rows that may still become lines behind the store.  A row whose read is
 // marked ALREADY is dropped here, which only bounds the store: a mark that arrives later is seen by the final pass (graph_compact).
 void graph_take(pgx_dedup_stream *s, const Row *d_rows, uint32_t m) {
   hipStream_t st = ctx().stream;
-  uint32_t *d_g = ws<uint32_t>("dd.g", 3);   // [0]: rows that mark, [1]: the largest id they mark, [2]: a count
-  PGX_HIP(hipMemsetAsync(d_g, 0, 3 * sizeof(uint32_t), st));
+  uint32_t *d_g = ws<uint32_t>("dd.g", 2);   // [0]: rows that mark, [1]: the largest id they mark
+  PGX_HIP(hipMemsetAsync(d_g, 0, 2 * sizeof(uint32_t), st));
   hipLaunchKernelGGL(k_mark_extent, dim3(cdiv(m, 256)), dim3(256), 0, st, d_rows, m, d_g);
   uint32_t ext[2] = {0, 0};
   PGX_HIP(hipMemcpyAsync(ext, d_g, sizeof(ext), hipMemcpyDeviceToHost, st));
@@ -622,7 +557,7 @@ void graph_take(pgx_dedup_stream *s, const Row *d_rows, uint32_t m) {
     hipLaunchKernelGGL(k_mark, dim3(cdiv(m, 256)), dim3(256), 0, st, d_rows, m, s->bits.p, (uint32_t)s->bits.n);
   }
   uint32_t *sel = ws<uint32_t>("dd.gsel", m);
-  const uint32_t k = select_kept(s, d_rows, m, sel, d_g + 2);
+  const uint32_t k = select_kept(s, d_rows, m, sel);
   if (k == 0) return;
   store_reserve(s, k);
   hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(k, 256)), dim3(256), 0, st, d_rows, sel, k, s->store.p + s->store_n);
@@ -639,10 +574,10 @@ void graph_compact(pgx_dedup_stream *s) {
     const uint32_t piece = (uint32_t)std::min<uint64_t>(n, COMPACT_ROWS);
     DevBuf<Row> scratch;
     graph_alloc(scratch, piece, "the compaction's scratch");
-    uint32_t *sel = ws<uint32_t>("dd.gsel", piece), *d_g = ws<uint32_t>("dd.g", 3);
+    uint32_t *sel = ws<uint32_t>("dd.gsel", piece);
     for (uint64_t at = 0; at < n; at += piece) {
       const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
-      const uint32_t k = select_kept(s, s->store.p + at, m, sel, d_g + 2);
+      const uint32_t k = select_kept(s, s->store.p + at, m, sel);
       if (k == 0) continue;
       if (kept == at && k == m) {   // nothing dropped so far: the rows are in place
         kept += k;
@@ -668,71 +603,78 @@ uint64_t graph_count_marked(pgx_dedup_stream *s) {
   return total;
 }
 
-// one feed over records that are on the device
-void feed_device(pgx_dedup_stream *s, const pgx_ovlp *d_in, size_t n, char **text, size_t *text_len) {
+// The first record of every read pair of d_in[0 .. n) (n > 0) as rows, in stream order ("dd.rows"; returns how many): pair keys, stable
+// sort, heads of the runs of equal keys, select, coordinate transform.  s != nullptr: only the pairs its seen-pair set does not hold yet,
+// which enter it (d_new: a zero on the device, counts them) and are counted in its statistics; without a set the run heads alone decide.
+uint32_t first_wins_rows(const pgx_ovlp *d_in, size_t n, pgx_dedup_stream *s, uint32_t *d_new, Row **d_rows) {
   hipStream_t st = ctx().stream;
-  KernelTimer tm("dedup", n);
   uint64_t *key = ws<uint64_t>("dd.key", n), *skey = ws<uint64_t>("dd.skey", n);
   uint32_t *idx = ws<uint32_t>("dd.idx", n), *sidx = ws<uint32_t>("dd.sidx", n), *sel = ws<uint32_t>("dd.sel", n);
-  uint8_t *keep = ws<uint8_t>("dd.keep", n), *head = ws<uint8_t>("dd.head", n);
-  uint32_t *d_m = ws<uint32_t>("dd.m", 2);   // [0]: a count; [1]: rows the host formats
-  PGX_HIP(hipMemsetAsync(d_m, 0, 2 * sizeof(uint32_t), st));
+  uint8_t *keep = ws<uint8_t>("dd.keep", n);
+  PrimWs tmp;
   hipLaunchKernelGGL(k_pair_keys, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, (uint32_t)n, key, idx);
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
-  void *tmp = ws_raw("dd.tmp", bytes);
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, skey, idx, sidx, (int)n, 0, 64, st));
-  hipLaunchKernelGGL(k_run_heads, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, (uint32_t)n, s->tab.p, s->cap - 1, head, d_m);
-  uint32_t n_new = 0;
-  PGX_HIP(hipMemcpyAsync(&n_new, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  pgx::sync();
-  seen_reserve(s, n_new);
-  hipLaunchKernelGGL(k_seen_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, sidx, head, (uint32_t)n, s->tab.p, s->cap - 1, keep);
-  bytes = 0;
-  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> it(0);
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, it, keep, sel, d_m, (int)n, st));
-  tmp = ws_raw("dd.tmp", bytes);
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, it, keep, sel, d_m, (int)n, st));
-  uint32_t m = 0;
-  PGX_HIP(hipMemcpyAsync(&m, d_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  pgx::sync();
-  s->n_records += n, s->n_unique += m;   // (the set holds them from here on, whatever happens to the text)
-  if (m == 0) {
-    *text = empty_text(), *text_len = 0;
-    return;
+  sort_pairs(key, skey, idx, sidx, n, 0, 64, &tmp);
+  if (s) {
+    uint8_t *head = ws<uint8_t>("dd.head", n);
+    hipLaunchKernelGGL(k_run_heads, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, (uint32_t)n, s->tab.p, s->cap - 1, head, d_new);
+    uint32_t n_new = 0;
+    PGX_HIP(hipMemcpyAsync(&n_new, d_new, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    pgx::sync();
+    seen_reserve(s, n_new);
+    hipLaunchKernelGGL(k_seen_insert, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, sidx, head, (uint32_t)n, s->tab.p, s->cap - 1, keep);
+  } else {
+    hipLaunchKernelGGL(k_first_flags, dim3(cdiv(n, 256)), dim3(256), 0, st, skey, sidx, (uint32_t)n, keep);
   }
-  Row *d_rows = ws<Row>("dd.rows", m);
-  hipLaunchKernelGGL(k_rows, dim3(cdiv(m, 256)), dim3(256), 0, st, d_in, sel, m, d_rows);
-  if (s->graph) {   // the lines wait for the end of the stream (pgx_dedup_drain)
-    graph_take(s, d_rows, m);
-    *text = empty_text(), *text_len = 0;
-    return;
-  }
-  rows_to_text(s, d_rows, m, d_m, text, text_len);
+  const uint32_t m = select_indices(keep, n, sel, &tmp);
+  if (s) s->n_records += n, s->n_unique += m;   // (the set holds them from here on, whatever happens to the rows and the text)
+  *d_rows = ws<Row>("dd.rows", m);
+  if (m) hipLaunchKernelGGL(k_rows, dim3(cdiv(m, 256)), dim3(256), 0, st, d_in, sel, m, *d_rows);
+  return m;
 }
 
-// (*text was cleared before anything could throw: what it holds now is this call's own allocation)
-void feed_failed(pgx_dedup_stream *s, char **text, size_t *text_len) {
-  if (s) s->failed = true;
-  if (text && *text) free(*text), *text = nullptr;
-  if (text_len) *text_len = 0;
+// one feed over records that are on the device
+void feed_device(pgx_dedup_stream *s, const pgx_ovlp *d_in, size_t n, char **text, size_t *text_len) {
+  KernelTimer tm("dedup", n);
+  uint32_t *d_m = ws<uint32_t>("dd.m", 2);   // [0]: the pairs that are new; [1]: rows the host formats
+  PGX_HIP(hipMemsetAsync(d_m, 0, 2 * sizeof(uint32_t), ctx().stream));
+  Row *d_rows = nullptr;
+  const uint32_t m = first_wins_rows(d_in, n, s, d_m, &d_rows);
+  if (m && s->graph) graph_take(s, d_rows, m);   // the lines wait for the end of the stream (pgx_dedup_drain)
+  if (m == 0 || s->graph) *text = empty_text(), *text_len = 0;
+  else rows_to_text(s, d_rows, m, d_m, text, text_len);
+}
+
+// The epilogue of the entry points that hand out text: guarded(), and after an error the call's text is freed (*text was cleared before
+// anything could throw: what it holds now is this call's own allocation) and the stream that body left in `blame`, if any, has failed.
+template <class F>
+int text_call(char **text, size_t *text_len, F &&body) {
+  pgx_dedup_stream *blame = nullptr;
+  const int rc = guarded([&] { return body(blame); });
+  if (rc != PGX_OK) {
+    if (blame) blame->failed = true;
+    if (text && *text) free(*text), *text = nullptr;
+    if (text_len) *text_len = 0;
+  }
+  return rc;
 }
 int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, bool on_device, const char *who) {
   if (text) *text = nullptr;   // the outputs first: the caller's variables may hold anything, and the error paths free only what
   if (text_len) *text_len = 0;  // this call put there
-  try {
+  return text_call(text, text_len, [&](pgx_dedup_stream *&blame) {
+    blame = s;
     PGX_REQUIRE(s && text && text_len && (n == 0 || recs), PGX_EARG, "%s: null argument", who);
     PGX_REQUIRE(!s->shut, PGX_ESTATE, "%s: pgx_shutdown ran while the stream was open (close it)", who);
     PGX_REQUIRE(!s->failed, PGX_ESTATE, "%s: the stream returned an error before (close it)", who);
     if (s->draining) {   // (refused, not an error of the stream: the drain goes on)
       set_error("%s: the stream is being drained (pgx_dedup_drain ran)", who);
-      return PGX_ESTATE;
+      blame = nullptr;
+      return (int)PGX_ESTATE;
     }
     require_ready();
     PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many records for one feed");
     if (n == 0) {
       *text = empty_text();
-      return PGX_OK;
+      return (int)PGX_OK;
     }
     const pgx_ovlp *d_in = recs;
     if (!on_device) {
@@ -742,18 +684,33 @@ int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, s
     }
     feed_device(s, d_in, n, text, text_len);
     timing_flush();   // (synchronises: the caller's records are no longer read when the feed returns)
-  } catch (const Fail &f) {
-    feed_failed(s, text, text_len);
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    feed_failed(s, text, text_len);
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
-  return PGX_OK;
+    return (int)PGX_OK;
+  });
 }
 }  // namespace
 }  // namespace pgx
+
+extern "C" int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, uint64_t *n_unique) {
+  return guarded([&] {
+    require_ready();
+    PGX_REQUIRE(text && text_len && (n == 0 || recs), PGX_EARG, "pgx_dedup: null argument");
+    PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many records for one call");
+    std::string out;
+    uint64_t m = 0;
+    if (n) {
+      KernelTimer tm("dedup", n);
+      pgx_ovlp *d_in = ws<pgx_ovlp>("dd.in", n);
+      PGX_HIP(hipMemcpyAsync(d_in, recs, n * sizeof(pgx_ovlp), hipMemcpyHostToDevice, ctx().stream));
+      Row *d_rows = nullptr;
+      m = first_wins_rows(d_in, n, nullptr, nullptr, &d_rows);
+      out = rows_to_host_text(d_rows, m);
+    }
+    *text = caller_text(out.data(), out.size());
+    *text_len = out.size();
+    if (n_unique) *n_unique = m;
+    timing_flush();
+  });
+}
 
 static int open_any(uint64_t expected_pairs, pgx_dedup_stream **out, bool graph, const char *who) {
   pgx_dedup_stream *s = nullptr;
@@ -822,22 +779,14 @@ extern "C" int pgx_dedup_drain(pgx_dedup_stream *s, uint64_t max_lines, char **t
   if (text) *text = nullptr;
   if (text_len) *text_len = 0;
   if (done) *done = 0;
-  bool mine = false;   // the checks passed: an error from here on is the stream's
-  try {
+  return text_call(text, text_len, [&](pgx_dedup_stream *&blame) {
     require_graph_stream(s, "pgx_dedup_drain");
     PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_dedup_drain: null argument or max_lines == 0");
-    mine = true;
+    blame = s;   // the checks passed: an error from here on is the stream's
     drain_lines(s, max_lines, text, text_len, done);
     timing_flush();
-  } catch (const Fail &f) {
-    feed_failed(mine ? s : nullptr, text, text_len);
-    return f.code;
-  } catch (const std::bad_alloc &) {
-    feed_failed(mine ? s : nullptr, text, text_len);
-    set_error("out of host memory");
-    return PGX_ENOMEM;
-  }
-  return PGX_OK;
+    return (int)PGX_OK;
+  });
 }
 
 extern "C" int pgx_dedup_graph_stats(pgx_dedup_stream *s, uint64_t *n_contained_reads, uint64_t *n_lines_kept, uint64_t *n_lines_total) {

@@ -154,6 +154,57 @@ T *ws(const char *name, size_t count) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// device-wide primitives (pgx_prims.hip, the one file that includes hipcub): sorts, selects, sums, reductions over device arrays
+// ---------------------------------------------------------------------------------------------------------
+// hipcub's two-call idiom (size query, workspace, run; one number back and a synchronisation where a count or total is returned), once
+// per primitive and element type.  n == 0 is defined by each: no launch, no workspace, count or total 0, offs[0] = 0.  A count that does
+// not fit hipcub's int is refused (PGX_EARG).  Nothing here synchronises unless it returns a number.
+// tmp: the workspace, a block of the block cache grown with a quarter of slack.  A caller that runs several primitives in a row passes its
+// own, so that the sequence allocates once; with none given a call uses one of its own and hands it back to the block cache on return,
+// while its kernels are still enqueued -- which is safe on ctx().stream ONLY (the cache's next user comes behind them on that stream).
+// A call on any other stream must pass a workspace that outlives the work.
+struct PrimWs {
+  DevBuf<uint8_t> buf;
+  void *get(size_t bytes) {
+    if (bytes > buf.n) buf.alloc(bytes + (bytes >> 2) + 256);
+    return buf.p;
+  }
+};
+#define PGX_PRIM_TAIL PrimWs *tmp = nullptr, hipStream_t st = ctx().stream
+// stable radix sort by the key bits [begin_bit, end_bit), values carried along
+void sort_pairs(const uint64_t *k_in, uint64_t *k_out, const uint32_t *v_in, uint32_t *v_out, size_t n, int begin_bit, int end_bit, PGX_PRIM_TAIL);
+void sort_pairs(const uint32_t *k_in, uint32_t *k_out, const uint32_t *v_in, uint32_t *v_out, size_t n, int begin_bit, int end_bit, PGX_PRIM_TAIL);
+void sort_pairs(const uint8_t *k_in, uint8_t *k_out, const uint32_t *v_in, uint32_t *v_out, size_t n, int begin_bit, int end_bit, PGX_PRIM_TAIL);
+void sort_keys(const uint64_t *k_in, uint64_t *k_out, size_t n, int begin_bit, int end_bit, PGX_PRIM_TAIL);
+// list = the i < n, ascending, with flags[i] != 0; returns how many (_dev: leaves the number at d_num instead, no synchronisation)
+uint32_t select_indices(const uint8_t *d_flags, size_t n, uint32_t *d_list, PGX_PRIM_TAIL);
+uint32_t select_indices(const uint32_t *d_flags, size_t n, uint32_t *d_list, PGX_PRIM_TAIL);
+uint64_t select_indices(const uint8_t *d_flags, size_t n, uint64_t *d_list, PGX_PRIM_TAIL);
+void select_indices_dev(const uint8_t *d_flags, size_t n, uint32_t *d_list, uint32_t *d_num, PGX_PRIM_TAIL);
+// ... with flags[i] != 0 and none of skip_bits set in it
+uint32_t select_flagged(const uint32_t *d_flags, size_t n, uint32_t *d_list, uint32_t skip_bits = 0, PGX_PRIM_TAIL);
+// out = the in[i] with flags[i] != 0, in order; returns how many
+uint64_t select_values(const pgx_mm128 *d_in, const uint8_t *d_flags, size_t n, pgx_mm128 *d_out, PGX_PRIM_TAIL);
+// out[i] = in[0] + .. + in[i - 1] (in == out scans in place)
+void exclusive_sum(const uint32_t *d_in, uint32_t *d_out, size_t n, PGX_PRIM_TAIL);
+void exclusive_sum(const uint64_t *d_in, uint64_t *d_out, size_t n, PGX_PRIM_TAIL);
+// offs[0] = 0, offs[i + 1] = vals[0] + .. + vals[i] (n + 1 entries; vals == offs + 1 scans in place); scan_to_total returns offs[n]
+void scan_offsets(const uint32_t *d_vals, uint32_t *d_offs, size_t n, PGX_PRIM_TAIL);
+uint32_t scan_to_total(const uint32_t *d_vals, uint32_t *d_offs, size_t n, PGX_PRIM_TAIL);
+uint64_t scan_to_total(const uint32_t *d_vals, uint64_t *d_offs, size_t n, PGX_PRIM_TAIL);
+uint64_t scan_to_total(const uint64_t *d_vals, uint64_t *d_offs, size_t n, PGX_PRIM_TAIL);
+// out[i] = max(in[0], .., in[i]) (in == out scans in place)
+void running_max(const int32_t *d_in, int32_t *d_out, size_t n, PGX_PRIM_TAIL);
+void running_max(const uint64_t *d_in, uint64_t *d_out, size_t n, PGX_PRIM_TAIL);
+// *d_out = the sum / the maximum of in[0 .. n) (0 for none), left on the device
+void reduce_sum(const uint32_t *d_in, uint32_t *d_out, size_t n, PGX_PRIM_TAIL);
+void reduce_max(const uint32_t *d_in, uint32_t *d_out, size_t n, PGX_PRIM_TAIL);
+// the runs of equal keys: uniq[r] = the run's key, sums[r] = the sum of its values / counts[r] = its length; return the number of runs
+uint32_t sum_by_key(const uint64_t *d_keys, uint64_t *d_uniq, const uint32_t *d_vals, uint32_t *d_sums, size_t n, PGX_PRIM_TAIL);
+uint64_t run_lengths(const uint64_t *d_in, uint64_t *d_uniq, uint32_t *d_counts, size_t n, PGX_PRIM_TAIL);
+#undef PGX_PRIM_TAIL
+
+// ---------------------------------------------------------------------------------------------------------
 // per-kernel timing with HIP events on the library stream
 // ---------------------------------------------------------------------------------------------------------
 struct KernelTimer {
@@ -281,12 +332,6 @@ void dev_reduce_nreads(const DevBuf<pgx_mm128> &nl0, const DevBuf<uint64_t> &nl0
                        DevBuf<pgx_mm128> &top, DevBuf<uint32_t> &cnt);
 void dev_scatter_counts(uint32_t *d_counts_by_slot, const uint32_t *d_list, uint32_t nn, const uint64_t *d_off, const uint32_t *d_cnt);
 void dev_mark_slots(uint32_t *d_by_slot, const uint32_t *d_list, uint32_t nn, uint32_t v);
-// hipcub's two-call idiom, once each (size query, workspace, run, one number back, sync):
-// list = the i < n, ascending, with flags[i] != 0 and none of skip_bits set in it; returns how many
-uint32_t select_flagged(const uint32_t *d_flags, uint32_t n, uint32_t *d_list, uint32_t skip_bits = 0);
-// offs[0] = 0, offs[i + 1] = vals[0] + .. + vals[i] (n + 1 entries; vals == offs + 1 scans in place); returns offs[n]
-uint64_t scan_to_total(const uint32_t *d_vals, uint64_t *d_offs, size_t n);
-uint64_t scan_to_total(const uint64_t *d_vals, uint64_t *d_offs, size_t n);
 // banded O(ND) confirmation of n candidate alignments (keys on device)
 void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int band, pgx_match *d_out,
                int tail_batch = 0);   // tail_batch: 1 = the second request batch of a stage, 2 = a later one (mostly hard candidates: pgx_align.hip)
@@ -594,5 +639,13 @@ T *host_copy(const std::vector<T> &v) {
   T *p = (T *)malloc(v.size() ? v.size() * sizeof(T) : 1);
   if (v.size()) memcpy(p, v.data(), v.size() * sizeof(T));
   return p;
+}
+// n bytes of text as a NUL-terminated string of the caller's (pgx_free); src == nullptr: room for n bytes, still to be filled
+inline char *caller_text(const char *src, size_t n) {
+  char *t = (char *)malloc(n + 1);
+  if (!t) throw std::bad_alloc();
+  if (src && n) memcpy(t, src, n);
+  t[n] = 0;
+  return t;
 }
 }  // namespace pgx

@@ -8,8 +8,6 @@
 //   k_reduce_*       : mm_reduce      src/shmr_reduce.c:53-90
 //   count            : mm_count       src/shmr_utils.c:131-160  radix sort + run-length
 //   k_align_ph       : ovlp_match     src/DWmatch.c:66-204      eight candidates per wavefront         (pgx_align.hip)
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 
 #include "pgx_internal.h"
@@ -92,17 +90,6 @@ __global__ void k_reduce_flag(const pgx_mm128 *__restrict__ in, size_t n, const 
   flag[t] = f;
 }
 
-// generic temp-storage helper for hipcub
-struct CubTemp {
-  DevBuf<uint8_t> buf;
-  void *get(size_t bytes) {
-    if (bytes > buf.n) buf.alloc(bytes + (bytes >> 2) + 256);
-    return buf.p;
-  }
-};
-
-using CountIt = hipcub::CountingInputIterator<uint64_t, ptrdiff_t>;
-
 void dev_reduce(const pgx_mm128 *d_in, size_t n, int rs, DevBuf<pgx_mm128> &out, size_t &n_out) {
   n_out = 0;
   if (n == 0) { out.alloc(0); return; }
@@ -110,26 +97,14 @@ void dev_reduce(const pgx_mm128 *d_in, size_t n, int rs, DevBuf<pgx_mm128> &out,
   KernelTimer tm("reduce", n);
   DevBuf<uint8_t> flag(n);
   DevBuf<uint64_t> starts(n);  // worst case every element its own read
-  DevBuf<uint64_t> d_num(1);
-  CubTemp tmp;
+  PrimWs tmp;
   hipLaunchKernelGGL(k_mark_starts, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, n, flag.p);
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, CountIt(0), flag.p, starts.p, d_num.p, (int)n, st));
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp.get(bytes), bytes, CountIt(0), flag.p, starts.p, d_num.p, (int)n, st));
-  uint64_t nseg = 0;
-  d_num.download(&nseg, 1);
-  sync();
+  const uint64_t nseg = select_indices(flag.p, n, starts.p, &tmp);
   DevBuf<pgx_mm128> win(n);
   hipLaunchKernelGGL(k_reduce_flag, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, n, starts.p, (uint32_t)nseg, rs, win.p,
                      flag.p);
   out.alloc(n);
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, win.p, flag.p, out.p, d_num.p, (int)n, st));
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp.get(bytes), bytes, win.p, flag.p, out.p, d_num.p, (int)n, st));
-  uint64_t m = 0;
-  d_num.download(&m, 1);
-  sync();
-  n_out = (size_t)m;
+  n_out = (size_t)select_values(win.p, flag.p, n, out.p, &tmp);
 }
 
 // =========================================================================================================
@@ -152,19 +127,10 @@ void dev_count(const pgx_mm128 *d_in, size_t n, int kmer_bits, DevBuf<pgx_mm_cou
   KernelTimer tm("count", n);
   DevBuf<uint64_t> keys(n), sorted(n), uniq(n);
   DevBuf<uint32_t> cnt(n);
-  DevBuf<uint64_t> d_num(1);
-  CubTemp tmp;
+  PrimWs tmp;
   hipLaunchKernelGGL(k_extract_hash, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, n, keys.p);
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, keys.p, sorted.p, (int)n, 0, kmer_bits, st));
-  PGX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.get(bytes), bytes, keys.p, sorted.p, (int)n, 0, kmer_bits, st));
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, bytes, sorted.p, uniq.p, cnt.p, d_num.p, (int)n, st));
-  PGX_HIP(hipcub::DeviceRunLengthEncode::Encode(tmp.get(bytes), bytes, sorted.p, uniq.p, cnt.p, d_num.p, (int)n, st));
-  uint64_t m = 0;
-  d_num.download(&m, 1);
-  sync();
-  n_out = (size_t)m;
+  sort_keys(keys.p, sorted.p, n, 0, kmer_bits, &tmp);
+  n_out = (size_t)run_lengths(sorted.p, uniq.p, cnt.p, n, &tmp);
   out.alloc(n_out);
   if (n_out) hipLaunchKernelGGL(k_pack_counts, dim3(cdiv(n_out, 256)), dim3(256), 0, st, uniq.p, cnt.p, n_out, out.p);
 }
@@ -172,43 +138,6 @@ void dev_count(const pgx_mm128 *d_in, size_t n, int kmer_bits, DevBuf<pgx_mm_cou
 // =========================================================================================================
 // sketch driver
 // =========================================================================================================
-// The flags of the reads (uint32 per read; non-zero: the read is unfinished, the bits say why) as hipcub select flags
-struct FlaggedFor {
-  uint32_t skip_bits;
-  __host__ __device__ bool operator()(uint32_t f) const { return f != 0 && !(f & skip_bits); }
-};
-uint32_t select_flagged(const uint32_t *d_flags, uint32_t n, uint32_t *d_list, uint32_t skip_bits) {
-  hipStream_t st = ctx().stream;
-  hipcub::CountingInputIterator<uint32_t, ptrdiff_t> iota(0);
-  hipcub::TransformInputIterator<bool, FlaggedFor, const uint32_t *> flagged(d_flags, FlaggedFor{skip_bits});
-  uint32_t *d_num = ws<uint32_t>("ix.sel_n", 1);
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flagged, d_list, d_num, (int)n, st));
-  void *tmp = ws_raw("ix.sel_tmp", bytes);
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp, bytes, iota, flagged, d_list, d_num, (int)n, st));
-  uint32_t num = 0;
-  PGX_HIP(hipMemcpyAsync(&num, d_num, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  sync();
-  return num;
-}
-
-template <typename T>
-static uint64_t scan_to_total_of(const T *d_vals, uint64_t *d_offs, size_t n) {
-  hipStream_t st = ctx().stream;
-  PGX_HIP(hipMemsetAsync(d_offs, 0, sizeof(uint64_t), st));
-  if (n == 0) return 0;
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, d_vals, d_offs + 1, (int)n, st));
-  void *tmp = ws_raw("ix.scan_tmp", bytes);
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_vals, d_offs + 1, (int)n, st));
-  uint64_t total = 0;
-  PGX_HIP(hipMemcpyAsync(&total, d_offs + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  sync();
-  return total;
-}
-uint64_t scan_to_total(const uint32_t *d_vals, uint64_t *d_offs, size_t n) { return scan_to_total_of(d_vals, d_offs, n); }
-uint64_t scan_to_total(const uint64_t *d_vals, uint64_t *d_offs, size_t n) { return scan_to_total_of(d_vals, d_offs, n); }
-
 // slab of read i: len / slab_div + slab_min elements from off[i] on (off: n + 1 entries); returns the bases of the reads
 static uint64_t slab_offsets(const std::vector<ReadDesc> &reads, uint64_t slab_div, uint64_t slab_min, std::vector<uint64_t> &off) {
   off.assign(reads.size() + 1, 0);

@@ -20,7 +20,6 @@
 // The packs are a CACHE of the immutable seqdb bytes, kept with the pgx_seqdb for as long as it lives: built by the first large
 // alignment launch (or ahead of it, beside the join: dev_align_prepare) and reused by every later stage on the same database, on every
 // rank of a multi-GPU job.  If their HBM (seqdb / 2) cannot be had, the alignment launches stay on the byte-wise kernels.
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
@@ -167,13 +166,10 @@ const uint32_t *seq_packs(const pgx_seqdb *db) {
     DevBuf<uint32_t> r_in(nr), ord(nr);
     hipLaunchKernelGGL(k_iota_key, dim3((n + 255) / 256), dim3(256), 0, st, n, by_locus ? db->d_locus_key.p : (const uint64_t *)nullptr, db->d_roff.p,
                        db->d_rlen.p, k_in.p, r_in.p);
-    size_t tb = 0, tb2 = 0;
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k_in.p, k_out.p, r_in.p, ord.p, (int)n, 0, 64, st));
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, words.p, start.p, (int)n, st));
-    DevBuf<uint8_t> tmp(std::max(tb, tb2) + 256);
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, k_in.p, k_out.p, r_in.p, ord.p, (int)n, 0, 64, st));
+    PrimWs tmp;
+    sort_pairs(k_in.p, k_out.p, r_in.p, ord.p, n, 0, 64, &tmp);
     hipLaunchKernelGGL(k_words_of, dim3((n + 255) / 256), dim3(256), 0, st, n, ord.p, db->d_rlen.p, words.p);
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb2, words.p, start.p, (int)n, st));
+    exclusive_sum(words.p, start.p, n, &tmp);
     hipLaunchKernelGGL(k_scatter_layout, dim3((n + 255) / 256), dim3(256), 0, st, n, ord.p, start.p, db->d_poff.p, db->d_prank.p);
     hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)std::min<size_t>(nr, (size_t)ctx().num_cu * 64)), dim3(256), 0, st, db->d_seq.p, ord.p, n, db->d_roff.p,
                        db->d_rlen.p, db->d_poff.p, db->d_pack.p, db->d_nflag.p);
@@ -181,10 +177,7 @@ const uint32_t *seq_packs(const pgx_seqdb *db) {
     {   // how many reads hold a byte without a 2-bit code (0 for everything the reference's encoder wrote from ACGT reads): the alignment
         // launches only start their byte-wise second launch when there is one
       uint32_t *d_cnt = ws<uint32_t>("pack.nflag_count", 1);
-      size_t rb = 0;
-      PGX_HIP(hipcub::DeviceReduce::Sum(nullptr, rb, db->d_nflag.p, d_cnt, (int)nr, st));
-      void *rt = ws_raw("pack.red_tmp", rb);
-      PGX_HIP(hipcub::DeviceReduce::Sum(rt, rb, db->d_nflag.p, d_cnt, (int)nr, st));
+      reduce_sum(db->d_nflag.p, d_cnt, nr, &tmp);
       PGX_HIP(hipMemcpyAsync(&db->n_flagged_reads, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     sync();   // (the temporaries above go back to the block cache here)

@@ -14,8 +14,6 @@
 //              key0 group, which is all the host needs to replay klib-khash's slot order on DISTINCT keys only.
 #include <chrono>
 
-#include <hipcub/hipcub.hpp>
-
 #include "pgx_internal.h"
 
 namespace pgx {
@@ -23,15 +21,6 @@ namespace pgx {
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 namespace {
-struct Tmp {
-  DevBuf<uint8_t> buf;
-  void *get(size_t bytes) {
-    if (bytes > buf.n) buf.alloc(bytes + (bytes >> 2) + 256);
-    return buf.p;
-  }
-};
-using CountIt = hipcub::CountingInputIterator<uint32_t, ptrdiff_t>;
-
 __global__ void k_split_counts(const pgx_mm_count *__restrict__ in, size_t n, uint64_t *__restrict__ mer,
                                uint32_t *__restrict__ cnt) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -116,10 +105,6 @@ __global__ void k_chain_in(const uint8_t *__restrict__ keep, uint32_t n, const u
   if (i >= n) return;
   v[i] = (keep[i] && i >= *first_strict) ? (int32_t)i : -1;
 }
-
-struct MaxOp {
-  __host__ __device__ int32_t operator()(int32_t a, int32_t b) const { return a > b ? a : b; }
-};
 
 __device__ __forceinline__ uint32_t pos28(uint64_t y) { return (uint32_t)((y >> 1) & 0xFFFFFFF); }
 __device__ __forceinline__ uint32_t pos_of(uint64_t y) { return (uint32_t)((y & 0xFFFFFFFFu) >> 1); }
@@ -367,24 +352,16 @@ struct CountTable {
   DevBuf<CSlot> tab;            // the same entries as an open-addressing table (lookup_count)
   uint32_t tmask = 0;
 };
-static void aggregate_counts_now(const pgx_mm_count *cin, size_t n_counts, CountTable &ct, Tmp &tmp) {
+static void aggregate_counts_now(const pgx_mm_count *cin, size_t n_counts, CountTable &ct, PrimWs &tmp) {
   hipStream_t st = ctx().stream;
   ct.umer.alloc(n_counts), ct.ucnt.alloc(n_counts);
   ct.nu = 0;
   if (!n_counts) return;
   DevBuf<uint64_t> mer(n_counts), mer_s(n_counts);
-  DevBuf<uint32_t> cnt(n_counts), cnt_s(n_counts), d_nu(1);
-  size_t bytes = 0;
+  DevBuf<uint32_t> cnt(n_counts), cnt_s(n_counts);
   hipLaunchKernelGGL(k_split_counts, dim3(cdiv(n_counts, 256)), dim3(256), 0, st, cin, n_counts, mer.p, cnt.p);
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, mer.p, mer_s.p, cnt.p, cnt_s.p, (int)n_counts, 0, 56, st));
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(bytes), bytes, mer.p, mer_s.p, cnt.p, cnt_s.p, (int)n_counts, 0, 56, st));
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceReduce::ReduceByKey(nullptr, bytes, mer_s.p, ct.umer.p, cnt_s.p, ct.ucnt.p, d_nu.p, hipcub::Sum(),
-                                           (int)n_counts, st));
-  PGX_HIP(hipcub::DeviceReduce::ReduceByKey(tmp.get(bytes), bytes, mer_s.p, ct.umer.p, cnt_s.p, ct.ucnt.p, d_nu.p, hipcub::Sum(),
-                                           (int)n_counts, st));
-  d_nu.download(&ct.nu, 1);
-  sync();
+  sort_pairs(mer.p, mer_s.p, cnt.p, cnt_s.p, n_counts, 0, 56, &tmp);
+  ct.nu = sum_by_key(mer_s.p, ct.umer.p, cnt_s.p, ct.ucnt.p, n_counts, &tmp);
   ct.tmask = 0;
   if (!ct.nu) return;
   uint32_t cap = 1024;
@@ -436,7 +413,7 @@ struct CountCache {   // (DbCaches: the read database the job runs on keeps the 
   bool valid = false;
 };
 void CacheFree::operator()(CountCache *c) const { delete c; }
-static const CountTable &aggregate_counts(CountCache &cc, const pgx_mm_count *cin, size_t n_counts, Tmp &tmp) {
+static const CountTable &aggregate_counts(CountCache &cc, const pgx_mm_count *cin, size_t n_counts, PrimWs &tmp) {
   unsigned long long sum[2] = {0, 0};
   if (n_counts) {
     hipStream_t st = ctx().stream;
@@ -474,19 +451,17 @@ static uint32_t keep_flags(const pgx_mm128 *mm_dev, uint32_t n, const CountTable
 }
 
 // chain of kept shimmers from `start` on: chain[i] == i <=> i is kept; chain[i-1] = previous kept shimmer (or -1)
-static void chain_scan(const DevBuf<uint8_t> &keep, uint32_t n, const uint32_t *d_start, DevBuf<int32_t> &chain, Tmp &tmp) {
+static void chain_scan(const DevBuf<uint8_t> &keep, uint32_t n, const uint32_t *d_start, DevBuf<int32_t> &chain, PrimWs &tmp) {
   hipStream_t st = ctx().stream;
   DevBuf<int32_t> chain_in(n);
   chain.alloc(n);
   hipLaunchKernelGGL(k_chain_in, dim3(cdiv(n, 256)), dim3(256), 0, st, keep.p, n, d_start, chain_in.p);
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, bytes, chain_in.p, chain.p, MaxOp(), (int)n, st));
-  PGX_HIP(hipcub::DeviceScan::InclusiveScan(tmp.get(bytes), bytes, chain_in.p, chain.p, MaxOp(), (int)n, st));
+  running_max(chain_in.p, chain.p, n, &tmp);
   // (chain_in goes back to the block cache on return: stream-ordered reuse on the library's one stream)
 }
 
-static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs *keep_dev, Tmp &tmp);
-static void early_groups(const PairRecs &R, Tmp &tmp, const EarlyFn &early);
+static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs *keep_dev, PrimWs &tmp);
+static void early_groups(const PairRecs &R, PrimWs &tmp, const EarlyFn &early);
 
 void dev_build_pairs(const uint32_t *d_rlen, const Lists &lists, const PairParams &pp, PairTables &out, unsigned flags, DevicePairs *keep_dev,
                      const EarlyFn &early, const pgx_seqdb *db) {
@@ -497,8 +472,7 @@ void dev_build_pairs(const uint32_t *d_rlen, const Lists &lists, const PairParam
   PGX_REQUIRE(n_mm < (1ULL << 31) && n_counts < (1ULL << 31), PGX_EARG, "shimmer list too long for one chunk");
   hipStream_t st = ctx().stream;
   KernelTimer tm("pairs", n_mm);
-  Tmp tmp;
-  size_t bytes = 0;
+  PrimWs tmp;
   const uint32_t n = (uint32_t)n_mm;
 
   // ---- aggregated counts ----------------------------------------------------------------------------------
@@ -522,13 +496,7 @@ void dev_build_pairs(const uint32_t *d_rlen, const Lists &lists, const PairParam
   hipLaunchKernelGGL(k_records<0>, dim3(cdiv(n, 256)), dim3(256), 0, st, mm_dev, n, chain.p, T, c, d_rlen, nrec.p,
                      (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr,
                      (uint8_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr);
-  PGX_HIP(hipMemsetAsync(off.p, 0, sizeof(uint32_t), st));
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, nrec.p, off.p + 1, (int)n, st));
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp.get(bytes), bytes, nrec.p, off.p + 1, (int)n, st));
-  uint32_t nr = 0;
-  PGX_HIP(hipMemcpyAsync(&nr, off.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  sync();
+  const uint32_t nr = scan_to_total(nrec.p, off.p, n, &tmp);
   out.n_rec = nr;
   if (flags & PAIRS_COUNTS) {  // the aggregated multiplicity table, sorted by mer
     out.umer = to_host(ct.umer, ct.nu);
@@ -566,7 +534,7 @@ int64_t dev_pairs_prepare(const pgx_seqdb *db, const pgx_mm128 *d_mm, size_t n_m
   g_scatter.mm = d_mm, g_scatter.n = (uint32_t)n_mm;
   g_scatter.ready = true, g_scatter.ix_gen = index_owns(d_mm) ? index_generation() : 0;
   if (n_mm == 0) return -1;
-  Tmp tmp;
+  PrimWs tmp;
   const CountTable &ct = aggregate_counts(get_or_make(db->caches.counts), d_counts, n_counts, tmp);
   DevBuf<uint32_t> d_misc;
   PairParams pp{1, 1, lower, upper, (uint32_t)db->rlen_by_rid.size()};
@@ -586,7 +554,7 @@ void dev_pairs_scatter(const uint32_t *d_rlen, uint32_t T, int64_t start, const 
   if (n == 0 || start < 0 || start >= (int64_t)n) return;  // (no eligible anchor on this rank: shmr_utils.c:311-320)
   hipStream_t st = ctx().stream;
   KernelTimer tm("pairs_scatter", n);
-  Tmp tmp;
+  PrimWs tmp;
   DevBuf<uint32_t> d_start(1);
   const uint32_t s32 = (uint32_t)start;
   d_start.upload(&s32, 1);
@@ -595,13 +563,7 @@ void dev_pairs_scatter(const uint32_t *d_rlen, uint32_t T, int64_t start, const 
   DevBuf<uint32_t> nrec(n), off(n + 1);
   hipLaunchKernelGGL(k_records_all<0>, dim3(cdiv(n, 256)), dim3(256), 0, st, g_scatter.mm, n, chain.p, T, d_rlen, nrec.p,
                      (const uint32_t *)nullptr, (pgx_pair_rec *)nullptr, (uint8_t *)nullptr);
-  PGX_HIP(hipMemsetAsync(off.p, 0, sizeof(uint32_t), st));
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, nrec.p, off.p + 1, (int)n, st));
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp.get(bytes), bytes, nrec.p, off.p + 1, (int)n, st));
-  uint32_t nr = 0;
-  PGX_HIP(hipMemcpyAsync(&nr, off.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  sync();
+  const uint32_t nr = scan_to_total(nrec.p, off.p, n, &tmp);
   if (nr == 0) return;
   PGX_REQUIRE(nr < (1u << 31), PGX_EARG, "too many pair records for one index chunk");
   DevBuf<pgx_pair_rec> rec(nr);
@@ -611,9 +573,7 @@ void dev_pairs_scatter(const uint32_t *d_rlen, uint32_t T, int64_t start, const 
                      off.p, rec.p, dest.p);
   // stable by destination: the records of a destination stay in scan order (= insertion order of the receiving chunk)
   hipLaunchKernelGGL(k_iota, dim3(cdiv(nr, 256)), dim3(256), 0, st, idx.p, nr);
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, dest.p, dest_s.p, idx.p, perm.p, (int)nr, 0, 8, st));
-  PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(bytes), bytes, dest.p, dest_s.p, idx.p, perm.p, (int)nr, 0, 8, st));
+  sort_pairs(dest.p, dest_s.p, idx.p, perm.p, nr, 0, 8, &tmp);
   g_scatter.send.alloc(nr);
   hipLaunchKernelGGL(k_gather_rec, dim3(cdiv(nr, 256)), dim3(256), 0, st, rec.p, perm.p, nr, g_scatter.send.p);
   PGX_HIP(hipMemsetAsync(hist.p, 0, 256 * sizeof(uint32_t), st));
@@ -668,7 +628,7 @@ void dev_pairs_from_records(const pgx_pair_rec *d_rec, size_t n, PairTables &out
   if (n == 0) return;
   PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many pair records for one overlap chunk");
   KernelTimer tm("pairs", n);
-  Tmp tmp;
+  PrimWs tmp;
   const uint32_t nr = (uint32_t)n;
   PairRecs R;
   R.nr = nr;
@@ -681,7 +641,7 @@ void dev_pairs_from_records(const pgx_pair_rec *d_rec, size_t n, PairTables &out
   bucketize(R, flags, out, keep_dev, tmp);
 }
 
-static void early_groups(const PairRecs &R, Tmp &tmp, const EarlyFn &early) {
+static void early_groups(const PairRecs &R, PrimWs &tmp, const EarlyFn &early) {
   if (!early || R.nr == 0) return;
   hipStream_t st = ctx().stream;
   const uint32_t nr = R.nr;
@@ -692,10 +652,10 @@ static void early_groups(const PairRecs &R, Tmp &tmp, const EarlyFn &early) {
   // uncalled and the outer table is replayed after the join, exactly as with PGX_EARLY_OUTER=0 -- instead of failing a chunk
   // that fits without it.
   DevBuf<unsigned long long> tkeys;
-  DevBuf<uint32_t> tseq, idx, d_n;
+  DevBuf<uint32_t> tseq, idx;
   DevBuf<uint8_t> flag;
   try {
-    tkeys.alloc(cap), tseq.alloc(cap), idx.alloc(nr), d_n.alloc(1), flag.alloc(nr);
+    tkeys.alloc(cap), tseq.alloc(cap), idx.alloc(nr), flag.alloc(nr);
   } catch (const Fail &) {
     (void)hipGetLastError();
     if (getenv("PGX_TRACE")) fprintf(stderr, "[pgx] join: no device memory for the early outer-key pass (%zu MB); skipped\n", (cap * 12 + (size_t)nr * 5) >> 20);
@@ -705,12 +665,7 @@ static void early_groups(const PairRecs &R, Tmp &tmp, const EarlyFn &early) {
   PGX_HIP(hipMemsetAsync(tseq.p, 0xFF, cap * sizeof(uint32_t), st));
   hipLaunchKernelGGL(k_first_insert, dim3(cdiv(nr, 256)), dim3(256), 0, st, R.key0.p, nr, tkeys.p, tseq.p, (uint32_t)(cap - 1));
   hipLaunchKernelGGL(k_first_flag, dim3(cdiv(nr, 256)), dim3(256), 0, st, R.key0.p, nr, tkeys.p, tseq.p, (uint32_t)(cap - 1), flag.p);
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, CountIt(0), flag.p, idx.p, d_n.p, (int)nr, st));
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp.get(bytes), bytes, CountIt(0), flag.p, idx.p, d_n.p, (int)nr, st));
-  uint32_t nd = 0;
-  d_n.download(&nd, 1);
-  sync();
+  const uint32_t nd = select_indices(flag.p, nr, idx.p, &tmp);
   EarlyGroups eg;
   eg.n = nd;
   if (nd) {
@@ -758,9 +713,8 @@ static int bit_length(unsigned long long v) {
   return b < 1 ? 1 : b;
 }
 
-static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs *keep_dev, Tmp &tmp) {
+static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs *keep_dev, PrimWs &tmp) {
   hipStream_t st = ctx().stream;
-  size_t bytes = 0;
   const uint32_t nr = R.nr;
   DevBuf<uint64_t> &key0 = R.key0, &key1 = R.key1, &y0 = R.y0, &y1 = R.y1;
   DevBuf<uint8_t> &dir = R.dir;
@@ -784,18 +738,12 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
       hipLaunchKernelGGL(k_iota, dim3(cdiv(nr, 256)), dim3(256), 0, st, perm_a.p, nr);
     } else {
       hipLaunchKernelGGL(k_iota, dim3(cdiv(nr, 256)), dim3(256), 0, st, idx.p, nr);
-      bytes = 0;
-      PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, npos.p, k32s.p, idx.p, perm_a.p, (int)nr, 0, pbits, st));
-      PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(bytes), bytes, npos.p, k32s.p, idx.p, perm_a.p, (int)nr, 0, pbits, st));
+      sort_pairs(npos.p, k32s.p, idx.p, perm_a.p, nr, 0, pbits, &tmp);
     }
     hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nr, 256)), dim3(256), 0, st, key1.p, perm_a.p, nr, kg.p);
-    bytes = 0;
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, kg.p, kgs.p, perm_a.p, perm_b.p, (int)nr, 0, kbits, st));
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(bytes), bytes, kg.p, kgs.p, perm_a.p, perm_b.p, (int)nr, 0, kbits, st));
+    sort_pairs(kg.p, kgs.p, perm_a.p, perm_b.p, nr, 0, kbits, &tmp);
     hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nr, 256)), dim3(256), 0, st, key0.p, perm_b.p, nr, kg.p);
-    bytes = 0;
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, kg.p, kgs.p, perm_b.p, perm_a.p, (int)nr, 0, kbits, st));
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(bytes), bytes, kg.p, kgs.p, perm_b.p, perm_a.p, (int)nr, 0, kbits, st));
+    sort_pairs(kg.p, kgs.p, perm_b.p, perm_a.p, nr, 0, kbits, &tmp);
   }
   // perm_a = final order; kgs = sorted key0
   DevBuf<uint64_t> sk1(nr), sy0(nr);
@@ -804,12 +752,8 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
   hipLaunchKernelGGL(k_gather_out, dim3(cdiv(nr, 256)), dim3(256), 0, st, y0.p, dir.p, perm_a.p, nr, sy0.p, sdir.p);
   hipLaunchKernelGGL(k_flags, dim3(cdiv(nr, 256)), dim3(256), 0, st, kgs.p, sk1.p, nr, fb.p, fg.p);
   DevBuf<uint32_t> bstart(nr + 1), gstart(nr + 1), d_n(2);
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, CountIt(0), fb.p, bstart.p, d_n.p, (int)nr, st));
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp.get(bytes), bytes, CountIt(0), fb.p, bstart.p, d_n.p, (int)nr, st));
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, bytes, CountIt(0), fg.p, gstart.p, d_n.p + 1, (int)nr, st));
-  PGX_HIP(hipcub::DeviceSelect::Flagged(tmp.get(bytes), bytes, CountIt(0), fg.p, gstart.p, d_n.p + 1, (int)nr, st));
+  select_indices_dev(fb.p, nr, bstart.p, d_n.p, &tmp);
+  select_indices_dev(fg.p, nr, gstart.p, d_n.p + 1, &tmp);
   uint32_t nbg[2];
   d_n.download(nbg, 2);
   sync();
@@ -835,14 +779,10 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
     while (fbits < 32 && ((uint64_t)1 << fbits) < (uint64_t)nr) ++fbits;
     while (gbits < 32 && ((uint64_t)1 << gbits) < (uint64_t)ng) ++gbits;
     hipLaunchKernelGGL(k_iota, dim3(cdiv(ng, 256)), dim3(256), 0, st, iota_g.p, ng);
-    bytes = 0;
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, gfirst.p, gf_sorted.p, iota_g.p, gord.p, (int)ng, 0, fbits, st));
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(bytes), bytes, gfirst.p, gf_sorted.p, iota_g.p, gord.p, (int)ng, 0, fbits, st));
+    sort_pairs(gfirst.p, gf_sorted.p, iota_g.p, gord.p, ng, 0, fbits, &tmp);
     hipLaunchKernelGGL(k_iota, dim3(cdiv(nbk, 256)), dim3(256), 0, st, iota_b.p, nbk);
     hipLaunchKernelGGL(k_bucket_order_key, dim3(cdiv(nbk, 256)), dim3(256), 0, st, gbucket.p, ng, bfirst.p, nbk, fbits, bok.p);
-    bytes = 0;
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, bok.p, bok_sorted.p, iota_b.p, bord.p, (int)nbk, 0, fbits + gbits, st));
-    PGX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(bytes), bytes, bok.p, bok_sorted.p, iota_b.p, bord.p, (int)nbk, 0, fbits + gbits, st));
+    sort_pairs(bok.p, bok_sorted.p, iota_b.p, bord.p, nbk, 0, fbits + gbits, &tmp);
   }
 
   const bool trace = getenv("PGX_TRACE") != nullptr;

@@ -7,8 +7,6 @@
 //       matching buckets are expanded to rows there; the host only formats the text.
 #include <glob.h>
 
-#include <hipcub/hipcub.hpp>
-
 #include "pgx_internal.h"
 #include "pgx_khash.h"
 
@@ -123,9 +121,6 @@ __global__ void k_ref_chain_in(const uint8_t *__restrict__ keep, uint32_t n, con
   const uint32_t s = *first_key0;
   v[i] = (i == s || (i > s && keep[i])) ? (int32_t)i : -1;
 }
-struct MaxOp {
-  __host__ __device__ int32_t operator()(int32_t a, int32_t b) const { return a > b ? a : b; }
-};
 // the bucket a chained pair (previous kept shimmer, shimmer i) hits, if any (shmr_map.c:100-121)
 __global__ void k_ref_hits(const pgx_mm128 *__restrict__ ref, uint32_t n, const int32_t *__restrict__ chain,
                            const uint32_t *__restrict__ first_key0, const uint64_t *__restrict__ gkey0, uint32_t ng,
@@ -215,20 +210,10 @@ void run_map(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t 
   hipLaunchKernelGGL(k_ref_flags, dim3(cdiv(n, 256)), dim3(256), 0, st, d_ref.p, n, gkey0.p, ng, umer.p, ucnt.p, nu,
                      (uint32_t)p->mc_lower, (uint32_t)p->mc_upper, keep.p, cnt.p, first.p);
   hipLaunchKernelGGL(k_ref_chain_in, dim3(cdiv(n, 256)), dim3(256), 0, st, keep.p, n, first.p, chain_in.p);
-  size_t bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, bytes, chain_in.p, chain.p, MaxOp(), (int)n, st));
-  DevBuf<uint8_t> tmp(bytes);
-  PGX_HIP(hipcub::DeviceScan::InclusiveScan(tmp.p, bytes, chain_in.p, chain.p, MaxOp(), (int)n, st));
+  running_max(chain_in.p, chain.p, n);
   hipLaunchKernelGGL(k_ref_hits, dim3(cdiv(n, 256)), dim3(256), 0, st, d_ref.p, n, chain.p, first.p, gkey0.p, ng, gbucket.p, bkey1.p,
                      bstart.p, bucket.p, rows.p);
-  PGX_HIP(hipMemsetAsync(off.p, 0, sizeof(uint32_t), st));
-  bytes = 0;
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, rows.p, off.p + 1, (int)n, st));
-  DevBuf<uint8_t> tmp2(bytes);
-  PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp2.p, bytes, rows.p, off.p + 1, (int)n, st));
-  uint32_t total = 0;
-  PGX_HIP(hipMemcpyAsync(&total, off.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  sync();
+  const uint32_t total = scan_to_total(rows.p, off.p, n);
   if (total == 0) return;
   DevBuf<MapRow> d_rows(total);
   hipLaunchKernelGGL(k_ref_rows, dim3(cdiv(n, 256)), dim3(256), 0, st, d_ref.p, n, chain.p, bucket.p, rows.p, off.p, cnt.p, bstart.p,
@@ -271,11 +256,7 @@ int pgx_map(const pgx_mm128 *ref_mmers, size_t n_ref, const pgx_mm128 *mmers, si
     uint64_t nl = 0;
     run_map(ref_mmers, n_ref, mmers, n_mm, counts, n_counts, rlen_by_rid, n_rid, p, s, nl);
     timing_flush();
-    char *out = (char *)malloc(s.size() + 1);
-    if (!out) throw std::bad_alloc();
-    memcpy(out, s.data(), s.size());
-    out[s.size()] = 0;
-    *text = out, *text_len = s.size();
+    *text = caller_text(s.data(), s.size()), *text_len = s.size();
     if (n_lines) *n_lines = nl;
   });
 }

@@ -25,8 +25,6 @@
 #include <chrono>
 #include <optional>
 
-#include <hipcub/hipcub.hpp>
-
 #include "pgx_replay.h"
 
 namespace pgx {
@@ -463,10 +461,7 @@ uint32_t replay_attempt(const pgx_seqdb *db, const DevicePairs &dp, const uint32
   {
     const double e0 = now_ms();
     DevBuf<uint32_t> off(nb + 1);
-    size_t tb = 0;
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, r.inum, off.p, (int)nb, s));
-    DevBuf<uint8_t> tmp(tb + 256);
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, r.inum, off.p, (int)nb, s));
+    exclusive_sum(r.inum, off.p, nb);
     uint32_t last_off = 0, last_num = 0;
     PGX_HIP(hipMemcpyAsync(&last_off, off.p + nb - 1, 4, hipMemcpyDeviceToHost, s));
     PGX_HIP(hipMemcpyAsync(&last_num, r.inum + nb - 1, 4, hipMemcpyDeviceToHost, s));

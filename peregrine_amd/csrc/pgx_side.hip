@@ -14,7 +14,6 @@
 //                inverse of pgx_pack.hip's pack4; shmr_utils.c:44-51).  The scratch uses the side store's slot rule.
 // Bytes outside a read (a slot's lead and padding) are never looked at by a result: every kernel clips to the read's length, as it must on
 // the seqdb, where the neighbours are other reads.
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
@@ -188,27 +187,15 @@ void side_build(pgx_seqdb *db) {
   hipStream_t st = ctx().stream;
   const uint32_t nr = (uint32_t)db->rlen_by_rid.size(), nf = db->n_flagged_reads;
   MemTag mem_tag("seqdb.side");
-  DevBuf<uint32_t> rids(nf), count(1);
+  DevBuf<uint32_t> rids(nf);
   DevBuf<uint64_t> offs(nf), slot((size_t)nf + 1);
-  {   // the flagged rids, ascending
-    hipcub::CountingInputIterator<uint32_t, ptrdiff_t> iota(0);
-    size_t sb = 0;
-    PGX_HIP(hipcub::DeviceSelect::Flagged(nullptr, sb, iota, db->d_nflag.p, rids.p, count.p, (int)nr, st));
-    DevBuf<uint8_t> tmp(sb + 256);
-    PGX_HIP(hipcub::DeviceSelect::Flagged(tmp.p, sb, iota, db->d_nflag.p, rids.p, count.p, (int)nr, st));
-    uint32_t got = 0;
-    PGX_HIP(hipMemcpyAsync(&got, count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    sync();
-    PGX_REQUIRE(got == nf, PGX_EHIP, "the flag table names %u reads, the packs counted %u", got, nf);
-  }
+  const uint32_t got = select_indices(db->d_nflag.p, nr, rids.p);   // the flagged rids, ascending
+  PGX_REQUIRE(got == nf, PGX_EHIP, "the flag table names %u reads, the packs counted %u", got, nf);
   hipLaunchKernelGGL(k_side_need, dim3(cdiv(nf, 256)), dim3(256), 0, st, rids.p, nf, db->d_roff.p, db->d_rlen.p, slot.p);
   uint64_t total = 0;
   {
     PGX_HIP(hipMemsetAsync(slot.p + nf, 0, sizeof(uint64_t), st));
-    size_t sb = 0;
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, slot.p, slot.p, (int)nf + 1, st));
-    DevBuf<uint8_t> tmp(sb + 256);
-    PGX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, sb, slot.p, slot.p, (int)nf + 1, st));
+    exclusive_sum(slot.p, slot.p, (size_t)nf + 1);
     PGX_HIP(hipMemcpyAsync(&total, slot.p + nf, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     sync();
   }

@@ -28,7 +28,6 @@
 // (k_sketch_wave / k_sketch_general: unchanged), k_nread_end (a lane per read: the last w entries, found from a bounded look-back
 // that is widened until it provably covers them), k_nread_assemble (a wavefront per read), and for the fused index path
 // k_reduce_long (mm_reduce x levels per read, any length, /root/reference/src/shmr_reduce.c:53-90).
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
@@ -400,10 +399,7 @@ void dev_sketch_nreads(const pgx_seqdb *db, const ReadDesc *d_reads, const uint3
       }
       uint32_t *d_anybad = ws<uint32_t>("nsk.nbad", 1);
       PGX_HIP(hipMemsetAsync(d_anybad, 0, sizeof(uint32_t), st));
-      size_t rb = 0;
-      PGX_HIP(hipcub::DeviceReduce::Max(nullptr, rb, vflag.p, d_anybad, (int)ns, st));
-      void *rt = ws_raw("nsk.red_tmp", rb);
-      PGX_HIP(hipcub::DeviceReduce::Max(rt, rb, vflag.p, d_anybad, (int)ns, st));
+      reduce_max(vflag.p, d_anybad, ns);
       uint32_t anybad = 0;
       PGX_HIP(hipMemcpyAsync(&anybad, d_anybad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       sync();

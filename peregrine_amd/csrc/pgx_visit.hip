@@ -15,7 +15,6 @@
 // Slot word: hash bits | 2-bit state | id, as in DistinctSlotTable: the keys of a table are distinct and never compared, a resize
 // needs only the low bits of the hash, and "occupied" alternates between 1 and 2 from one resize to the next, which tells
 // "not moved yet" from "placed" during a rehash (khash.h:258-284 does that with two flag arrays).
-#include <hipcub/hipcub.hpp>
 
 #include "pgx_internal.h"
 
@@ -243,11 +242,7 @@ void dev_visit_place(const DevicePairs &dp, DevVisit &v, const uint64_t *slots, 
     PGX_HIP(hipMemcpyAsync(d_own.p, slots, (size_t)n_slots * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     const uint64_t *d_slots_p = d_own.p;
     hipLaunchKernelGGL(k_outer_counts, dim3((n_slots + 255) / 256), dim3(256), 0, st, d_slots_p, n_slots, dp.gord.p, v.gnb.p, cnt.p);
-    PGX_HIP(hipMemsetAsync(off.p, 0, sizeof(uint32_t), st));
-    size_t bytes = 0;
-    PGX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, cnt.p, off.p + 1, (int)n_slots, st));
-    DevBuf<uint8_t> tmp(bytes + 256);
-    PGX_HIP(hipcub::DeviceScan::InclusiveSum(tmp.p, bytes, cnt.p, off.p + 1, (int)n_slots, st));
+    scan_offsets(cnt.p, off.p, n_slots);
     hipLaunchKernelGGL(k_outer_place, dim3((n_slots + 255) / 256), dim3(256), 0, st, d_slots_p, n_slots, dp.gord.p, dp.gbucket.p,
                        v.ids_all.p, off.p, bid.p);
     PGX_HIP(hipGetLastError());
