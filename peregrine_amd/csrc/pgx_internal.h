@@ -227,7 +227,7 @@ struct ReadDesc {
 // What the library keeps between the stages of the job running on one read database: each part is built on first use by the file
 // that owns its type and released with the database (two live databases each hold their own).
 struct CountCache;    // the aggregated count table (pgx_pairs.hip)
-struct ReplayState;   // the device replay's learned table sizes and the tables it cleared ahead of time (pgx_replay.hip)
+struct ReplayState;   // the device replay's learned table sizes, the tables it cleared ahead of time, its pinned mirrors and second stream (pgx_replay.hip)
 struct ServedCache;   // device copies of the list / count files index commands wrote, the assembled lists of the last prefix (pgx_served.cpp)
 struct CacheFree {    // (each operator() is defined in the file that owns the type)
   void operator()(CountCache *) const;
@@ -597,7 +597,7 @@ void overlap_stage(pgx_seqdb *db, const StageInput &in, const pgx_overlap_params
 // its record buffer over right behind k_emit -- take() returns at once, the transfer runs on the sink's own threads and streams -- and
 // allocates no host array; the host replay (small sets, fall-back) delivers a host array that the caller writes itself.
 struct RecordSink {
-  virtual void take(DevBuf<pgx_ovlp> &&dev, size_t n) = 0;   // ordered behind what is enqueued on ctx().stream
+  virtual void take(DevBuf<pgx_ovlp> &&dev, size_t n) = 0;   // ordered behind what is enqueued on ctx().stream; at most once per stage (the attempt's last overflow check has passed)
   virtual ~RecordSink() {}
 };
 // Served jobs: an index command leaves with the database a device copy of every final-level list / count file it wrote (keyed by the

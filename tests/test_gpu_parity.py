@@ -699,6 +699,28 @@ def test_device_replay_equals_oracle(small, monkeypatch):
     rdb2.close()
 
 
+def test_device_replay_timed_path_equals_oracle(small, monkeypatch):
+    """PGX_REPLAY_TIMING=1 brackets every replay kernel with events and therefore runs k_eval_big BEHIND the narrow kernel of a pass
+    instead of beside it on the second stream: the same stream and checksum, and every timing key of the replay reports launches;
+    with nearly every bucket sent to the workgroup kernel (PGX_REPLAY_BIG=2, PGX_REPLAY_DUP=2) "replay_big" does too"""
+    db, rdb = small
+    ix = rdb.index()
+    want, ost = U.orc_overlap(db, ix.top, ix.top_mc)
+    monkeypatch.setenv("PGX_GPU_REPLAY", "1")
+    monkeypatch.setenv("PGX_REPLAY_TIMING", "1")
+    keys = ["replay_dense", "replay_rows", "replay_update", "replay_misc", "replay_emit"]
+    for env, names in ((dict(), keys), (dict(PGX_REPLAY_BIG="2", PGX_REPLAY_DUP="2"), keys + ["replay_big"])):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        _lib.timing_reset()
+        got, st = rdb.overlap(ix.top, ix.top_mc)
+        assert st["device_replay"] == 1 and formats.ovlp_fields_equal(got, want), env
+        assert st["stream_checksum"] == formats.stream_checksum(want), env
+        launches = {n: _lib.timing(n)[1] for n in names}
+        print(env, launches)
+        assert all(v > 0 for v in launches.values()), (env, launches)
+
+
 def test_asynchronous_record_delivery(small, monkeypatch):
     """pgx_results_async (round 4): the overlap stage returns once the copy of its records is enqueued on a stream of its own; the NEXT
     stage, pgx_free of the array and pgx_results_wait wait for it.  Two chunks back to back, arrays read after the wait, equal to the
