@@ -109,11 +109,18 @@ def small():
     rdb.close()
 
 
-def test_small_dataset_index_vs_oracle(small):
+@pytest.fixture(scope="module")
+def small_l0(small):
+    """the oracle's level-0 list of the `small` set at w = 80, k = 16"""
+    db, _ = small
+    return np.concatenate([U.orc_sketch_seqdb(db.seqdb[int(o):int(o) + int(n)], 80, 16, int(r))
+                           for r, n, o in zip(db.rid, db.rlen, db.roff)])
+
+
+def test_small_dataset_index_vs_oracle(small, small_l0):
     db, rdb = small
     ix = rdb.index(want_l0=True)
-    l0 = np.concatenate([U.orc_sketch_seqdb(db.seqdb[int(o):int(o) + int(n)], 80, 16, int(r))
-                         for r, n, o in zip(db.rid, db.rlen, db.roff)])
+    l0 = small_l0
     assert np.array_equal(ix.l0, l0)
     l1 = U.orc_reduce(l0, 6)
     l2 = U.orc_reduce(l1, 6)
@@ -136,8 +143,27 @@ def test_small_dataset_index_vs_oracle(small):
         b0 = np.concatenate([U.orc_sketch_seqdb(db.seqdb[int(o):int(o) + int(n)], w, k, int(rr))
                              for rr, n, o in list(zip(db.rid, db.rlen, db.roff))])
         assert np.array_equal(a.l0, b0), (w, k)
-        assert np.array_equal(a.top, U.orc_reduce(U.orc_reduce(b0, r), r)), (w, k, r)
+        b2 = U.orc_reduce(U.orc_reduce(b0, r), r)
+        assert np.array_equal(a.top, b2), (w, k, r)
+        assert np.array_equal(formats.mc_as_sorted_pairs(a.top_mc), formats.mc_as_sorted_pairs(U.orc_count(b2))), (w, k, r)   # (dev_count sorts 2k bits)
         assert a.reads_literal == 0, (w, k, a.reads_literal)   # (only reads with ambiguous bases need the state machine)
+
+
+@pytest.mark.parametrize("r", [1, 4, 5, 7, 16, 17, 18, 255])
+def test_reduction_factors_across_the_switch(small, small_l0, r):
+    """The fused streaming reduce carries r - 1 elements from tile to tile and serves r <= 17 (pgx_sketch_fast.hip: RCARRY + 1); from
+    r = 18 on the wave sketch + k_reduce_read (a read's level-0 list in LDS) take over.  Both sides of the switch, the factors next to
+    those the suite always ran (2, 3, 6, 24), r = 1 (a window of one element: every shimmer is its window's minimum) and the largest
+    factor the stage accepts; one and two levels, and the count table of the top level."""
+    db, rdb = small
+    l1 = U.orc_reduce(small_l0, r)
+    l2 = U.orc_reduce(l1, r)
+    assert len(l1) > 1000 and (len(l2) > 1000 or r == 255), (len(l1), len(l2))   # (two levels of 255 leave nothing of reads this long: an empty list is the answer)
+    a, b = rdb.index(reduction=r), rdb.index(reduction=r, levels=1)
+    assert np.array_equal(b.top, l1) and np.array_equal(a.top, l2)
+    assert a.reads_literal == 0 and b.reads_literal == 0
+    assert np.array_equal(formats.mc_as_sorted_pairs(a.top_mc), formats.mc_as_sorted_pairs(U.orc_count(l2)))
+    assert np.array_equal(formats.mc_as_sorted_pairs(b.top_mc), formats.mc_as_sorted_pairs(U.orc_count(l1)))
 
 
 @pytest.mark.parametrize("OT", [1, 3])

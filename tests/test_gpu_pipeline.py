@@ -35,7 +35,9 @@ def _ref(tool, *args, cwd=None, stdin=None):
 
 
 @pytest.mark.skipif(not (U.have_ref() and os.path.exists(os.path.join(U.REF_DIR, "shmr_map"))), reason="needs the prebuilt reference binaries (oracle/_ref)")
-def test_pipeline_like_the_reference_test_scripts(tmp_path):
+@pytest.mark.parametrize("index_flags", [("-r", 6), ("-w", 64, "-k", 24, "-r", 3, "-l", 2)], ids=["r6", "w64-k24-r3-l2"])
+def test_pipeline_like_the_reference_test_scripts(tmp_path, index_flags):
+    lv = dict(zip(index_flags[0::2], index_flags[1::2])).get("-l", 2)   # the level the lists are named after: shmr_index's -l, 2 unless given
     g = simreads.make_genome(300_000, 21, repeat_families=2, repeat_len=3000, repeat_copies=4, divergence=0.02, tandem=2)
     db = simreads.simulate_reads(g, coverage=14.0, seed=3, mean_len=7000, sd_len=1500, err=0.01, n_files=1)
     # reads in three FASTA files, contigs = two pieces of the genome (one reverse-complemented) in a fourth
@@ -65,15 +67,15 @@ def test_pipeline_like_the_reference_test_scripts(tmp_path):
         run("shmr_mkseqdb", "-p", f"{ix}/seq_dataset", "-d", tmp_path / "seq_dataset.lst")
         run("shmr_mkseqdb", "-p", f"{ix}/p_ctg", "-d", tmp_path / "ctg.lst")
         for c in (1, 2, 3):
-            run("shmr_index", "-p", f"{ix}/seq_dataset", "-r", 6, "-t", 3, "-c", c, "-o", f"{ix}/shmr")
-        run("shmr_index", "-p", f"{ix}/p_ctg", "-r", 6, "-t", 1, "-c", 1, "-o", f"{ix}/p_ctg")
+            run("shmr_index", "-p", f"{ix}/seq_dataset", *index_flags, "-t", 3, "-c", c, "-o", f"{ix}/shmr")
+        run("shmr_index", "-p", f"{ix}/p_ctg", *index_flags, "-t", 1, "-c", 1, "-o", f"{ix}/p_ctg")
         for c in (1, 2):
-            run("shmr_overlap", "-p", f"{ix}/seq_dataset", "-l", f"{ix}/shmr-L2", "-t", 2, "-c", f"{c:02d}", "-o", d / "ovlp" / f"ovlp.{c:02d}")
+            run("shmr_overlap", "-p", f"{ix}/seq_dataset", "-l", f"{ix}/shmr-L{lv}", "-t", 2, "-c", f"{c:02d}", "-o", d / "ovlp" / f"ovlp.{c:02d}")
         cat = b"".join((d / "ovlp" / f"ovlp.{c:02d}").read_bytes() for c in (1, 2))
         out[who, "preads.ovl"] = run("shmr_dedup", stdin=cat)
-        out[who, "read_map.txt"] = run("shmr_map", "-r", f"{ix}/p_ctg", "-m", f"{ix}/p_ctg-L2", "-p", f"{ix}/seq_dataset", "-l",
-                                       f"{ix}/shmr-L2", "-t", 1, "-c", 1)
-        out[who, "ref2ref.out"] = run("shmr_map", "-r", f"{ix}/p_ctg", "-m", f"{ix}/p_ctg-L2", "-p", f"{ix}/p_ctg", "-l", f"{ix}/p_ctg-L2",
+        out[who, "read_map.txt"] = run("shmr_map", "-r", f"{ix}/p_ctg", "-m", f"{ix}/p_ctg-L{lv}", "-p", f"{ix}/seq_dataset", "-l",
+                                       f"{ix}/shmr-L{lv}", "-t", 1, "-c", 1)
+        out[who, "ref2ref.out"] = run("shmr_map", "-r", f"{ix}/p_ctg", "-m", f"{ix}/p_ctg-L{lv}", "-p", f"{ix}/p_ctg", "-l", f"{ix}/p_ctg-L{lv}",
                                       "-t", 1, "-c", 1)
     names = sorted(os.listdir(tmp_path / "ref" / "index")) + [os.path.join("..", "ovlp", f) for f in sorted(os.listdir(tmp_path / "ref" / "ovlp"))]
     for who in ("mine", "native"):   # the Python drop-ins of bin/ and the native multi-call binary of bin/native/
@@ -96,7 +98,7 @@ def test_pipeline_like_the_reference_test_scripts(tmp_path):
     for c in (1, 2):
         exe = os.path.join(ROOT, "bin", "native", "pgx_cli")
         o = tmp_path / f"ovlp_dev.{c:02d}"
-        subprocess.run([exe, "shmr_overlap", "-p", str(tmp_path / "native" / "index" / "seq_dataset"), "-l", str(tmp_path / "native" / "index" / "shmr-L2"),
+        subprocess.run([exe, "shmr_overlap", "-p", str(tmp_path / "native" / "index" / "seq_dataset"), "-l", str(tmp_path / "native" / "index" / f"shmr-L{lv}"),
                         "-t", "2", "-c", f"{c:02d}", "-o", str(o)], check=True, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert o.read_bytes() == (tmp_path / "ref" / "ovlp" / f"ovlp.{c:02d}").read_bytes(), c
 
