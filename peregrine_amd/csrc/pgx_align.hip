@@ -292,10 +292,11 @@ __global__ __launch_bounds__(64) void k_align1_list(const uint8_t *__restrict__ 
 // step, and as many snake iterations, as the NEEDIEST group of the wavefront.  Here every group carries its own phase
 //   FETCH -> STEP (loop conditions of DWmatch.c:118-122) -> ROUND (start points + 8-code probe of GL diagonals) -> SNAKE (one
 //   128- or 256-code extension of the group's lowest unfinished diagonal per iteration) -> END (the order-dependent side results
-//   of the round, V, best_m, the first diagonal that reaches an end) -> next ROUND, or BAND (one round of the band scan per
-//   iteration, DWmatch.c:166-183) -> STEP of d + 1
+//   of the round, V, best_m, the first diagonal that reaches an end, and the band update DWmatch.c:166-183 from the rounds' own
+//   masks) -> next ROUND, or STEP of d + 1; BAND (one round of the band scan per iteration) only for the multi-round steps whose
+//   masks do not settle the band
 // and an iteration of the wavefront runs every phase body once, each under its groups' predicate; a group passes through
-// ROUND, SNAKE, END and BAND within ONE iteration when its step has a single round and a single extension (the common case),
+// ROUND, SNAKE and END within ONE iteration when its step has a single round and a single extension (the common case),
 // and only the groups that need more take more iterations.
 enum { PH_FETCH = 0, PH_STEP = 1, PH_ROUND = 2, PH_SNAKE = 3, PH_END = 4, PH_BAND = 5, PH_DONE = 6 };
 // The V rings are exchanged between the lanes of ONE wavefront (the block is a wavefront): its LDS instructions execute in program
@@ -363,10 +364,11 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
   uint32_t my_iters = 0;
   int my_maxnk = 0;
   bool has_cand = false;
+  const bool stats_on = !redo_list || redo_n == esc_n + 3;   // (the launch on dev_align's own counter block, order list or not)
 #endif
   for (;;) {
 #ifdef PGX_ALIGN_STATS
-    if (phase == PH_FETCH && has_cand && gl == 0 && !redo_list) {   // (stats build: counter[1..32] / [33..64]: log2 histogram of the wavefront iterations a candidate took / their sums)
+    if (phase == PH_FETCH && has_cand && gl == 0 && stats_on) {   // (stats build: counter[1..32] / [33..64]: log2 histogram of the wavefront iterations a candidate took / their sums)
       const uint32_t b = my_iters ? 31u - (uint32_t)__builtin_clz(my_iters) : 0u;
       atomicAdd(counter + 1 + min(b, 31u), 1u);
 #ifdef PGX_ALIGN_STATS_NK
@@ -628,24 +630,59 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       }
       // The band update (DWmatch.c:166-183) of a step whose diagonals all sat in this one round -- 98.7 % of the steps -- right here, from
       // the registers: U = x + y of the group's lanes, the qualifying diagonals as a mask, its lowest and highest bit.  (hit lanes: the
-      // candidate is finished, the update is not looked at.)  Wider bands go through BAND below, a round of GL diagonals per iteration.
+      // candidate is finished, the update is not looked at.)
+      // A WIDER band (nk > GL) keeps the extremes of its rounds' masks in new_min / new_max as it goes.  best_m only rises within a step, so
+      // a diagonal that failed its own round's threshold fails the final one: nothing below the recorded new_min and nothing above the
+      // recorded new_max qualifies, and if those two still pass the FINAL threshold -- re-read from the ring in the last round, a lane each --
+      // they are the scan's answer and the step is done here.  Only when a later round raised best_m past one of them (5 % of the wide
+      // steps) does the step go through BAND below, a round of GL diagonals per iteration.
       const uint32_t qm = group_bits(ballot64((e && active ? u : INT32_MIN) >= best_m - band), gbase);
-      if (e) {
-        if (matched) {
-          phase = PH_FETCH;
-        } else if (nk <= GL) {
-          const int lo = qm ? min_k + 2 * __builtin_ctz(qm) : max_k, hi = qm ? min_k + 2 * (31 - __builtin_clz(qm)) : min_k;
-          max_k = hi + 1, min_k = lo - 1, ++d, phase = PH_STEP;
-        } else {
+      const bool wide_step = e && !matched && nk > GL;
+      if (ballot64(wide_step)) {   // (1.4 % of the steps)
+        const bool last = wide_step && base + GL >= nk;
+        if (wide_step) {
+          if (base == 0) new_min = max_k, new_max = min_k;   // (what the scan starts from)
+          if (qm) {
+            new_min = min(new_min, min_k + 2 * (base + __builtin_ctz(qm)));
+            new_max = max(new_max, min_k + 2 * (base + 31 - __builtin_clz(qm)));
+          }
           base += GL;
           phase = PH_ROUND;
-          if (base >= nk) bbase = 0, new_min = max_k, new_max = min_k, phase = PH_BAND;
+        }
+        if (ballot64(last)) {
+          // (this round's V is in the ring: the store above precedes these loads in program order.  An extreme inside this round was
+          //  judged by the final qm already and passes again.  Nothing recorded = new_min > new_max: the scan would find nothing either.)
+          const bool some = last && new_min <= new_max;
+          const int ke = gl ? new_max : new_min;
+          int ue = INT32_MIN;
+          if (some && gl < 2) ue = 2 * (int)V[ke & mask] - ke;
+          const uint32_t pm = group_bits(ballot64(ue >= best_m - band), gbase);
+          if (last) {
+            if (!some || (pm & 3u) == 3u) {
+              max_k = new_max + 1, min_k = new_min - 1, ++d, phase = PH_STEP;
+            } else {
+              bbase = 0, new_min = max_k, new_max = min_k, phase = PH_BAND;
+            }
+#ifdef PGX_ALIGN_STATS
+            if (gl == 0 && stats_on) atomicAdd(counter + (phase == PH_BAND ? 66 : 65), 1u);   // ([65] wide steps settled in END, [66] fallbacks to BAND)
+#endif
+          }
+        }
+      }
+      if (e && !wide_step) {
+        if (matched) {
+          phase = PH_FETCH;
+        } else {   // (nk <= GL)
+          const int lo = qm ? min_k + 2 * __builtin_ctz(qm) : max_k, hi = qm ? min_k + 2 * (31 - __builtin_clz(qm)) : min_k;
+          max_k = hi + 1, min_k = lo - 1, ++d, phase = PH_STEP;
         }
       }
     }
     PH_SYNC();
 
     // ---- BAND: one round of the band update (DWmatch.c:166-183) ------------------------------------------------------
+    // The full scan, V read back from the ring: only for the multi-round steps whose recorded extremes did not survive the final
+    // threshold (END above), and for the degenerate step.  Its first round shares the iteration with the step's last END.
     {
       const bool bnd = phase == PH_BAND;
       if (ballot64(bnd)) {
@@ -780,8 +817,13 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
     PGX_HIP(hipGetLastError());
     return;
   }
-  uint32_t *counter = ws<uint32_t>("align.counter", 8);
-  PGX_HIP(hipMemsetAsync(counter, 0, 8 * sizeof(uint32_t), st));
+#ifdef PGX_ALIGN_STATS
+  constexpr size_t n_counter = 72;   // [0] the work counter, [1 .. 66] what the kernel's stats build counts
+#else
+  constexpr size_t n_counter = 8;
+#endif
+  uint32_t *counter = ws<uint32_t>("align.counter", n_counter);
+  PGX_HIP(hipMemsetAsync(counter, 0, n_counter * sizeof(uint32_t), st));
   // k_align_ph: workgroups of NW wavefronts (a V ring of `ring` elements per 8-lane group), as many as give a CU its 32 wavefronts.  x <= read
   // length must fit the ring's element: 32-bit rings when a read is longer than 65,535 bases (19 wavefronts per CU at ring 256)
   const bool wide = db->max_rlen > 65535u;
@@ -834,6 +876,20 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
   const auto ph_bytes = wide ? k_align_ph<int32_t, false> : k_align_ph<uint16_t, false>;   // (the packs never serve a wide launch)
   launch_on(src.grouped, k_align_ph<uint16_t, true>, ph_bytes, dim3(grid), dim3(64 * NW), lds, db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out,
             counter, order ? esc + 3 : nullptr, order, esc, esc ? esc + 4 : nullptr, db->d_nflag.p, seg, iter_limit);
+#ifdef PGX_ALIGN_STATS
+  {
+    uint32_t h[n_counter];
+    PGX_HIP(hipMemcpyAsync(h, counter, sizeof(h), hipMemcpyDeviceToHost, st));
+    sync();
+    unsigned long long cand = 0, total = 0;
+    for (int b = 0; b < 32; ++b) cand += h[1 + b], total += h[33 + b];
+    fprintf(stderr, "[pgx] align stats: %llu candidates, %llu wavefront iterations of theirs (tail_batch %d); per candidate (log2 classes: count, share of all iterations):",
+            cand, total, tail_batch);
+    for (int b = 0; b < 32; ++b)
+      if (h[1 + b]) fprintf(stderr, " 2^%d: %u (%.1f %%)", b, h[1 + b], total ? 100.0 * h[33 + b] / (double)total : 0.0);
+    fprintf(stderr, "; wide steps settled in END %u, sent to BAND %u\n", h[65], h[66]);
+  }
+#endif
   if (esc) {
     // candidates on reads with ambiguous bases: the same phase machine on the seqdb bytes, eight per wavefront, from their list (round 3 gave
     // each a wavefront of its own through k_align1_list: 5 % of the reads flagged = +64 % alignment time at c3).  Only when the database
