@@ -28,6 +28,7 @@ extern "C" {
 #define PGX_EHIP -3    /* HIP runtime error / no device */
 #define PGX_ENOMEM -4
 #define PGX_ESTATE -5  /* pgx_init not called; or the call needs something the state no longer has (the seqdb bytes after pgx_seqdb_release_bytes / pgx_seqdb_compact_bytes) */
+#define PGX_EINVAL -6  /* the input holds, or the call asks for, something this library refuses to approximate (pgx_sgraph_build) */
 
 /* ---- types shared with the on-disk formats (src/shimmer.h:24-30,61-64,97-110) ---- */
 typedef struct { uint64_t x, y; } pgx_mm128;                        /* x = hash<<8|span ; y = rid<<32|lastPos<<1|strand */
@@ -61,7 +62,8 @@ void pgx_free(void *p);              /* releases any host array returned by this
 
 /* per-kernel device time (HIP events on the library's stream), accumulated since the last reset.
  * names: "sketch", "sketch_general", "sketch_redo", "sketch_nreads", "sketch_gather", "pack", "reduce", "count", "pairs", "replay_dense" / "replay_rows" / "replay_update" (k_eval, k_eval_rows, k_update of the device replay; only with PGX_REPLAY_TIMING=1), "align" (k_align_ph), "align1" (k_align1: launches of
- * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map". */
+ * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map", "sgraph" (the string graph: build and text; its parts also as "sgraph_edges", "sgraph_adj", "sgraph_tr", "sgraph_spur",
+ * "sgraph_best", "sgraph_text"). */
 int pgx_timing_get(const char *kernel, double *total_ms, uint64_t *launches, uint64_t *units);
 void pgx_timing_reset(void);
 /* HBM ledger: JSON text of the library's device memory -- live bytes, bytes held in the block cache, and the live bytes BY OWNER (seqdb,
@@ -288,6 +290,55 @@ int pgx_dedup_close(pgx_dedup_stream *s, uint64_t *n_records, uint64_t *n_unique
 int pgx_dedup_open_graph(uint64_t expected_pairs, pgx_dedup_stream **out);
 int pgx_dedup_drain(pgx_dedup_stream *s, uint64_t max_lines, char **text, size_t *text_len, int *done);
 int pgx_dedup_graph_stats(pgx_dedup_stream *s, uint64_t *n_contained_reads, uint64_t *n_lines_kept, uint64_t *n_lines_total);
+
+/* ---- string graph (the first half of py/scripts/ovlp_to_graph.py: generate_string_graph, :658-905, with
+ * disable_chimer_bridge_removal=True and lfc=False): from the rows a graph-mode dedup stream keeps in HBM to the sg_edges_list text,
+ * byte-identical to the script's file.  Load filter (--min_len, --min_idt), edge construction (two edges per surviving row, numbered in
+ * creation order: edge e's reverse is e ^ 1), transitive reduction, spur removal, best-overlap selection, spur removal again; the
+ * file lists the edges in creation order, "%s %s %s %5d %5d %5d %5.2f %s\n" (:901).  All on the device, on the library's stream;
+ * device memory is booked as "sgraph" (pgx_mem_ledger), time as "sgraph" (pgx_timing_get).
+ *   pgx_sgraph_build : on a graph-mode stream after its last feed.  Runs the stream's final compaction if no drain has run yet (feeds are
+ *                      refused afterwards, as after a drain); the rows stay with the stream, which can still be drained or closed, before
+ *                      or after pgx_sgraph_free: the graph owns its arrays.  PGX_ESTATE: a plain or failed stream, or one whose last
+ *                      line was drained (the rows are gone).  PGX_EINVAL, with a message that says why: any bit of `flags` (the chimer
+ *                      bridge step and --lfc are not offered: the first pops from a set of objects, so the script's own output changes
+ *                      with the hash seed); more than 2^31 - 1 kept rows; a kept row with m_size == 0 (its identity prints as nan or
+ *                      inf; the message names the row).  PGX_ENOMEM: no device memory -- the stream stays usable for pgx_dedup_drain.
+ *                      A line whose first field is negative (a read id of 2^31 and more as rid0) would end the script's file; such rows
+ *                      are built like any other here.
+ *   pgx_sgraph_stats : the counts of the graph.
+ *   pgx_sgraph_edges : n edge records from edge `first` on (first + n <= stats.edges), in creation order.
+ *   pgx_sgraph_text  : the file in pieces with pgx_dedup_drain's conventions: the next lines, at most max_lines (> 0) and 2^24 per call,
+ *                      *text malloc'd (pgx_free), *done != 0 with the last of them (at once for an empty graph).
+ *   pgx_sgraph_free  : releases the graph (NULL is accepted).
+ * PGX_SGRAPH_DEG_MAX (a test hook, read by every build): the most out-edges of a node whose transitive reduction runs from LDS tables
+ * (default and maximum 256); nodes with more run the same pass on tables in HBM. */
+#define PGX_SGRAPH_CHIMER_BRIDGE 1u  /* ask for the chimer bridge step: refused */
+#define PGX_SGRAPH_LFC 2u            /* ask for --lfc: refused */
+enum { PGX_SGRAPH_G = 0, PGX_SGRAPH_TR = 1, PGX_SGRAPH_S = 2, PGX_SGRAPH_R = 3 };
+typedef struct {
+  uint32_t v_rid, w_rid;     /* the edge leaves node (v_rid, v_end) and enters (w_rid, w_end) */
+  uint32_t label_rid;
+  int32_t sp, tp;            /* the label's coordinates; the edge's length is |sp - tp| */
+  uint8_t v_end, w_end;      /* 0: B, 1: E */
+  uint8_t type;              /* PGX_SGRAPH_G .. _R */
+  uint8_t pad;
+  int64_t score;             /* m_size */
+  int64_t idt_tenths;        /* identity in tenths, as the dedup line prints it */
+} pgx_sgraph_edge;
+typedef struct {
+  uint64_t rows_in, rows_pass;    /* kept rows of the stream; of them past --min_len / --min_idt */
+  uint64_t edges, nodes;
+  uint64_t n_g, n_tr, n_s, n_r;   /* edges by type */
+  uint64_t max_out_degree;
+  uint64_t spur_candidates;       /* nodes the spur pass visits */
+} pgx_sgraph_stats_t;
+typedef struct pgx_sgraph pgx_sgraph;
+int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min_idt, uint32_t flags, pgx_sgraph **out);
+int pgx_sgraph_stats(const pgx_sgraph *g, pgx_sgraph_stats_t *out);
+int pgx_sgraph_edges(const pgx_sgraph *g, uint64_t first, uint64_t n, pgx_sgraph_edge *out);
+int pgx_sgraph_text(pgx_sgraph *g, uint64_t max_lines, char **text, size_t *text_len, int *done);
+int pgx_sgraph_free(pgx_sgraph *g);
 
 /* ---- reads -> contigs mapping (replaces shmr_map, src/shmr_map.c:48-161,163-373) ----
  * The reads' shimmer-pair map is built exactly as in the overlap stage (build_map with -t/-c/-n/-M); the reference

@@ -75,6 +75,7 @@ EXPORTS = [
     "pgx_overlap_resident", "pgx_overlap_chunk", "pgx_index_chunk_db", "pgx_overlap_chunk_db", "pgx_overlap_chunk_db_begin", "pgx_output_finish", "pgx_index_overlap_resident", "pgx_mkseqdb", "pgx_dedup",
     "pgx_dedup_open", "pgx_dedup_feed", "pgx_dedup_feed_dev", "pgx_dedup_close",
     "pgx_dedup_open_graph", "pgx_dedup_drain", "pgx_dedup_graph_stats",
+    "pgx_sgraph_build", "pgx_sgraph_stats", "pgx_sgraph_edges", "pgx_sgraph_text", "pgx_sgraph_free",
     "pgx_sketch_batch", "pgx_reduce_batch", "pgx_count_batch", "pgx_align_batch",
     "decode_biseq", "encode_biseq", "mm_sketch", "mm_reduce", "ovlp_match", "free_ovlp_match", "read_mmlist", "write_mmlist",
     "pgx_map", "pgx_map_chunk", "pgx_khash_slot_order", "pgx_khash_slot_order_ex",
@@ -148,6 +149,11 @@ def load():
         lib.pgx_dedup_open_graph.argtypes = [C.c_uint64, C.c_void_p]
         lib.pgx_dedup_drain.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_dedup_graph_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_sgraph_build.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_uint32, C.c_void_p]
+        lib.pgx_sgraph_stats.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pgx_sgraph_edges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.pgx_sgraph_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_sgraph_free.argtypes = [C.c_void_p]
         lib.pgx_sketch_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.pgx_reduce_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         lib.pgx_count_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
@@ -175,7 +181,7 @@ def load():
     return _lib
 
 
-PGX_EARG, PGX_ESTATE = -1, -5   # include/pgx.h
+PGX_EARG, PGX_ENOMEM, PGX_ESTATE, PGX_EINVAL = -1, -4, -5, -6   # include/pgx.h
 
 
 def check(rc: int, what: str = "pgx"):

@@ -388,29 +388,33 @@ static void *dedup_read_piece(void *arg) {
   r->got = n;
   return NULL;
 }
-static int main_dedup(int argc, char **argv) {
-  int graph = 0;
-  for (int i = 1; i < argc; ++i) graph |= strcmp(argv[i], "-g") == 0;   /* (other arguments are ignored, as ever) */
+/* stdin through a dedup stream piece by piece.  graph: a graph-mode stream, whose lines come after the end of the input; sg != NULL: instead
+ * of those lines the string graph of them, as the sg_edges_list text (shmr_sgraph) */
+struct sgraph_opts {
+  long long min_len;
+  double min_idt;
+};
+static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg) {
   size_t piece = (size_t)16 << 20;
   const char *pe = getenv("PGX_DEDUP_PIECE");
   if (pe && atoll(pe) > 0) piece = (size_t)atoll(pe);
   if (piece >= ((size_t)1 << 31)) piece = ((size_t)1 << 31) - 1;
   char *bufs[2] = {(char *)malloc(piece * sizeof(pgx_ovlp)), (char *)malloc(piece * sizeof(pgx_ovlp))};
   if (!bufs[0] || !bufs[1]) {
-    fprintf(stderr, "shmr_dedup: out of host memory\n");
+    fprintf(stderr, "%s: out of host memory\n", tool);
     return 1;
   }
   struct dedup_reader rd = {bufs[0], piece * sizeof(pgx_ovlp), 0};
   pthread_t th;
   if (pthread_create(&th, NULL, dedup_read_piece, &rd)) {   /* the first piece is read while the device context comes up */
-    fprintf(stderr, "shmr_dedup: cannot start the reader thread\n");
+    fprintf(stderr, "%s: cannot start the reader thread\n", tool);
     free(bufs[0]), free(bufs[1]);
     return 1;
   }
   pgx_dedup_stream *ds = NULL;
   int rc = 0, open_failed = 0;
-  if (pgx_init(device_of_env())) rc = fail("shmr_dedup", "pgx_init"), open_failed = 1;
-  else if (graph ? pgx_dedup_open_graph(0, &ds) : pgx_dedup_open(0, &ds)) rc = fail("shmr_dedup", "pgx_dedup_open"), open_failed = 1;
+  if (pgx_init(device_of_env())) rc = fail(tool, "pgx_init"), open_failed = 1;
+  else if (graph ? pgx_dedup_open_graph(0, &ds) : pgx_dedup_open(0, &ds)) rc = fail(tool, "pgx_dedup_open"), open_failed = 1;
   for (int k = 0;; k ^= 1) {
     pthread_join(th, NULL);
     const size_t got = rd.got;
@@ -418,14 +422,14 @@ static int main_dedup(int argc, char **argv) {
     rd.buf = bufs[k ^ 1];
     const int more = got == rd.cap;   /* a short piece was the last one (a trailing partial record is dropped, as today) */
     if (more && pthread_create(&th, NULL, dedup_read_piece, &rd)) {
-      fprintf(stderr, "shmr_dedup: cannot start the reader thread\n");
+      fprintf(stderr, "%s: cannot start the reader thread\n", tool);
       rc = 1;
       break;
     }
     char *text = NULL;
     size_t len = 0;
-    if (pgx_dedup_feed(ds, (const pgx_ovlp *)bufs[k], got / sizeof(pgx_ovlp), &text, &len)) rc = fail("shmr_dedup", "pgx_dedup_feed");
-    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("shmr_dedup: stdout");
+    if (pgx_dedup_feed(ds, (const pgx_ovlp *)bufs[k], got / sizeof(pgx_ovlp), &text, &len)) rc = fail(tool, "pgx_dedup_feed");
+    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("stdout");
     pgx_free(text);
     if (rc) {
       if (more) pthread_join(th, NULL);
@@ -433,17 +437,67 @@ static int main_dedup(int argc, char **argv) {
     }
     if (!more) break;
   }
-  for (int done = !graph || !ds || rc; !done;) {
+  pgx_sgraph *g = NULL;
+  if (sg && ds && !rc && pgx_sgraph_build(ds, sg->min_len, sg->min_idt, 0, &g)) rc = fail(tool, "pgx_sgraph_build");
+  for (int done = !g; !done;) {
     char *text = NULL;
     size_t len = 0;
-    if (pgx_dedup_drain(ds, piece, &text, &len, &done)) rc = fail("shmr_dedup", "pgx_dedup_drain");
-    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("shmr_dedup: stdout");
+    if (pgx_sgraph_text(g, piece, &text, &len, &done)) rc = fail(tool, "pgx_sgraph_text");
+    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("stdout");
+    pgx_free(text);
+    if (rc) break;
+  }
+  pgx_sgraph_free(g);
+  for (int done = !graph || sg || !ds || rc; !done;) {
+    char *text = NULL;
+    size_t len = 0;
+    if (pgx_dedup_drain(ds, piece, &text, &len, &done)) rc = fail(tool, "pgx_dedup_drain");
+    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("stdout");
     pgx_free(text);
     if (rc) break;
   }
   if (ds) pgx_dedup_close(ds, NULL, NULL);
   free(bufs[0]), free(bufs[1]);
   return rc;
+}
+
+static int main_dedup(int argc, char **argv) {
+  int graph = 0;
+  for (int i = 1; i < argc; ++i) graph |= strcmp(argv[i], "-g") == 0;   /* (other arguments are ignored, as ever) */
+  return dedup_stdin("shmr_dedup", graph, NULL);
+}
+
+/* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
+ * --disable_chimer_bridge_removal and without --lfc -- the only setting offered */
+static int main_sgraph(int argc, char **argv) {
+  struct sgraph_opts o = {4000, 96.0};
+  for (int i = 1; i < argc; ++i) {
+    const char *a = argv[i], *v = NULL;
+    const int len_opt = strncmp(a, "--min_len", 9) == 0 && (a[9] == 0 || a[9] == '='), idt_opt = strncmp(a, "--min_idt", 9) == 0 && (a[9] == 0 || a[9] == '=');
+    if (len_opt || idt_opt) {
+      v = a[9] ? a + 10 : (i + 1 < argc ? argv[++i] : NULL);
+      char *end = NULL;
+      if (v && len_opt) o.min_len = strtoll(v, &end, 10);
+      else if (v) o.min_idt = strtod(v, &end);
+      if (!v || end == v || *end) {
+        fprintf(stderr, "shmr_sgraph: %.9s needs a number\n", a);
+        return 2;
+      }
+    } else if (strcmp(a, "--lfc") == 0) {
+      fprintf(stderr, "shmr_sgraph: --lfc is not offered (pg_run.py leaves it off)\n");
+      return 2;
+    } else if (strcmp(a, "--disable_chimer_bridge_removal") == 0) {
+      /* what this tool always does */
+    } else if (strcmp(a, "--chimer_bridge_removal") == 0) {
+      fprintf(stderr, "shmr_sgraph: the chimer bridge step is not offered (it pops from a set of objects: the script's own output changes with the hash seed); "
+                      "compare with ovlp_to_graph.py --disable_chimer_bridge_removal\n");
+      return 2;
+    } else {
+      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal] < ovlp.dat > sg_edges_list\n");
+      return 2;
+    }
+  }
+  return dedup_stdin("shmr_sgraph", 1, &o);
 }
 
 static int main_map(int argc, char **argv) {
@@ -498,11 +552,12 @@ int main(int argc, char **argv) {
   else if (strcmp(tool, "shmr_index") == 0) rc = main_index(argc, argv);
   else if (strcmp(tool, "shmr_overlap") == 0) rc = main_overlap(argc, argv);
   else if (strcmp(tool, "shmr_dedup") == 0) rc = main_dedup(argc, argv);
+  else if (strcmp(tool, "shmr_sgraph") == 0) rc = main_sgraph(argc, argv);
   else if (strcmp(tool, "shmr_map") == 0) rc = main_map(argc, argv);
   else if (strcmp(tool, "path_to_contig.py") == 0) rc = main_path_to_contig(argc, argv);
   else if (strcmp(tool, "serve") == 0) rc = main_serve(argc, argv);
   else {
-    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_map|path_to_contig.py} [flags]   (or invoke through a link of that name)\n"
+    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_sgraph|shmr_map|path_to_contig.py} [flags]   (or invoke through a link of that name)\n"
                     "       pgx_cli serve -p seqdb_prefix [-i idle_seconds]   (keeps the read database in HBM; the drop-ins attach to it)\n");
     rc = 2;
   }

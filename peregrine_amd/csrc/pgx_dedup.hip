@@ -12,17 +12,11 @@
 
 #include <mutex>
 
-#include "pgx_internal.h"
+#include "pgx_dedup_rows.h"
 
 namespace pgx {
 namespace {
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
-struct Row {
-  uint32_t rid0, rid1;
-  int32_t m_size, dist;
-  uint32_t a_bgn, a_end, rlen0, strand, b_bgn, b_end, rlen1, type;
-};
 
 __global__ void k_pair_keys(const pgx_ovlp *__restrict__ in, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ idx) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,83 +130,6 @@ __global__ void k_seen_rehash(const unsigned long long *__restrict__ old_tab, ui
 // ---------------------------------------------------------------------------------------------------------
 // streaming form: the text lines, "%09d %09d %d %0.1f %u %d %d %u %u %d %d %u %s\n" as glibc prints them
 // ---------------------------------------------------------------------------------------------------------
-__device__ inline uint32_t div10(uint32_t v) { return __umulhi(v, 0xCCCCCCCDu) >> 3; }
-__device__ inline uint64_t div10(uint64_t v) { return __umul64hi(v, 0xCCCCCCCCCCCCCCCDULL) >> 3; }
-__device__ inline uint32_t ndigits(uint32_t v) {
-  return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8
-         : v < 1000000000u ? 9 : 10;
-}
-// WRITE == false: only counts (k_line_len and k_format share one definition of a line)
-template <bool WRITE>
-struct LineOut {
-  char *p;
-  uint32_t n;
-  __device__ void ch(char c) {
-    if (WRITE) p[n] = c;
-    ++n;
-  }
-  __device__ void u32(uint32_t v, uint32_t min_digits = 1) {
-    const uint32_t nd = max(ndigits(v), min_digits);
-    if (WRITE)
-      for (uint32_t k = nd; k-- > 0;) {
-        const uint32_t q = div10(v);
-        p[n + k] = (char)('0' + (v - q * 10u));
-        v = q;
-      }
-    n += nd;
-  }
-  __device__ void u64(uint64_t v) {
-    uint32_t nd = 1;
-    for (uint64_t t = div10(v); t; t = div10(t)) ++nd;
-    if (WRITE)
-      for (uint32_t k = nd; k-- > 0;) {
-        const uint64_t q = div10(v);
-        p[n + k] = (char)('0' + (uint32_t)(v - q * 10u));
-        v = q;
-      }
-    n += nd;
-  }
-  __device__ void i32(int32_t v) {  // %d
-    if (v < 0) ch('-'), u32(0u - (uint32_t)v);
-    else u32((uint32_t)v);
-  }
-  __device__ void rid(int32_t v) {  // %09d: zero padding to width 9, the sign counts
-    if (v < 0) ch('-'), u32(0u - (uint32_t)v, 8);
-    else u32((uint32_t)v, 9);
-  }
-  // %0.1f of a finite double: the EXACT binary value M * 2^e rounded to one decimal, ties to even, in integer arithmetic
-  __device__ void f1(double x) {
-    const uint64_t bits = (uint64_t)__double_as_longlong(x);
-    if (bits >> 63) ch('-');  // also for a value that rounds to 0.0: "-0.0"
-    const uint32_t ex = (uint32_t)(bits >> 52) & 0x7FFu;
-    uint64_t M = bits & ((1ULL << 52) - 1);
-    int e = -1074;
-    if (ex) M |= 1ULL << 52, e = (int)ex - 1075;
-    const uint64_t m10 = M * 10u;  // < 2^57; tenths = m10 * 2^e
-    uint64_t t;
-    if (e >= 0) {
-      t = m10 << min(e, 6);  // (not reached: |err_est| < 2^38, so e <= -15)
-    } else if (-e >= 58) {
-      t = 0;  // m10 < 2^57 <= half a unit
-    } else {
-      const int s = -e;
-      t = m10 >> s;
-      const uint64_t rem = m10 & ((1ULL << s) - 1), half = 1ULL << (s - 1);
-      if (rem > half || (rem == half && (t & 1))) ++t;
-    }
-    const uint64_t whole = div10(t);
-    u64(whole);
-    ch('.');
-    ch((char)('0' + (uint32_t)(t - whole * 10u)));
-  }
-};
-// the three IEEE double operations of shmr_dedup.c:89-90 in that order, never contracted
-__device__ inline double err_est_of(int32_t dist, int32_t m_size) {
-#pragma clang fp contract(off)
-  const double p = 100.0 * (double)dist;
-  const double q = p / (double)m_size;
-  return 100.0 - q;
-}
 constexpr uint32_t FMT_MAXLINE = 148;  // longest line: 11 + 11 + 11 + 15 + 1 + 11 + 11 + 10 + 10 + 11 + 11 + 10 + 9 + 12 blanks + '\n' = 145
 template <bool WRITE>
 __device__ inline uint32_t format_row(const Row &r, char *dst) {  // m_size != 0
@@ -342,22 +259,6 @@ using namespace pgx;
 // ---------------------------------------------------------------------------------------------------------
 // the streaming entry points
 // ---------------------------------------------------------------------------------------------------------
-struct pgx_dedup_stream {
-  DevBuf<unsigned long long> tab;   // the seen-pair set: cap slots + the word of the all-ones key; owned by the stream (MemTag "dedup")
-  uint64_t cap = 0;
-  uint64_t n_records = 0, n_unique = 0;
-  bool failed = false;              // an entry point returned an error: only pgx_dedup_close is accepted
-  bool shut = false;                // pgx_shutdown ran while the stream was open: its device state is gone
-  char *pin[2] = {nullptr, nullptr};   // text staging (pinned), made at the first feed that has text
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  // graph mode (pgx_dedup_open_graph): the lines wait in HBM as rows until the end of the stream says which reads are contained
-  bool graph = false;
-  bool draining = false;            // the first pgx_dedup_drain ran: the store holds exactly the kept lines' rows, no feed is accepted
-  DevBuf<uint32_t> bits;            // contained reads, one bit per read id (MemTag "dedup"); bits.n words, a power of two
-  DevBuf<pgx::Row> store;           // rows of the `overlap` lines between two unmarked reads, in stream order; store.n is the capacity
-  uint64_t store_n = 0, drained = 0;   // rows held; rows handed out as text
-};
-
 namespace pgx {
 namespace {
 constexpr uint64_t SEEN_MIN_CAP = 1ULL << 16;
@@ -368,11 +269,7 @@ std::vector<pgx_dedup_stream *> g_streams;   // the open ones
 void stream_drop_device_state(pgx_dedup_stream *s) {
   s->tab.release();
   s->bits.release(), s->store.release();
-  for (int k = 0; k < 2; ++k) {
-    if (s->pin[k]) (void)hipHostFree(s->pin[k]);
-    if (s->ev[k]) (void)hipEventDestroy(s->ev[k]);
-    s->pin[k] = nullptr, s->ev[k] = nullptr;
-  }
+  s->stage.drop();
 }
 ShutdownHook g_streams_hook([] {
   std::lock_guard<std::mutex> lk(g_streams_mu);
@@ -403,28 +300,6 @@ void seen_reserve(pgx_dedup_stream *s, uint64_t more) {
   s->cap = cap;
 }
 
-// `total` bytes of device text to host memory through the two pinned buffers: the copy of one piece runs while the host moves the last
-void text_download(pgx_dedup_stream *s, const char *d_text, size_t total, char *dst) {
-  hipStream_t st = ctx().stream;
-  for (int k = 0; k < 2; ++k)
-    if (!s->pin[k]) {
-      PGX_HIP(hipHostMalloc((void **)&s->pin[k], PIN_BYTES, hipHostMallocDefault));
-      PGX_HIP(hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming));
-    }
-  const size_t np = (total + PIN_BYTES - 1) / PIN_BYTES;
-  for (size_t i = 0; i <= np; ++i) {
-    if (i < np) {
-      PGX_HIP(hipMemcpyAsync(s->pin[i & 1], d_text + i * PIN_BYTES, std::min(PIN_BYTES, total - i * PIN_BYTES), hipMemcpyDeviceToHost, st));
-      PGX_HIP(hipEventRecord(s->ev[i & 1], st));
-    }
-    if (i > 0) {
-      const size_t j = i - 1;
-      PGX_HIP(hipEventSynchronize(s->ev[j & 1]));
-      memcpy(dst + j * PIN_BYTES, s->pin[j & 1], std::min(PIN_BYTES, total - j * PIN_BYTES));
-    }
-  }
-}
-
 char *empty_text() { return caller_text("", 0); }
 
 // The text the device wrote for m rows: `total` bytes, row j's line at off[j] -- none for the n_special rows with m_size == 0
@@ -445,7 +320,7 @@ std::string rows_to_host_text(const Row *d_rows, size_t m, const DeviceLines *de
   PGX_HIP(hipMemcpyAsync(rows.data(), d_rows, m * sizeof(Row), hipMemcpyDeviceToHost, st));
   if (dev) {
     PGX_HIP(hipMemcpyAsync(off.data(), dev->d_off, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    text_download(dev->s, dev->d_text, dev->total, dev_text.data());
+    text_download(dev->s->stage, dev->d_text, dev->total, dev_text.data());
   }
   pgx::sync();
   std::string out;
@@ -487,7 +362,7 @@ void rows_to_text(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *
   if (n_special == 0) {
     *text = caller_text(nullptr, total);   // (the caller's from here: released by its pgx_free also when the download fails)
     *text_len = total;
-    text_download(s, d_text, total, *text);
+    text_download(s->stage, d_text, total, *text);
     return;
   }
   // rows with m_size == 0 (no real overlap record has one): the host's snprintf prints them, spliced in at their place
@@ -563,34 +438,6 @@ void graph_take(pgx_dedup_stream *s, const Row *d_rows, uint32_t m) {
   hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(k, 256)), dim3(256), 0, st, d_rows, sel, k, s->store.p + s->store_n);
   PGX_HIP(hipGetLastError());
   s->store_n += k;
-}
-// the end of the stream: one stable pass over the store against the FINAL bitmap, piece by piece and in place (a piece's kept rows go
-// to a scratch buffer and from there to the store's front, which the pass has read already)
-void graph_compact(pgx_dedup_stream *s) {
-  hipStream_t st = ctx().stream;
-  const uint64_t n = s->store_n;
-  uint64_t kept = 0;
-  if (n) {
-    const uint32_t piece = (uint32_t)std::min<uint64_t>(n, COMPACT_ROWS);
-    DevBuf<Row> scratch;
-    graph_alloc(scratch, piece, "the compaction's scratch");
-    uint32_t *sel = ws<uint32_t>("dd.gsel", piece);
-    for (uint64_t at = 0; at < n; at += piece) {
-      const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
-      const uint32_t k = select_kept(s, s->store.p + at, m, sel);
-      if (k == 0) continue;
-      if (kept == at && k == m) {   // nothing dropped so far: the rows are in place
-        kept += k;
-        continue;
-      }
-      hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(k, 256)), dim3(256), 0, st, s->store.p + at, sel, k, scratch.p);
-      PGX_HIP(hipMemcpyAsync(s->store.p + kept, scratch.p, (size_t)k * sizeof(Row), hipMemcpyDeviceToDevice, st));
-      kept += k;
-    }
-    PGX_HIP(hipGetLastError());
-  }
-  s->store_n = kept;
-  s->draining = true;
 }
 uint64_t graph_count_marked(pgx_dedup_stream *s) {
   if (!s->bits.n) return 0;
@@ -688,6 +535,65 @@ int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, s
   });
 }
 }  // namespace
+
+// `total` bytes of device text to host memory through the two pinned buffers: the copy of one piece runs while the host moves the last
+void text_download(TextStage &ts, const char *d_text, size_t total, char *dst) {
+  hipStream_t st = ctx().stream;
+  for (int k = 0; k < 2; ++k)
+    if (!ts.pin[k]) {
+      PGX_HIP(hipHostMalloc((void **)&ts.pin[k], PIN_BYTES, hipHostMallocDefault));
+      PGX_HIP(hipEventCreateWithFlags(&ts.ev[k], hipEventDisableTiming));
+    }
+  const size_t np = (total + PIN_BYTES - 1) / PIN_BYTES;
+  for (size_t i = 0; i <= np; ++i) {
+    if (i < np) {
+      PGX_HIP(hipMemcpyAsync(ts.pin[i & 1], d_text + i * PIN_BYTES, std::min(PIN_BYTES, total - i * PIN_BYTES), hipMemcpyDeviceToHost, st));
+      PGX_HIP(hipEventRecord(ts.ev[i & 1], st));
+    }
+    if (i > 0) {
+      const size_t j = i - 1;
+      PGX_HIP(hipEventSynchronize(ts.ev[j & 1]));
+      memcpy(dst + j * PIN_BYTES, ts.pin[j & 1], std::min(PIN_BYTES, total - j * PIN_BYTES));
+    }
+  }
+}
+
+void TextStage::drop() {
+  for (int k = 0; k < 2; ++k) {
+    if (pin[k]) (void)hipHostFree(pin[k]);
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+    pin[k] = nullptr, ev[k] = nullptr;
+  }
+}
+
+// the end of the stream: one stable pass over the store against the FINAL bitmap, piece by piece and in place (a piece's kept rows go
+// to a scratch buffer and from there to the store's front, which the pass has read already)
+void graph_compact(pgx_dedup_stream *s) {
+  hipStream_t st = ctx().stream;
+  const uint64_t n = s->store_n;
+  uint64_t kept = 0;
+  if (n) {
+    const uint32_t piece = (uint32_t)std::min<uint64_t>(n, COMPACT_ROWS);
+    DevBuf<Row> scratch;
+    graph_alloc(scratch, piece, "the compaction's scratch");
+    uint32_t *sel = ws<uint32_t>("dd.gsel", piece);
+    for (uint64_t at = 0; at < n; at += piece) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - at);
+      const uint32_t k = select_kept(s, s->store.p + at, m, sel);
+      if (k == 0) continue;
+      if (kept == at && k == m) {   // nothing dropped so far: the rows are in place
+        kept += k;
+        continue;
+      }
+      hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(k, 256)), dim3(256), 0, st, s->store.p + at, sel, k, scratch.p);
+      PGX_HIP(hipMemcpyAsync(s->store.p + kept, scratch.p, (size_t)k * sizeof(Row), hipMemcpyDeviceToDevice, st));
+      kept += k;
+    }
+    PGX_HIP(hipGetLastError());
+  }
+  s->store_n = kept;
+  s->draining = true;
+}
 }  // namespace pgx
 
 extern "C" int pgx_dedup(const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, uint64_t *n_unique) {
@@ -772,6 +678,7 @@ static void drain_lines(pgx_dedup_stream *s, uint64_t max_lines, char **text, si
   if (s->drained == s->store_n) {
     *done = 1;
     s->store.release();   // (the counters stay for pgx_dedup_graph_stats)
+    s->released = true;
   }
 }
 

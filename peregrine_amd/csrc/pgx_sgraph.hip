@@ -1,0 +1,694 @@
+// pgx_sgraph.hip -- the string graph: what generate_string_graph of the reference (py/scripts/ovlp_to_graph.py:658-905) does with
+// disable_chimer_bridge_removal=True and lfc=False, on the rows a graph-mode dedup stream keeps in HBM (pgx_dedup.hip), down to the
+// sg_edges_list text.  What the kernels rely on ("string graph"):
+//   * the stream's pairs are unique, so the loader's overlap_set rejects nothing and no add_edge meets an edge that exists;
+//   * a row that passes the filter and its geometry case adds exactly two edges, 2k and 2k + 1, each other's reverse (e ^ 1);
+//   * nodes are (rid, end) numbered in creation order -- only the spur pass depends on the numbering;
+//   * mark_tr_edges works node by node on state it resets after every node: a node's pass is independent of every other's;
+//   * out-lists are in (length, creation) order from the first stable sort on; in-lists stay in creation order;
+//   * every pass reduces an edge together with its reverse, so `reduced` is symmetric and an edge's type is the pass that reduced it first.
+// Device layout: edge records in creation order; node_of[2e] / node_of[2e + 1] = dense ids of e's in- / out-node; out-lists
+// (out_off / out_e / out_w / out_len) sorted by (node, length, edge), in-lists (in_off / in_e) by (node, edge); type[e] (0 = G).
+// No result depends on the order in which atomics land: they only count (degrees, statistics), claim hash slots whose layout no answer
+// depends on, or take a minimum.
+
+#include <mutex>
+
+#include "pgx_dedup_rows.h"
+
+using pgx::Row;
+typedef pgx_sgraph_edge Edge;
+
+namespace pgx {
+namespace {
+static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+constexpr uint32_t FUZZ = 500;
+constexpr uint32_t DEG_CAP = 256;      // most out-edges of a node whose transitive reduction runs from LDS
+constexpr uint32_t TAB_SLOTS = 512;    // its neighbour table (open addressing, load <= 1/2)
+constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
+enum : uint8_t { T_G = PGX_SGRAPH_G, T_TR = PGX_SGRAPH_TR, T_S = PGX_SGRAPH_S, T_R = PGX_SGRAPH_R };
+
+// ---------------------------------------------------------------------------------------------------------
+// rows -> edges
+// ---------------------------------------------------------------------------------------------------------
+// the identity of a row in tenths, as `%0.1f` prints it (LineOut::f1's rounding: the exact binary value, ties to even); x is finite
+__device__ inline int64_t idt_tenths(double x) {
+  const uint64_t bits = (uint64_t)__double_as_longlong(x);
+  const uint32_t ex = (uint32_t)(bits >> 52) & 0x7FFu;
+  uint64_t M = bits & ((1ULL << 52) - 1);
+  int e = -1074;
+  if (ex) M |= 1ULL << 52, e = (int)ex - 1075;
+  const uint64_t m10 = M * 10u;
+  uint64_t t;
+  if (e >= 0) {
+    t = m10 << min(e, 6);
+  } else if (-e >= 58) {
+    t = 0;
+  } else {
+    const int s = -e;
+    t = m10 >> s;
+    const uint64_t rem = m10 & ((1ULL << s) - 1), half = 1ULL << (s - 1);
+    if (rem > half || (rem == half && (t & 1))) ++t;
+  }
+  return (bits >> 63) ? -(int64_t)t : (int64_t)t;
+}
+__device__ inline void set_edge(Edge &e, uint32_t v_rid, uint8_t v_end, uint32_t w_rid, uint8_t w_end, uint32_t rid, int32_t sp, int32_t tp) {
+  e.v_rid = v_rid, e.v_end = v_end, e.w_rid = w_rid, e.w_end = w_end, e.label_rid = rid, e.sp = sp, e.tp = tp;
+}
+// the four geometry cases of ovlp_to_graph.py:768-841, each with its own skip test; false: the row adds nothing
+__device__ inline bool row_geometry(const Row &r, Edge &e0, Edge &e1) {
+  const uint32_t f = r.rid0, g = r.rid1;
+  const int32_t f_b = (int32_t)r.a_bgn, f_e = (int32_t)r.a_end, f_l = (int32_t)r.rlen0, g_l = (int32_t)r.rlen1;   // (lengths < 2^31: checked)
+  int32_t g_b = (int32_t)r.b_bgn, g_e = (int32_t)r.b_end;
+  if (r.strand == 1) {
+    const int32_t t = g_b;
+    g_b = g_e, g_e = t;
+  }
+  constexpr uint8_t B = 0, E = 1;
+  if (f_b > 0) {
+    if (g_b < g_e) {
+      if (g_e == g_l) return false;
+      set_edge(e0, g, B, f, B, f, f_b, 0), set_edge(e1, f, E, g, E, g, g_e, g_l);
+    } else {
+      if (g_e == 0) return false;
+      set_edge(e0, g, E, f, B, f, f_b, 0), set_edge(e1, f, E, g, B, g, g_e, 0);
+    }
+  } else {
+    if (g_b < g_e) {
+      if (g_b == 0 || f_e == f_l) return false;
+      set_edge(e0, f, B, g, B, g, g_b, 0), set_edge(e1, g, E, f, E, f, f_e, f_l);
+    } else {
+      if (g_b == g_l || f_e == f_l) return false;
+      set_edge(e0, f, B, g, E, g, g_b, g_l), set_edge(e1, g, B, f, E, f, f_e, f_l);
+    }
+  }
+  return true;
+}
+__device__ inline uint32_t edge_len(const Edge &e) { return (uint32_t)llabs((long long)e.sp - (long long)e.tp); }
+
+// flag[j]: row j passes the load filter and its geometry case.  cnt[0] += rows past the filter; cnt[1] = min(cnt[1], the first row that
+// cannot be built: m_size == 0 -- its identity prints as nan or inf -- or a read length of 2^31 and more)
+__global__ void k_sg_filter(const Row *__restrict__ rows, uint32_t n, int64_t min_len, double min_idt, uint8_t *__restrict__ flag,
+                            uint32_t *__restrict__ cnt) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  bool pass = false, ok = false;
+  if (j < n) {
+    const Row r = rows[j];
+    if (r.m_size == 0 || (r.rlen0 | r.rlen1) >> 31) {
+      atomicMin(&cnt[1], j);
+    } else {
+      const int64_t t = idt_tenths(err_est_of(r.dist, r.m_size));
+      pass = !((double)t / 10.0 < min_idt) && (int64_t)r.rlen0 >= min_len && (int64_t)r.rlen1 >= min_len;
+      Edge e0, e1;
+      ok = pass && row_geometry(r, e0, e1);
+    }
+    flag[j] = ok;
+  }
+  const uint64_t b = __ballot(pass);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&cnt[0], (uint32_t)__popcll(b));
+}
+// the two edges of every selected row, and the four node keys ((rid << 1) | end) in the order add_edge meets them
+__global__ void k_sg_edges(const Row *__restrict__ rows, const uint32_t *__restrict__ sel, uint32_t m, Edge *__restrict__ edges,
+                           uint64_t *__restrict__ nkey, uint32_t *__restrict__ npos) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const Row r = rows[sel[j]];
+  Edge e0 = {}, e1 = {};
+  row_geometry(r, e0, e1);
+  e0.score = e1.score = -(int64_t)(int32_t)(0u - (uint32_t)r.m_size);   // the line prints -m_size as an int, the loader negates the number it reads
+  e0.idt_tenths = e1.idt_tenths = idt_tenths(err_est_of(r.dist, r.m_size));
+  edges[2 * (size_t)j] = e0, edges[2 * (size_t)j + 1] = e1;
+  const uint64_t k[4] = {(uint64_t)e0.v_rid << 1 | e0.v_end, (uint64_t)e0.w_rid << 1 | e0.w_end, (uint64_t)e1.v_rid << 1 | e1.v_end,
+                         (uint64_t)e1.w_rid << 1 | e1.w_end};
+  for (uint32_t q = 0; q < 4; ++q) nkey[4 * (size_t)j + q] = k[q], npos[4 * (size_t)j + q] = 4 * j + q;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// nodes in creation order, adjacency
+// ---------------------------------------------------------------------------------------------------------
+// the sorted (key, position) list: a run's head is the key's first position (stable sort); first[p] = 1 at those positions, head[i] = index
+// of the head of i's run once the running maximum has passed over it
+__global__ void k_sg_heads(const uint64_t *__restrict__ skey, const uint32_t *__restrict__ spos, uint32_t n, uint32_t *__restrict__ first,
+                           int32_t *__restrict__ head) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool h = i == 0 || skey[i] != skey[i - 1];
+  first[spos[i]] = h;
+  head[i] = h ? (int32_t)i : 0;
+}
+__global__ void k_sg_node_ids(const uint32_t *__restrict__ spos, const int32_t *__restrict__ head, const uint32_t *__restrict__ rank, uint32_t n,
+                              uint32_t *__restrict__ node_of) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) node_of[spos[i]] = rank[spos[head[i]]];
+}
+__global__ void k_sg_degrees(const uint32_t *__restrict__ node_of, const Edge *__restrict__ edges, uint32_t n_e, uint32_t *__restrict__ outdeg,
+                             uint32_t *__restrict__ indeg, uint64_t *__restrict__ okey, uint32_t *__restrict__ ikey, uint32_t *__restrict__ iota) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_e) return;
+  const uint32_t v = node_of[2 * (size_t)e], w = node_of[2 * (size_t)e + 1];
+  atomicAdd(&outdeg[v], 1u), atomicAdd(&indeg[w], 1u);
+  okey[e] = (uint64_t)v << 32 | edge_len(edges[e]);
+  ikey[e] = w, iota[e] = e;
+}
+__global__ void k_sg_out_lists(const uint32_t *__restrict__ out_e, const uint64_t *__restrict__ skey, const uint32_t *__restrict__ node_of, uint32_t n_e,
+                               uint32_t *__restrict__ out_w, uint32_t *__restrict__ out_len, uint64_t *__restrict__ vw_key, uint32_t *__restrict__ vw_pos) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_e) return;
+  const uint32_t w = node_of[2 * (size_t)out_e[k] + 1];
+  out_w[k] = w, out_len[k] = (uint32_t)skey[k];
+  if (vw_key) vw_key[k] = (skey[k] & 0xFFFFFFFF00000000ULL) | w, vw_pos[k] = k;
+}
+__global__ void k_sg_big_flags(const uint32_t *__restrict__ out_off, uint32_t n_nodes, uint32_t cap, uint8_t *__restrict__ flag) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n_nodes) flag[v] = out_off[v + 1] - out_off[v] > cap;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// transitive reduction: the hot path.  One wavefront (a workgroup of 64) per node v with out-list w_0 .. w_{d-1}.
+//   marks    all neighbours in play (0); 1 = eliminated
+//   loop 1   i in order: unless w_i is eliminated, every e2 of w_i's out-list with len(e2) + len_i < max_len (a prefix: the list is sorted)
+//            eliminates its end if that is a neighbour.  Sequential in i -- an earlier i decides whether a later w_i is read -- and
+//            parallel inside: the lanes take w_i's out-list.
+//   loop 2   every i, eliminated or not: the end of w_i's first out-edge, and of every e2 shorter than FUZZ.  Order-free: a lane per i.
+//   then     an eliminated neighbour's edge and its reverse are reduced.
+// Where the marks live and how "is x a neighbour, and which" is answered is the policy: NbLds (d <= cap: marks and a hash table of the
+// neighbours in LDS) or NbGlobal (any d: the marks are the node's own slice of an array in HBM, the lookup a binary search of the edge
+// list sorted by (v, w)).  Both run the same passes.
+// ---------------------------------------------------------------------------------------------------------
+struct NbLds {
+  uint32_t *tkey;   // TAB_SLOTS node ids, ~0 = empty
+  uint16_t *tval;   // the neighbour's index in v's out-list
+  uint8_t *mark;    // DEG_CAP
+  __device__ void build(const uint32_t *__restrict__ nb, uint32_t d, uint32_t lane) {
+    for (uint32_t s = lane; s < TAB_SLOTS; s += 64) tkey[s] = ~0u;
+    for (uint32_t i = lane; i < d; i += 64) mark[i] = 0;
+    __syncthreads();
+    for (uint32_t i = lane; i < d; i += 64) {
+      const uint32_t key = nb[i];
+      for (uint32_t s = (key * 0x9E3779B1u) >> 23;; s = (s + 1) & (TAB_SLOTS - 1))   // (top 9 bits: TAB_SLOTS == 512)
+        if (atomicCAS(&tkey[s], ~0u, key) == ~0u) {
+          tval[s] = (uint16_t)i;
+          break;
+        }
+    }
+    __syncthreads();
+  }
+  __device__ int find(uint32_t x) const {
+    for (uint32_t s = (x * 0x9E3779B1u) >> 23;; s = (s + 1) & (TAB_SLOTS - 1)) {
+      const uint32_t k = tkey[s];
+      if (k == x) return tval[s];
+      if (k == ~0u) return -1;
+    }
+  }
+  __device__ bool gone(uint32_t i) const { return mark[i] != 0; }
+  __device__ void eliminate(uint32_t i) { mark[i] = 1; }
+};
+static_assert(TAB_SLOTS == 512, "the table's hash takes the top 9 bits");
+struct NbGlobal {
+  const uint64_t *vw_key;   // every edge's (v << 32 | w), ascending
+  const uint32_t *vw_pos;   // its position in the out-lists
+  uint32_t n_e, v, base;    // base: out_off[v]
+  uint32_t *mark;           // v's slice of the per-edge marks (zero before the launch)
+  __device__ void build(const uint32_t *, uint32_t, uint32_t) {}
+  __device__ int find(uint32_t x) const {
+    const uint64_t want = (uint64_t)v << 32 | x;
+    uint32_t lo = 0, hi = n_e;
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (vw_key[mid] < want) lo = mid + 1;
+      else hi = mid;
+    }
+    return lo < n_e && vw_key[lo] == want ? (int)(vw_pos[lo] - base) : -1;
+  }
+  // (device-scope accesses: what a lane wrote before the barrier is what every lane reads after it, whatever the vector cache holds)
+  __device__ bool gone(uint32_t i) const { return __hip_atomic_load(&mark[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; }
+  __device__ void eliminate(uint32_t i) { __hip_atomic_store(&mark[i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+template <class Nb>
+__device__ inline void tr_node(Nb &nb, uint32_t o, uint32_t d, uint32_t lane, const uint32_t *__restrict__ out_off, const uint32_t *__restrict__ out_e,
+                               const uint32_t *__restrict__ out_w, const uint32_t *__restrict__ out_len, uint8_t *__restrict__ type) {
+  nb.build(out_w + o, d, lane);
+  const uint64_t max_len = (uint64_t)out_len[o + d - 1] + FUZZ;
+  for (uint32_t i = 0; i < d; ++i) {
+    if (nb.gone(i)) continue;   // (uniform: every lane reads the same mark, behind the barrier that ended the last round)
+    const uint32_t w = out_w[o + i], wo = out_off[w], wd = out_off[w + 1] - wo;
+    const uint64_t len_i = out_len[o + i];
+    for (uint32_t k0 = 0; k0 < wd; k0 += 64) {
+      const uint32_t k = k0 + lane;
+      const bool in = k < wd && (uint64_t)out_len[wo + k] + len_i < max_len;
+      if (in) {
+        const int j = nb.find(out_w[wo + k]);
+        if (j >= 0) nb.eliminate((uint32_t)j);
+      }
+      if (__ballot(in) != ~0ULL) break;   // the prefix ended in this chunk
+    }
+    __syncthreads();
+  }
+  for (uint32_t i = lane; i < d; i += 64) {
+    const uint32_t w = out_w[o + i], wo = out_off[w], wd = out_off[w + 1] - wo;
+    for (uint32_t k = 0; k < wd && (k == 0 || out_len[wo + k] < FUZZ); ++k) {
+      const int j = nb.find(out_w[wo + k]);
+      if (j >= 0) nb.eliminate((uint32_t)j);
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = lane; i < d; i += 64)
+    if (nb.gone(i)) {
+      const uint32_t e = out_e[o + i];
+      type[e] = T_TR, type[e ^ 1u] = T_TR;   // (other nodes' passes may store the same value to the same bytes)
+    }
+  __syncthreads();   // the tables are reused by the workgroup's next node
+}
+// every node with 1 .. cap out-edges, a workgroup per node, grid-stride
+__global__ __launch_bounds__(64) void k_sg_tr_lds(uint32_t n_nodes, uint32_t cap, const uint32_t *__restrict__ out_off, const uint32_t *__restrict__ out_e,
+                                                  const uint32_t *__restrict__ out_w, const uint32_t *__restrict__ out_len, uint8_t *__restrict__ type) {
+  __shared__ uint32_t tkey[TAB_SLOTS];
+  __shared__ uint16_t tval[TAB_SLOTS];
+  __shared__ uint8_t mark[DEG_CAP];
+  NbLds nb{tkey, tval, mark};
+  for (uint32_t v = blockIdx.x; v < n_nodes; v += gridDim.x) {
+    const uint32_t o = out_off[v], d = out_off[v + 1] - o;
+    if (d == 0 || d > cap) continue;
+    tr_node(nb, o, d, threadIdx.x, out_off, out_e, out_w, out_len, type);
+  }
+}
+// the listed nodes (more than cap out-edges)
+__global__ __launch_bounds__(64) void k_sg_tr_global(const uint32_t *__restrict__ list, uint32_t n_list, const uint32_t *__restrict__ out_off,
+                                                     const uint32_t *__restrict__ out_e, const uint32_t *__restrict__ out_w, const uint32_t *__restrict__ out_len,
+                                                     const uint64_t *__restrict__ vw_key, const uint32_t *__restrict__ vw_pos, uint32_t n_e,
+                                                     uint32_t *__restrict__ marks, uint8_t *__restrict__ type) {
+  for (uint32_t q = blockIdx.x; q < n_list; q += gridDim.x) {
+    const uint32_t v = list[q], o = out_off[v], d = out_off[v + 1] - o;
+    NbGlobal nb{vw_key, vw_pos, n_e, v, o, marks + o};
+    tr_node(nb, o, d, threadIdx.x, out_off, out_e, out_w, out_len, type);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// spur pass, best overlap
+// ---------------------------------------------------------------------------------------------------------
+// a node the spur pass can act on: an out-edge into a node without out-edges, or an in-edge from a node without in-edges (the degrees
+// never change: the passes only reduce)
+__global__ void k_sg_spur_flags(uint32_t n_nodes, const uint32_t *__restrict__ out_off, const uint32_t *__restrict__ out_w, const uint32_t *__restrict__ in_off,
+                                const uint32_t *__restrict__ in_e, const uint32_t *__restrict__ node_of, uint8_t *__restrict__ flag) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_nodes) return;
+  bool c = false;
+  for (uint32_t k = out_off[v]; k < out_off[v + 1] && !c; ++k) c = out_off[out_w[k] + 1] == out_off[out_w[k]];
+  for (uint32_t k = in_off[v]; k < in_off[v + 1] && !c; ++k) {
+    const uint32_t u = node_of[2 * (size_t)in_e[k]];
+    c = in_off[u + 1] == in_off[u];
+  }
+  flag[v] = c;
+}
+__device__ inline uint8_t type_now(const uint8_t *type, uint32_t e) { return __hip_atomic_load(&type[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline void type_set(uint8_t *type, uint32_t e, uint8_t t) { __hip_atomic_store(&type[e], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// one side of mark_spur_edge at node v: with more than one unreduced edge in the list, every unreduced one whose far node is a dead end
+// goes, with its reverse.  far_off: the far node's degree table (out-degrees for the out side, in-degrees for the in side).
+__device__ inline void spur_side(const uint32_t *__restrict__ lst, uint32_t d, uint32_t far_slot, const uint32_t *__restrict__ node_of,
+                                 const uint32_t *__restrict__ far_off, uint8_t *type, uint32_t lane) {
+  uint32_t live = 0;
+  for (uint32_t k = lane; k < d; k += 64) live += type_now(type, lst[k]) == T_G;
+  for (int s = 32; s; s >>= 1) live += (uint32_t)__shfl_xor((int)live, s);
+  __syncthreads();
+  if (live > 1)
+    for (uint32_t k = lane; k < d; k += 64) {
+      const uint32_t e = lst[k], far = node_of[2 * (size_t)e + far_slot];
+      if (far_off[far + 1] == far_off[far] && type_now(type, e) == T_G) type_set(type, e, T_S), type_set(type, e ^ 1u, T_S);
+    }
+  __syncthreads();
+}
+// mark_spur_edge over the candidate nodes in creation order, ONE workgroup of one wavefront: a node's counts see what every earlier
+// node reduced
+__global__ __launch_bounds__(64) void k_sg_spur(const uint32_t *__restrict__ cand, uint32_t n_cand, const uint32_t *__restrict__ out_off,
+                                                const uint32_t *__restrict__ out_e, const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_e,
+                                                const uint32_t *__restrict__ node_of, uint8_t *type) {
+  for (uint32_t c = 0; c < n_cand; ++c) {
+    const uint32_t v = cand[c];
+    spur_side(out_e + out_off[v], out_off[v + 1] - out_off[v], 1, node_of, out_off, type, threadIdx.x);
+    spur_side(in_e + in_off[v], in_off[v + 1] - in_off[v], 0, node_of, in_off, type, threadIdx.x);
+  }
+}
+// per node the best unreduced out-edge and in-edge: the largest m_size, the first of equals in the list's own order
+__device__ inline void best_of(const uint32_t *__restrict__ lst, uint32_t d, const Edge *__restrict__ edges, const uint8_t *__restrict__ type,
+                               uint8_t *__restrict__ best) {
+  uint32_t pick = ~0u;
+  int64_t top = 0;
+  for (uint32_t k = 0; k < d; ++k) {
+    const uint32_t e = lst[k];
+    if (type[e] != T_G) continue;
+    const int64_t s = edges[e].score;
+    if (pick == ~0u || s > top) pick = e, top = s;
+  }
+  if (pick != ~0u) best[pick] = 1;
+}
+__global__ void k_sg_best(uint32_t n_nodes, const uint32_t *__restrict__ out_off, const uint32_t *__restrict__ out_e, const uint32_t *__restrict__ in_off,
+                          const uint32_t *__restrict__ in_e, const Edge *__restrict__ edges, const uint8_t *__restrict__ type, uint8_t *__restrict__ best) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_nodes) return;
+  best_of(out_e + out_off[v], out_off[v + 1] - out_off[v], edges, type, best);
+  best_of(in_e + in_off[v], in_off[v + 1] - in_off[v], edges, type, best);
+}
+// an unreduced pair goes unless both of its edges are best edges (a thread per pair)
+__global__ void k_sg_not_best(uint32_t n_pairs, const uint8_t *__restrict__ best, uint8_t *__restrict__ type) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  if (type[2 * (size_t)p] == T_G && !(best[2 * (size_t)p] && best[2 * (size_t)p + 1])) type[2 * (size_t)p] = T_R, type[2 * (size_t)p + 1] = T_R;
+}
+__global__ void k_sg_finish(Edge *__restrict__ edges, const uint8_t *__restrict__ type, uint32_t n_e, uint32_t *__restrict__ by_type) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint8_t t = e < n_e ? type[e] : 0xFF;
+  if (e < n_e) edges[e].type = t;
+  for (uint8_t q = 0; q < 4; ++q) {
+    const uint64_t b = __ballot(t == q);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&by_type[q], (uint32_t)__popcll(b));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the text: '%s %s %s %5d %5d %5d %5.2f %s' (ovlp_to_graph.py:901), a line per edge
+// ---------------------------------------------------------------------------------------------------------
+template <bool WRITE>
+__device__ inline void pad_i64(LineOut<WRITE> &o, int64_t v, uint32_t width) {   // %<width>d
+  const bool neg = v < 0;
+  const uint64_t a = neg ? 0ULL - (uint64_t)v : (uint64_t)v;
+  uint32_t nd = neg ? 2 : 1;
+  for (uint64_t t = div10(a); t; t = div10(t)) ++nd;
+  for (; nd < width; ++nd) o.ch(' ');
+  if (neg) o.ch('-');
+  o.u64(a);
+}
+constexpr uint32_t SG_MAXLINE = 112;   // 13 + 13 + 11 + 11 + 11 + 20 + 17 + 2 + 7 blanks + '\n' = 106
+template <bool WRITE>
+__device__ inline uint32_t format_edge(const Edge &e, char *dst) {
+  LineOut<WRITE> o{dst, 0};
+  o.rid((int32_t)e.v_rid), o.ch(':'), o.ch(e.v_end ? 'E' : 'B'), o.ch(' ');
+  o.rid((int32_t)e.w_rid), o.ch(':'), o.ch(e.w_end ? 'E' : 'B'), o.ch(' ');
+  o.rid((int32_t)e.label_rid), o.ch(' ');
+  pad_i64(o, e.sp, 5), o.ch(' ');
+  pad_i64(o, e.tp, 5), o.ch(' ');
+  pad_i64(o, e.score, 5), o.ch(' ');
+  {   // %5.2f of the number the line's `%0.1f` text parses to: the tenths with one more 0
+    const bool neg = e.idt_tenths < 0;
+    const uint64_t a = neg ? 0ULL - (uint64_t)e.idt_tenths : (uint64_t)e.idt_tenths, whole = div10(a);
+    uint32_t nd = neg ? 5 : 4;
+    for (uint64_t t = div10(whole); t; t = div10(t)) ++nd;
+    for (; nd < 5; ++nd) o.ch(' ');
+    if (neg) o.ch('-');
+    o.u64(whole), o.ch('.'), o.ch((char)('0' + (uint32_t)(a - whole * 10u))), o.ch('0');
+  }
+  o.ch(' ');
+  if (e.type == T_G) o.ch('G');
+  else if (e.type == T_TR) o.ch('T'), o.ch('R');
+  else o.ch(e.type == T_S ? 'S' : 'R');
+  o.ch('\n');
+  return o.n;
+}
+__global__ void k_sg_line_len(const Edge *__restrict__ edges, uint32_t m, uint64_t *__restrict__ len) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > m) return;
+  len[j] = j < m ? format_edge<false>(edges[j], nullptr) : 0;   // len[m] = 0: the exclusive scan's last entry is the total
+}
+// as k_format of pgx_dedup.hip: a workgroup formats a tile of lines into LDS at the scan's offsets, then streams the tile out with 16-byte stores
+constexpr uint32_t SG_TILE = 256;
+__global__ __launch_bounds__(SG_TILE) void k_sg_format(const Edge *__restrict__ edges, const uint64_t *__restrict__ off, uint32_t m, char *__restrict__ text) {
+  __shared__ __attribute__((aligned(16))) char tile[SG_TILE * SG_MAXLINE + 16];
+  const uint32_t j0 = blockIdx.x * SG_TILE, j = j0 + threadIdx.x, j1 = min(m, j0 + SG_TILE);
+  const uint64_t base = off[j0], end = off[j1];
+  const uint32_t pad = (uint32_t)((uintptr_t)(text + base) & 15u);
+  if (j < m) format_edge<true>(edges[j], tile + pad + (uint32_t)(off[j] - base));
+  __syncthreads();
+  char *g = text + base - pad;
+  const uint32_t lo = pad, hi = pad + (uint32_t)(end - base);
+  const uint32_t body_lo = min(hi, (lo + 15u) & ~15u), body_hi = max(body_lo, hi & ~15u);
+  for (uint32_t k = lo + threadIdx.x; k < body_lo; k += SG_TILE) g[k] = tile[k];
+  for (uint32_t k = body_lo + threadIdx.x * 16u; k < body_hi; k += SG_TILE * 16u)
+    *reinterpret_cast<uint4 *>(g + k) = *reinterpret_cast<const uint4 *>(tile + k);
+  for (uint32_t k = body_hi + threadIdx.x; k < hi; k += SG_TILE) g[k] = tile[k];
+}
+}  // namespace
+}  // namespace pgx
+
+using namespace pgx;
+
+struct pgx_sgraph {
+  DevBuf<Edge> edges;            // creation order, types final (MemTag "sgraph")
+  pgx_sgraph_stats_t st = {};
+  uint64_t cursor = 0;           // edges handed out as text
+  TextStage stage;
+  bool shut = false;             // pgx_shutdown ran: the device state is gone
+};
+
+namespace pgx {
+namespace {
+constexpr uint64_t TEXT_MAX_LINES = 1ULL << 24;
+std::mutex g_graphs_mu;
+std::vector<pgx_sgraph *> g_graphs;
+void graph_drop_device_state(pgx_sgraph *g) {
+  g->edges.release();
+  g->stage.drop();
+}
+ShutdownHook g_graphs_hook([] {
+  std::lock_guard<std::mutex> lk(g_graphs_mu);
+  for (pgx_sgraph *g : g_graphs) graph_drop_device_state(g), g->shut = true;
+});
+
+uint32_t deg_cap() {   // PGX_SGRAPH_DEG_MAX: a test hook that shrinks the LDS path so that small graphs reach the other one
+  const char *v = getenv("PGX_SGRAPH_DEG_MAX");
+  const long c = v ? atol(v) : (long)DEG_CAP;
+  return (uint32_t)std::min<long>(std::max<long>(c, 0), (long)DEG_CAP);
+}
+
+#define LAUNCH(kernel, n, ...) hipLaunchKernelGGL(kernel, dim3(cdiv((n), 256)), dim3(256), 0, st, __VA_ARGS__)
+
+// the passes over n_rows rows at d_rows; fills g
+void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min_idt, pgx_sgraph *g) {
+  hipStream_t st = ctx().stream;
+  MemTag tag("sgraph");
+  PrimWs tmp;
+  g->st.rows_in = n_rows;
+  if (n_rows == 0) return;
+  // ---- filter and geometry (the parts are timed one by one as well: "sgraph_edges", "_adj", "_tr", "_spur", "_best")
+  std::unique_ptr<KernelTimer> part(new KernelTimer("sgraph_edges", n_rows));
+  DevBuf<uint32_t> cnt(8);   // [0] rows past the filter, [1] first row that cannot be built, [2] largest out-degree, [4 .. 8) edges by type
+  PGX_HIP(hipMemsetAsync(cnt.p, 0, 8 * sizeof(uint32_t), st));
+  PGX_HIP(hipMemsetAsync(cnt.p + 1, 0xFF, sizeof(uint32_t), st));
+  DevBuf<uint8_t> flag(n_rows);
+  DevBuf<uint32_t> sel(n_rows);
+  LAUNCH(k_sg_filter, n_rows, d_rows, n_rows, min_len, min_idt, flag.p, cnt.p);
+  const uint32_t m = select_indices(flag.p, n_rows, sel.p, &tmp);
+  uint32_t h_cnt[2];
+  cnt.download(h_cnt, 2);
+  pgx::sync();
+  PGX_REQUIRE(h_cnt[1] == NO_ROW, PGX_EINVAL,
+              "pgx_sgraph_build: kept row %u has m_size == 0 (its identity prints as nan or inf) or a read length of 2^31 and more", h_cnt[1]);
+  g->st.rows_pass = h_cnt[0];
+  PGX_REQUIRE((uint64_t)m * 4 <= (uint64_t)INT32_MAX, PGX_EINVAL, "pgx_sgraph_build: %u rows make edges: more than one device-wide sort takes (2^29 - 1)", m);
+  if (m == 0) return;
+  flag.release();
+  const uint32_t n_e = 2 * m, n_k = 4 * m;
+  g->edges.alloc(n_e);
+  Edge *edges = g->edges.p;
+  // ---- node ids in creation order
+  DevBuf<uint32_t> node_of(n_k);
+  uint32_t n_nodes = 0;
+  {
+    DevBuf<uint64_t> nkey(n_k), skey(n_k);
+    DevBuf<uint32_t> npos(n_k), spos(n_k), first(n_k), rank((size_t)n_k + 1);
+    DevBuf<int32_t> head(n_k);
+    LAUNCH(k_sg_edges, m, d_rows, sel.p, m, edges, nkey.p, npos.p);
+    sort_pairs(nkey.p, skey.p, npos.p, spos.p, n_k, 0, 33, &tmp);
+    LAUNCH(k_sg_heads, n_k, skey.p, spos.p, n_k, first.p, head.p);
+    n_nodes = scan_to_total(first.p, rank.p, n_k, &tmp);
+    running_max(head.p, head.p, n_k, &tmp);
+    LAUNCH(k_sg_node_ids, n_k, spos.p, head.p, rank.p, n_k, node_of.p);
+  }
+  sel.release();
+  part.reset(), part.reset(new KernelTimer("sgraph_adj", n_e));
+  // ---- adjacency: out-lists by (node, length, edge), in-lists by (node, edge)
+  DevBuf<uint32_t> out_off((size_t)n_nodes + 1), in_off((size_t)n_nodes + 1), out_e(n_e), in_e(n_e), out_w(n_e), out_len(n_e);
+  DevBuf<uint64_t> vw_key;
+  DevBuf<uint32_t> vw_pos;
+  const uint32_t cap = deg_cap();
+  uint32_t max_deg = 0;
+  {
+    DevBuf<uint32_t> outdeg(n_nodes), indeg(n_nodes), ikey(n_e), ikey_s(n_e), iota(n_e);
+    DevBuf<uint64_t> okey(n_e), okey_s(n_e);
+    PGX_HIP(hipMemsetAsync(outdeg.p, 0, (size_t)n_nodes * sizeof(uint32_t), st));
+    PGX_HIP(hipMemsetAsync(indeg.p, 0, (size_t)n_nodes * sizeof(uint32_t), st));
+    LAUNCH(k_sg_degrees, n_e, node_of.p, edges, n_e, outdeg.p, indeg.p, okey.p, ikey.p, iota.p);
+    scan_offsets(outdeg.p, out_off.p, n_nodes, &tmp);
+    scan_offsets(indeg.p, in_off.p, n_nodes, &tmp);
+    reduce_max(outdeg.p, cnt.p + 2, n_nodes, &tmp);
+    sort_pairs(okey.p, okey_s.p, iota.p, out_e.p, n_e, 0, 64, &tmp);
+    sort_pairs(ikey.p, ikey_s.p, iota.p, in_e.p, n_e, 0, 32, &tmp);
+    PGX_HIP(hipMemcpyAsync(&max_deg, cnt.p + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    pgx::sync();
+    if (max_deg > cap) {   // the nodes beyond the LDS tables look their neighbours up in the edge list sorted by (v, w)
+      DevBuf<uint64_t> raw(n_e);
+      DevBuf<uint32_t> raw_pos(n_e);
+      vw_key.alloc(n_e), vw_pos.alloc(n_e);
+      LAUNCH(k_sg_out_lists, n_e, out_e.p, okey_s.p, node_of.p, n_e, out_w.p, out_len.p, raw.p, raw_pos.p);
+      sort_pairs(raw.p, vw_key.p, raw_pos.p, vw_pos.p, n_e, 0, 64, &tmp);
+    } else {
+      LAUNCH(k_sg_out_lists, n_e, out_e.p, okey_s.p, node_of.p, n_e, out_w.p, out_len.p, (uint64_t *)nullptr, (uint32_t *)nullptr);
+    }
+  }
+  // ---- transitive reduction
+  part.reset(), part.reset(new KernelTimer("sgraph_tr", n_e));
+  DevBuf<uint8_t> type(n_e), best(n_e), nflag(n_nodes);
+  PGX_HIP(hipMemsetAsync(type.p, 0, n_e, st));
+  hipLaunchKernelGGL(k_sg_tr_lds, dim3(std::min<uint32_t>(n_nodes, (uint32_t)ctx().num_cu * 32u)), dim3(64), 0, st, n_nodes, cap, out_off.p, out_e.p, out_w.p,
+                     out_len.p, type.p);
+  if (max_deg > cap) {
+    DevBuf<uint32_t> big(n_nodes), marks(n_e);
+    LAUNCH(k_sg_big_flags, n_nodes, out_off.p, n_nodes, cap, nflag.p);
+    const uint32_t n_big = select_indices(nflag.p, n_nodes, big.p, &tmp);
+    PGX_HIP(hipMemsetAsync(marks.p, 0, (size_t)n_e * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_sg_tr_global, dim3(std::min<uint32_t>(n_big, (uint32_t)ctx().num_cu * 32u)), dim3(64), 0, st, big.p, n_big, out_off.p, out_e.p, out_w.p,
+                       out_len.p, vw_key.p, vw_pos.p, n_e, marks.p, type.p);
+    PGX_HIP(hipGetLastError());
+    pgx::sync();   // (big and marks go back to the block cache behind the kernel anyway: one stream)
+  }
+  vw_key.release(), vw_pos.release();
+  // ---- spur, best overlap, spur
+  part.reset(), part.reset(new KernelTimer("sgraph_spur", n_e));
+  DevBuf<uint32_t> cand(n_nodes);
+  LAUNCH(k_sg_spur_flags, n_nodes, n_nodes, out_off.p, out_w.p, in_off.p, in_e.p, node_of.p, nflag.p);
+  const uint32_t n_cand = select_indices(nflag.p, n_nodes, cand.p, &tmp);
+  if (n_cand) hipLaunchKernelGGL(k_sg_spur, dim3(1), dim3(64), 0, st, cand.p, n_cand, out_off.p, out_e.p, in_off.p, in_e.p, node_of.p, type.p);
+  part.reset(), part.reset(new KernelTimer("sgraph_best", n_e));
+  PGX_HIP(hipMemsetAsync(best.p, 0, n_e, st));
+  LAUNCH(k_sg_best, n_nodes, n_nodes, out_off.p, out_e.p, in_off.p, in_e.p, edges, type.p, best.p);
+  LAUNCH(k_sg_not_best, m, m, best.p, type.p);
+  part.reset(), part.reset(new KernelTimer("sgraph_spur", n_e));
+  if (n_cand) hipLaunchKernelGGL(k_sg_spur, dim3(1), dim3(64), 0, st, cand.p, n_cand, out_off.p, out_e.p, in_off.p, in_e.p, node_of.p, type.p);
+  part.reset();
+  LAUNCH(k_sg_finish, n_e, edges, type.p, n_e, cnt.p + 4);
+  PGX_HIP(hipGetLastError());
+  uint32_t by_type[4];
+  PGX_HIP(hipMemcpyAsync(by_type, cnt.p + 4, sizeof(by_type), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  g->st.edges = n_e, g->st.nodes = n_nodes, g->st.max_out_degree = max_deg, g->st.spur_candidates = n_cand;
+  g->st.n_g = by_type[T_G], g->st.n_tr = by_type[T_TR], g->st.n_s = by_type[T_S], g->st.n_r = by_type[T_R];
+}
+#undef LAUNCH
+
+void require_graph(const pgx_sgraph *g, const char *who) {
+  PGX_REQUIRE(g, PGX_EARG, "%s: null argument", who);
+  PGX_REQUIRE(!g->shut && ctx().ready, PGX_ESTATE, "%s: pgx_shutdown ran while the graph was alive (free it)", who);
+}
+}  // namespace
+}  // namespace pgx
+
+extern "C" int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min_idt, uint32_t flags, pgx_sgraph **out) {
+  pgx_sgraph *g = nullptr;
+  const int rc = guarded([&] {
+    PGX_REQUIRE(out, PGX_EARG, "pgx_sgraph_build: null argument");
+    *out = nullptr;
+    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "pgx_sgraph_build: no device context (pgx_init has not been called, or found no HIP device)");
+    PGX_REQUIRE(s, PGX_EARG, "pgx_sgraph_build: null argument");
+    PGX_REQUIRE(!s->shut, PGX_ESTATE, "pgx_sgraph_build: pgx_shutdown ran while the stream was open (close it)");
+    PGX_REQUIRE(!s->failed, PGX_ESTATE, "pgx_sgraph_build: the stream returned an error before (close it)");
+    PGX_REQUIRE(s->graph, PGX_ESTATE, "pgx_sgraph_build: not a graph-mode stream (pgx_dedup_open_graph)");
+    PGX_REQUIRE(!s->released, PGX_ESTATE, "pgx_sgraph_build: the stream's last line was drained: its rows are gone");
+    PGX_REQUIRE(!(flags & PGX_SGRAPH_CHIMER_BRIDGE), PGX_EINVAL,
+                "pgx_sgraph_build: the chimer bridge step is not offered (it pops from a set of objects: the script's own output changes with the hash "
+                "seed); run ovlp_to_graph.py with --disable_chimer_bridge_removal to compare");
+    PGX_REQUIRE(!(flags & PGX_SGRAPH_LFC), PGX_EINVAL, "pgx_sgraph_build: --lfc is not offered (pg_run.py leaves it off)");
+    PGX_REQUIRE(flags == 0, PGX_EINVAL, "pgx_sgraph_build: unknown flag bits 0x%x", flags);
+    PGX_REQUIRE(!(min_idt != min_idt), PGX_EARG, "pgx_sgraph_build: min_idt is not a number");
+    int code = PGX_OK;
+    try {
+      KernelTimer tm("sgraph", s->store_n);
+      if (!s->draining) graph_compact(s);
+      PGX_REQUIRE(s->store_n <= (uint64_t)INT32_MAX, PGX_EINVAL, "pgx_sgraph_build: %llu kept rows, more than 2^31 - 1", (unsigned long long)s->store_n);
+      g = new pgx_sgraph;
+      build_graph(s->store.p, (uint32_t)s->store_n, min_len, min_idt, g);
+    } catch (const Fail &f) {
+      code = f.code;
+      if (code == PGX_EHIP && hipGetLastError() == hipErrorOutOfMemory) {   // (the stream is untouched: pgx_dedup_drain still has its rows)
+        set_error("pgx_sgraph_build: no device memory for the graph of %llu rows", (unsigned long long)s->store_n);
+        code = PGX_ENOMEM;
+      }
+    }
+    timing_flush();
+    if (code != PGX_OK) return code;
+    std::lock_guard<std::mutex> lk(g_graphs_mu);
+    g_graphs.push_back(g);
+    *out = g;
+    return (int)PGX_OK;
+  });
+  if (rc != PGX_OK) delete g;
+  return rc;
+}
+
+extern "C" int pgx_sgraph_stats(const pgx_sgraph *g, pgx_sgraph_stats_t *out) {
+  return guarded([&] {
+    PGX_REQUIRE(g && out, PGX_EARG, "pgx_sgraph_stats: null argument");
+    *out = g->st;
+  });
+}
+
+extern "C" int pgx_sgraph_edges(const pgx_sgraph *g, uint64_t first, uint64_t n, pgx_sgraph_edge *out) {
+  return guarded([&] {
+    require_graph(g, "pgx_sgraph_edges");
+    PGX_REQUIRE(first <= g->st.edges && n <= g->st.edges - first && (n == 0 || out), PGX_EARG, "pgx_sgraph_edges: edges %llu .. + %llu of %llu",
+                (unsigned long long)first, (unsigned long long)n, (unsigned long long)g->st.edges);
+    if (n == 0) return;
+    PGX_HIP(hipMemcpyAsync(out, g->edges.p + first, n * sizeof(Edge), hipMemcpyDeviceToHost, ctx().stream));
+    pgx::sync();
+  });
+}
+
+extern "C" int pgx_sgraph_text(pgx_sgraph *g, uint64_t max_lines, char **text, size_t *text_len, int *done) {
+  if (text) *text = nullptr;
+  if (text_len) *text_len = 0;
+  if (done) *done = 0;
+  const int rc = guarded([&] {
+    require_graph(g, "pgx_sgraph_text");
+    PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_sgraph_text: null argument or max_lines == 0");
+    hipStream_t st = ctx().stream;
+    const uint32_t m = (uint32_t)std::min<uint64_t>({max_lines, g->st.edges - g->cursor, TEXT_MAX_LINES});
+    if (m == 0) {
+      *text = caller_text("", 0);
+    } else {
+      KernelTimer tm("sgraph", m), tm_text("sgraph_text", m);
+      const Edge *edges = g->edges.p + g->cursor;
+      uint64_t *d_off = ws<uint64_t>("sg.off", (size_t)m + 1), *d_len = ws<uint64_t>("sg.len", (size_t)m + 1);
+      hipLaunchKernelGGL(k_sg_line_len, dim3(cdiv((size_t)m + 1, 256)), dim3(256), 0, st, edges, m, d_len);
+      exclusive_sum(d_len, d_off, (size_t)m + 1);
+      uint64_t total = 0;
+      PGX_HIP(hipMemcpyAsync(&total, d_off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      pgx::sync();
+      char *d_text = ws<char>("sg.text", total);
+      hipLaunchKernelGGL(k_sg_format, dim3(cdiv(m, SG_TILE)), dim3(SG_TILE), 0, st, edges, d_off, m, d_text);
+      PGX_HIP(hipGetLastError());
+      *text = caller_text(nullptr, total);
+      *text_len = total;
+      text_download(g->stage, d_text, total, *text);
+    }
+    g->cursor += m;
+    if (g->cursor == g->st.edges) *done = 1;
+    timing_flush();
+  });
+  if (rc != PGX_OK) {
+    if (text && *text) free(*text), *text = nullptr;
+    if (text_len) *text_len = 0;
+  }
+  return rc;
+}
+
+extern "C" int pgx_sgraph_free(pgx_sgraph *g) {
+  if (!g) return PGX_OK;
+  {
+    std::lock_guard<std::mutex> lk(g_graphs_mu);
+    for (size_t i = 0; i < g_graphs.size(); ++i)
+      if (g_graphs[i] == g) g_graphs.erase(g_graphs.begin() + i), i = g_graphs.size();
+    if (!g->shut && ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+    graph_drop_device_state(g);
+  }
+  delete g;
+  return PGX_OK;
+}

@@ -361,6 +361,17 @@ class DedupStream:
         _lib.check(self._lib.pgx_dedup_graph_stats(self.h, C.byref(nc), C.byref(nk), C.byref(nt)), "pgx_dedup_graph_stats")
         return dict(contained_reads=int(nc.value), lines_kept=int(nk.value), lines_total=int(nt.value))
 
+    def string_graph(self, min_len: int = 4000, min_idt: float = 96.0, chimer_bridge_removal: bool = False, lfc: bool = False) -> "StringGraph":
+        """graph_ready streams, after the last feed: the string graph of the kept lines (pgx_sgraph_build), what ovlp_to_graph.py's
+        generate_string_graph builds with --disable_chimer_bridge_removal and without --lfc.  Either option set is refused, not approximated.
+        The stream can still be drained or closed; feeds are refused afterwards, as after a drain."""
+        if not self.h:
+            raise _lib.PgxError("pgx_sgraph_build: the stream is closed")
+        flags = (SGRAPH_CHIMER_BRIDGE if chimer_bridge_removal else 0) | (SGRAPH_LFC if lfc else 0)
+        g = C.c_void_p()
+        _lib.check(self._lib.pgx_sgraph_build(self.h, int(min_len), float(min_idt), flags, C.byref(g)), "pgx_sgraph_build")
+        return StringGraph(g)
+
     def close(self):
         """frees the stream; returns (records fed, lines written -- by a plain stream: a graph_ready one reports its kept lines in stats)"""
         if not self.h:
@@ -384,6 +395,107 @@ class DedupStream:
                 self.close()
         except Exception:
             pass
+
+
+SGRAPH_CHIMER_BRIDGE, SGRAPH_LFC = 1, 2   # pgx_sgraph_build's flags: both are refused
+SGRAPH_EDGE_DTYPE = np.dtype([("v_rid", "<u4"), ("w_rid", "<u4"), ("label_rid", "<u4"), ("sp", "<i4"), ("tp", "<i4"), ("v_end", "u1"), ("w_end", "u1"),
+                              ("type", "u1"), ("pad", "u1"), ("score", "<i8"), ("idt_tenths", "<i8")])   # pgx_sgraph_edge
+SGRAPH_TYPES = ("G", "TR", "S", "R")
+_SGRAPH_STATS = ("rows_in", "rows_pass", "edges", "nodes", "n_g", "n_tr", "n_s", "n_r", "max_out_degree", "spur_candidates")
+
+
+class StringGraph:
+    """The string graph of a graph-mode dedup stream (DedupStream.string_graph): its arrays live on the device and belong to this object,
+    whatever becomes of the stream."""
+
+    def __init__(self, handle):
+        self._lib = _lib.load()
+        self.h = handle
+        st = (C.c_uint64 * len(_SGRAPH_STATS))()
+        _lib.check(self._lib.pgx_sgraph_stats(self.h, st), "pgx_sgraph_stats")
+        self.stats = dict(zip(_SGRAPH_STATS, (int(v) for v in st)))
+
+    def _handle(self, who):
+        if not self.h:
+            raise _lib.PgxError(f"{who}: the graph is closed")
+        return self.h
+
+    def edges(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """edge records (SGRAPH_EDGE_DTYPE) in creation order: edge e's reverse is e ^ 1; `type` indexes SGRAPH_TYPES"""
+        n = self.stats["edges"] - first if n is None else n
+        out = np.zeros(n, SGRAPH_EDGE_DTYPE)
+        _lib.check(self._lib.pgx_sgraph_edges(self._handle("pgx_sgraph_edges"), int(first), int(n), _ptr(out)), "pgx_sgraph_edges")
+        return out
+
+    def text(self, max_lines: int = 1 << 20):
+        """sg_edges_list, as bytes of at most max_lines lines each (the next lines: a second iteration goes on where the first stopped)"""
+        done = C.c_int(0)
+        while not done.value:
+            text, tl = C.c_void_p(), C.c_size_t(0)
+            _lib.check(self._lib.pgx_sgraph_text(self._handle("pgx_sgraph_text"), int(max_lines), C.byref(text), C.byref(tl), C.byref(done)), "pgx_sgraph_text")
+            data = C.string_at(text.value, tl.value)
+            self._lib.pgx_free(text)
+            if data:
+                yield data
+
+    def write(self, path: str) -> int:
+        """the lines not handed out yet to `path` (the whole sg_edges_list on a fresh graph; an empty graph writes an empty file); returns the bytes written"""
+        n = 0
+        with open(path, "wb") as f:
+            for piece in self.text():
+                f.write(piece)
+                n += len(piece)
+        return n
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _lib.check(self._lib.pgx_sgraph_free(h), "pgx_sgraph_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def string_graph(records, min_len: int = 4000, min_idt: float = 96.0, device=None, piece: int = 0) -> StringGraph:
+    """The string graph of `records` (OVLP_DTYPE) in one call: a graph-mode dedup stream fed the records (in pieces of `piece`, 0: one
+    feed), then DedupStream.string_graph.  The stream is closed; the graph stays."""
+    recs = np.ascontiguousarray(records, OVLP_DTYPE)
+    piece = piece or max(len(recs), 1)
+    with DedupStream(device=device, graph_ready=True) as ds:
+        for a in range(0, len(recs), piece):
+            ds.feed(recs[a:a + piece])
+        return ds.string_graph(min_len, min_idt)
+
+
+def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None) -> dict:
+    """cat ovlp*.dat | shmr_sgraph > sg_edges_list: the files through a graph-mode DedupStream piece by piece, the graph, its text to
+    out_path.  Returns the graph's statistics."""
+    _lib.init(device)
+    if isinstance(ovlp_paths, (str, bytes)):
+        ovlp_paths = [ovlp_paths]
+    piece = dedup_piece_records()
+    with DedupStream(device=device, graph_ready=True) as ds:
+        for p in ovlp_paths:
+            with open(p, "rb") as f:
+                while True:
+                    recs = np.fromfile(f, dtype=OVLP_DTYPE, count=piece)
+                    if len(recs):
+                        ds.feed(recs)
+                    if len(recs) < piece:
+                        break
+        with ds.string_graph(min_len, min_idt) as g:
+            g.write(out_path)
+            return g.stats
 
 
 def shmr_dedup(ovlp_paths, out_path: str | None = None, device=None):
