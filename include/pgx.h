@@ -63,7 +63,7 @@ void pgx_free(void *p);              /* releases any host array returned by this
 /* per-kernel device time (HIP events on the library's stream), accumulated since the last reset.
  * names: "sketch", "sketch_general", "sketch_redo", "sketch_nreads", "sketch_gather", "pack", "reduce", "count", "pairs", "replay_dense" / "replay_rows" / "replay_update" (k_eval, k_eval_rows, k_update of the device replay; only with PGX_REPLAY_TIMING=1), "align" (k_align_ph), "align1" (k_align1: launches of
  * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map", "sgraph" (the string graph: build and text; its parts also as "sgraph_edges", "sgraph_adj", "sgraph_tr", "sgraph_spur",
- * "sgraph_best", "sgraph_text"). */
+ * "sgraph_best", "sgraph_text"), "unitigs" (its parts: "unitigs_links", "unitigs_rank", "unitigs_paths", "unitigs_text"). */
 int pgx_timing_get(const char *kernel, double *total_ms, uint64_t *launches, uint64_t *units);
 void pgx_timing_reset(void);
 /* HBM ledger: JSON text of the library's device memory -- live bytes, bytes held in the block cache, and the live bytes BY OWNER (seqdb,
@@ -339,6 +339,54 @@ int pgx_sgraph_stats(const pgx_sgraph *g, pgx_sgraph_stats_t *out);
 int pgx_sgraph_edges(const pgx_sgraph *g, uint64_t first, uint64_t n, pgx_sgraph_edge *out);
 int pgx_sgraph_text(pgx_sgraph *g, uint64_t max_lines, char **text, size_t *text_len, int *done);
 int pgx_sgraph_free(pgx_sgraph *g);
+
+/* ---- unitigs (phase 1 of unitig construction in py/scripts/ovlp_to_graph.py: identify_simple_paths, :1033-1144): every maximal simple
+ * path of the string graph's G edges as one unitig, and the `simple` lines of utg_data (:1478-1487).  Only edges of type G take part;
+ * a node (rid, end) is simple when its G in-degree and out-degree are both 1.
+ *   linear    every G edge that leaves a non-simple node starts a unitig; it follows the single out-edge of each simple node it reaches
+ *             and ends at the first non-simple node (which may be the start node: s == t, not circular).
+ *   circular  what no such start reaches lies on rings of simple nodes: a ring is one unitig, cut at the tail of its edge with the
+ *             smallest creation index; its path is closed (the first node again at the end).
+ *   fields    length = the sum of |sp - tp|, score = the sum of the edges' scores; via = the path's SECOND node (the script's via is the
+ *             second or the second-to-last node, whichever of a path and its reverse it happens to walk: it varies with the hash seed,
+ *             as do the order of the unitigs and the place where a ring is opened).
+ *   order     every directed G edge lies in exactly one unitig (a path and its reverse are two); unitigs are numbered, and lines written,
+ *             in ascending creation index of their first edge.
+ *   line      "s via t simple length score n0~n1~...~nk\n", node names as in sg_edges_list ("%09d" of the signed rid, ":B" or ":E").
+ * The later phases of the script (unitig spurs, duplicate paths, compound paths, contig paths) pop from sets of strings and are not offered.
+ * All on the device, on the library's stream: one sort per edge list, list ranking by pointer doubling (a logarithmic number of passes
+ * whatever the length of a path), no launch per unitig.  Device memory is booked as "unitigs", time as "unitigs" with the parts
+ * "unitigs_links", "unitigs_rank", "unitigs_paths", "unitigs_text".
+ *   pgx_sgraph_unitigs : of a built graph, whose edges stay on the device.  The unitigs own their arrays: the graph may be freed first.
+ *   pgx_unitigs_build  : of n host edge records in creation order (a parsed sg_edges_list, whoever wrote it); `type` != PGX_SGRAPH_G
+ *                        is ignored.  Fewer than 2^31 records.
+ *     Both check what the script asserts, and answer PGX_EINVAL with a message that names the smallest offending edge index: a G edge
+ *     with v_rid == w_rid; a G edge whose (v, w) an earlier G edge has; a G edge (v, w) without its reverse (rev w, rev v) among the
+ *     G edges.  PGX_ENOMEM: no device memory (the graph stays usable).  No G edge: zero unitigs, an empty text.
+ *   pgx_unitigs_stats  : the counts.            pgx_unitigs_table : n table entries from unitig `first` on.
+ *   pgx_unitigs_paths  : n entries of the path array from entry `first` on (g_edges in all): creation indices of the edges, unitig after
+ *                        unitig; unitig u's are [table[u].first, + table[u].n_edges).
+ *   pgx_unitigs_text   : the lines in pieces, with pgx_sgraph_text's conventions (at most max_lines (> 0) and 2^24 lines per call).
+ *   pgx_unitigs_free   : releases them (NULL is accepted).
+ * After pgx_shutdown every call but pgx_unitigs_free answers PGX_ESTATE, as for graphs. */
+typedef struct {
+  uint32_t s_rid, t_rid, via_rid;              /* first, last and second node of the path */
+  uint8_t s_end, t_end, via_end, circular;     /* 0: B, 1: E; circular: a ring of simple nodes */
+  uint32_t n_edges;
+  uint64_t first;                              /* offset of its first edge in the path array */
+  int64_t length, score;
+} pgx_unitig;
+typedef struct {
+  uint64_t g_edges, unitigs, circular, longest_edges;
+} pgx_unitigs_stats_t;
+typedef struct pgx_unitigs pgx_unitigs;
+int pgx_sgraph_unitigs(pgx_sgraph *g, pgx_unitigs **out);
+int pgx_unitigs_build(const pgx_sgraph_edge *edges, uint64_t n, pgx_unitigs **out);
+int pgx_unitigs_stats(const pgx_unitigs *u, pgx_unitigs_stats_t *out);
+int pgx_unitigs_table(const pgx_unitigs *u, uint64_t first, uint64_t n, pgx_unitig *out);
+int pgx_unitigs_paths(const pgx_unitigs *u, uint64_t first, uint64_t n, uint32_t *edge_index);
+int pgx_unitigs_text(pgx_unitigs *u, uint64_t max_lines, char **text, size_t *text_len, int *done);
+int pgx_unitigs_free(pgx_unitigs *u);
 
 /* ---- reads -> contigs mapping (replaces shmr_map, src/shmr_map.c:48-161,163-373) ----
  * The reads' shimmer-pair map is built exactly as in the overlap stage (build_map with -t/-c/-n/-M); the reference

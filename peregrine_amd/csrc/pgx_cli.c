@@ -393,7 +393,30 @@ static void *dedup_read_piece(void *arg) {
 struct sgraph_opts {
   long long min_len;
   double min_idt;
+  const char *utg;   /* --utg FILE: the unitigs' lines go there (NULL: none are made) */
 };
+/* the unitigs of g as text to the file at path */
+static int write_unitigs(const char *tool, pgx_sgraph *g, const char *path, size_t piece) {
+  FILE *f = fopen(path, "wb");
+  if (!f) {
+    perror(path);
+    return 1;
+  }
+  pgx_unitigs *u = NULL;
+  int rc = 0;
+  if (pgx_sgraph_unitigs(g, &u)) rc = fail(tool, "pgx_sgraph_unitigs");
+  for (int done = rc; !done;) {
+    char *text = NULL;
+    size_t len = 0;
+    if (pgx_unitigs_text(u, piece, &text, &len, &done)) rc = fail(tool, "pgx_unitigs_text");
+    else if (fwrite(text, 1, len, f) != len) rc = 1, perror(path);
+    pgx_free(text);
+    if (rc) break;
+  }
+  pgx_unitigs_free(u);
+  if (fclose(f) && !rc) rc = 1, perror(path);
+  return rc;
+}
 static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg) {
   size_t piece = (size_t)16 << 20;
   const char *pe = getenv("PGX_DEDUP_PIECE");
@@ -447,6 +470,7 @@ static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg
     pgx_free(text);
     if (rc) break;
   }
+  if (g && sg->utg && !rc) rc = write_unitigs(tool, g, sg->utg, piece);
   pgx_sgraph_free(g);
   for (int done = !graph || sg || !ds || rc; !done;) {
     char *text = NULL;
@@ -467,10 +491,10 @@ static int main_dedup(int argc, char **argv) {
   return dedup_stdin("shmr_dedup", graph, NULL);
 }
 
-/* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
+/* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] [--utg FILE] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
  * --disable_chimer_bridge_removal and without --lfc -- the only setting offered */
 static int main_sgraph(int argc, char **argv) {
-  struct sgraph_opts o = {4000, 96.0};
+  struct sgraph_opts o = {4000, 96.0, NULL};
   for (int i = 1; i < argc; ++i) {
     const char *a = argv[i], *v = NULL;
     const int len_opt = strncmp(a, "--min_len", 9) == 0 && (a[9] == 0 || a[9] == '='), idt_opt = strncmp(a, "--min_idt", 9) == 0 && (a[9] == 0 || a[9] == '=');
@@ -483,6 +507,12 @@ static int main_sgraph(int argc, char **argv) {
         fprintf(stderr, "shmr_sgraph: %.9s needs a number\n", a);
         return 2;
       }
+    } else if (strncmp(a, "--utg", 5) == 0 && (a[5] == 0 || a[5] == '=')) {
+      o.utg = a[5] ? a + 6 : (i + 1 < argc ? argv[++i] : NULL);
+      if (!o.utg || !*o.utg) {
+        fprintf(stderr, "shmr_sgraph: --utg needs a file name\n");
+        return 2;
+      }
     } else if (strcmp(a, "--lfc") == 0) {
       fprintf(stderr, "shmr_sgraph: --lfc is not offered (pg_run.py leaves it off)\n");
       return 2;
@@ -493,7 +523,7 @@ static int main_sgraph(int argc, char **argv) {
                       "compare with ovlp_to_graph.py --disable_chimer_bridge_removal\n");
       return 2;
     } else {
-      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal] < ovlp.dat > sg_edges_list\n");
+      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal] [--utg FILE] < ovlp.dat > sg_edges_list\n");
       return 2;
     }
   }

@@ -119,4 +119,7 @@ struct pgx_dedup_stream {
 namespace pgx {
 // the end of a graph-mode stream: the store compacted against the final bitmap (sets s->draining; from then on feeds are refused)
 void graph_compact(pgx_dedup_stream *s);
+// a live graph's edge records on the device, in creation order with their final types (pgx_sgraph.hip; `who` names the caller in the
+// error a freed context gives); what reads them runs on ctx().stream, behind the build
+const pgx_sgraph_edge *sgraph_device_edges(const pgx_sgraph *g, const char *who, uint64_t *n);
 }  // namespace pgx

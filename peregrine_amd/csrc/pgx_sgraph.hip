@@ -580,6 +580,11 @@ void require_graph(const pgx_sgraph *g, const char *who) {
   PGX_REQUIRE(!g->shut && ctx().ready, PGX_ESTATE, "%s: pgx_shutdown ran while the graph was alive (free it)", who);
 }
 }  // namespace
+const pgx_sgraph_edge *sgraph_device_edges(const pgx_sgraph *g, const char *who, uint64_t *n) {
+  require_graph(g, who);
+  *n = g->st.edges;
+  return g->edges.p;
+}
 }  // namespace pgx
 
 extern "C" int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min_idt, uint32_t flags, pgx_sgraph **out) {

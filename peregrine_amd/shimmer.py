@@ -427,6 +427,12 @@ class StringGraph:
         _lib.check(self._lib.pgx_sgraph_edges(self._handle("pgx_sgraph_edges"), int(first), int(n), _ptr(out)), "pgx_sgraph_edges")
         return out
 
+    def unitigs(self) -> "Unitigs":
+        """the maximal simple paths of the graph's G edges (pgx_sgraph_unitigs); they own their arrays: the graph may be closed first"""
+        u = C.c_void_p()
+        _lib.check(self._lib.pgx_sgraph_unitigs(self._handle("pgx_sgraph_unitigs"), C.byref(u)), "pgx_sgraph_unitigs")
+        return Unitigs(u)
+
     def text(self, max_lines: int = 1 << 20):
         """sg_edges_list, as bytes of at most max_lines lines each (the next lines: a second iteration goes on where the first stopped)"""
         done = C.c_int(0)
@@ -477,9 +483,114 @@ def string_graph(records, min_len: int = 4000, min_idt: float = 96.0, device=Non
         return ds.string_graph(min_len, min_idt)
 
 
-def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None) -> dict:
+UNITIG_DTYPE = np.dtype([("s_rid", "<u4"), ("t_rid", "<u4"), ("via_rid", "<u4"), ("s_end", "u1"), ("t_end", "u1"), ("via_end", "u1"), ("circular", "u1"),
+                         ("n_edges", "<u4"), ("pad", "<u4"), ("first", "<u8"), ("length", "<i8"), ("score", "<i8")])   # pgx_unitig
+_UNITIGS_STATS = ("g_edges", "unitigs", "circular", "longest_edges")   # pgx_unitigs_stats_t
+
+
+class Unitigs:
+    """The unitigs of a string graph (StringGraph.unitigs, shimmer.unitigs): every maximal simple path of the G edges, numbered by the
+    creation index of its first edge.  `via` is always the path's second node and a ring of simple nodes is cut at the tail of its
+    smallest-index edge -- the two places where ovlp_to_graph.py's own choice varies with the hash seed."""
+
+    def __init__(self, handle):
+        self._lib = _lib.load()
+        self.h = handle
+        st = (C.c_uint64 * len(_UNITIGS_STATS))()
+        _lib.check(self._lib.pgx_unitigs_stats(self.h, st), "pgx_unitigs_stats")
+        self.stats = dict(zip(_UNITIGS_STATS, (int(v) for v in st)))
+
+    def _handle(self, who):
+        if not self.h:
+            raise _lib.PgxError(f"{who}: the unitigs are closed")
+        return self.h
+
+    def table(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """UNITIG_DTYPE records: unitig u's edges are paths()[first : first + n_edges]"""
+        n = self.stats["unitigs"] - first if n is None else n
+        out = np.zeros(n, UNITIG_DTYPE)
+        _lib.check(self._lib.pgx_unitigs_table(self._handle("pgx_unitigs_table"), int(first), int(n), _ptr(out)), "pgx_unitigs_table")
+        return out
+
+    def paths(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """the creation indices of the G edges, unitig after unitig"""
+        n = self.stats["g_edges"] - first if n is None else n
+        out = np.zeros(n, np.uint32)
+        _lib.check(self._lib.pgx_unitigs_paths(self._handle("pgx_unitigs_paths"), int(first), int(n), _ptr(out)), "pgx_unitigs_paths")
+        return out
+
+    def text(self, max_lines: int = 1 << 20):
+        """the `simple` lines of utg_data, as bytes of at most max_lines lines each (the next lines: a second iteration goes on where the first stopped)"""
+        done = C.c_int(0)
+        while not done.value:
+            text, tl = C.c_void_p(), C.c_size_t(0)
+            _lib.check(self._lib.pgx_unitigs_text(self._handle("pgx_unitigs_text"), int(max_lines), C.byref(text), C.byref(tl), C.byref(done)), "pgx_unitigs_text")
+            data = C.string_at(text.value, tl.value)
+            self._lib.pgx_free(text)
+            if data:
+                yield data
+
+    def write(self, path: str) -> int:
+        """the lines not handed out yet to `path`; returns the bytes written"""
+        n = 0
+        with open(path, "wb") as f:
+            for piece in self.text():
+                f.write(piece)
+                n += len(piece)
+        return n
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _lib.check(self._lib.pgx_unitigs_free(h), "pgx_unitigs_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def unitigs(edges, device=None) -> Unitigs:
+    """The unitigs of edge records (SGRAPH_EDGE_DTYPE) in creation order, e.g. read_sg_edges_list's; only `type` 0 (G) takes part"""
+    _lib.init(device)
+    e = np.ascontiguousarray(edges, SGRAPH_EDGE_DTYPE)
+    u = C.c_void_p()
+    _lib.check(_lib.load().pgx_unitigs_build(_ptr(e) if len(e) else None, len(e), C.byref(u)), "pgx_unitigs_build")
+    return Unitigs(u)
+
+
+SGRAPH_TYPE_OTHER = 4   # read_sg_edges_list's `type` of a C edge (the script's chimer bridge step): any value but 0 is "not G"
+
+
+def read_sg_edges_list(path: str) -> np.ndarray:
+    """A sg_edges_list file, whoever wrote it, as edge records (SGRAPH_EDGE_DTYPE) in the file's order: 'v w rid sp tp score identity type'
+    with the types G, TR, S, R and C (C becomes SGRAPH_TYPE_OTHER)."""
+    code = {b"G": 0, b"TR": 1, b"S": 2, b"R": 3, b"C": SGRAPH_TYPE_OTHER}
+    with open(path, "rb") as f:
+        lines = f.read().split(b"\n")
+    lines = [ln for ln in lines if ln.strip()]
+    out = np.zeros(len(lines), SGRAPH_EDGE_DTYPE)
+    for k, ln in enumerate(lines):
+        f = ln.split()
+        if len(f) != 8 or f[7] not in code or f[0][-2:] not in (b":B", b":E") or f[1][-2:] not in (b":B", b":E"):
+            raise ValueError(f"{path}: line {k + 1} is not a sg_edges_list line: {ln[:80]!r}")
+        t = round(float(f[6]) * 10)
+        out[k] = (int(f[0][:-2]) & 0xFFFFFFFF, int(f[1][:-2]) & 0xFFFFFFFF, int(f[2]) & 0xFFFFFFFF, int(f[3]), int(f[4]), f[0][-1:] == b"E", f[1][-1:] == b"E",
+                  code[f[7]], 0, int(f[5]), t)
+    return out
+
+
+def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None, utg_path: str | None = None) -> dict:
     """cat ovlp*.dat | shmr_sgraph > sg_edges_list: the files through a graph-mode DedupStream piece by piece, the graph, its text to
-    out_path.  Returns the graph's statistics."""
+    out_path (and, with utg_path, its unitigs' lines to that file).  Returns the graph's statistics."""
     _lib.init(device)
     if isinstance(ovlp_paths, (str, bytes)):
         ovlp_paths = [ovlp_paths]
@@ -495,6 +606,9 @@ def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float =
                         break
         with ds.string_graph(min_len, min_idt) as g:
             g.write(out_path)
+            if utg_path is not None:
+                with g.unitigs() as u:
+                    u.write(utg_path)
             return g.stats
 
 
