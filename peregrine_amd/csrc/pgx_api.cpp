@@ -14,7 +14,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include "pgx_internal.h"
+#include "pgx_text.h"
 
 namespace pgx {
 
@@ -491,6 +491,48 @@ void timing_flush() {
     (void)hipEventDestroy(p.e1);
   }
   g_pending.swap(later);
+}
+
+// ---- device text on its way to the caller (pgx_text.h) -----------------------------------------------------------
+constexpr size_t PIN_BYTES = (size_t)8 << 20;
+// `total` bytes of device text to host memory through the two pinned buffers: the copy of one piece runs while the host moves the last
+void text_download(TextStage &ts, const char *d_text, size_t total, char *dst) {
+  hipStream_t st = ctx().stream;
+  for (int k = 0; k < 2; ++k)
+    if (!ts.pin[k]) {
+      PGX_HIP(hipHostMalloc((void **)&ts.pin[k], PIN_BYTES, hipHostMallocDefault));
+      PGX_HIP(hipEventCreateWithFlags(&ts.ev[k], hipEventDisableTiming));
+    }
+  const size_t np = (total + PIN_BYTES - 1) / PIN_BYTES;
+  for (size_t i = 0; i <= np; ++i) {
+    if (i < np) {
+      PGX_HIP(hipMemcpyAsync(ts.pin[i & 1], d_text + i * PIN_BYTES, std::min(PIN_BYTES, total - i * PIN_BYTES), hipMemcpyDeviceToHost, st));
+      PGX_HIP(hipEventRecord(ts.ev[i & 1], st));
+    }
+    if (i > 0) {
+      const size_t j = i - 1;
+      PGX_HIP(hipEventSynchronize(ts.ev[j & 1]));
+      memcpy(dst + j * PIN_BYTES, ts.pin[j & 1], std::min(PIN_BYTES, total - j * PIN_BYTES));
+    }
+  }
+}
+
+void TextStage::drop() {
+  for (int k = 0; k < 2; ++k) {
+    if (pin[k]) (void)hipHostFree(pin[k]);
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+    pin[k] = nullptr, ev[k] = nullptr;
+  }
+}
+
+void text_hand_out(TextStage &ts, const char *d_text, size_t total, char **text, size_t *text_len) {
+  if (total == 0) {
+    *text = caller_text("", 0);
+    return;
+  }
+  *text = caller_text(nullptr, total);   // (the caller's from here: released by its pgx_free also when the download fails)
+  *text_len = total;
+  text_download(ts, d_text, total, *text);
 }
 
 // ---- files -----------------------------------------------------------------------------------------------

@@ -395,6 +395,31 @@ struct sgraph_opts {
   double min_idt;
   const char *utg;   /* --utg FILE: the unitigs' lines go there (NULL: none are made) */
 };
+/* What every hand-out of text ends with: the status of the call `what` reported, or its text written to f (named fname in the
+ * complaint); the text is freed either way.  Returns the exit code so far. */
+static int put_text(const char *tool, const char *what, int status, char *text, size_t len, FILE *f, const char *fname) {
+  int rc = 0;
+  if (status) rc = fail(tool, what);
+  else if (fwrite(text, 1, len, f) != len) rc = 1, perror(fname);
+  pgx_free(text);
+  return rc;
+}
+/* the three hand-outs that go piece by piece, with one signature (obj: the handle) */
+typedef int (*next_text_fn)(void *obj, uint64_t max_lines, char **text, size_t *len, int *done);
+static int next_sgraph_text(void *g, uint64_t n, char **text, size_t *len, int *done) { return pgx_sgraph_text((pgx_sgraph *)g, n, text, len, done); }
+static int next_unitigs_text(void *u, uint64_t n, char **text, size_t *len, int *done) { return pgx_unitigs_text((pgx_unitigs *)u, n, text, len, done); }
+static int next_drain_text(void *s, uint64_t n, char **text, size_t *len, int *done) { return pgx_dedup_drain((pgx_dedup_stream *)s, n, text, len, done); }
+/* all the text obj still has, in pieces of `piece` lines, to f */
+static int write_pieces(const char *tool, const char *what, next_text_fn next, void *obj, size_t piece, FILE *f, const char *fname) {
+  for (int done = 0; !done;) {
+    char *text = NULL;
+    size_t len = 0;
+    const int status = next(obj, piece, &text, &len, &done);
+    const int rc = put_text(tool, what, status, text, len, f, fname);
+    if (rc) return rc;
+  }
+  return 0;
+}
 /* the unitigs of g as text to the file at path */
 static int write_unitigs(const char *tool, pgx_sgraph *g, const char *path, size_t piece) {
   FILE *f = fopen(path, "wb");
@@ -405,14 +430,7 @@ static int write_unitigs(const char *tool, pgx_sgraph *g, const char *path, size
   pgx_unitigs *u = NULL;
   int rc = 0;
   if (pgx_sgraph_unitigs(g, &u)) rc = fail(tool, "pgx_sgraph_unitigs");
-  for (int done = rc; !done;) {
-    char *text = NULL;
-    size_t len = 0;
-    if (pgx_unitigs_text(u, piece, &text, &len, &done)) rc = fail(tool, "pgx_unitigs_text");
-    else if (fwrite(text, 1, len, f) != len) rc = 1, perror(path);
-    pgx_free(text);
-    if (rc) break;
-  }
+  else rc = write_pieces(tool, "pgx_unitigs_text", next_unitigs_text, u, piece, f, path);
   pgx_unitigs_free(u);
   if (fclose(f) && !rc) rc = 1, perror(path);
   return rc;
@@ -451,9 +469,8 @@ static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg
     }
     char *text = NULL;
     size_t len = 0;
-    if (pgx_dedup_feed(ds, (const pgx_ovlp *)bufs[k], got / sizeof(pgx_ovlp), &text, &len)) rc = fail(tool, "pgx_dedup_feed");
-    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("stdout");
-    pgx_free(text);
+    const int status = pgx_dedup_feed(ds, (const pgx_ovlp *)bufs[k], got / sizeof(pgx_ovlp), &text, &len);
+    rc = put_text(tool, "pgx_dedup_feed", status, text, len, stdout, "stdout");
     if (rc) {
       if (more) pthread_join(th, NULL);
       break;
@@ -462,24 +479,10 @@ static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg
   }
   pgx_sgraph *g = NULL;
   if (sg && ds && !rc && pgx_sgraph_build(ds, sg->min_len, sg->min_idt, 0, &g)) rc = fail(tool, "pgx_sgraph_build");
-  for (int done = !g; !done;) {
-    char *text = NULL;
-    size_t len = 0;
-    if (pgx_sgraph_text(g, piece, &text, &len, &done)) rc = fail(tool, "pgx_sgraph_text");
-    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("stdout");
-    pgx_free(text);
-    if (rc) break;
-  }
+  if (g) rc = write_pieces(tool, "pgx_sgraph_text", next_sgraph_text, g, piece, stdout, "stdout");
   if (g && sg->utg && !rc) rc = write_unitigs(tool, g, sg->utg, piece);
   pgx_sgraph_free(g);
-  for (int done = !graph || sg || !ds || rc; !done;) {
-    char *text = NULL;
-    size_t len = 0;
-    if (pgx_dedup_drain(ds, piece, &text, &len, &done)) rc = fail(tool, "pgx_dedup_drain");
-    else if (fwrite(text, 1, len, stdout) != len) rc = 1, perror("stdout");
-    pgx_free(text);
-    if (rc) break;
-  }
+  if (graph && !sg && ds && !rc) rc = write_pieces(tool, "pgx_dedup_drain", next_drain_text, ds, piece, stdout, "stdout");
   if (ds) pgx_dedup_close(ds, NULL, NULL);
   free(bufs[0]), free(bufs[1]);
   return rc;

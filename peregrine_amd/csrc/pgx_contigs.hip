@@ -45,8 +45,6 @@ constexpr int OVERHANG = 500;   // stitching_overhang_size (path_to_contig.py:9)
 constexpr int BAND = 100;       // (path_to_contig.py:84)
 constexpr uint32_t TILE = 4096, STITCH_THREADS = 256;
 
-inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
 struct Seg {
   uint64_t dst;   // offset in the concatenated output
   uint64_t src;   // offset of its first byte from the byte source's base (modulo 2^64, as a byte view counts)

@@ -10,13 +10,10 @@
 // addressing, one 64-bit word per slot) says which of them are new, and the text lines are written on the device too (k_line_len ->
 // exclusive scan -> k_format) and leave through a pinned staging buffer.
 
-#include <mutex>
-
 #include "pgx_dedup_rows.h"
 
 namespace pgx {
 namespace {
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 __global__ void k_pair_keys(const pgx_ovlp *__restrict__ in, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ idx) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -166,9 +163,8 @@ __global__ void k_line_len(const Row *__restrict__ rows, uint32_t m, uint64_t *_
   }
   len[j] = l;
 }
-// A workgroup formats a tile of rows into LDS at the offsets the scan gives (a lane per row), then streams the tile out with 16-byte
-// stores.  The tile sits in LDS at the global address's offset within 16 bytes, so the aligned chunks line up on both sides; the head
-// and tail bytes that share a chunk with the neighbouring tiles go out byte by byte.
+// A workgroup formats a tile of rows into LDS at the offsets the scan gives (a lane per row), then streams the tile out (tile_out: the
+// tile sits in LDS at the global address's offset within 16 bytes).
 constexpr uint32_t FMT_TILE = 256;
 __global__ __launch_bounds__(FMT_TILE) void k_format(const Row *__restrict__ rows, const uint64_t *__restrict__ off, uint32_t m,
                                                      char *__restrict__ text) {
@@ -181,13 +177,7 @@ __global__ __launch_bounds__(FMT_TILE) void k_format(const Row *__restrict__ row
     if (r.m_size != 0) format_row<true>(r, tile + pad + (uint32_t)(off[j] - base));
   }
   __syncthreads();
-  char *g = text + base - pad;  // 16-byte aligned; g[k] <-> tile[k] for k in [lo, hi)
-  const uint32_t lo = pad, hi = pad + (uint32_t)(end - base);
-  const uint32_t body_lo = min(hi, (lo + 15u) & ~15u), body_hi = max(body_lo, hi & ~15u);
-  for (uint32_t k = lo + threadIdx.x; k < body_lo; k += FMT_TILE) g[k] = tile[k];
-  for (uint32_t k = body_lo + threadIdx.x * 16u; k < body_hi; k += FMT_TILE * 16u)
-    *reinterpret_cast<uint4 *>(g + k) = *reinterpret_cast<const uint4 *>(tile + k);
-  for (uint32_t k = body_hi + threadIdx.x; k < hi; k += FMT_TILE) g[k] = tile[k];
+  tile_out<FMT_TILE>(tile, text + base - pad, pad, pad + (uint32_t)(end - base));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -262,19 +252,8 @@ using namespace pgx;
 namespace pgx {
 namespace {
 constexpr uint64_t SEEN_MIN_CAP = 1ULL << 16;
-constexpr size_t PIN_BYTES = (size_t)8 << 20;
-std::mutex g_streams_mu;
-std::vector<pgx_dedup_stream *> g_streams;   // the open ones
-
-void stream_drop_device_state(pgx_dedup_stream *s) {
-  s->tab.release();
-  s->bits.release(), s->store.release();
-  s->stage.drop();
-}
-ShutdownHook g_streams_hook([] {
-  std::lock_guard<std::mutex> lk(g_streams_mu);
-  for (pgx_dedup_stream *s : g_streams) stream_drop_device_state(s), s->shut = true;
-});
+LiveSet<pgx_dedup_stream> g_streams;   // the open ones
+ShutdownHook g_streams_hook([] { g_streams.shutdown(); });
 
 void seen_alloc(DevBuf<unsigned long long> &tab, uint64_t cap) {
   MemTag tag("dedup");
@@ -299,8 +278,6 @@ void seen_reserve(pgx_dedup_stream *s, uint64_t more) {
   s->tab = std::move(bigger);   // (the old table goes back to the block cache: one stream, so its next user comes after the rehash)
   s->cap = cap;
 }
-
-char *empty_text() { return caller_text("", 0); }
 
 // The text the device wrote for m rows: `total` bytes, row j's line at off[j] -- none for the n_special rows with m_size == 0
 struct DeviceLines {
@@ -359,12 +336,7 @@ void rows_to_text(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *
   char *d_text = ws<char>("dd.text", total);
   hipLaunchKernelGGL(k_format, dim3(cdiv(m, FMT_TILE)), dim3(FMT_TILE), 0, st, d_rows, d_off, m, d_text);
   PGX_HIP(hipGetLastError());
-  if (n_special == 0) {
-    *text = caller_text(nullptr, total);   // (the caller's from here: released by its pgx_free also when the download fails)
-    *text_len = total;
-    text_download(s->stage, d_text, total, *text);
-    return;
-  }
+  if (n_special == 0) return text_hand_out(s->stage, d_text, total, text, text_len);
   // rows with m_size == 0 (no real overlap record has one): the host's snprintf prints them, spliced in at their place
   const DeviceLines dev{s, d_off, d_text, total, n_special};
   const std::string out = rows_to_host_text(d_rows, m, &dev);
@@ -375,7 +347,6 @@ void rows_to_text(pgx_dedup_stream *s, const Row *d_rows, uint32_t m, uint32_t *
 constexpr uint64_t BITS_MIN_WORDS = 2;   // doubled up to the word of the largest marked id: 2^27 words = 512 MiB at most
 constexpr uint64_t STORE_MIN_ROWS = 1ULL << 16;
 constexpr uint32_t COMPACT_ROWS = 1u << 22;    // rows per piece of the final compaction (its scratch: 192 MiB)
-constexpr uint64_t DRAIN_MAX_LINES = 1ULL << 24;   // lines per drain call at most (their text: < 2.4 GB)
 
 template <typename T>
 void graph_alloc(DevBuf<T> &buf, uint64_t count, const char *what) {
@@ -487,27 +458,20 @@ void feed_device(pgx_dedup_stream *s, const pgx_ovlp *d_in, size_t n, char **tex
   Row *d_rows = nullptr;
   const uint32_t m = first_wins_rows(d_in, n, s, d_m, &d_rows);
   if (m && s->graph) graph_take(s, d_rows, m);   // the lines wait for the end of the stream (pgx_dedup_drain)
-  if (m == 0 || s->graph) *text = empty_text(), *text_len = 0;
+  if (m == 0 || s->graph) text_hand_out(s->stage, nullptr, 0, text, text_len);
   else rows_to_text(s, d_rows, m, d_m, text, text_len);
 }
 
-// The epilogue of the entry points that hand out text: guarded(), and after an error the call's text is freed (*text was cleared before
-// anything could throw: what it holds now is this call's own allocation) and the stream that body left in `blame`, if any, has failed.
+// text_call for a stream's entry points: after an error the stream that body left in `blame`, if any, has failed
 template <class F>
-int text_call(char **text, size_t *text_len, F &&body) {
+int stream_text_call(char **text, size_t *text_len, int *done, F &&body) {
   pgx_dedup_stream *blame = nullptr;
-  const int rc = guarded([&] { return body(blame); });
-  if (rc != PGX_OK) {
-    if (blame) blame->failed = true;
-    if (text && *text) free(*text), *text = nullptr;
-    if (text_len) *text_len = 0;
-  }
+  const int rc = text_call(text, text_len, done, [&] { return body(blame); });
+  if (rc != PGX_OK && blame) blame->failed = true;
   return rc;
 }
 int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, size_t *text_len, bool on_device, const char *who) {
-  if (text) *text = nullptr;   // the outputs first: the caller's variables may hold anything, and the error paths free only what
-  if (text_len) *text_len = 0;  // this call put there
-  return text_call(text, text_len, [&](pgx_dedup_stream *&blame) {
+  return stream_text_call(text, text_len, nullptr, [&](pgx_dedup_stream *&blame) {
     blame = s;
     PGX_REQUIRE(s && text && text_len && (n == 0 || recs), PGX_EARG, "%s: null argument", who);
     PGX_REQUIRE(!s->shut, PGX_ESTATE, "%s: pgx_shutdown ran while the stream was open (close it)", who);
@@ -520,7 +484,7 @@ int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, s
     require_ready();
     PGX_REQUIRE(n < (1ULL << 31), PGX_EARG, "too many records for one feed");
     if (n == 0) {
-      *text = empty_text();
+      text_hand_out(s->stage, nullptr, 0, text, text_len);
       return (int)PGX_OK;
     }
     const pgx_ovlp *d_in = recs;
@@ -535,36 +499,6 @@ int feed_any(pgx_dedup_stream *s, const pgx_ovlp *recs, size_t n, char **text, s
   });
 }
 }  // namespace
-
-// `total` bytes of device text to host memory through the two pinned buffers: the copy of one piece runs while the host moves the last
-void text_download(TextStage &ts, const char *d_text, size_t total, char *dst) {
-  hipStream_t st = ctx().stream;
-  for (int k = 0; k < 2; ++k)
-    if (!ts.pin[k]) {
-      PGX_HIP(hipHostMalloc((void **)&ts.pin[k], PIN_BYTES, hipHostMallocDefault));
-      PGX_HIP(hipEventCreateWithFlags(&ts.ev[k], hipEventDisableTiming));
-    }
-  const size_t np = (total + PIN_BYTES - 1) / PIN_BYTES;
-  for (size_t i = 0; i <= np; ++i) {
-    if (i < np) {
-      PGX_HIP(hipMemcpyAsync(ts.pin[i & 1], d_text + i * PIN_BYTES, std::min(PIN_BYTES, total - i * PIN_BYTES), hipMemcpyDeviceToHost, st));
-      PGX_HIP(hipEventRecord(ts.ev[i & 1], st));
-    }
-    if (i > 0) {
-      const size_t j = i - 1;
-      PGX_HIP(hipEventSynchronize(ts.ev[j & 1]));
-      memcpy(dst + j * PIN_BYTES, ts.pin[j & 1], std::min(PIN_BYTES, total - j * PIN_BYTES));
-    }
-  }
-}
-
-void TextStage::drop() {
-  for (int k = 0; k < 2; ++k) {
-    if (pin[k]) (void)hipHostFree(pin[k]);
-    if (ev[k]) (void)hipEventDestroy(ev[k]);
-    pin[k] = nullptr, ev[k] = nullptr;
-  }
-}
 
 // the end of the stream: one stable pass over the store against the FINAL bitmap, piece by piece and in place (a piece's kept rows go
 // to a scratch buffer and from there to the store's front, which the pass has read already)
@@ -632,8 +566,7 @@ static int open_any(uint64_t expected_pairs, pgx_dedup_stream **out, bool graph,
     seen_alloc(s->tab, cap);
     s->cap = cap;
     pgx::sync();
-    std::lock_guard<std::mutex> lk(g_streams_mu);
-    g_streams.push_back(s);
+    g_streams.add(s);
     *out = s;
   });
   if (rc) delete s;
@@ -667,8 +600,8 @@ static void require_graph_stream(const pgx_dedup_stream *s, const char *who) {
 static void drain_lines(pgx_dedup_stream *s, uint64_t max_lines, char **text, size_t *text_len, int *done) {
   KernelTimer tm("dedup", std::min<uint64_t>(max_lines, s->store_n - s->drained));
   if (!s->draining) graph_compact(s);
-  const uint32_t m = (uint32_t)std::min<uint64_t>({max_lines, s->store_n - s->drained, DRAIN_MAX_LINES});
-  if (m == 0) *text = empty_text();
+  const uint32_t m = (uint32_t)text_lines(max_lines, s->store_n - s->drained);
+  if (m == 0) text_hand_out(s->stage, nullptr, 0, text, text_len);
   else {
     uint32_t *d_m = ws<uint32_t>("dd.m", 2);
     PGX_HIP(hipMemsetAsync(d_m, 0, 2 * sizeof(uint32_t), ctx().stream));
@@ -683,10 +616,7 @@ static void drain_lines(pgx_dedup_stream *s, uint64_t max_lines, char **text, si
 }
 
 extern "C" int pgx_dedup_drain(pgx_dedup_stream *s, uint64_t max_lines, char **text, size_t *text_len, int *done) {
-  if (text) *text = nullptr;
-  if (text_len) *text_len = 0;
-  if (done) *done = 0;
-  return text_call(text, text_len, [&](pgx_dedup_stream *&blame) {
+  return stream_text_call(text, text_len, done, [&](pgx_dedup_stream *&blame) {
     require_graph_stream(s, "pgx_dedup_drain");
     PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_dedup_drain: null argument or max_lines == 0");
     blame = s;   // the checks passed: an error from here on is the stream's
@@ -712,13 +642,6 @@ extern "C" int pgx_dedup_close(pgx_dedup_stream *s, uint64_t *n_records, uint64_
   }
   if (n_records) *n_records = s->n_records;
   if (n_unique) *n_unique = s->n_unique;
-  {
-    std::lock_guard<std::mutex> lk(g_streams_mu);
-    for (size_t i = 0; i < g_streams.size(); ++i)
-      if (g_streams[i] == s) g_streams.erase(g_streams.begin() + i), i = g_streams.size();
-    if (!s->shut && ctx().ready) (void)hipStreamSynchronize(ctx().stream);
-    stream_drop_device_state(s);
-  }
-  delete s;
+  g_streams.destroy(s);
   return PGX_OK;
 }

@@ -1,7 +1,7 @@
-// pgx_dedup_rows.h -- what pgx_dedup.hip shares with the stages that read a graph-mode stream's rows in HBM (pgx_sgraph.hip): the row,
-// the stream, the pieces of a text line as glibc prints them, and the pinned staging that device text leaves through.
+// pgx_dedup_rows.h -- what pgx_dedup.hip shares with the stages that read a graph-mode stream's rows in HBM (pgx_sgraph.hip): the row
+// and the stream.  (The pieces of a text line and the staging that device text leaves through: pgx_text.h.)
 #pragma once
-#include "pgx_internal.h"
+#include "pgx_text.h"
 
 namespace pgx {
 // a line of the dedup text before it is printed (shmr_dedup.c:44-89: the coordinates already transformed)
@@ -11,77 +11,6 @@ struct Row {
   uint32_t a_bgn, a_end, rlen0, strand, b_bgn, b_end, rlen1, type;
 };
 
-// ---- text: "%d", "%09d", "%u", "%0.1f" as glibc prints them -------------------------------------------------------------------------------
-__device__ inline uint32_t div10(uint32_t v) { return __umulhi(v, 0xCCCCCCCDu) >> 3; }
-__device__ inline uint64_t div10(uint64_t v) { return __umul64hi(v, 0xCCCCCCCCCCCCCCCDULL) >> 3; }
-__device__ inline uint32_t ndigits(uint32_t v) {
-  return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8
-         : v < 1000000000u ? 9 : 10;
-}
-// WRITE == false: only counts (k_line_len and k_format share one definition of a line)
-template <bool WRITE>
-struct LineOut {
-  char *p;
-  uint32_t n;
-  __device__ void ch(char c) {
-    if (WRITE) p[n] = c;
-    ++n;
-  }
-  __device__ void u32(uint32_t v, uint32_t min_digits = 1) {
-    const uint32_t nd = max(ndigits(v), min_digits);
-    if (WRITE)
-      for (uint32_t k = nd; k-- > 0;) {
-        const uint32_t q = div10(v);
-        p[n + k] = (char)('0' + (v - q * 10u));
-        v = q;
-      }
-    n += nd;
-  }
-  __device__ void u64(uint64_t v) {
-    uint32_t nd = 1;
-    for (uint64_t t = div10(v); t; t = div10(t)) ++nd;
-    if (WRITE)
-      for (uint32_t k = nd; k-- > 0;) {
-        const uint64_t q = div10(v);
-        p[n + k] = (char)('0' + (uint32_t)(v - q * 10u));
-        v = q;
-      }
-    n += nd;
-  }
-  __device__ void i32(int32_t v) {  // %d
-    if (v < 0) ch('-'), u32(0u - (uint32_t)v);
-    else u32((uint32_t)v);
-  }
-  __device__ void rid(int32_t v) {  // %09d: zero padding to width 9, the sign counts
-    if (v < 0) ch('-'), u32(0u - (uint32_t)v, 8);
-    else u32((uint32_t)v, 9);
-  }
-  // %0.1f of a finite double: the EXACT binary value M * 2^e rounded to one decimal, ties to even, in integer arithmetic
-  __device__ void f1(double x) {
-    const uint64_t bits = (uint64_t)__double_as_longlong(x);
-    if (bits >> 63) ch('-');  // also for a value that rounds to 0.0: "-0.0"
-    const uint32_t ex = (uint32_t)(bits >> 52) & 0x7FFu;
-    uint64_t M = bits & ((1ULL << 52) - 1);
-    int e = -1074;
-    if (ex) M |= 1ULL << 52, e = (int)ex - 1075;
-    const uint64_t m10 = M * 10u;  // < 2^57; tenths = m10 * 2^e
-    uint64_t t;
-    if (e >= 0) {
-      t = m10 << min(e, 6);  // (not reached: |err_est| < 2^38, so e <= -15)
-    } else if (-e >= 58) {
-      t = 0;  // m10 < 2^57 <= half a unit
-    } else {
-      const int s = -e;
-      t = m10 >> s;
-      const uint64_t rem = m10 & ((1ULL << s) - 1), half = 1ULL << (s - 1);
-      if (rem > half || (rem == half && (t & 1))) ++t;
-    }
-    const uint64_t whole = div10(t);
-    u64(whole);
-    ch('.');
-    ch((char)('0' + (uint32_t)(t - whole * 10u)));
-  }
-};
 // the three IEEE double operations of shmr_dedup.c:89-90 in that order, never contracted
 __device__ inline double err_est_of(int32_t dist, int32_t m_size) {
 #pragma clang fp contract(off)
@@ -90,14 +19,6 @@ __device__ inline double err_est_of(int32_t dist, int32_t m_size) {
   return 100.0 - q;
 }
 
-// Device text on its way to host memory: two pinned buffers, the copy of one piece runs while the host moves the last.  Owned by whoever
-// hands out text (a dedup stream, a string graph); made at the first download.
-struct TextStage {
-  char *pin[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  void drop();   // frees the buffers and events (idempotent)
-};
-void text_download(TextStage &ts, const char *d_text, size_t total, char *dst);
 }  // namespace pgx
 
 struct pgx_dedup_stream {
@@ -114,6 +35,11 @@ struct pgx_dedup_stream {
   pgx::DevBuf<pgx::Row> store;           // rows of the `overlap` lines between two unmarked reads, in stream order; store.n is the capacity
   uint64_t store_n = 0, drained = 0;   // rows held; rows handed out as text
   bool released = false;            // the last line was handed out and the store went back: nothing left for pgx_sgraph_build
+  void drop_device_state() {
+    tab.release();
+    bits.release(), store.release();
+    stage.drop();
+  }
 };
 
 namespace pgx {

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -63,6 +64,13 @@ int guarded(F &&body) {
     return PGX_ENOMEM;
   }
   return PGX_OK;
+}
+// The code a stage's builder answers for the Fail its passes threw: a HIP error that is the device running out of memory becomes
+// PGX_ENOMEM with "<who>: no device memory for the <what> of <n> <units>" (whatever the builder read is untouched).
+inline int build_fail_code(const Fail &f, const char *who, const char *what, uint64_t n, const char *units) {
+  if (f.code != PGX_EHIP || hipGetLastError() != hipErrorOutOfMemory) return f.code;
+  set_error("%s: no device memory for the %s of %llu %s", who, what, (unsigned long long)n, units);
+  return PGX_ENOMEM;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -144,6 +152,40 @@ struct DevBuf {
   }
 };
 inline void sync() { PGX_HIP(hipStreamSynchronize(ctx().stream)); }
+// blocks of b for a items; LAUNCH: a thread per item, 256 to a block, on the `st` of the scope it is used in
+static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+#define LAUNCH(kernel, n, ...) hipLaunchKernelGGL(kernel, dim3(pgx::cdiv((n), 256)), dim3(256), 0, st, __VA_ARGS__)
+
+// The live objects of one kind that keep device state between calls and are handed to the caller (dedup streams, string graphs,
+// unitigs).  T supplies `bool shut` and drop_device_state(), which releases what the object holds on the device (idempotent).  The
+// shutdown rule: pgx_shutdown drops the device state of every member and marks it `shut` -- the caller still holds the handle, whose
+// entry points then refuse it, and destroys it whenever it likes.  Use: LiveSet<T> g_set; ShutdownHook g_hook([] { g_set.shutdown(); });
+template <class T>
+class LiveSet {
+  std::mutex mu;
+  std::vector<T *> live;
+
+ public:
+  void add(T *t) {
+    std::lock_guard<std::mutex> lk(mu);
+    live.push_back(t);
+  }
+  void shutdown() {
+    std::lock_guard<std::mutex> lk(mu);
+    for (T *t : live) t->drop_device_state(), t->shut = true;
+  }
+  // the end of t (a member or not): what is enqueued may still read its buffers, so the stream drains first
+  void destroy(T *t) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      for (size_t i = 0; i < live.size(); ++i)
+        if (live[i] == t) live.erase(live.begin() + i), i = live.size();
+      if (!t->shut && ctx().ready) (void)hipStreamSynchronize(ctx().stream);
+      t->drop_device_state();
+    }
+    delete t;
+  }
+};
 inline double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // grow-only named device buffers that persist across calls (hipMalloc/hipFree are synchronous and slow)

@@ -14,8 +14,6 @@
 
 namespace pgx {
 
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
 // =========================================================================================================
 // minimizer hash (src/mm_sketch.c:23-32), 64-bit form for any k <= 28
 // =========================================================================================================

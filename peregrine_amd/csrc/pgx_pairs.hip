@@ -18,8 +18,6 @@
 
 namespace pgx {
 
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
 namespace {
 __global__ void k_split_counts(const pgx_mm_count *__restrict__ in, size_t n, uint64_t *__restrict__ mer,
                                uint32_t *__restrict__ cnt) {

@@ -12,7 +12,6 @@
 
 namespace pgx {
 namespace {
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // ---------------------------------------------------------------------------------------------------------
 // shared: shimmer / count files of a prefix (shimmer4py.c:94-116, shmr_map.c:285-345), read lengths by rid

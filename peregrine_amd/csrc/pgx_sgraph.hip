@@ -12,8 +12,6 @@
 // No result depends on the order in which atomics land: they only count (degrees, statistics), claim hash slots whose layout no answer
 // depends on, or take a minimum.
 
-#include <mutex>
-
 #include "pgx_dedup_rows.h"
 
 using pgx::Row;
@@ -21,7 +19,6 @@ typedef pgx_sgraph_edge Edge;
 
 namespace pgx {
 namespace {
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 constexpr uint32_t FUZZ = 500;
 constexpr uint32_t DEG_CAP = 256;      // most out-edges of a node whose transitive reduction runs from LDS
@@ -369,32 +366,20 @@ __global__ void k_sg_finish(Edge *__restrict__ edges, const uint8_t *__restrict_
 // ---------------------------------------------------------------------------------------------------------
 // the text: '%s %s %s %5d %5d %5d %5.2f %s' (ovlp_to_graph.py:901), a line per edge
 // ---------------------------------------------------------------------------------------------------------
-template <bool WRITE>
-__device__ inline void pad_i64(LineOut<WRITE> &o, int64_t v, uint32_t width) {   // %<width>d
-  const bool neg = v < 0;
-  const uint64_t a = neg ? 0ULL - (uint64_t)v : (uint64_t)v;
-  uint32_t nd = neg ? 2 : 1;
-  for (uint64_t t = div10(a); t; t = div10(t)) ++nd;
-  for (; nd < width; ++nd) o.ch(' ');
-  if (neg) o.ch('-');
-  o.u64(a);
-}
 constexpr uint32_t SG_MAXLINE = 112;   // 13 + 13 + 11 + 11 + 11 + 20 + 17 + 2 + 7 blanks + '\n' = 106
 template <bool WRITE>
 __device__ inline uint32_t format_edge(const Edge &e, char *dst) {
   LineOut<WRITE> o{dst, 0};
-  o.rid((int32_t)e.v_rid), o.ch(':'), o.ch(e.v_end ? 'E' : 'B'), o.ch(' ');
-  o.rid((int32_t)e.w_rid), o.ch(':'), o.ch(e.w_end ? 'E' : 'B'), o.ch(' ');
+  o.node(e.v_rid, e.v_end), o.ch(' ');
+  o.node(e.w_rid, e.w_end), o.ch(' ');
   o.rid((int32_t)e.label_rid), o.ch(' ');
-  pad_i64(o, e.sp, 5), o.ch(' ');
-  pad_i64(o, e.tp, 5), o.ch(' ');
-  pad_i64(o, e.score, 5), o.ch(' ');
+  o.i64(e.sp, 5), o.ch(' ');
+  o.i64(e.tp, 5), o.ch(' ');
+  o.i64(e.score, 5), o.ch(' ');
   {   // %5.2f of the number the line's `%0.1f` text parses to: the tenths with one more 0
     const bool neg = e.idt_tenths < 0;
     const uint64_t a = neg ? 0ULL - (uint64_t)e.idt_tenths : (uint64_t)e.idt_tenths, whole = div10(a);
-    uint32_t nd = neg ? 5 : 4;
-    for (uint64_t t = div10(whole); t; t = div10(t)) ++nd;
-    for (; nd < 5; ++nd) o.ch(' ');
+    for (uint32_t nd = ndigits(whole, neg ? 5 : 4); nd < 5; ++nd) o.ch(' ');
     if (neg) o.ch('-');
     o.u64(whole), o.ch('.'), o.ch((char)('0' + (uint32_t)(a - whole * 10u))), o.ch('0');
   }
@@ -410,7 +395,7 @@ __global__ void k_sg_line_len(const Edge *__restrict__ edges, uint32_t m, uint64
   if (j > m) return;
   len[j] = j < m ? format_edge<false>(edges[j], nullptr) : 0;   // len[m] = 0: the exclusive scan's last entry is the total
 }
-// as k_format of pgx_dedup.hip: a workgroup formats a tile of lines into LDS at the scan's offsets, then streams the tile out with 16-byte stores
+// as k_format of pgx_dedup.hip: a workgroup formats a tile of lines into LDS at the scan's offsets, then streams the tile out (tile_out)
 constexpr uint32_t SG_TILE = 256;
 __global__ __launch_bounds__(SG_TILE) void k_sg_format(const Edge *__restrict__ edges, const uint64_t *__restrict__ off, uint32_t m, char *__restrict__ text) {
   __shared__ __attribute__((aligned(16))) char tile[SG_TILE * SG_MAXLINE + 16];
@@ -419,13 +404,7 @@ __global__ __launch_bounds__(SG_TILE) void k_sg_format(const Edge *__restrict__ 
   const uint32_t pad = (uint32_t)((uintptr_t)(text + base) & 15u);
   if (j < m) format_edge<true>(edges[j], tile + pad + (uint32_t)(off[j] - base));
   __syncthreads();
-  char *g = text + base - pad;
-  const uint32_t lo = pad, hi = pad + (uint32_t)(end - base);
-  const uint32_t body_lo = min(hi, (lo + 15u) & ~15u), body_hi = max(body_lo, hi & ~15u);
-  for (uint32_t k = lo + threadIdx.x; k < body_lo; k += SG_TILE) g[k] = tile[k];
-  for (uint32_t k = body_lo + threadIdx.x * 16u; k < body_hi; k += SG_TILE * 16u)
-    *reinterpret_cast<uint4 *>(g + k) = *reinterpret_cast<const uint4 *>(tile + k);
-  for (uint32_t k = body_hi + threadIdx.x; k < hi; k += SG_TILE) g[k] = tile[k];
+  tile_out<SG_TILE>(tile, text + base - pad, pad, pad + (uint32_t)(end - base));
 }
 }  // namespace
 }  // namespace pgx
@@ -438,29 +417,22 @@ struct pgx_sgraph {
   uint64_t cursor = 0;           // edges handed out as text
   TextStage stage;
   bool shut = false;             // pgx_shutdown ran: the device state is gone
+  void drop_device_state() {
+    edges.release();
+    stage.drop();
+  }
 };
 
 namespace pgx {
 namespace {
-constexpr uint64_t TEXT_MAX_LINES = 1ULL << 24;
-std::mutex g_graphs_mu;
-std::vector<pgx_sgraph *> g_graphs;
-void graph_drop_device_state(pgx_sgraph *g) {
-  g->edges.release();
-  g->stage.drop();
-}
-ShutdownHook g_graphs_hook([] {
-  std::lock_guard<std::mutex> lk(g_graphs_mu);
-  for (pgx_sgraph *g : g_graphs) graph_drop_device_state(g), g->shut = true;
-});
+LiveSet<pgx_sgraph> g_graphs;
+ShutdownHook g_graphs_hook([] { g_graphs.shutdown(); });
 
 uint32_t deg_cap() {   // PGX_SGRAPH_DEG_MAX: a test hook that shrinks the LDS path so that small graphs reach the other one
   const char *v = getenv("PGX_SGRAPH_DEG_MAX");
   const long c = v ? atol(v) : (long)DEG_CAP;
   return (uint32_t)std::min<long>(std::max<long>(c, 0), (long)DEG_CAP);
 }
-
-#define LAUNCH(kernel, n, ...) hipLaunchKernelGGL(kernel, dim3(cdiv((n), 256)), dim3(256), 0, st, __VA_ARGS__)
 
 // the passes over n_rows rows at d_rows; fills g
 void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min_idt, pgx_sgraph *g) {
@@ -573,7 +545,6 @@ void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min
   g->st.edges = n_e, g->st.nodes = n_nodes, g->st.max_out_degree = max_deg, g->st.spur_candidates = n_cand;
   g->st.n_g = by_type[T_G], g->st.n_tr = by_type[T_TR], g->st.n_s = by_type[T_S], g->st.n_r = by_type[T_R];
 }
-#undef LAUNCH
 
 void require_graph(const pgx_sgraph *g, const char *who) {
   PGX_REQUIRE(g, PGX_EARG, "%s: null argument", who);
@@ -612,16 +583,11 @@ extern "C" int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min
       g = new pgx_sgraph;
       build_graph(s->store.p, (uint32_t)s->store_n, min_len, min_idt, g);
     } catch (const Fail &f) {
-      code = f.code;
-      if (code == PGX_EHIP && hipGetLastError() == hipErrorOutOfMemory) {   // (the stream is untouched: pgx_dedup_drain still has its rows)
-        set_error("pgx_sgraph_build: no device memory for the graph of %llu rows", (unsigned long long)s->store_n);
-        code = PGX_ENOMEM;
-      }
+      code = build_fail_code(f, "pgx_sgraph_build", "graph", s->store_n, "rows");   // (the stream is untouched: pgx_dedup_drain still has its rows)
     }
     timing_flush();
     if (code != PGX_OK) return code;
-    std::lock_guard<std::mutex> lk(g_graphs_mu);
-    g_graphs.push_back(g);
+    g_graphs.add(g);
     *out = g;
     return (int)PGX_OK;
   });
@@ -648,21 +614,18 @@ extern "C" int pgx_sgraph_edges(const pgx_sgraph *g, uint64_t first, uint64_t n,
 }
 
 extern "C" int pgx_sgraph_text(pgx_sgraph *g, uint64_t max_lines, char **text, size_t *text_len, int *done) {
-  if (text) *text = nullptr;
-  if (text_len) *text_len = 0;
-  if (done) *done = 0;
-  const int rc = guarded([&] {
+  return text_call(text, text_len, done, [&] {
     require_graph(g, "pgx_sgraph_text");
     PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_sgraph_text: null argument or max_lines == 0");
     hipStream_t st = ctx().stream;
-    const uint32_t m = (uint32_t)std::min<uint64_t>({max_lines, g->st.edges - g->cursor, TEXT_MAX_LINES});
+    const uint32_t m = (uint32_t)text_lines(max_lines, g->st.edges - g->cursor);
     if (m == 0) {
-      *text = caller_text("", 0);
+      text_hand_out(g->stage, nullptr, 0, text, text_len);
     } else {
       KernelTimer tm("sgraph", m), tm_text("sgraph_text", m);
       const Edge *edges = g->edges.p + g->cursor;
       uint64_t *d_off = ws<uint64_t>("sg.off", (size_t)m + 1), *d_len = ws<uint64_t>("sg.len", (size_t)m + 1);
-      hipLaunchKernelGGL(k_sg_line_len, dim3(cdiv((size_t)m + 1, 256)), dim3(256), 0, st, edges, m, d_len);
+      LAUNCH(k_sg_line_len, (size_t)m + 1, edges, m, d_len);
       exclusive_sum(d_len, d_off, (size_t)m + 1);
       uint64_t total = 0;
       PGX_HIP(hipMemcpyAsync(&total, d_off + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -670,30 +633,15 @@ extern "C" int pgx_sgraph_text(pgx_sgraph *g, uint64_t max_lines, char **text, s
       char *d_text = ws<char>("sg.text", total);
       hipLaunchKernelGGL(k_sg_format, dim3(cdiv(m, SG_TILE)), dim3(SG_TILE), 0, st, edges, d_off, m, d_text);
       PGX_HIP(hipGetLastError());
-      *text = caller_text(nullptr, total);
-      *text_len = total;
-      text_download(g->stage, d_text, total, *text);
+      text_hand_out(g->stage, d_text, total, text, text_len);
     }
     g->cursor += m;
     if (g->cursor == g->st.edges) *done = 1;
     timing_flush();
   });
-  if (rc != PGX_OK) {
-    if (text && *text) free(*text), *text = nullptr;
-    if (text_len) *text_len = 0;
-  }
-  return rc;
 }
 
 extern "C" int pgx_sgraph_free(pgx_sgraph *g) {
-  if (!g) return PGX_OK;
-  {
-    std::lock_guard<std::mutex> lk(g_graphs_mu);
-    for (size_t i = 0; i < g_graphs.size(); ++i)
-      if (g_graphs[i] == g) g_graphs.erase(g_graphs.begin() + i), i = g_graphs.size();
-    if (!g->shut && ctx().ready) (void)hipStreamSynchronize(ctx().stream);
-    graph_drop_device_state(g);
-  }
-  delete g;
+  if (g) g_graphs.destroy(g);
   return PGX_OK;
 }

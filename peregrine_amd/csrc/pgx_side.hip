@@ -22,8 +22,6 @@
 namespace pgx {
 namespace {
 
-inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
 __host__ __device__ inline uint64_t slot_bytes(uint64_t roff, uint32_t len) { return (((roff & 15u) + len + 15u) & ~15ULL) + 16u; }
 
 // ---- building the side store -------------------------------------------------------------------------------------------------------

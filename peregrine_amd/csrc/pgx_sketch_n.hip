@@ -37,8 +37,6 @@ namespace pgx {
 
 namespace {
 
-inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
 __device__ __forceinline__ uint64_t kmer_hash(uint64_t key, uint64_t mask) {   // src/mm_sketch.c:23-32
   key = (~key + (key << 21)) & mask;
   key = key ^ key >> 24;

@@ -17,15 +17,12 @@
 // pred, and a second ranking settles the rings like paths.
 // No result depends on the order in which atomics land: they take a minimum (the first offending edge) or count.
 
-#include <mutex>
-
 #include "pgx_dedup_rows.h"
 
 typedef pgx_sgraph_edge Edge;
 
 namespace pgx {
 namespace {
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 // ---------------------------------------------------------------------------------------------------------
@@ -203,27 +200,18 @@ __global__ void k_ut_firsts(const uint64_t *__restrict__ off, uint32_t n_u, pgx_
 // ---------------------------------------------------------------------------------------------------------
 constexpr uint32_t PIECE_MAX = 128;   // 5 names of <= 13, " simple ", two numbers of <= 20, 4 blanks, 2 separators = 119
 template <bool WRITE>
-__device__ inline void put_name(LineOut<WRITE> &o, uint32_t rid, uint32_t end) {
-  o.rid((int32_t)rid), o.ch(':'), o.ch(end ? 'E' : 'B');
-}
-template <bool WRITE>
-__device__ inline void put_i64(LineOut<WRITE> &o, int64_t v) {
-  if (v < 0) o.ch('-'), o.u64(0ULL - (uint64_t)v);
-  else o.u64((uint64_t)v);
-}
-template <bool WRITE>
 __device__ inline uint32_t format_piece(uint64_t slot, uint32_t u, uint64_t w, const pgx_unitig *__restrict__ tab, char *dst) {
   LineOut<WRITE> o{dst, 0};
   const uint64_t first = tab[u].first;
   const uint32_t n_edges = tab[u].n_edges;
   if (slot == first) {
     const pgx_unitig t = tab[u];
-    put_name(o, t.s_rid, t.s_end), o.ch(' '), put_name(o, t.via_rid, t.via_end), o.ch(' '), put_name(o, t.t_rid, t.t_end);
+    o.node(t.s_rid, t.s_end), o.ch(' '), o.node(t.via_rid, t.via_end), o.ch(' '), o.node(t.t_rid, t.t_end);
     for (const char *c = " simple "; *c; ++c) o.ch(*c);
-    put_i64(o, t.length), o.ch(' '), put_i64(o, t.score), o.ch(' ');
-    put_name(o, t.s_rid, t.s_end), o.ch('~');
+    o.i64(t.length), o.ch(' '), o.i64(t.score), o.ch(' ');
+    o.node(t.s_rid, t.s_end), o.ch('~');
   }
-  put_name(o, (uint32_t)(w >> 1), (uint32_t)(w & 1));
+  o.node((uint32_t)(w >> 1), (uint32_t)(w & 1));
   o.ch(slot == first + n_edges - 1 ? '\n' : '~');
   return o.n;
 }
@@ -239,7 +227,7 @@ __global__ void k_ut_line_off(const uint64_t *__restrict__ off, const uint64_t *
 // A workgroup per tile of UT_TILE output bytes: text[t * UT_TILE ..) holds the characters base + t * UT_TILE .. of the whole file.  The
 // pieces that cover the tile are found by binary search of the pieces' offsets (as k_stitch finds its segments); each is formatted whole
 // into LDS, which has PIECE_MAX bytes of margin on either side for the pieces that straddle the tile's ends, and the tile streams out
-// with 16-byte stores (text is 16-byte aligned and UT_TILE a multiple of 16).
+// (tile_out from its byte 0: text is 16-byte aligned, UT_TILE and PIECE_MAX are multiples of 16).
 constexpr uint32_t UT_TILE = 8192, UT_THREADS = 256;
 __global__ __launch_bounds__(UT_THREADS) void k_ut_format(const uint64_t *__restrict__ poff, const uint32_t *__restrict__ slot_u, const uint64_t *__restrict__ slot_w,
                                                           const pgx_unitig *__restrict__ tab, uint32_t m, uint64_t base, uint64_t total, char *__restrict__ text) {
@@ -258,11 +246,7 @@ __global__ __launch_bounds__(UT_THREADS) void k_ut_format(const uint64_t *__rest
     format_piece<true>(j, slot_u[j], slot_w[j], tab, tile + PIECE_MAX + (int64_t)(at - lo));   // (at - lo > -PIECE_MAX: the piece reaches past lo)
   }
   __syncthreads();
-  const uint32_t nb = (uint32_t)(hi - lo), body = nb & ~15u;
-  const char *src = tile + PIECE_MAX;
-  char *g = text + t0;
-  for (uint32_t k = threadIdx.x * 16u; k < body; k += UT_THREADS * 16u) *reinterpret_cast<uint4 *>(g + k) = *reinterpret_cast<const uint4 *>(src + k);
-  for (uint32_t k = body + threadIdx.x; k < nb; k += UT_THREADS) g[k] = src[k];
+  tile_out<UT_THREADS>(tile + PIECE_MAX, text + t0, 0, (uint32_t)(hi - lo));
 }
 }  // namespace
 }  // namespace pgx
@@ -280,23 +264,16 @@ struct pgx_unitigs {
   uint64_t cursor = 0;           // lines handed out as text
   TextStage stage;
   bool shut = false;
+  void drop_device_state() {
+    tab.release(), paths.release(), slot_u.release(), slot_w.release(), poff.release(), line_off.release();
+    stage.drop();
+  }
 };
 
 namespace pgx {
 namespace {
-constexpr uint64_t TEXT_MAX_LINES = 1ULL << 24;
-std::mutex g_ut_mu;
-std::vector<pgx_unitigs *> g_ut;
-void ut_drop_device_state(pgx_unitigs *u) {
-  u->tab.release(), u->paths.release(), u->slot_u.release(), u->slot_w.release(), u->poff.release(), u->line_off.release();
-  u->stage.drop();
-}
-ShutdownHook g_ut_hook([] {
-  std::lock_guard<std::mutex> lk(g_ut_mu);
-  for (pgx_unitigs *u : g_ut) ut_drop_device_state(u), u->shut = true;
-});
-
-#define LAUNCH(kernel, n, ...) hipLaunchKernelGGL(kernel, dim3(cdiv((n), 256)), dim3(256), 0, st, __VA_ARGS__)
+LiveSet<pgx_unitigs> g_ut;
+ShutdownHook g_ut_hook([] { g_ut.shutdown(); });
 
 // pointer doubling over pred until every edge has reached the start of its path, max_rounds at the most; returns the edges that still
 // have a pointer.  The answer is in *cur.
@@ -410,7 +387,6 @@ void build_unitigs(const Edge *d_edges, uint64_t n64, pgx_unitigs *u) {
   PGX_REQUIRE(h[2] == 0, PGX_EHIP, "pgx_unitigs: %u edges found no place in a path (a bug)", h[2]);
   u->st.unitigs = n_u, u->st.circular = h[0], u->st.longest_edges = h[1];
 }
-#undef LAUNCH
 
 void require_unitigs(const pgx_unitigs *u, const char *who) {
   PGX_REQUIRE(u, PGX_EARG, "%s: null argument", who);
@@ -435,16 +411,11 @@ int build_entry(const char *who, pgx_unitigs **out, EdgesFn &&edges) {
       u = new pgx_unitigs;
       build_unitigs(d_edges, n, u);
     } catch (const Fail &f) {
-      code = f.code;
-      if (code == PGX_EHIP && hipGetLastError() == hipErrorOutOfMemory) {
-        set_error("%s: no device memory for the unitigs of %llu edges", who, (unsigned long long)n);
-        code = PGX_ENOMEM;
-      }
+      code = build_fail_code(f, who, "unitigs", n, "edges");
     }
     timing_flush();
     if (code != PGX_OK) return code;
-    std::lock_guard<std::mutex> lk(g_ut_mu);
-    g_ut.push_back(u);
+    g_ut.add(u);
     *out = u;
     return (int)PGX_OK;
   });
@@ -501,16 +472,13 @@ extern "C" int pgx_unitigs_paths(const pgx_unitigs *u, uint64_t first, uint64_t 
 }
 
 extern "C" int pgx_unitigs_text(pgx_unitigs *u, uint64_t max_lines, char **text, size_t *text_len, int *done) {
-  if (text) *text = nullptr;
-  if (text_len) *text_len = 0;
-  if (done) *done = 0;
-  const int rc = guarded([&] {
+  return text_call(text, text_len, done, [&] {
     require_unitigs(u, "pgx_unitigs_text");
     PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_unitigs_text: null argument or max_lines == 0");
     hipStream_t st = ctx().stream;
-    const uint64_t nl = std::min<uint64_t>({max_lines, u->st.unitigs - u->cursor, TEXT_MAX_LINES});
+    const uint64_t nl = text_lines(max_lines, u->st.unitigs - u->cursor);
     if (nl == 0) {
-      *text = caller_text("", 0);
+      text_hand_out(u->stage, nullptr, 0, text, text_len);
     } else {
       KernelTimer tm("unitigs", nl), tm_text("unitigs_text", nl);
       MemTag tag("unitigs");
@@ -523,30 +491,15 @@ extern "C" int pgx_unitigs_text(pgx_unitigs *u, uint64_t max_lines, char **text,
       hipLaunchKernelGGL(k_ut_format, dim3(cdiv(total, UT_TILE)), dim3(UT_THREADS), 0, st, u->poff.p, u->slot_u.p, u->slot_w.p, u->tab.p, (uint32_t)u->st.g_edges,
                          range[0], total, d_text);
       PGX_HIP(hipGetLastError());
-      *text = caller_text(nullptr, total);
-      *text_len = total;
-      text_download(u->stage, d_text, total, *text);
+      text_hand_out(u->stage, d_text, total, text, text_len);
     }
     u->cursor += nl;
     if (u->cursor == u->st.unitigs) *done = 1;
     timing_flush();
   });
-  if (rc != PGX_OK) {
-    if (text && *text) free(*text), *text = nullptr;
-    if (text_len) *text_len = 0;
-  }
-  return rc;
 }
 
 extern "C" int pgx_unitigs_free(pgx_unitigs *u) {
-  if (!u) return PGX_OK;
-  {
-    std::lock_guard<std::mutex> lk(g_ut_mu);
-    for (size_t i = 0; i < g_ut.size(); ++i)
-      if (g_ut[i] == u) g_ut.erase(g_ut.begin() + i), i = g_ut.size();
-    if (!u->shut && ctx().ready) (void)hipStreamSynchronize(ctx().stream);
-    ut_drop_device_state(u);
-  }
-  delete u;
+  if (u) g_ut.destroy(u);
   return PGX_OK;
 }

@@ -32,6 +32,26 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _take_text(name, call) -> bytes:
+    """The text an entry point hands out: call(text, text_len) makes the C call `name` with the two by reference; the bytes are copied
+    and the C string goes back (pgx_free)."""
+    text, tl = C.c_void_p(), C.c_size_t(0)
+    _lib.check(call(C.byref(text), C.byref(tl)), name)
+    data = C.string_at(text.value, tl.value)
+    _lib.load().pgx_free(text)
+    return data
+
+
+def _text_pieces(fn, name, handle, max_lines):
+    """The piece loop of pgx_dedup_drain / pgx_sgraph_text / pgx_unitigs_text: the next lines as bytes of at most max_lines lines each, until
+    the call says done.  handle(name) answers the live handle before every call (or raises: the object was closed meanwhile)."""
+    done = C.c_int(0)
+    while not done.value:
+        data = _take_text(name, lambda text, tl: fn(handle(name), int(max_lines), text, tl, C.byref(done)))
+        if data:
+            yield data
+
+
 class ResidentDB:
     """A read database uploaded once to HBM (pgx_seqdb)."""
 
@@ -237,11 +257,8 @@ class ResidentDB:
         rows = np.ascontiguousarray(rows, _lib.TILE_ROW_DTYPE)
         n_ctg = int(rows["ctg"].max()) + 1 if len(rows) else 0
         off = np.zeros(n_ctg + 1, np.uint64)
-        text, tl = C.c_void_p(), C.c_uint64(0)
-        _lib.check(self._lib.pgx_contigs_resident(self.h, _ptr(rows), len(rows), n_ctg, C.byref(text), _ptr(off), C.byref(tl)),
-                   "pgx_contigs_resident")
-        data = C.string_at(text.value, tl.value)
-        self._lib.pgx_free(text)
+        data = _take_text("pgx_contigs_resident",
+                          lambda text, tl: self._lib.pgx_contigs_resident(self.h, _ptr(rows), len(rows), n_ctg, text, _ptr(off), tl))
         return data, off
 
 
@@ -318,14 +335,14 @@ class DedupStream:
         name = "pgx_dedup_open_graph" if graph_ready else "pgx_dedup_open"
         _lib.check(getattr(self._lib, name)(int(expected_pairs), C.byref(self.h)), name)
 
-    def _feed(self, fn, name, ptr, n) -> bytes:
+    def _handle(self, who):
         if not self.h:
-            raise _lib.PgxError(f"{name}: the stream is closed")
-        text, tl = C.c_void_p(), C.c_size_t(0)
-        _lib.check(fn(self.h, ptr, int(n), C.byref(text), C.byref(tl)), name)
-        data = C.string_at(text.value, tl.value)
-        self._lib.pgx_free(text)
-        return data
+            raise _lib.PgxError(f"{who}: the stream is closed")
+        return self.h
+
+    def _feed(self, fn, name, ptr, n) -> bytes:
+        h = self._handle(name)
+        return _take_text(name, lambda text, tl: fn(h, ptr, int(n), text, tl))
 
     def feed(self, records: np.ndarray) -> bytes:
         """records: ovlp_t records on the host (OVLP_DTYPE)"""
@@ -341,43 +358,28 @@ class DedupStream:
 
     def drain(self, max_lines: int = 1 << 20):
         """graph_ready streams, after the last feed: the kept lines in order, as bytes of at most max_lines lines each"""
-        done = C.c_int(0)
-        while not done.value:
-            if not self.h:
-                raise _lib.PgxError("pgx_dedup_drain: the stream is closed")
-            text, tl = C.c_void_p(), C.c_size_t(0)
-            _lib.check(self._lib.pgx_dedup_drain(self.h, int(max_lines), C.byref(text), C.byref(tl), C.byref(done)), "pgx_dedup_drain")
-            data = C.string_at(text.value, tl.value)
-            self._lib.pgx_free(text)
-            if data:
-                yield data
+        return _text_pieces(self._lib.pgx_dedup_drain, "pgx_dedup_drain", self._handle, max_lines)
 
     @property
     def stats(self) -> dict:
         """graph_ready streams: reads marked contained, lines kept (final once drain() has started), lines a plain stream writes"""
-        if not self.h:
-            raise _lib.PgxError("pgx_dedup_graph_stats: the stream is closed")
         nc, nk, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _lib.check(self._lib.pgx_dedup_graph_stats(self.h, C.byref(nc), C.byref(nk), C.byref(nt)), "pgx_dedup_graph_stats")
+        _lib.check(self._lib.pgx_dedup_graph_stats(self._handle("pgx_dedup_graph_stats"), C.byref(nc), C.byref(nk), C.byref(nt)), "pgx_dedup_graph_stats")
         return dict(contained_reads=int(nc.value), lines_kept=int(nk.value), lines_total=int(nt.value))
 
     def string_graph(self, min_len: int = 4000, min_idt: float = 96.0, chimer_bridge_removal: bool = False, lfc: bool = False) -> "StringGraph":
         """graph_ready streams, after the last feed: the string graph of the kept lines (pgx_sgraph_build), what ovlp_to_graph.py's
         generate_string_graph builds with --disable_chimer_bridge_removal and without --lfc.  Either option set is refused, not approximated.
         The stream can still be drained or closed; feeds are refused afterwards, as after a drain."""
-        if not self.h:
-            raise _lib.PgxError("pgx_sgraph_build: the stream is closed")
         flags = (SGRAPH_CHIMER_BRIDGE if chimer_bridge_removal else 0) | (SGRAPH_LFC if lfc else 0)
         g = C.c_void_p()
-        _lib.check(self._lib.pgx_sgraph_build(self.h, int(min_len), float(min_idt), flags, C.byref(g)), "pgx_sgraph_build")
+        _lib.check(self._lib.pgx_sgraph_build(self._handle("pgx_sgraph_build"), int(min_len), float(min_idt), flags, C.byref(g)), "pgx_sgraph_build")
         return StringGraph(g)
 
     def close(self):
         """frees the stream; returns (records fed, lines written -- by a plain stream: a graph_ready one reports its kept lines in stats)"""
-        if not self.h:
-            raise _lib.PgxError("pgx_dedup_close: the stream is closed")
         nr, nu = C.c_uint64(0), C.c_uint64(0)
-        h, self.h = self.h, C.c_void_p()
+        h, self.h = self._handle("pgx_dedup_close"), C.c_void_p()
         _lib.check(self._lib.pgx_dedup_close(h, C.byref(nr), C.byref(nu)), "pgx_dedup_close")
         return int(nr.value), int(nu.value)
 
@@ -404,48 +406,29 @@ SGRAPH_TYPES = ("G", "TR", "S", "R")
 _SGRAPH_STATS = ("rows_in", "rows_pass", "edges", "nodes", "n_g", "n_tr", "n_s", "n_r", "max_out_degree", "spur_candidates")
 
 
-class StringGraph:
-    """The string graph of a graph-mode dedup stream (DedupStream.string_graph): its arrays live on the device and belong to this object,
-    whatever becomes of the stream."""
+class _DeviceText:
+    """A live device object that hands its result out as text: what StringGraph and Unitigs share.  A subclass names its C entry points
+    (_STATS_FN, _TEXT_FN, _FREE_FN), the fields of its statistics (_STATS) and how it is spoken of once closed (_CLOSED).
+    text(max_lines) yields the lines as bytes of at most max_lines lines each (the next lines: a second iteration goes on where the
+    first stopped); write(path) puts the lines not handed out yet into that file (an empty object writes an empty file) and returns the
+    bytes written.  close() may be called more than once."""
 
     def __init__(self, handle):
         self._lib = _lib.load()
         self.h = handle
-        st = (C.c_uint64 * len(_SGRAPH_STATS))()
-        _lib.check(self._lib.pgx_sgraph_stats(self.h, st), "pgx_sgraph_stats")
-        self.stats = dict(zip(_SGRAPH_STATS, (int(v) for v in st)))
+        st = (C.c_uint64 * len(self._STATS))()
+        _lib.check(getattr(self._lib, self._STATS_FN)(self.h, st), self._STATS_FN)
+        self.stats = dict(zip(self._STATS, (int(v) for v in st)))
 
     def _handle(self, who):
         if not self.h:
-            raise _lib.PgxError(f"{who}: the graph is closed")
+            raise _lib.PgxError(f"{who}: {self._CLOSED}")
         return self.h
 
-    def edges(self, first: int = 0, n: int | None = None) -> np.ndarray:
-        """edge records (SGRAPH_EDGE_DTYPE) in creation order: edge e's reverse is e ^ 1; `type` indexes SGRAPH_TYPES"""
-        n = self.stats["edges"] - first if n is None else n
-        out = np.zeros(n, SGRAPH_EDGE_DTYPE)
-        _lib.check(self._lib.pgx_sgraph_edges(self._handle("pgx_sgraph_edges"), int(first), int(n), _ptr(out)), "pgx_sgraph_edges")
-        return out
-
-    def unitigs(self) -> "Unitigs":
-        """the maximal simple paths of the graph's G edges (pgx_sgraph_unitigs); they own their arrays: the graph may be closed first"""
-        u = C.c_void_p()
-        _lib.check(self._lib.pgx_sgraph_unitigs(self._handle("pgx_sgraph_unitigs"), C.byref(u)), "pgx_sgraph_unitigs")
-        return Unitigs(u)
-
     def text(self, max_lines: int = 1 << 20):
-        """sg_edges_list, as bytes of at most max_lines lines each (the next lines: a second iteration goes on where the first stopped)"""
-        done = C.c_int(0)
-        while not done.value:
-            text, tl = C.c_void_p(), C.c_size_t(0)
-            _lib.check(self._lib.pgx_sgraph_text(self._handle("pgx_sgraph_text"), int(max_lines), C.byref(text), C.byref(tl), C.byref(done)), "pgx_sgraph_text")
-            data = C.string_at(text.value, tl.value)
-            self._lib.pgx_free(text)
-            if data:
-                yield data
+        return _text_pieces(getattr(self._lib, self._TEXT_FN), self._TEXT_FN, self._handle, max_lines)
 
     def write(self, path: str) -> int:
-        """the lines not handed out yet to `path` (the whole sg_edges_list on a fresh graph; an empty graph writes an empty file); returns the bytes written"""
         n = 0
         with open(path, "wb") as f:
             for piece in self.text():
@@ -456,7 +439,7 @@ class StringGraph:
     def close(self):
         h, self.h = self.h, C.c_void_p()
         if h:
-            _lib.check(self._lib.pgx_sgraph_free(h), "pgx_sgraph_free")
+            _lib.check(getattr(self._lib, self._FREE_FN)(h), self._FREE_FN)
 
     def __enter__(self):
         return self
@@ -470,6 +453,26 @@ class StringGraph:
             self.close()
         except Exception:
             pass
+
+
+class StringGraph(_DeviceText):
+    """The string graph of a graph-mode dedup stream (DedupStream.string_graph): its arrays live on the device and belong to this object,
+    whatever becomes of the stream.  Its text is sg_edges_list."""
+    _STATS_FN, _TEXT_FN, _FREE_FN = "pgx_sgraph_stats", "pgx_sgraph_text", "pgx_sgraph_free"
+    _STATS, _CLOSED = _SGRAPH_STATS, "the graph is closed"
+
+    def edges(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """edge records (SGRAPH_EDGE_DTYPE) in creation order: edge e's reverse is e ^ 1; `type` indexes SGRAPH_TYPES"""
+        n = self.stats["edges"] - first if n is None else n
+        out = np.zeros(n, SGRAPH_EDGE_DTYPE)
+        _lib.check(self._lib.pgx_sgraph_edges(self._handle("pgx_sgraph_edges"), int(first), int(n), _ptr(out)), "pgx_sgraph_edges")
+        return out
+
+    def unitigs(self) -> "Unitigs":
+        """the maximal simple paths of the graph's G edges (pgx_sgraph_unitigs); they own their arrays: the graph may be closed first"""
+        u = C.c_void_p()
+        _lib.check(self._lib.pgx_sgraph_unitigs(self._handle("pgx_sgraph_unitigs"), C.byref(u)), "pgx_sgraph_unitigs")
+        return Unitigs(u)
 
 
 def string_graph(records, min_len: int = 4000, min_idt: float = 96.0, device=None, piece: int = 0) -> StringGraph:
@@ -488,22 +491,13 @@ UNITIG_DTYPE = np.dtype([("s_rid", "<u4"), ("t_rid", "<u4"), ("via_rid", "<u4"),
 _UNITIGS_STATS = ("g_edges", "unitigs", "circular", "longest_edges")   # pgx_unitigs_stats_t
 
 
-class Unitigs:
+class Unitigs(_DeviceText):
     """The unitigs of a string graph (StringGraph.unitigs, shimmer.unitigs): every maximal simple path of the G edges, numbered by the
     creation index of its first edge.  `via` is always the path's second node and a ring of simple nodes is cut at the tail of its
-    smallest-index edge -- the two places where ovlp_to_graph.py's own choice varies with the hash seed."""
-
-    def __init__(self, handle):
-        self._lib = _lib.load()
-        self.h = handle
-        st = (C.c_uint64 * len(_UNITIGS_STATS))()
-        _lib.check(self._lib.pgx_unitigs_stats(self.h, st), "pgx_unitigs_stats")
-        self.stats = dict(zip(_UNITIGS_STATS, (int(v) for v in st)))
-
-    def _handle(self, who):
-        if not self.h:
-            raise _lib.PgxError(f"{who}: the unitigs are closed")
-        return self.h
+    smallest-index edge -- the two places where ovlp_to_graph.py's own choice varies with the hash seed.  Their text is the `simple`
+    lines of utg_data."""
+    _STATS_FN, _TEXT_FN, _FREE_FN = "pgx_unitigs_stats", "pgx_unitigs_text", "pgx_unitigs_free"
+    _STATS, _CLOSED = _UNITIGS_STATS, "the unitigs are closed"
 
     def table(self, first: int = 0, n: int | None = None) -> np.ndarray:
         """UNITIG_DTYPE records: unitig u's edges are paths()[first : first + n_edges]"""
@@ -518,44 +512,6 @@ class Unitigs:
         out = np.zeros(n, np.uint32)
         _lib.check(self._lib.pgx_unitigs_paths(self._handle("pgx_unitigs_paths"), int(first), int(n), _ptr(out)), "pgx_unitigs_paths")
         return out
-
-    def text(self, max_lines: int = 1 << 20):
-        """the `simple` lines of utg_data, as bytes of at most max_lines lines each (the next lines: a second iteration goes on where the first stopped)"""
-        done = C.c_int(0)
-        while not done.value:
-            text, tl = C.c_void_p(), C.c_size_t(0)
-            _lib.check(self._lib.pgx_unitigs_text(self._handle("pgx_unitigs_text"), int(max_lines), C.byref(text), C.byref(tl), C.byref(done)), "pgx_unitigs_text")
-            data = C.string_at(text.value, tl.value)
-            self._lib.pgx_free(text)
-            if data:
-                yield data
-
-    def write(self, path: str) -> int:
-        """the lines not handed out yet to `path`; returns the bytes written"""
-        n = 0
-        with open(path, "wb") as f:
-            for piece in self.text():
-                f.write(piece)
-                n += len(piece)
-        return n
-
-    def close(self):
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            _lib.check(self._lib.pgx_unitigs_free(h), "pgx_unitigs_free")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def unitigs(edges, device=None) -> Unitigs:
@@ -654,11 +610,9 @@ def shmr_map(ref_shimmer_prefix: str = "ref-L2", seqdb_prefix: str = "seq_datase
     reference's stdout text (bytes) and the number of lines."""
     _lib.init(device)
     p = _lib.MapParams(total_chunk, mychunk, mc_lower, mc_upper)
-    text, tl, nl = C.c_void_p(), C.c_size_t(0), C.c_uint64(0)
-    _lib.check(_lib.load().pgx_map_chunk(refdb_prefix.encode(), ref_shimmer_prefix.encode(), seqdb_prefix.encode(),
-                                         shimmer_prefix.encode(), C.byref(p), C.byref(text), C.byref(tl), C.byref(nl)), "pgx_map_chunk")
-    data = C.string_at(text.value, tl.value)
-    _lib.load().pgx_free(text)
+    nl = C.c_uint64(0)
+    data = _take_text("pgx_map_chunk", lambda text, tl: _lib.load().pgx_map_chunk(
+        refdb_prefix.encode(), ref_shimmer_prefix.encode(), seqdb_prefix.encode(), shimmer_prefix.encode(), C.byref(p), text, tl, C.byref(nl)))
     if out_path:
         with open(out_path, "wb") as f:
             f.write(data)
@@ -686,11 +640,9 @@ def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychu
     mc = np.ascontiguousarray(counts, MC_DTYPE)
     rl = np.ascontiguousarray(rlen_by_rid, np.uint32)
     p = _lib.MapParams(total_chunk, mychunk, mc_lower, mc_upper)
-    text, tl, nl = C.c_void_p(), C.c_size_t(0), C.c_uint64(0)
-    _lib.check(_lib.load().pgx_map(_ptr(rf), len(rf), _ptr(mm), len(mm), _ptr(mc), len(mc), _ptr(rl), len(rl), C.byref(p),
-                                   C.byref(text), C.byref(tl), C.byref(nl)), "pgx_map")
-    data = C.string_at(text.value, tl.value)
-    _lib.load().pgx_free(text)
+    nl = C.c_uint64(0)
+    data = _take_text("pgx_map", lambda text, tl: _lib.load().pgx_map(_ptr(rf), len(rf), _ptr(mm), len(mm), _ptr(mc), len(mc), _ptr(rl), len(rl),
+                                                                 C.byref(p), text, tl, C.byref(nl)))
     return data, int(nl.value)
 
 
