@@ -436,6 +436,55 @@ int pgx_contigs_resident(pgx_seqdb *db, const pgx_tile_row *rows, size_t n_rows,
                          uint64_t *text_len);
 int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const char *out_path, uint64_t *n_ctg, uint64_t *n_bases);
 
+/* ---- tiling paths (replaces py/scripts/graph_to_path.py, pg_run.py:355): from sg_edges_list, utg_data and ctg_paths to p_ctg_tiling_path
+ * and a_ctg_tiling_path, byte for byte the script's files, and to the same rows as pgx_tile_row ("tiling paths", states the rule).
+ *   pgx_sgraph_parse : a sg_edges_list file as edge records in the file's order, tokenised on the device (the file goes up in pieces of
+ *                      PGX_TILING_PIECE bytes, default and maximum 1 GiB, a test hook; a lane per line).  Blank lines are skipped; types
+ *                      other than G, TR, S, R become 4.  *edges and *idt_hundredths (may be NULL) are the caller's (pgx_free);
+ *                      idt_tenths is the identity's exact decimal rounded half to even.
+ *   pgx_tiling_build : sg_edges_list_fn, or a built graph g whose edges stay on the device (exactly one of the two), plus the texts of
+ *                      utg_data and ctg_paths.  The tiling paths own their arrays: the graph may be freed first.
+ *   pgx_tiling_stats : the counts.  ctg_kept + ctg_skipped + ctg_empty = the rows of ctg_paths; compound_tie_rounds: the shortest-path
+ *                      rounds in which more than one path had the minimum weight (0: the output is the script's under any networkx;
+ *                      else ours is forward Dijkstra's); host_us: the host's time over utg_data, ctg_paths and the bundles.
+ *   pgx_tiling_rows  : n rows of file `which` (0: primary, 1: alternate) from row `first` on; `ctg` numbers the distinct contig names of
+ *                      that file in order of first appearance, strand 0 for E, 1 for B.
+ *   pgx_tiling_names : those names, a line each (*text malloc'd, pgx_free).
+ *   pgx_tiling_text  : the lines of file `which` in pieces, with pgx_sgraph_text's conventions.
+ *   pgx_tiling_contigs : contig FASTA of file `which` from the rows of the built tiling and <seqdb_prefix>.idx / .seqdb, to out_path (NULL:
+ *                      stdout): byte for byte pgx_contigs_chunk's on the written file, with its errors (rows are numbered as its lines).  The
+ *                      24-byte rows come to the host once; no text is written and parsed again.
+ *   pgx_tiling_free  : releases them (NULL is accepted).
+ *   pgx_tiling_chunk : the file level; both files are written only after everything was built.
+ * PGX_EINVAL with a message that names the file and the 0-based line, and nothing written, where the script would raise: a line of
+ * sg_edges_list without 8 fields or of the other two without 7; a G line whose w does not end in E for s < t, in B otherwise; a unitig
+ * that a kept row of ctg_paths or a compound line names and utg_data lacks as simple, contained or compound; an edge of a path that is
+ * not a G line; a compound sub-unitig that is itself compound; s or t absent from a compound unitig's graph, or no path between them.
+ * Beyond the script: a field that would not print back as it was read (a node name that is not "%09d:B|E" of a read id below 2^31, an
+ * identity with more than two fraction digits, an exponent, nan; in G lines only, the script reads no more of the others -- pgx_sgraph_parse
+ * checks every line); a line of sg_edges_list longer than 256 bytes; a (v, w) or (s, via, t) that occurs twice (the later line is named:
+ * the script's dicts would keep it, its own files never repeat a key); a compound unitig's edge with aln_score <= 0 or >= 2^40, or one with s == t; a
+ * path of one node (the script writes an empty line); a contig name longer than 89 bytes.  PGX_ENOMEM leaves the inputs usable.
+ * Device memory is booked as "tiling", time as "tiling" with the parts "tiling_parse", "tiling_index", "tiling_paths", "tiling_text". */
+typedef struct {
+  uint64_t sg_lines, g_edges;                       /* edge lines read; of them G */
+  uint64_t utg_simple, utg_contained, utg_compound; /* lines of utg_data by type (other types are dropped) */
+  uint64_t ctg_kept, ctg_skipped, ctg_empty;        /* rows of ctg_paths: written; dropped by the dual rule; kept with an empty path */
+  uint64_t p_rows, a_rows, alternates;              /* lines of the two files; paths of the alternate file */
+  uint64_t compound_tie_rounds;
+  uint64_t host_us;
+} pgx_tiling_stats_t;
+typedef struct pgx_tiling pgx_tiling;
+int pgx_sgraph_parse(const char *sg_edges_list_fn, pgx_sgraph_edge **edges, int64_t **idt_hundredths, uint64_t *n);
+int pgx_tiling_build(const char *sg_edges_list_fn, pgx_sgraph *g, const char *utg_text, size_t utg_len, const char *ctg_text, size_t ctg_len, pgx_tiling **out);
+int pgx_tiling_stats(const pgx_tiling *t, pgx_tiling_stats_t *out);
+int pgx_tiling_rows(const pgx_tiling *t, int which, uint64_t first, uint64_t n, pgx_tile_row *out);
+int pgx_tiling_names(const pgx_tiling *t, int which, char **text, size_t *text_len, uint64_t *n_ctg);
+int pgx_tiling_text(pgx_tiling *t, int which, uint64_t max_lines, char **text, size_t *text_len, int *done);
+int pgx_tiling_contigs(const pgx_tiling *t, int which, const char *seqdb_prefix, const char *out_path, uint64_t *n_ctg, uint64_t *n_bases);
+int pgx_tiling_free(pgx_tiling *t);
+int pgx_tiling_chunk(const char *sg_edges_list_fn, const char *utg_data_fn, const char *ctg_paths_fn, const char *p_out, const char *a_out, pgx_tiling_stats_t *stats);
+
 /* host utility: the order in which klib khash (src/khash.h:232-336, integer hash :373) iterates n DISTINCT 64-bit keys
  * inserted in the given order -- the order shmr_overlap visits its tables in (src/shmr_overlap.c:206-215).  out receives
  * the n keys in ascending slot order.  Runs on the host (it is the routine the overlap stage uses for its outer table). */

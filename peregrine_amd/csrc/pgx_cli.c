@@ -1,6 +1,6 @@
 /*
  * pgx_cli.c -- native drop-ins for the reference's stage executables, one multi-call binary (the tool is chosen by the
- * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map, path_to_contig.py.  Same getopt strings, defaults
+ * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map, path_to_contig.py, graph_to_path.py.  Same getopt strings, defaults
  * and output files / streams as /root/reference/src/shmr_mkseqdb.c:14-128, shmr_index.c:37-245, shmr_overlap.c:233-419,
  * shmr_dedup.c:19-104, shmr_map.c:163-373; everything else happens behind the C-ABI of include/pgx.h on the GPU.
  * Plain C against libpgx.so: this is the cgo / FFI-free form of the boundary (the Python shims in bin/ do the same).
@@ -573,6 +573,76 @@ static int main_path_to_contig(int argc, char **argv) {
   return 0;
 }
 
+/* graph_to_path.py [--improper-p-ctg] [--proper-a-ctg] [--seqdb-prefix P] [--sg-edges-list-fn F] [--utg-data-fn F] [--ctg-paths-fn F]
+ * (py/scripts/graph_to_path.py): p_ctg_tiling_path and a_ctg_tiling_path into the working directory, nothing on stdout.  The first three
+ * options change nothing in the script's tiling paths either. */
+static int main_graph_to_path(int argc, char **argv) {
+  const char *sg = "./sg_edges_list", *utg = "./utg_data", *ctg = "./ctg_paths", *seqdb = "./seq_dataset", *fa[2] = {NULL, NULL};
+  for (int i = 1; i < argc; ++i) {
+    const char *a = argv[i];
+    const char **dst = NULL;
+    size_t len = 0;
+    if (strcmp(a, "--improper-p-ctg") == 0 || strcmp(a, "--proper-a-ctg") == 0) continue;
+    if (strncmp(a, "--seqdb-prefix", len = 14) == 0) dst = &seqdb;
+    else if (strncmp(a, "--p-ctg-fa", len = 10) == 0) dst = &fa[0];
+    else if (strncmp(a, "--a-ctg-fa", len = 10) == 0) dst = &fa[1];
+    else if (strncmp(a, "--sg-edges-list-fn", len = 18) == 0) dst = &sg;
+    else if (strncmp(a, "--utg-data-fn", len = 13) == 0) dst = &utg;
+    else if (strncmp(a, "--ctg-paths-fn", len = 14) == 0) dst = &ctg;
+    if (dst && a[len] == '=') *dst = a + len + 1;
+    else if (dst && a[len] == 0 && i + 1 < argc) *dst = argv[++i];
+    else {
+      fprintf(stderr, "usage: graph_to_path.py [--improper-p-ctg] [--proper-a-ctg] [--seqdb-prefix P] [--sg-edges-list-fn F] [--utg-data-fn F] [--ctg-paths-fn F] [--p-ctg-fa FILE] [--a-ctg-fa FILE]\n");
+      return 2;
+    }
+  }
+  if (pgx_init(device_of_env())) return fail("graph_to_path.py", "pgx_init");
+  if (!fa[0] && !fa[1]) {
+    if (pgx_tiling_chunk(sg, utg, ctg, "p_ctg_tiling_path", "a_ctg_tiling_path", NULL)) return fail("graph_to_path.py", "pgx_tiling_chunk");
+    return 0;
+  }
+  /* with FASTA: the tiling stays alive; both texts are whole in memory before the first file is opened, the contigs come from its rows */
+  char *small[2] = {NULL, NULL}, *text[2] = {NULL, NULL};
+  size_t small_len[2] = {0, 0}, text_len[2] = {0, 0};
+  const char *small_fn[2] = {utg, ctg}, *out_fn[2] = {"p_ctg_tiling_path", "a_ctg_tiling_path"};
+  for (int k = 0; k < 2; ++k) {
+    FILE *f = fopen(small_fn[k], "rb");
+    if (!f) {
+      fprintf(stderr, "graph_to_path.py: cannot read %s\n", small_fn[k]);
+      return 1;
+    }
+    size_t cap = 1 << 20, got;
+    small[k] = malloc(cap);
+    while (small[k] && (got = fread(small[k] + small_len[k], 1, cap - small_len[k], f)) > 0)
+      if ((small_len[k] += got) == cap) small[k] = realloc(small[k], cap *= 2);
+    fclose(f);
+    if (!small[k]) return 1;
+  }
+  pgx_tiling *t = NULL;
+  if (pgx_tiling_build(sg, NULL, small[0], small_len[0], small[1], small_len[1], &t)) return fail("graph_to_path.py", "pgx_tiling_build");
+  for (int w = 0; w < 2; ++w)
+    for (int done = 0; !done;) {
+      char *piece = NULL;
+      size_t len = 0;
+      if (pgx_tiling_text(t, w, (uint64_t)1 << 22, &piece, &len, &done)) return fail("graph_to_path.py", "pgx_tiling_text");
+      text[w] = realloc(text[w], text_len[w] + len + 1);
+      if (!text[w]) return 1;
+      memcpy(text[w] + text_len[w], piece, len), text_len[w] += len;
+      pgx_free(piece);
+    }
+  for (int w = 0; w < 2; ++w) {
+    FILE *f = fopen(out_fn[w], "wb");
+    if (!f || fwrite(text[w], 1, text_len[w], f) != text_len[w] || fclose(f)) {
+      fprintf(stderr, "graph_to_path.py: cannot write %s\n", out_fn[w]);
+      return 1;
+    }
+  }
+  for (int w = 0; w < 2; ++w)
+    if (fa[w] && pgx_tiling_contigs(t, w, seqdb, fa[w], NULL, NULL)) return fail("graph_to_path.py", "pgx_tiling_contigs");
+  pgx_tiling_free(t);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   char *self = strdup(argv[0]);
   const char *tool = basename(self);
@@ -588,9 +658,10 @@ int main(int argc, char **argv) {
   else if (strcmp(tool, "shmr_sgraph") == 0) rc = main_sgraph(argc, argv);
   else if (strcmp(tool, "shmr_map") == 0) rc = main_map(argc, argv);
   else if (strcmp(tool, "path_to_contig.py") == 0) rc = main_path_to_contig(argc, argv);
+  else if (strcmp(tool, "graph_to_path.py") == 0) rc = main_graph_to_path(argc, argv);
   else if (strcmp(tool, "serve") == 0) rc = main_serve(argc, argv);
   else {
-    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_sgraph|shmr_map|path_to_contig.py} [flags]   (or invoke through a link of that name)\n"
+    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_sgraph|shmr_map|path_to_contig.py|graph_to_path.py} [flags]   (or invoke through a link of that name)\n"
                     "       pgx_cli serve -p seqdb_prefix [-i idle_seconds]   (keeps the read database in HBM; the drop-ins attach to it)\n");
     rc = 2;
   }

@@ -342,51 +342,42 @@ struct PathRow {
 }  // namespace
 }  // namespace pgx
 
-using namespace pgx;
-
-extern "C" {
-
-int pgx_align_batch2(pgx_seqdb *db, const pgx_align_key2 *keys, size_t n, int band, pgx_match *out) {
-  return guarded([&]() -> int {
-    require_ready();
-    PGX_REQUIRE(db && (n == 0 || (keys && out)), PGX_EARG, "pgx_align_batch2: null argument");
-    PGX_REQUIRE(band > 0 && band < (1 << 20), PGX_EARG, "bad band");
-    PGX_REQUIRE(n < (1ULL << 30), PGX_EARG, "too many alignments for one call");
-    for (size_t i = 0; i < n; ++i) {
-      const auto &k = keys[i];
-      PGX_REQUIRE(k.rid0 < db->rlen_by_rid.size() && k.rid1 < db->rlen_by_rid.size() && k.q_off <= db->rlen_by_rid[k.rid0] &&
-                      k.t_off <= db->rlen_by_rid[k.rid1],
-                  PGX_EARG, "alignment key %zu out of range", i);
+namespace pgx {
+namespace {
+// the rows of a tiling path file, in file order (path_to_contig.py:32-39): where the text route and the row route of the layout part
+void feed_path_text(const char *tiling_path, const TileRowFn &add) {
+  Mapped path;
+  PGX_REQUIRE(path.open(tiling_path), PGX_EIO, "cannot read %s", tiling_path);
+  {
+    const char *p = (const char *)path.p, *end = p + path.n;
+    std::vector<std::string> f;
+    for (uint64_t line = 0; p < end; ++line) {
+      const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
+      const char *le = nl ? nl : end;
+      f.clear();
+      for (const char *q = p; q < le;) {
+        while (q < le && isspace((unsigned char)*q)) ++q;
+        const char *t0 = q;
+        while (q < le && !isspace((unsigned char)*q)) ++q;
+        if (q > t0) f.emplace_back(t0, q);
+      }
+      p = nl ? nl + 1 : end;
+      PGX_REQUIRE(f.size() == 10, PGX_EARG, "tiling path row %llu: %zu fields, not 10", (unsigned long long)line, f.size());
+      int64_t r0 = 0, r1 = 0, s = 0, e = 0;
+      uint8_t st0 = 0, st1 = 0;
+      PGX_REQUIRE(parse_node(f[1], &r0, &st0) && parse_node(f[2], &r1, &st1), PGX_EARG, "tiling path row %llu: cannot read the nodes '%s' '%s' (rid:E or rid:B)",
+                  (unsigned long long)line, f[1].c_str(), f[2].c_str());
+      PGX_REQUIRE(parse_int(f[4], INT32_MIN, INT32_MAX, &s) && parse_int(f[5], INT32_MIN, INT32_MAX, &e), PGX_EARG,
+                  "tiling path row %llu: cannot read s, e = '%s', '%s'", (unsigned long long)line, f[4].c_str(), f[5].c_str());
+      add(f[0], r0, r1, s, e, st0, st1, line);
     }
-    if (n == 0) return PGX_OK;
-    MemTag mem_tag("contigs");
-    DevBuf<pgx_align_key2> d_keys(n);
-    DevBuf<pgx_match> d_out(n);
-    DevBuf<uint32_t> d_rids(db->d_seq.p ? 0 : 2 * n);
-    d_keys.upload(keys, n);
-    if (d_rids.n) hipLaunchKernelGGL(k_key_rids, dim3(cdiv(n, 256)), dim3(256), 0, ctx().stream, d_keys.p, (uint32_t)n, d_rids.p);
-    ByteSource src(db, d_rids.p, (uint32_t)d_rids.n);
-    dev_align2(db, src.seq, src.off, d_keys.p, n, band, d_out.p);
-    d_out.download(out, n);
-    pgx::sync();
-    return PGX_OK;
-  });
+  }
 }
+}  // namespace
 
-int pgx_contigs_resident(pgx_seqdb *db, const pgx_tile_row *rows, size_t n_rows, size_t n_ctg, char **text, uint64_t *ctg_off, uint64_t *text_len) {
-  return guarded([&]() -> int {
-    require_ready();
-    PGX_REQUIRE(db && text && ctg_off && text_len && (n_rows == 0 || rows), PGX_EARG, "pgx_contigs_resident: null argument");
-    PGX_REQUIRE(db->max_rlen < (1u << 30), PGX_EARG, "pgx_contigs_resident: a read of %u bases", db->max_rlen);
-    std::vector<pgx_tile_row> r(rows, rows + n_rows);
-    std::vector<uint32_t> first_row;
-    check_rows(db, r, n_ctg, nullptr, first_row);
-    contigs_layout(db, r, first_row, nullptr, text, ctg_off, text_len);
-    return PGX_OK;
-  });
-}
-
-int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const char *out_path, uint64_t *n_ctg_out, uint64_t *n_bases_out) {
+// The layout behind pgx_contigs_chunk and pgx_tiling_contigs: feed hands over the rows in order (contig name, the two reads' ids as the idx
+// names them, s, e, strands, the row's number for messages); every check runs in that order, then the batching, the layout, the FASTA.
+int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFeed &feed, const char *out_path, uint64_t *n_ctg_out, uint64_t *n_bases_out) {
   struct Piece {   // a batch's contig bytes, kept until every batch is through: an error in a later batch must leave nothing written
     char *text = nullptr;
     std::vector<uint64_t> off;
@@ -395,14 +386,13 @@ int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const c
   std::vector<Piece> pieces;
   const int rc = guarded([&]() -> int {
     require_ready();
-    PGX_REQUIRE(seqdb_prefix && tiling_path, PGX_EARG, "pgx_contigs_chunk: null argument");
+    PGX_REQUIRE(seqdb_prefix, PGX_EARG, "%s: null argument", who);
     const std::string prefix(seqdb_prefix);
     std::vector<uint32_t> rid, rlen;
     std::vector<uint64_t> roff;
     PGX_REQUIRE(load_idx((prefix + ".idx").c_str(), rid, rlen, roff) == 0, PGX_EIO, "cannot open %s.idx", seqdb_prefix);
-    Mapped seqdb, path;
+    Mapped seqdb;
     PGX_REQUIRE(seqdb.open((prefix + ".seqdb").c_str()), PGX_EIO, "cannot read %s.seqdb", seqdb_prefix);
-    PGX_REQUIRE(path.open(tiling_path), PGX_EIO, "cannot read %s", tiling_path);
     std::unordered_map<uint32_t, uint32_t> slot_of;   // rid -> its LAST slot in the idx file (the script's dict keeps the last entry)
     slot_of.reserve(rid.size() * 2);
     for (size_t i = 0; i < rid.size(); ++i) {
@@ -413,45 +403,24 @@ int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const c
     std::vector<std::string> ctg_names;
     std::unordered_map<std::string, uint32_t> ctg_of;
     std::vector<std::vector<PathRow>> by_ctg;
-    {
-      const char *p = (const char *)path.p, *end = p + path.n;
-      std::vector<std::string> f;
-      for (uint64_t line = 0; p < end; ++line) {
-        const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
-        const char *le = nl ? nl : end;
-        f.clear();
-        for (const char *q = p; q < le;) {
-          while (q < le && isspace((unsigned char)*q)) ++q;
-          const char *t0 = q;
-          while (q < le && !isspace((unsigned char)*q)) ++q;
-          if (q > t0) f.emplace_back(t0, q);
-        }
-        p = nl ? nl + 1 : end;
-        PGX_REQUIRE(f.size() == 10, PGX_EARG, "tiling path row %llu: %zu fields, not 10", (unsigned long long)line, f.size());
-        int64_t r0 = 0, r1 = 0, s = 0, e = 0;
-        uint8_t st0 = 0, st1 = 0;
-        PGX_REQUIRE(parse_node(f[1], &r0, &st0) && parse_node(f[2], &r1, &st1), PGX_EARG, "tiling path row %llu: cannot read the nodes '%s' '%s' (rid:E or rid:B)",
-                    (unsigned long long)line, f[1].c_str(), f[2].c_str());
-        PGX_REQUIRE(parse_int(f[4], INT32_MIN, INT32_MAX, &s) && parse_int(f[5], INT32_MIN, INT32_MAX, &e), PGX_EARG,
-                    "tiling path row %llu: cannot read s, e = '%s', '%s'", (unsigned long long)line, f[4].c_str(), f[5].c_str());
-        const auto i0 = slot_of.find((uint32_t)r0), i1 = slot_of.find((uint32_t)r1);
-        PGX_REQUIRE(i0 != slot_of.end() && i1 != slot_of.end(), PGX_EARG, "tiling path row %llu: read %lld is not in %s.idx", (unsigned long long)line,
-                    (long long)(i0 == slot_of.end() ? r0 : r1), seqdb_prefix);
-        auto it = ctg_of.find(f[0]);
-        if (it == ctg_of.end()) {
-          it = ctg_of.emplace(f[0], (uint32_t)ctg_names.size()).first;
-          ctg_names.push_back(f[0]), by_ctg.emplace_back();
-        }
-        by_ctg[it->second].push_back(PathRow{it->second, i0->second, i1->second, (int32_t)s, (int32_t)e, st0, st1, line});
-        // the checks of the row itself, here so that the FIRST bad row of the file is the one reported
-        const int64_t l0 = rlen[i0->second], l1 = rlen[i1->second];
-        PGX_REQUIRE(l0 >= OVERHANG, PGX_EARG, "tiling path row %llu: read %lld has %lld bases, fewer than the overhang of %d", (unsigned long long)line,
-                    (long long)r0, (long long)l0, OVERHANG);
-        PGX_REQUIRE(l1 < (1LL << 30) && std::llabs(e - s) + OVERHANG <= l1, PGX_EARG, "tiling path row %llu: |e - s| + %d = %lld exceeds the %lld bases of read %lld",
-                    (unsigned long long)line, OVERHANG, (long long)(std::llabs(e - s) + OVERHANG), (long long)l1, (long long)r1);
-        PGX_REQUIRE(st1 ? l1 - e > l1 - s : e > s, PGX_EARG, "tiling path row %llu: e <= s%s", (unsigned long long)line, st1 ? " after the strand transform" : "");
+    feed([&](const std::string &ctg, int64_t r0, int64_t r1, int64_t s, int64_t e, uint8_t st0, uint8_t st1, uint64_t line) {
+      const auto i0 = slot_of.find((uint32_t)r0), i1 = slot_of.find((uint32_t)r1);
+      PGX_REQUIRE(i0 != slot_of.end() && i1 != slot_of.end(), PGX_EARG, "tiling path row %llu: read %lld is not in %s.idx", (unsigned long long)line,
+                  (long long)(i0 == slot_of.end() ? r0 : r1), seqdb_prefix);
+      auto it = ctg_of.find(ctg);
+      if (it == ctg_of.end()) {
+        it = ctg_of.emplace(ctg, (uint32_t)ctg_names.size()).first;
+        ctg_names.push_back(ctg), by_ctg.emplace_back();
       }
-    }
+      by_ctg[it->second].push_back(PathRow{it->second, i0->second, i1->second, (int32_t)s, (int32_t)e, st0, st1, line});
+      // the checks of the row itself, here so that the FIRST bad row of the file is the one reported
+      const int64_t l0 = rlen[i0->second], l1 = rlen[i1->second];
+      PGX_REQUIRE(l0 >= OVERHANG, PGX_EARG, "tiling path row %llu: read %lld has %lld bases, fewer than the overhang of %d", (unsigned long long)line,
+                  (long long)r0, (long long)l0, OVERHANG);
+      PGX_REQUIRE(l1 < (1LL << 30) && std::llabs(e - s) + OVERHANG <= l1, PGX_EARG, "tiling path row %llu: |e - s| + %d = %lld exceeds the %lld bases of read %lld",
+                  (unsigned long long)line, OVERHANG, (long long)(std::llabs(e - s) + OVERHANG), (long long)l1, (long long)r1);
+      PGX_REQUIRE(st1 ? l1 - e > l1 - s : e > s, PGX_EARG, "tiling path row %llu: e <= s%s", (unsigned long long)line, st1 ? " after the strand transform" : "");
+    });
     // ---- batches of whole contigs: the reads a batch names gathered into a sub-database of their own, rids remapped to 0 .. m - 1
     size_t free_b = 0, total_b = 0;
     PGX_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -536,6 +505,56 @@ int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const c
   });
   for (auto &pc : pieces) out_free(pc.text);
   return rc;
+}
+
+}  // namespace pgx
+
+using namespace pgx;
+
+extern "C" {
+
+int pgx_align_batch2(pgx_seqdb *db, const pgx_align_key2 *keys, size_t n, int band, pgx_match *out) {
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(db && (n == 0 || (keys && out)), PGX_EARG, "pgx_align_batch2: null argument");
+    PGX_REQUIRE(band > 0 && band < (1 << 20), PGX_EARG, "bad band");
+    PGX_REQUIRE(n < (1ULL << 30), PGX_EARG, "too many alignments for one call");
+    for (size_t i = 0; i < n; ++i) {
+      const auto &k = keys[i];
+      PGX_REQUIRE(k.rid0 < db->rlen_by_rid.size() && k.rid1 < db->rlen_by_rid.size() && k.q_off <= db->rlen_by_rid[k.rid0] &&
+                      k.t_off <= db->rlen_by_rid[k.rid1],
+                  PGX_EARG, "alignment key %zu out of range", i);
+    }
+    if (n == 0) return PGX_OK;
+    MemTag mem_tag("contigs");
+    DevBuf<pgx_align_key2> d_keys(n);
+    DevBuf<pgx_match> d_out(n);
+    DevBuf<uint32_t> d_rids(db->d_seq.p ? 0 : 2 * n);
+    d_keys.upload(keys, n);
+    if (d_rids.n) hipLaunchKernelGGL(k_key_rids, dim3(cdiv(n, 256)), dim3(256), 0, ctx().stream, d_keys.p, (uint32_t)n, d_rids.p);
+    ByteSource src(db, d_rids.p, (uint32_t)d_rids.n);
+    dev_align2(db, src.seq, src.off, d_keys.p, n, band, d_out.p);
+    d_out.download(out, n);
+    pgx::sync();
+    return PGX_OK;
+  });
+}
+
+int pgx_contigs_resident(pgx_seqdb *db, const pgx_tile_row *rows, size_t n_rows, size_t n_ctg, char **text, uint64_t *ctg_off, uint64_t *text_len) {
+  return guarded([&]() -> int {
+    require_ready();
+    PGX_REQUIRE(db && text && ctg_off && text_len && (n_rows == 0 || rows), PGX_EARG, "pgx_contigs_resident: null argument");
+    PGX_REQUIRE(db->max_rlen < (1u << 30), PGX_EARG, "pgx_contigs_resident: a read of %u bases", db->max_rlen);
+    std::vector<pgx_tile_row> r(rows, rows + n_rows);
+    std::vector<uint32_t> first_row;
+    check_rows(db, r, n_ctg, nullptr, first_row);
+    contigs_layout(db, r, first_row, nullptr, text, ctg_off, text_len);
+    return PGX_OK;
+  });
+}
+
+int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const char *out_path, uint64_t *n_ctg_out, uint64_t *n_bases_out) {
+  return contigs_from_rows("pgx_contigs_chunk", tiling_path ? seqdb_prefix : nullptr, [&](const TileRowFn &add) { feed_path_text(tiling_path, add); }, out_path, n_ctg_out, n_bases_out);
 }
 
 }  // extern "C"

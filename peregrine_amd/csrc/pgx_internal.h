@@ -673,6 +673,11 @@ __host__ __device__ inline uint64_t record_checksum(const pgx_ovlp &o, uint64_t 
 void defer_destroy(std::function<void()> fn);
 void drain_deferred();  // waits until every queued job has run (pgx_shutdown)
 
+// the contig layout from rows, however they were made (pgx_contigs.hip): a tiling path file's, or a built tiling's
+using TileRowFn = std::function<void(const std::string &ctg, int64_t rid0, int64_t rid1, int64_t s, int64_t e, uint8_t strand0, uint8_t strand1, uint64_t line)>;
+using TileRowFeed = std::function<void(const TileRowFn &add)>;
+int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFeed &feed, const char *out_path, uint64_t *n_ctg, uint64_t *n_bases);
+
 // host helpers (pgx_api.cpp)
 int load_idx(const char *path, std::vector<uint32_t> &rid, std::vector<uint32_t> &rlen, std::vector<uint64_t> &roff);
 bool read_file(const std::string &path, std::vector<uint8_t> &out);

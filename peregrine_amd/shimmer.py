@@ -474,6 +474,13 @@ class StringGraph(_DeviceText):
         _lib.check(self._lib.pgx_sgraph_unitigs(self._handle("pgx_sgraph_unitigs"), C.byref(u)), "pgx_sgraph_unitigs")
         return Unitigs(u)
 
+    def tiling(self, utg_text: bytes, ctg_text: bytes) -> "TilingPaths":
+        """the tiling paths of this graph's edges, which stay on the device, and the texts of utg_data and ctg_paths (pgx_tiling_build);
+        they own their arrays: the graph may be closed first"""
+        t = C.c_void_p()
+        _lib.check(self._lib.pgx_tiling_build(None, self._handle("pgx_tiling_build"), utg_text, len(utg_text), ctg_text, len(ctg_text), C.byref(t)), "pgx_tiling_build")
+        return TilingPaths(t)
+
 
 def string_graph(records, min_len: int = 4000, min_idt: float = 96.0, device=None, piece: int = 0) -> StringGraph:
     """The string graph of `records` (OVLP_DTYPE) in one call: a graph-mode dedup stream fed the records (in pieces of `piece`, 0: one
@@ -542,6 +549,136 @@ def read_sg_edges_list(path: str) -> np.ndarray:
         out[k] = (int(f[0][:-2]) & 0xFFFFFFFF, int(f[1][:-2]) & 0xFFFFFFFF, int(f[2]) & 0xFFFFFFFF, int(f[3]), int(f[4]), f[0][-1:] == b"E", f[1][-1:] == b"E",
                   code[f[7]], 0, int(f[5]), t)
     return out
+
+
+def parse_sg_edges_list(path: str, hundredths: bool = False):
+    """read_sg_edges_list on the device (pgx_sgraph_parse): the file goes up in pieces and a lane tokenises a line.  The same records
+    (a type other than G, TR, S, R becomes SGRAPH_TYPE_OTHER; idt_tenths is the exact decimal rounded half to even); with hundredths
+    also the identities in hundredths, as an int64 array.  A line that would not print back as it was read is refused (PgxError)."""
+    _lib.init(None)
+    e, h, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+    _lib.check(_lib.load().pgx_sgraph_parse(path.encode(), C.byref(e), C.byref(h), C.byref(n)), "pgx_sgraph_parse")
+    edges, hund = _lib.take(e.value, n.value, SGRAPH_EDGE_DTYPE), _lib.take(h.value, n.value, np.dtype("<i8"))
+    return (edges, hund) if hundredths else edges
+
+
+_TILING_STATS = ("sg_lines", "g_edges", "utg_simple", "utg_contained", "utg_compound", "ctg_kept", "ctg_skipped", "ctg_empty", "p_rows", "a_rows", "alternates",
+                 "compound_tie_rounds", "host_us")   # pgx_tiling_stats_t
+TILING_FILES = ("p_ctg_tiling_path", "a_ctg_tiling_path")   # `which` 0 and 1
+
+
+class TilingPaths:
+    """The tiling paths of a string graph, its unitigs and its contig paths (shimmer.graph_to_path, StringGraph.tiling): what
+    graph_to_path.py writes, byte for byte.  `which` is 0 (or "p") for the primary file and 1 (or "a") for the alternate one.
+    rows(which): TILE_ROW_DTYPE records, `ctg` indexing names(which); text(which): the lines not handed out yet, as pieces of bytes;
+    write(p_path, a_path): both files.  close() may be called more than once."""
+
+    def __init__(self, handle):
+        self._lib = _lib.load()
+        self.h = handle
+        st = (C.c_uint64 * len(_TILING_STATS))()
+        _lib.check(self._lib.pgx_tiling_stats(self.h, st), "pgx_tiling_stats")
+        self.stats = dict(zip(_TILING_STATS, (int(v) for v in st)))
+
+    def _handle(self, who):
+        if not self.h:
+            raise _lib.PgxError(f"{who}: the tiling paths are closed")
+        return self.h
+
+    @staticmethod
+    def _which(which) -> int:
+        w = {"p": 0, "a": 1, 0: 0, 1: 1}.get(which)
+        if w is None:
+            raise ValueError(f"which is 0 / 'p' (primary) or 1 / 'a' (alternate), not {which!r}")
+        return w
+
+    def rows(self, which, first: int = 0, n: int | None = None) -> np.ndarray:
+        w = self._which(which)
+        n = self.stats[("p_rows", "a_rows")[w]] - first if n is None else n
+        out = np.zeros(n, _lib.TILE_ROW_DTYPE)
+        _lib.check(self._lib.pgx_tiling_rows(self._handle("pgx_tiling_rows"), w, int(first), int(n), _ptr(out)), "pgx_tiling_rows")
+        return out
+
+    def names(self, which) -> list:
+        w = self._which(which)
+        data = _take_text("pgx_tiling_names", lambda text, tl: self._lib.pgx_tiling_names(self._handle("pgx_tiling_names"), w, text, tl, None))
+        return data.decode().split("\n")[:-1]
+
+    def text(self, which, max_lines: int = 1 << 20):
+        w = self._which(which)
+        return _text_pieces(lambda h, ml, text, tl, done: self._lib.pgx_tiling_text(h, w, ml, text, tl, done), "pgx_tiling_text", self._handle, max_lines)
+
+    def write(self, p_path: str, a_path: str) -> int:
+        """both files (the lines not handed out yet); the texts are whole in memory before the first file is opened"""
+        texts = [b"".join(self.text(w)) for w in (0, 1)]
+        for path, data in zip((p_path, a_path), texts):
+            with open(path, "wb") as f:
+                f.write(data)
+        return sum(len(d) for d in texts)
+
+    def contigs(self, which, seqdb_prefix: str, out: str | None = None) -> dict:
+        """the contigs of file `which` as FASTA, laid out from the rows on the device (pgx_tiling_contigs): byte for byte what path_to_contig
+        makes of the written file, to `out` (None: this process's stdout)"""
+        w = self._which(which)
+        if out is None:
+            import sys
+            sys.stdout.flush()
+        nc, nb = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(self._lib.pgx_tiling_contigs(self._handle("pgx_tiling_contigs"), w, seqdb_prefix.encode(), out.encode() if out is not None else None, C.byref(nc),
+                                                C.byref(nb)), "pgx_tiling_contigs")
+        return dict(contigs=int(nc.value), bases=int(nb.value))
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _lib.check(self._lib.pgx_tiling_free(h), "pgx_tiling_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def graph_to_path(sg, utg_data: str, ctg_paths: str, p_out: str | None = None, a_out: str | None = None, device=None, seqdb_prefix: str | None = None,
+                  p_ctg_fa: str | None = None, a_ctg_fa: str | None = None):
+    """graph_to_path.py: sg is the path of a sg_edges_list file or a live StringGraph; utg_data and ctg_paths are paths.  With p_out and
+    a_out the two files are written and the statistics returned (a file path as sg: pgx_tiling_chunk); without, the live TilingPaths.
+    p_ctg_fa / a_ctg_fa: also the contigs of that file as FASTA, laid out from the rows with the reads of seqdb_prefix."""
+    _lib.init(device)
+    if (p_out is None) != (a_out is None):
+        raise ValueError("p_out and a_out: both or neither")
+    fasta = [(w, fa) for w, fa in ((0, p_ctg_fa), (1, a_ctg_fa)) if fa is not None]
+    if fasta and (p_out is None or seqdb_prefix is None):
+        raise ValueError("p_ctg_fa / a_ctg_fa need p_out, a_out and seqdb_prefix")
+    if isinstance(sg, StringGraph) or p_out is None or fasta:
+        with open(utg_data, "rb") as f:
+            utg = f.read()
+        with open(ctg_paths, "rb") as f:
+            ctg = f.read()
+        if isinstance(sg, StringGraph):
+            t = sg.tiling(utg, ctg)
+        else:
+            h = C.c_void_p()
+            _lib.check(_lib.load().pgx_tiling_build(str(sg).encode(), None, utg, len(utg), ctg, len(ctg), C.byref(h)), "pgx_tiling_build")
+            t = TilingPaths(h)
+        if p_out is None:
+            return t
+        with t:
+            t.write(p_out, a_out)
+            for w, fa in fasta:
+                t.contigs(w, seqdb_prefix, fa)
+            return t.stats
+    st = (C.c_uint64 * len(_TILING_STATS))()
+    _lib.check(_lib.load().pgx_tiling_chunk(str(sg).encode(), utg_data.encode(), ctg_paths.encode(), p_out.encode(), a_out.encode(), st), "pgx_tiling_chunk")
+    return dict(zip(_TILING_STATS, (int(v) for v in st)))
 
 
 def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None, utg_path: str | None = None) -> dict:
