@@ -64,7 +64,7 @@ struct alignas(64) Counters {   // three cache lines: the arenas, the dirty stat
   unsigned long long lookups, skips, evals, records;
 #ifdef PGX_BIG_STATS
   uint32_t big_max_steps, big_long, big_long_n, big_evals;
-  unsigned long long pad2[2];
+  unsigned long long big_pairs, pad2[1];   // pairs k_eval_big's LOOK phase looked up
 #else
   unsigned long long pad2[4];
 #endif
@@ -276,6 +276,13 @@ __device__ __forceinline__ M128 shr128(M128 m, uint32_t s) {   // m >> s, s <= 1
   if (s == 0) return m;
   return M128{m.lo >> s | m.hi << (64 - s), m.hi >> s};
 }
+__device__ __forceinline__ M128 shl128(M128 m, uint32_t s) {   // m << s, s <= 128 (what leaves the 128 bits is dropped)
+  if (s >= 128) return M128{0, 0};
+  if (s >= 64) return M128{0, m.lo << (s - 64)};
+  if (s == 0) return m;
+  return M128{m.lo << s, m.hi << s | m.lo >> (64 - s)};
+}
+__device__ __forceinline__ M128 or128(M128 a, M128 b) { return M128{a.lo | b.lo, a.hi | b.hi}; }
 
 
 
@@ -289,6 +296,16 @@ __device__ __forceinline__ M128 shr128(M128 m, uint32_t s) {   // m >> s, s <= 1
 // wavefronts take FOUR rows x 128 partners per step (a bucket holds at most 128 entries, so a row is always complete within its
 // step): the rows are committed in order through masks exchanged in LDS, exactly like k_eval_rows' four-row form; a partner that an
 // earlier row of the step found contained is dropped from the later rows' masks in place (round 4).
+// The steps themselves touch LDS only.  What a step needs to know of a (row, partner) pair -- is it in the pair table under an earlier
+// bucket and with which type; if not, is its alignment filed, settled and accepted, and of which type, or which type is guessed -- depends
+// on the bucket's entries and on tables that nothing changes while the evaluation kernels run.  A bucket has at most 128 entries, 8,128
+// pairs: LOOK finds all of that for every pair first, LOOK_NB pairs per lane with their probes in flight together, and leaves a byte per
+// pair (FACT_*).  The walk notes what it visited and inserted in two 128-bit masks per row, and COMMIT, again parallel over the pairs,
+// registers the visited ones as readers and writes the inserted ones as the bucket's item list.  (Before, every step paid the chain
+// pair probe -> memo probe -> result -> slot -> reader header -> count, each as long as the unluckiest of 512 lanes made it.)
+constexpr int LOOK_NB = 4;   // pairs a lane looks up together
+constexpr uint8_t FACT_VALID = 1, FACT_PRESENT = 2, FACT_ACCEPTED = 4, FACT_GUESSED = 8, FACT_UNFILED = 16;   // (rid1 != rid0; owned by an earlier bucket; ...; mslot == NONE)
+constexpr int FACT_TYPE_SHIFT = 5;   // two bits: the owner's type when present, else the classified or guessed one
 #ifndef PGX_BIG_NW
 #define PGX_BIG_NW 8
 #endif

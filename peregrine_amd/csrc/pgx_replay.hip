@@ -282,6 +282,7 @@ struct Walk {
     // (round 4: 48 -- with k_eval_big's walk a third shorter the long buckets WITHOUT a repeated read are better off there too: k_eval_rows 38 -> 22 ms
     //  per c4s step, hidden behind k_eval_big as it is: 360 -> 354 ms; from 24 entries on k_eval_big doubles, 411 ms.  Sixteen wavefronts = eight
     //  rows a step (-DPGX_BIG_NW=16): k_eval_big 56 -> 186 ms.)
+    // (k_eval_big now looks a bucket's pairs up once and walks them from LDS, pgx_replay.h; the thresholds are those measured before that)
     r.big_min = (uint32_t)std::max(0, env_int("PGX_REPLAY_BIG", 48));
     r.dup_min = (uint32_t)std::max(0, env_int("PGX_REPLAY_DUP", 12));
     r.predict = std::max(END_FUZZ * 2 - 8, 1), r.predict2 = END_FUZZ * 2 - 8;
@@ -334,8 +335,8 @@ struct Walk {
 #ifdef PGX_BIG_STATS
     unsigned long long b3 = 0, b4 = 0, b5 = 0, b6 = 0, b7 = 0;
     for (uint32_t i = 0; i < SPREAD; ++i) b3 += hs[i * 8 + 3], b4 += hs[i * 8 + 4], b5 += hs[i * 8 + 5], b6 += hs[i * 8 + 6], b7 += hs[i * 8 + 7];
-    fprintf(stderr, "[pgx]   k_eval_big so far: %u evaluations, %llu steps, %llu rows committed; steps cut at a duplicate %llu, ended by a containment %llu, all rows %llu; longest %u steps, %u evaluations of >= 64 steps (entries %u)\n",
-            hc->big_evals, b3, b4, b5, b6, b7, hc->big_max_steps, hc->big_long, hc->big_long_n);
+    fprintf(stderr, "[pgx]   k_eval_big so far: %u evaluations, %llu steps, %llu rows committed; steps cut at a duplicate %llu, ended by a containment %llu, all rows %llu; longest %u steps, %u evaluations of >= 64 steps (entries %u); %llu pairs looked up\n",
+            hc->big_evals, b3, b4, b5, b6, b7, hc->big_max_steps, hc->big_long, hc->big_long_n, hc->big_pairs);
 #endif
 #ifdef PGX_SETTLE_STATS
     unsigned long long c3 = 0, c4 = 0, c5 = 0, c6 = 0;

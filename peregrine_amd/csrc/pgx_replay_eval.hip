@@ -567,6 +567,12 @@ __global__ __launch_bounds__(256) void k_eval_rows(R r, uint32_t lo, uint32_t hi
 }
 template __global__ void k_eval_rows<64, 16>(R r, uint32_t lo, uint32_t hi, uint32_t nlist);
 
+// ---- the same evaluation by a WHOLE WORKGROUP, in three phases (pgx_replay.h: LOOK / WALK / COMMIT) -------------------------------------
+// LOOK: every (row, partner) pair of the bucket is looked up once -- pair table, memo, settled result or guess -- LOOK_NB pairs per lane at a
+// time, the probes of all of them issued before any is tested; what the walk needs of a pair is one byte in LDS.  Nothing the lookups read
+// changes while the evaluation kernels run (owners: k_update; memo: k_file; results: the alignment launches; `settled`: the host).
+// WALK: the step loop, four rows x 128 partners per step, on LDS alone; what it visits and inserts is noted in two masks per row.
+// COMMIT: the visited pairs register as readers, the inserted ones become the bucket's item list, in walk order (row, then partner).
 __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint32_t hi, uint32_t nlist) {
   enum { MV = 0, MP, MPO, MA, MAO, MAC, MAP, MGU, MUF, MDF, NM };
   __shared__ uint32_t s_rid[128], s_pos[128], s_rl[128];
@@ -577,6 +583,9 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
   __shared__ uint8_t s_sett[SET_CAP];                 // ... and their types
   __shared__ unsigned long long s_clk[CLAIM_CAP];     // this step's claims: pair (key + 1) ...
   __shared__ uint32_t s_clw[CLAIM_CAP];               // ... and the lowest walk index claiming it
+  __shared__ uint8_t s_fact[128 * 128];               // LOOK's byte per pair, [row][partner] (FACT_*)
+  __shared__ M128 s_vis[128], s_ins[128];             // per row: the partners (bit = entry index) the walk visited / inserted
+  __shared__ uint32_t s_rbase[128], s_wsum[2];        // insertion ordinal of a row's first insertion; the scan's per-wavefront sums
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint32_t wave_id = r.wbig0 + blockIdx.x * BIG_NW + (uint32_t)w;
   const uint4 wc = r.wcur[wave_id];
@@ -610,6 +619,7 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       const uint32_t rid = (uint32_t)(y >> 32);
       s_rid[i] = rid, s_pos[i] = (((uint32_t)y) >> 1) + 1, s_dir[i] = r.dir[s0 + i], s_rl[i] = r.rlen[rid];
     }
+    if (threadIdx.x < 128) s_vis[threadIdx.x] = M128{0, 0}, s_ins[threadIdx.x] = M128{0, 0};
     if (dup) {
       for (uint32_t i = threadIdx.x; i < SET_CAP; i += blockDim.x) s_setk[i] = 0;
       for (uint32_t i = threadIdx.x; i < CLAIM_CAP; i += blockDim.x) s_clk[i] = 0, s_clw[i] = 0xFFFFFFFFu;
@@ -619,6 +629,111 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       r.dirty[j] = 0, r.evaluated[j] = 1, r.ever[j] = 1, r.parity[j] ^= 1, r.ohead[j] = r.ihead[j];
       atomicAdd(&r.spread[(blockIdx.x % SPREAD) * 8], 1ULL);
     }
+#ifdef PGX_BIG_STATS
+    uint32_t st_steps = 0, st_rows = 0, st_cut = 0, st_cont = 0, st_full = 0, st_pairs = 0;
+#endif
+    // ---- LOOK: the triangle of pairs (row i, partner p > i), folded into n / 2 lines of n (row f in front, row n - 2 - f behind it) ----
+    {
+      const uint32_t total = (n >> 1) * n;
+      for (uint32_t base = 0; base < total; base += LOOK_NB * blockDim.x) {
+        uint32_t row[LOOK_NB], par[LOOK_NB], at[LOOK_NB], own[LOOK_NB];
+        unsigned long long pair[LOOK_NB];
+        bool inb[LOOK_NB], live[LOOK_NB];
+#pragma unroll
+        for (int k = 0; k < LOOK_NB; ++k) {
+          const uint32_t idx = base + (uint32_t)k * blockDim.x + threadIdx.x;
+          const uint32_t f = idx / n, c = idx - f * n;
+          inb[k] = idx < total;
+          if (c < n - 1 - f) row[k] = f, par[k] = f + 1 + c;
+          else row[k] = n - 2 - f, par[k] = c, inb[k] = inb[k] && row[k] != f;   // (that row's partners sit at their own columns; the middle row of an odd n - 1 only once)
+          uint32_t rid0 = 0, rid1 = 0;
+          if (inb[k]) rid0 = s_rid[row[k]], rid1 = s_rid[par[k]];
+          live[k] = inb[k] && rid0 != rid1;
+          pair[k] = rid0 < rid1 ? ((unsigned long long)rid0 << 32 | rid1) : ((unsigned long long)rid1 << 32 | rid0);
+          at[k] = (uint32_t)mix64(pair[k]) & r.pmask, own[k] = 0;
+        }
+        uint8_t fact[LOOK_NB];
+        bool absent[LOOK_NB];
+#pragma unroll
+        for (int k = 0; k < LOOK_NB; ++k) fact[k] = live[k] ? FACT_VALID : 0, absent[k] = live[k];
+#ifdef PGX_BIG_STATS
+#pragma unroll
+        for (int k = 0; k < LOOK_NB; ++k) st_pairs += live[k] ? 1u : 0u;
+#endif
+        // pair_find of the LOOK_NB pairs: an iteration loads the slot of every one of them (a finished one its last slot again) and then tests
+        for (int probes = 0; probes < 1024; ++probes) {
+          uint4 h[LOOK_NB];
+#pragma unroll
+          for (int k = 0; k < LOOK_NB; ++k) h[k] = *reinterpret_cast<const uint4 *>(&r.ph[at[k]]);
+          bool more = false;
+#pragma unroll
+          for (int k = 0; k < LOOK_NB; ++k) {
+            if (!live[k]) continue;
+            const unsigned long long key = (unsigned long long)h[k].y << 32 | h[k].x;
+            if (key == pair[k] + 1) own[k] = h[k].z, live[k] = false;
+            else if (key == 0) live[k] = false;
+            else at[k] = (at[k] + 1) & r.pmask, more = true;
+          }
+          if (!more) break;
+        }
+        uint32_t q_off[LOOK_NB], rlen0[LOOK_NB], rlen1[LOOK_NB], mb[LOOK_NB], req[LOOK_NB];
+        unsigned long long ma[LOOK_NB];
+        bool unfiled[LOOK_NB];
+#pragma unroll
+        for (int k = 0; k < LOOK_NB; ++k) {
+          const bool present = own[k] != 0 && own_bucket(own[k]) < j;
+          if (present) fact[k] |= FACT_PRESENT | (uint8_t)(own_type(own[k]) << FACT_TYPE_SHIFT);
+          absent[k] = absent[k] && !present;
+          q_off[k] = rlen0[k] = rlen1[k] = mb[k] = 0, ma[k] = 0, req[k] = NONE, unfiled[k] = true, at[k] = 0;
+          if (absent[k]) {
+            const uint32_t dir0 = s_dir[row[k]], dir1 = s_dir[par[k]];
+            rlen0[k] = s_rl[row[k]], rlen1[k] = s_rl[par[k]];
+            q_off[k] = s_pos[row[k]] - s_pos[par[k]];
+            if (q_off[k] >= (1u << 30)) atomicOr(&r.c->overflow, OV_QOFF);
+            ma[k] = (unsigned long long)s_rid[row[k]] << 32 | s_rid[par[k]], mb[k] = q_off[k] << 2 | dir0 << 1 | dir1;
+            at[k] = (uint32_t)mix64(ma[k] ^ mix64(mb[k])) & r.mmask;
+          }
+          live[k] = absent[k] && r.memo_used != 0;
+        }
+        if (r.memo_used) {   // memo_find of the absent ones, in the same form
+          for (int probes = 0; probes < 1024; ++probes) {
+            uint4 h[LOOK_NB];
+#pragma unroll
+            for (int k = 0; k < LOOK_NB; ++k) h[k] = *reinterpret_cast<const uint4 *>(&r.mt[at[k]]);
+            bool more = false;
+#pragma unroll
+            for (int k = 0; k < LOOK_NB; ++k) {
+              if (!live[k]) continue;
+              const unsigned long long cur = (unsigned long long)h[k].y << 32 | h[k].x;
+              if (cur == 0) live[k] = false;
+              else if (cur == ma[k] && h[k].z == mb[k] + 1) req[k] = h[k].w, unfiled[k] = false, live[k] = false;
+              else at[k] = (at[k] + 1) & r.mmask, more = true;
+            }
+            if (!more) break;
+          }
+        }
+        pgx_match res[LOOK_NB];   // the settled results, all loaded before the first is classified
+#pragma unroll
+        for (int k = 0; k < LOOK_NB; ++k)
+          if (absent[k] && req[k] < r.settled) res[k] = r.rq_res[req[k]];
+#pragma unroll
+        for (int k = 0; k < LOOK_NB; ++k) {
+          if (absent[k]) {
+            bool accepted, guessed = false;
+            uint32_t type;
+            if (req[k] < r.settled) {
+              accepted = classify(res[k], rlen0[k], rlen1[k], q_off[k], &type);
+            } else {
+              accepted = true, guessed = true, type = T_OVERLAP;
+              if (r.predict && predict_contained(rlen0[k], rlen1[k], q_off[k], r.predict, r.predict2)) type = rlen0[k] >= rlen1[k] ? T_CONTAINS : T_CONTAINED;
+            }
+            fact[k] |= (uint8_t)((accepted ? FACT_ACCEPTED : 0) | (guessed ? FACT_GUESSED : 0) | (unfiled[k] ? FACT_UNFILED : 0) | type << FACT_TYPE_SHIFT);
+          }
+          if (inb[k]) s_fact[row[k] * 128 + par[k]] = fact[k];
+        }
+      }
+    }
+    __syncthreads();   // (the facts are there)
     // ---- workgroup-uniform state (every thread holds a copy and updates it identically) ----
     uint64_t clo = 0, chi = 0;   // "contained" flags of the bucket's entries
     auto cget = [&](uint32_t i) { return (((i < 64 ? clo : chi) >> (i & 63)) & 1) != 0; };
@@ -626,43 +741,13 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       if (i < 64) clo |= 1ULL << i;
       else chi |= 1ULL << (i - 64);
     };
-    uint32_t head = NIL, num = 0, lookups = 0, skips = 0, chunk = 0;
+    uint32_t head = NIL, num = 0, lookups = 0, skips = 0;
     bool any_guess = false, any_unfiled = false;
     int done_to = (int)n - 1;   // rows >= done_to are finished (the first row is n - 2)
     bool row_open = false;       // one row (cur_row) is being continued alone, from partner pbase, with `got` overlaps counted so far
     int cur_row = 0;
     uint32_t pbase = 0, got = 0;
-    bool p_reg = false;          // this lane has a registration whose list position (p_idx) has not been looked at yet
-    uint32_t p_idx = 0, p_slot = 0;
-    auto resolve_pending = [&]() {   // as in k_eval_rows; an exhausted arena raises s_abort instead of returning
-      if (p_reg && p_idx < NIN) r.pc[p_slot >> r.cshift].in[p_idx] = j + 1, p_reg = false;
-      const uint64_t rm = __ballot(p_reg);
-      if (rm) {
-        const uint32_t total = (uint32_t)__popcll(rm);
-        if (rcur + total > rend) {
-          uint32_t base = 0;
-          if (lane == 0) base = atomicAdd(&r.c->rnode_top, NCH);
-          base = (uint32_t)__shfl((int)base, 0, 64);
-          if ((uint64_t)base + NCH > r.rn_cap) {
-            atomicOr(&r.c->overflow, OV_NODES);
-            s_abort = 1;
-            p_reg = false;
-            return;
-          }
-          rcur = base, rend = base + NCH;
-        }
-        if (p_reg) {
-          const uint32_t node = rcur + lane_rank(rm);
-          const uint32_t old = atomicExch(&r.pc[p_slot >> r.cshift].rhead, node + 1);
-          r.rn[node] = RNode{old, j};
-        }
-        rcur += total;
-        p_reg = false;
-      }
-    };
-#ifdef PGX_BIG_STATS
-    uint32_t st_steps = 0, st_rows = 0, st_cut = 0, st_cont = 0, st_full = 0;
-#endif
+    // ---- WALK: no global access from here to the end of the loop ----
     for (;;) {
       // the rows of this step: the open row alone, or the next (up to four) rows that are not contained
       int a[BIG_NR], nrows = 0;
@@ -670,36 +755,41 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       for (int k = 0; k < BIG_NR; ++k) a[k] = -1;
       if (row_open) {
         a[0] = cur_row, nrows = 1;
-      } else {
-        for (int x = done_to; nrows < BIG_NR;) {
-          do --x;
-          while (x >= 0 && cget((uint32_t)x));
-          if (x < 0) break;
-          a[nrows++] = x;
+      } else {   // (a[] and proc[] are only ever indexed by unrolled loops: they stay in registers)
+        int x = done_to;
+#pragma unroll
+        for (int k = 0; k < BIG_NR; ++k) {
+          if (x >= 0) {
+            do --x;
+            while (x >= 0 && cget((uint32_t)x));
+          }
+          if (x >= 0) a[k] = x, nrows = k + 1;
         }
       }
       if (nrows == 0 || r.bestn == 0) break;
       // ---- this step's (row, partner) of the lane: slot q = wave / 2 takes row a[q], partners first + (wave % 2) * 64 + lane ----
       const int q = w >> 1, off = (w & 1) * 64 + lane;   // off: partner offset within the row's 128 (= its bit in the row's masks)
-      const int myrow = a[q];
+      int myrow = -1;
+#pragma unroll
+      for (int k = 0; k < BIG_NR; ++k)
+        if (k == q) myrow = a[k];
       const uint32_t first = row_open ? pbase : (uint32_t)(myrow + 1);
       const uint32_t pi = first + (uint32_t)off;
       const uint32_t wi = (uint32_t)(q * 128 + off);     // position in walk order
       bool valid = q < nrows && pi < n && !cget(pi);
-      uint32_t rid0 = 0, pos0 = 0, rlen0 = 0, dir0 = 0, rid1 = 0, pos1 = 0;
+      uint32_t fact = 0;
+      unsigned long long pair = 0;
       if (valid) {
-        rid0 = s_rid[myrow], pos0 = s_pos[myrow], rlen0 = s_rl[myrow], dir0 = s_dir[myrow];
-        rid1 = s_rid[pi], pos1 = s_pos[pi];
-        if (rid1 == rid0) valid = false;
+        fact = s_fact[myrow * 128 + (int)pi];
+        const uint32_t rid0 = s_rid[myrow], rid1 = s_rid[pi];
+        pair = rid0 < rid1 ? ((unsigned long long)rid0 << 32 | rid1) : ((unsigned long long)rid1 << 32 | rid0);
+        valid = (fact & FACT_VALID) != 0;
       }
-      uint32_t slot = NONE, v = 0;
-      const uint64_t pair = rid0 < rid1 ? ((uint64_t)rid0 << 32 | rid1) : ((uint64_t)rid1 << 32 | rid0);
-      if (valid) slot = pair_find(r, pair, &v);
-      bool present = false, accepted = false, guessed = false;
-      uint32_t ptype = 0, type = 0, mslot = NONE;
+      bool present = false, accepted = false, guessed = false, unfiled = true;
+      uint32_t ptype = 0, type = 0;
       if (valid) {
-        present = v != 0 && own_bucket(v) < j;
-        ptype = present ? own_type(v) : 0;
+        present = (fact & FACT_PRESENT) != 0;
+        ptype = present ? fact >> FACT_TYPE_SHIFT : 0;
         if (!present && dup) {   // inserted earlier in THIS evaluation?
           for (uint32_t i = (uint32_t)mix64(pair) & (SET_CAP - 1);; i = (i + 1) & (SET_CAP - 1)) {
             const unsigned long long kk = s_setk[i];
@@ -710,21 +800,8 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
             }
           }
         }
-        if (!present) {
-          const uint32_t rlen1 = s_rl[pi], dir1 = s_dir[pi];
-          const uint32_t q_off = pos0 - pos1;
-          if (q_off >= (1u << 30)) atomicOr(&r.c->overflow, OV_QOFF);
-          uint32_t req = NONE;
-          if (r.memo_used) mslot = memo_find(r, (unsigned long long)rid0 << 32 | rid1, q_off << 2 | dir0 << 1 | dir1, &req);
-          if (req < r.settled) {
-            accepted = classify(r.rq_res[req], rlen0, rlen1, q_off, &type);
-          } else {
-            accepted = true, guessed = true, type = T_OVERLAP;
-            if (r.predict && predict_contained(rlen0, rlen1, q_off, r.predict, r.predict2)) type = rlen0 >= rlen1 ? T_CONTAINS : T_CONTAINED;
-          }
-        }
+        if (!present) accepted = (fact & FACT_ACCEPTED) != 0, guessed = (fact & FACT_GUESSED) != 0, unfiled = (fact & FACT_UNFILED) != 0, type = fact >> FACT_TYPE_SHIFT;
       }
-      resolve_pending();   // (the previous step's registrations: their atomics have returned behind the loads above)
       const bool ins0 = valid && !present && accepted;
       uint32_t my_claim = NONE;
       if (dup) {   // would-be inserters claim their pair: the lowest walk index wins
@@ -743,7 +820,7 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       {
         const uint64_t mv = __ballot(valid), mp = __ballot(valid && present), mpo = __ballot(valid && present && ptype == T_OVERLAP);
         const uint64_t ma = __ballot(ins0), mao = __ballot(ins0 && type == T_OVERLAP), mac = __ballot(ins0 && type == T_CONTAINED);
-        const uint64_t map = __ballot(ins0 && type == T_CONTAINS), mgu = __ballot(ins0 && guessed), muf = __ballot(ins0 && mslot == NONE);
+        const uint64_t map = __ballot(ins0 && type == T_CONTAINS), mgu = __ballot(ins0 && guessed), muf = __ballot(ins0 && unfiled);
         if (lane == 0)
           s_m[w][MV] = mv, s_m[w][MP] = mp, s_m[w][MPO] = mpo, s_m[w][MA] = ma, s_m[w][MAO] = mao, s_m[w][MAC] = mac, s_m[w][MAP] = map,
           s_m[w][MGU] = mgu, s_m[w][MUF] = muf, s_m[w][MDF] = 0;
@@ -769,7 +846,6 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
         if (lane == 0) s_m[w][MDF] = mdf;
         __syncthreads();
       }
-      if (s_abort) break;
       // ---- the sequential semantics over this step: the rows in order, each over its 128 partners, lowest first (uniform) ----
       M128 proc[BIG_NR];
 #pragma unroll
@@ -778,7 +854,9 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       bool open_next = false;    // the row after them was cut: it is continued alone
       int open_row = 0;
       uint32_t open_pbase = 0, open_got = 0;
-      for (int k = 0; k < nrows; ++k) {
+#pragma unroll
+      for (int k = 0; k < BIG_NR; ++k) {
+        if (k >= nrows) break;
         // A partner that an EARLIER row of this step found contained (or that was such a row) is not examined by this row: its lane is dropped
         // from the row's masks right here.  (Round 3 ended the step at the first row that changed a flag and looked at the rows below again
         // in the next one.  Rows themselves are never flagged by an earlier row of the step: a row's partners lie above it.)
@@ -814,58 +892,34 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       ++st_steps, st_rows += (uint32_t)committed, st_cut += open_next ? 1u : 0u, st_full += (committed == nrows) ? 1u : 0u;
       st_cont += (!open_next && committed < nrows) ? 1u : 0u;
 #endif
-      if (committed) done_to = a[committed - 1];
+      // what the walk really visited and inserted of each row, for COMMIT: thread k notes row a[k] (offsets -> entry indices)
+#pragma unroll
+      for (int k = 0; k < BIG_NR; ++k)
+        if ((int)threadIdx.x == k && k < nrows && any128(proc[k])) {
+          const uint32_t first_k = row_open ? pbase : (uint32_t)(a[k] + 1);
+          const M128 v = shl128(and128(M128{s_m[2 * k][MV], s_m[2 * k + 1][MV]}, proc[k]), first_k);
+          const M128 in = shl128(and128(M128{s_m[2 * k][MA], s_m[2 * k + 1][MA]}, proc[k]), first_k);
+          s_vis[a[k]] = or128(s_vis[a[k]], v), s_ins[a[k]] = or128(s_ins[a[k]], in);
+        }
+#pragma unroll
+      for (int k = 0; k < BIG_NR; ++k)
+        if (k == committed - 1) done_to = a[k];
       row_open = open_next;
       if (open_next) cur_row = open_row, pbase = open_pbase, got = open_got;
-      // per wavefront: what the walk really visits, and the insertions in walk order (row, then partner)
-      uint32_t cins = 0, before = 0;
+      // per wavefront: what the walk really visits
       uint64_t myproc = 0;
+#pragma unroll
       for (int ww = 0; ww < BIG_NW; ++ww) {
         const int k = ww >> 1;
         const uint64_t pw = (ww & 1) ? proc[k].hi : proc[k].lo;
-        const uint32_t c = (uint32_t)__popcll(s_m[ww][MA] & pw);
-        if (ww < w) before += c;
         if (ww == w) myproc = pw;
-        cins += c;
+        num += (uint32_t)__popcll(s_m[ww][MA] & pw);
         skips += (uint32_t)__popcll(s_m[ww][MP] & pw);
         lookups += (uint32_t)__popcll(s_m[ww][MV] & ~s_m[ww][MP] & pw);
         any_guess |= (s_m[ww][MGU] & pw) != 0, any_unfiled |= (s_m[ww][MUF] & pw) != 0;
       }
-      // the item chunks this step opens (one allocation for the workgroup, by thread 0)
-      const uint32_t cur_no = num ? (num - 1) >> 4 : 0, first_new = num ? cur_no + 1 : 0;
-      const uint32_t last = num + cins - 1, last_no = last >> 4;
-      const uint32_t nnew = cins && last_no + 1 > first_new ? last_no + 1 - first_new : 0;
-      if (threadIdx.x == 0 && nnew) {
-        const uint32_t want = 16u * nnew;
-        if (icur + want > iend) {
-          const uint32_t take = want > ICH ? want : ICH;
-          const uint32_t base = atomicAdd(&r.c->item_top, take);
-          if ((uint64_t)base + take > r.item_cap) atomicOr(&r.c->overflow, OV_ITEMS), s_abort = 1;
-          icur = base, iend = base + take;
-        }
-        s_fresh = icur, icur += want;
-      }
-      const bool visited = valid && ((myproc >> lane) & 1);
-      {  // the partners the walk really examined register as readers of their pairs (as in k_eval_rows)
-        bool reg = visited;
-        if (reg && slot == NONE) slot = pair_slot(r, pair);
-        if (reg && !first_eval) {
-          const uint32_t *pw = reinterpret_cast<const uint32_t *>(&r.pc[slot >> r.cshift]);
-          const uint4 h1 = *reinterpret_cast<const uint4 *>(pw);  // cnt, rhead, in[0], in[1]
-          const uint32_t c = min(h1.x, NIN);
-          if ((c > 0 && h1.z == j + 1) || (c > 1 && h1.w == j + 1)) reg = false;
-          for (uint32_t qq = 2; qq < c && reg; qq += 8) {
-            const uint4 xa = *reinterpret_cast<const uint4 *>(pw + 2 + qq), xb = *reinterpret_cast<const uint4 *>(pw + 6 + qq);
-            const uint32_t x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k)
-              if (qq + k < c && x[k] == j + 1) reg = false;
-          }
-        }
-        if (reg) p_idx = atomicAdd(&r.pc[slot >> r.cshift].cnt, 1u), p_slot = slot, p_reg = true;
-      }
-      const bool my_ins = ins0 && visited;
       if (dup) {
+        const bool my_ins = ins0 && ((myproc >> lane) & 1);
         if (my_claim != NONE) s_clk[my_claim] = 0, s_clw[my_claim] = 0xFFFFFFFFu;   // (the claim table is empty again for the next step)
         if (my_ins) {   // this evaluation's insertions, for the probes of the steps to come
           uint32_t tries = 0;
@@ -882,32 +936,116 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
           }
         }
       }
-      __syncthreads();   // (s_fresh is there; nobody reads this step's masks any more; the set holds this step's insertions)
-      if (s_abort) break;
-      if (cins) {
-        const uint32_t fresh = s_fresh;
-        auto base_of = [&](uint32_t no) { return no >= first_new ? fresh + 16u * (no - first_new) : chunk; };
-        if (my_ins) {
-          const uint32_t ord = num + before + (uint32_t)__popcll(s_m[w][MA] & myproc & ((1ULL << lane) - 1ULL));   // insertion ordinal within the bucket
-          const uint32_t idx = base_of(ord >> 4) + (ord & 15);
-          uint32_t next;
-          if (ord == 0) next = NIL;
-          else if ((ord & 15) == 0) next = base_of((ord >> 4) - 1) + 16;  // the last item of the previous chunk, + 1
-          else next = idx;                                                // the item before this one, + 1
-          uint32_t info = (uint32_t)myrow | pi << 8 | type << 16;
-          if (guessed) info |= I_GUESS;
-          if (mslot == NONE) info |= I_UNFILED;
-          r.items[idx] = Item{slot, info, mslot, next};
-        }
-        chunk = base_of(last_no);
-        head = chunk + (last & 15) + 1;
-        num += cins;
-      }
-      __syncthreads();   // (s_m[w][MA] was read above: the next step may overwrite the masks now)
+      __syncthreads();   // (nobody reads this step's masks any more; the set holds this step's insertions; the rows' masks are noted)
       if (s_bail) break;
+    }
+    // ---- COMMIT (not on the guard path: nothing has been written for the bucket then) ----
+    bool p_reg = false;          // this lane has a registration whose list position (p_idx) has not been looked at yet
+    uint32_t p_idx = 0, p_slot = 0;
+    auto resolve_pending = [&]() {   // as in k_eval_rows; an exhausted arena raises s_abort instead of returning
+      if (p_reg && p_idx < NIN) r.pc[p_slot >> r.cshift].in[p_idx] = j + 1, p_reg = false;
+      const uint64_t rm = __ballot(p_reg);
+      if (rm) {
+        const uint32_t total = (uint32_t)__popcll(rm);
+        if (rcur + total > rend) {
+          uint32_t base = 0;
+          if (lane == 0) base = atomicAdd(&r.c->rnode_top, NCH);
+          base = (uint32_t)__shfl((int)base, 0, 64);
+          if ((uint64_t)base + NCH > r.rn_cap) {
+            atomicOr(&r.c->overflow, OV_NODES);
+            s_abort = 1;
+            p_reg = false;
+            return;
+          }
+          rcur = base, rend = base + NCH;
+        }
+        if (p_reg) {
+          const uint32_t node = rcur + lane_rank(rm);
+          const uint32_t old = atomicExch(&r.pc[p_slot >> r.cshift].rhead, node + 1);
+          r.rn[node] = RNode{old, j};
+        }
+        rcur += total;
+        p_reg = false;
+      }
+    };
+    if (!s_bail) {
+      // the rows' first insertion ordinals: a prefix count over the inserted masks in walk order (row n - 2 first)
+      if (threadIdx.x < 128) {
+        const int row = (int)n - 2 - (int)threadIdx.x;
+        const uint32_t c = row >= 0 ? (uint32_t)popc128(s_ins[row]) : 0u;
+        uint32_t incl = c;
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
+          if (lane >= o) incl += up;
+        }
+        if (lane == 63) s_wsum[w] = incl;
+        if (row >= 0) s_rbase[row] = incl - c;   // (the second wavefront's rows: + s_wsum[0], added where it is read)
+      }
+      if (threadIdx.x == 0 && num) {   // the item chunks of the evaluation: one allocation for the workgroup, by thread 0
+        const uint32_t want = 16u * ((num + 15) >> 4);
+        if (icur + want > iend) {
+          const uint32_t take = want > ICH ? want : ICH;
+          const uint32_t base = atomicAdd(&r.c->item_top, take);
+          if ((uint64_t)base + take > r.item_cap) atomicOr(&r.c->overflow, OV_ITEMS), s_abort = 1;
+          icur = base, iend = base + take;
+        }
+        s_fresh = icur, icur += want;
+      }
+      __syncthreads();   // (s_rbase, s_wsum, s_fresh)
+      if (!s_abort) {
+        const uint32_t fresh = s_fresh;   // the chunks are consecutive: the item of ordinal o is fresh + o
+        const int half = w & 1;
+        for (int row = (int)n - 2 - (w >> 1); row >= 0; row -= BIG_NR) {   // a wavefront per (row, half of its partners)
+          const uint64_t vm = half ? s_vis[row].hi : s_vis[row].lo, im = half ? s_ins[row].hi : s_ins[row].lo;
+          if (!vm) continue;
+          const uint32_t pi = (uint32_t)(half * 64 + lane);
+          bool reg = ((vm >> lane) & 1) != 0;   // the partners the walk really examined register as readers of their pairs (as in k_eval_rows)
+          const bool my_ins = ((im >> lane) & 1) != 0;
+          uint32_t slot = NONE, rid0 = 0, rid1 = 0;
+          if (reg) {
+            rid0 = s_rid[row], rid1 = s_rid[pi];
+            slot = pair_slot(r, rid0 < rid1 ? ((uint64_t)rid0 << 32 | rid1) : ((uint64_t)rid1 << 32 | rid0));
+          }
+          uint32_t mslot = NONE;
+          const uint32_t fact = my_ins ? s_fact[row * 128 + (int)pi] : 0u;
+          if (my_ins && !(fact & FACT_UNFILED)) {
+            uint32_t req;
+            mslot = memo_find(r, (unsigned long long)rid0 << 32 | rid1, (s_pos[row] - s_pos[pi]) << 2 | (uint32_t)s_dir[row] << 1 | s_dir[pi], &req);
+          }
+          resolve_pending();   // (the previous row's registrations: their atomics have returned behind the loads above)
+          if (reg && !first_eval) {
+            const uint32_t *pw = reinterpret_cast<const uint32_t *>(&r.pc[slot >> r.cshift]);
+            const uint4 h1 = *reinterpret_cast<const uint4 *>(pw);  // cnt, rhead, in[0], in[1]
+            const uint32_t c = min(h1.x, NIN);
+            if ((c > 0 && h1.z == j + 1) || (c > 1 && h1.w == j + 1)) reg = false;
+            for (uint32_t qq = 2; qq < c && reg; qq += 8) {
+              const uint4 xa = *reinterpret_cast<const uint4 *>(pw + 2 + qq), xb = *reinterpret_cast<const uint4 *>(pw + 6 + qq);
+              const uint32_t x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+              for (uint32_t k = 0; k < 8; ++k)
+                if (qq + k < c && x[k] == j + 1) reg = false;
+            }
+          }
+          if (reg) p_idx = atomicAdd(&r.pc[slot >> r.cshift].cnt, 1u), p_slot = slot, p_reg = true;
+          if (my_ins) {
+            const uint32_t ord = s_rbase[row] + ((int)n - 2 - row >= 64 ? s_wsum[0] : 0u) + (half ? (uint32_t)__popcll(s_ins[row].lo) : 0u) +
+                                 (uint32_t)__popcll(im & ((1ULL << lane) - 1ULL));   // insertion ordinal within the bucket
+            const uint32_t idx = fresh + ord;
+            uint32_t info = (uint32_t)row | pi << 8 | (fact >> FACT_TYPE_SHIFT) << 16;
+            if (fact & FACT_GUESSED) info |= I_GUESS;
+            if (mslot == NONE) info |= I_UNFILED;
+            r.items[idx] = Item{slot, info, mslot, ord == 0 ? NIL : idx};   // next: the item before this one, + 1 (also across a chunk's edge)
+          }
+        }
+        if (num) head = fresh + num;   // the last item, + 1
+      }
     }
     resolve_pending();
 #ifdef PGX_BIG_STATS
+    {
+      for (int o = 32; o; o >>= 1) st_pairs += (uint32_t)__shfl_xor((int)st_pairs, o, 64);
+      if (lane == 0) atomicAdd(&r.c->big_pairs, (unsigned long long)st_pairs);
+    }
     if (threadIdx.x == 0) {   // [3] steps, [4] rows committed, [5] steps cut at a duplicate, [6] steps ended by a containment, [7] steps that committed all their rows
       unsigned long long *line = r.spread + (blockIdx.x % SPREAD) * 8;
       atomicAdd(line + 3, (unsigned long long)st_steps), atomicAdd(line + 4, (unsigned long long)st_rows), atomicAdd(line + 5, (unsigned long long)st_cut);
@@ -918,7 +1056,7 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
     }
 #endif
     if (threadIdx.x == 0) {
-      if (s_bail) {   // (guard path: evaluated again by k_eval_rows, one partner at a time; the lists written so far are simply dropped)
+      if (s_bail) {   // (guard path: evaluated again by k_eval_rows, one partner at a time; COMMIT was skipped, so nothing of this evaluation is left)
         r.dirty[j] = 1, r.evaluated[j] = 0, r.parity[j] ^= 1;
         r.bflags[j] = (uint8_t)((r.bflags[j] & ~F_BIG));
       } else {
