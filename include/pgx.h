@@ -63,7 +63,8 @@ void pgx_free(void *p);              /* releases any host array returned by this
 /* per-kernel device time (HIP events on the library's stream), accumulated since the last reset.
  * names: "sketch", "sketch_general", "sketch_redo", "sketch_nreads", "sketch_gather", "pack", "reduce", "count", "pairs", "replay_dense" / "replay_rows" / "replay_update" (k_eval, k_eval_rows, k_update of the device replay; only with PGX_REPLAY_TIMING=1), "align" (k_align_ph), "align1" (k_align1: launches of
  * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map", "sgraph" (the string graph: build and text; its parts also as "sgraph_edges", "sgraph_adj", "sgraph_tr", "sgraph_spur",
- * "sgraph_best", "sgraph_text"), "unitigs" (its parts: "unitigs_links", "unitigs_rank", "unitigs_paths", "unitigs_text"). */
+ * "sgraph_best", "sgraph_text"), "unitigs" (its parts: "unitigs_links", "unitigs_rank", "unitigs_paths", "unitigs_text"), "ctg_paths" (its parts:
+ * "ctg_paths_graph", "ctg_paths_clean", "ctg_paths_walk", "ctg_paths_text"). */
 int pgx_timing_get(const char *kernel, double *total_ms, uint64_t *launches, uint64_t *units);
 void pgx_timing_reset(void);
 /* HBM ledger: JSON text of the library's device memory -- live bytes, bytes held in the block cache, and the live bytes BY OWNER (seqdb,
@@ -353,7 +354,8 @@ int pgx_sgraph_free(pgx_sgraph *g);
  *   order     every directed G edge lies in exactly one unitig (a path and its reverse are two); unitigs are numbered, and lines written,
  *             in ascending creation index of their first edge.
  *   line      "s via t simple length score n0~n1~...~nk\n", node names as in sg_edges_list ("%09d" of the signed rid, ":B" or ":E").
- * The later phases of the script (unitig spurs, duplicate paths, compound paths, contig paths) pop from sets of strings and are not offered.
+ * The later phases of the script (unitig spurs, duplicate paths, compound paths, contig paths) pop from sets of strings: they are offered
+ * with every such container given an order, below ("contig paths").
  * All on the device, on the library's stream: one sort per edge list, list ranking by pointer doubling (a logarithmic number of passes
  * whatever the length of a path), no launch per unitig.  Device memory is booked as "unitigs", time as "unitigs" with the parts
  * "unitigs_links", "unitigs_rank", "unitigs_paths", "unitigs_text".
@@ -435,6 +437,51 @@ typedef struct { uint32_t ctg, rid0, rid1; int32_t s, e; uint8_t strand0, strand
 int pgx_contigs_resident(pgx_seqdb *db, const pgx_tile_row *rows, size_t n_rows, size_t n_ctg, char **text, uint64_t *ctg_off,
                          uint64_t *text_len);
 int pgx_contigs_chunk(const char *seqdb_prefix, const char *tiling_path, const char *out_path, uint64_t *n_ctg, uint64_t *n_bases);
+
+/* ---- contig paths (the phases of py/scripts/ovlp_to_graph.py after identify_simple_paths, :1147-1555): from the unitigs to the final
+ * utg_data (:1478-1487) and ctg_paths (:1496-1555).  The script pops from sets of strings, so its files vary with PYTHONHASHSEED; the
+ * rule here is the script's algorithm with every unordered container given an order -- a node is its key
+ * (rid << 1) | end, a unitig its index (pgx_unitigs' numbering; compound unitigs follow in order of creation), sets pop their smallest
+ * element, a node's edges iterate in ascending unitig index -- and equals the script wherever the script has one answer, with one
+ * exception: where the script removes a spur it writes the spur's own length, score and path over its dual's entry (:1210-1212); here the
+ * dual's `spur:2` line keeps its own.  `via` stays
+ * the path's second node; a unitig's reverse is its DUAL by structure (the unitig that starts with the reverse of its last edge; a ring
+ * has none: PGX_CTG_NONE).  Chimer bridge removal and --lfc are off; c_path, chimers_nodes and utg_data0 are not written.
+ *   pgx_unitigs_contig_paths : of live unitigs (either builder's).  The unitigs are not changed; the simple lines of utg_data read their
+ *                              path arrays, so pgx_ctg_paths_utg_text answers PGX_ESTATE once they are freed (the rest keeps working).
+ *   pgx_ctg_paths_build      : of n host edge records in creation order (a parsed sg_edges_list, whoever wrote it): pgx_unitigs_build
+ *                              (its checks, its messages), then the above; the unitigs belong to the result.
+ *     PGX_EINVAL where the script asserts or raises, with the unitig or node named: a unitig without a dual, two short s == t loops at one
+ *     node, a bundle in which no in-edge has a positive score, a repeat bridge whose dual left the graph.  PGX_ENOMEM: no device memory
+ *     (the unitigs stay as they were).
+ *   pgx_ctg_paths_stats  : the counts; spur_rounds: paths removed by the two spur passes; host_us: the serial cascades over the unitig
+ *                          table, which run on the host; device_walks: contig walks made on the device (a lane per start edge):
+ *                          all that leave a start node, unless walks sharing a stretch are still unsettled after 64 rounds -- those go to the host,
+ *                          and which ones they are may differ from run to run (the files never do).
+ *   pgx_ctg_paths_table  : n entries from unitig `first` on (stats.unitigs in all): final type (PGX_CTG_*) and dual.
+ *   pgx_ctg_paths_rows   : the unitig lists of the lines of ctg_paths, as indices: line l's are unitig[row_off[l] .. row_off[l + 1])
+ *                          (row_off: ctg_lines + 1 entries, unitig: row_entries; either may be NULL).
+ *   pgx_ctg_paths_utg_text / _ctg_text : the lines of the two files in pieces, with pgx_sgraph_text's conventions; each keeps its own place.
+ *   pgx_ctg_paths_free   : releases them (NULL is accepted).
+ * After pgx_shutdown every call but pgx_ctg_paths_free answers PGX_ESTATE.  Device memory is booked as "ctg_paths", time as "ctg_paths"
+ * with the parts "ctg_paths_graph", "ctg_paths_clean", "ctg_paths_walk", "ctg_paths_text". */
+enum { PGX_CTG_SIMPLE = 0, PGX_CTG_SPUR2 = 1, PGX_CTG_SIMPLE_DUP = 2, PGX_CTG_CONTAINED = 3, PGX_CTG_REPEAT_BRIDGE = 4, PGX_CTG_COMPOUND = 5 };
+#define PGX_CTG_NONE 0xFFFFFFFFu
+typedef struct {
+  uint32_t type, dual;
+} pgx_ctg_unitig;
+typedef struct {
+  uint64_t unitigs, simple, spur2, simple_dup, contained, repeat_bridge, compound, ctg_linear, ctg_circular, ctg_lines, row_entries, longest_ctg, spur_rounds, host_us, device_walks;
+} pgx_ctg_paths_stats_t;
+typedef struct pgx_ctg_paths pgx_ctg_paths;
+int pgx_unitigs_contig_paths(pgx_unitigs *u, pgx_ctg_paths **out);
+int pgx_ctg_paths_build(const pgx_sgraph_edge *edges, uint64_t n, pgx_ctg_paths **out);
+int pgx_ctg_paths_stats(const pgx_ctg_paths *c, pgx_ctg_paths_stats_t *out);
+int pgx_ctg_paths_table(const pgx_ctg_paths *c, uint64_t first, uint64_t n, pgx_ctg_unitig *out);
+int pgx_ctg_paths_rows(const pgx_ctg_paths *c, uint64_t *row_off, uint32_t *unitig);
+int pgx_ctg_paths_utg_text(pgx_ctg_paths *c, uint64_t max_lines, char **text, size_t *text_len, int *done);
+int pgx_ctg_paths_ctg_text(pgx_ctg_paths *c, uint64_t max_lines, char **text, size_t *text_len, int *done);
+int pgx_ctg_paths_free(pgx_ctg_paths *c);
 
 /* ---- tiling paths (replaces py/scripts/graph_to_path.py, pg_run.py:355): from sg_edges_list, utg_data and ctg_paths to p_ctg_tiling_path
  * and a_ctg_tiling_path, byte for byte the script's files, and to the same rows as pgx_tile_row ("tiling paths", states the rule).

@@ -394,6 +394,7 @@ struct sgraph_opts {
   long long min_len;
   double min_idt;
   const char *utg;   /* --utg FILE: the unitigs' lines go there (NULL: none are made) */
+  const char *utg_data, *ctg_paths;   /* --utg-data FILE, --ctg-paths FILE: the final utg_data and ctg_paths (NULL: not written) */
 };
 /* What every hand-out of text ends with: the status of the call `what` reported, or its text written to f (named fname in the
  * complaint); the text is freed either way.  Returns the exit code so far. */
@@ -408,6 +409,8 @@ static int put_text(const char *tool, const char *what, int status, char *text, 
 typedef int (*next_text_fn)(void *obj, uint64_t max_lines, char **text, size_t *len, int *done);
 static int next_sgraph_text(void *g, uint64_t n, char **text, size_t *len, int *done) { return pgx_sgraph_text((pgx_sgraph *)g, n, text, len, done); }
 static int next_unitigs_text(void *u, uint64_t n, char **text, size_t *len, int *done) { return pgx_unitigs_text((pgx_unitigs *)u, n, text, len, done); }
+static int next_ctg_utg_text(void *c, uint64_t n, char **text, size_t *len, int *done) { return pgx_ctg_paths_utg_text((pgx_ctg_paths *)c, n, text, len, done); }
+static int next_ctg_ctg_text(void *c, uint64_t n, char **text, size_t *len, int *done) { return pgx_ctg_paths_ctg_text((pgx_ctg_paths *)c, n, text, len, done); }
 static int next_drain_text(void *s, uint64_t n, char **text, size_t *len, int *done) { return pgx_dedup_drain((pgx_dedup_stream *)s, n, text, len, done); }
 /* all the text obj still has, in pieces of `piece` lines, to f */
 static int write_pieces(const char *tool, const char *what, next_text_fn next, void *obj, size_t piece, FILE *f, const char *fname) {
@@ -420,19 +423,29 @@ static int write_pieces(const char *tool, const char *what, next_text_fn next, v
   }
   return 0;
 }
-/* the unitigs of g as text to the file at path */
-static int write_unitigs(const char *tool, pgx_sgraph *g, const char *path, size_t piece) {
+/* all the text of obj to the file at path */
+static int write_text_file(const char *tool, const char *what, next_text_fn next, void *obj, size_t piece, const char *path) {
   FILE *f = fopen(path, "wb");
   if (!f) {
     perror(path);
     return 1;
   }
+  int rc = write_pieces(tool, what, next, obj, piece, f, path);
+  if (fclose(f) && !rc) rc = 1, perror(path);
+  return rc;
+}
+/* the unitigs of g: their lines to sg->utg, the final utg_data and ctg_paths made of them to sg->utg_data and sg->ctg_paths (each if named) */
+static int write_unitigs(const char *tool, pgx_sgraph *g, const struct sgraph_opts *sg, size_t piece) {
   pgx_unitigs *u = NULL;
+  pgx_ctg_paths *c = NULL;
   int rc = 0;
   if (pgx_sgraph_unitigs(g, &u)) rc = fail(tool, "pgx_sgraph_unitigs");
-  else rc = write_pieces(tool, "pgx_unitigs_text", next_unitigs_text, u, piece, f, path);
+  if (!rc && sg->utg) rc = write_text_file(tool, "pgx_unitigs_text", next_unitigs_text, u, piece, sg->utg);
+  if (!rc && (sg->utg_data || sg->ctg_paths) && pgx_unitigs_contig_paths(u, &c)) rc = fail(tool, "pgx_unitigs_contig_paths");
+  if (!rc && sg->utg_data) rc = write_text_file(tool, "pgx_ctg_paths_utg_text", next_ctg_utg_text, c, piece, sg->utg_data);
+  if (!rc && sg->ctg_paths) rc = write_text_file(tool, "pgx_ctg_paths_ctg_text", next_ctg_ctg_text, c, piece, sg->ctg_paths);
+  pgx_ctg_paths_free(c);
   pgx_unitigs_free(u);
-  if (fclose(f) && !rc) rc = 1, perror(path);
   return rc;
 }
 static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg) {
@@ -480,7 +493,7 @@ static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg
   pgx_sgraph *g = NULL;
   if (sg && ds && !rc && pgx_sgraph_build(ds, sg->min_len, sg->min_idt, 0, &g)) rc = fail(tool, "pgx_sgraph_build");
   if (g) rc = write_pieces(tool, "pgx_sgraph_text", next_sgraph_text, g, piece, stdout, "stdout");
-  if (g && sg->utg && !rc) rc = write_unitigs(tool, g, sg->utg, piece);
+  if (g && (sg->utg || sg->utg_data || sg->ctg_paths) && !rc) rc = write_unitigs(tool, g, sg, piece);
   pgx_sgraph_free(g);
   if (graph && !sg && ds && !rc) rc = write_pieces(tool, "pgx_dedup_drain", next_drain_text, ds, piece, stdout, "stdout");
   if (ds) pgx_dedup_close(ds, NULL, NULL);
@@ -494,10 +507,10 @@ static int main_dedup(int argc, char **argv) {
   return dedup_stdin("shmr_dedup", graph, NULL);
 }
 
-/* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] [--utg FILE] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
+/* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
  * --disable_chimer_bridge_removal and without --lfc -- the only setting offered */
 static int main_sgraph(int argc, char **argv) {
-  struct sgraph_opts o = {4000, 96.0, NULL};
+  struct sgraph_opts o = {4000, 96.0, NULL, NULL, NULL};
   for (int i = 1; i < argc; ++i) {
     const char *a = argv[i], *v = NULL;
     const int len_opt = strncmp(a, "--min_len", 9) == 0 && (a[9] == 0 || a[9] == '='), idt_opt = strncmp(a, "--min_idt", 9) == 0 && (a[9] == 0 || a[9] == '=');
@@ -516,6 +529,14 @@ static int main_sgraph(int argc, char **argv) {
         fprintf(stderr, "shmr_sgraph: --utg needs a file name\n");
         return 2;
       }
+    } else if ((strncmp(a, "--utg-data", 10) == 0 && (a[10] == 0 || a[10] == '=')) || (strncmp(a, "--ctg-paths", 11) == 0 && (a[11] == 0 || a[11] == '='))) {
+      const size_t nl = a[2] == 'u' ? 10 : 11;
+      const char **dst = a[2] == 'u' ? &o.utg_data : &o.ctg_paths;
+      *dst = a[nl] ? a + nl + 1 : (i + 1 < argc ? argv[++i] : NULL);
+      if (!*dst || !**dst) {
+        fprintf(stderr, "shmr_sgraph: %.*s needs a file name\n", (int)nl, a);
+        return 2;
+      }
     } else if (strcmp(a, "--lfc") == 0) {
       fprintf(stderr, "shmr_sgraph: --lfc is not offered (pg_run.py leaves it off)\n");
       return 2;
@@ -526,7 +547,7 @@ static int main_sgraph(int argc, char **argv) {
                       "compare with ovlp_to_graph.py --disable_chimer_bridge_removal\n");
       return 2;
     } else {
-      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal] [--utg FILE] < ovlp.dat > sg_edges_list\n");
+      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] < ovlp.dat > sg_edges_list\n");
       return 2;
     }
   }

@@ -48,4 +48,15 @@ void graph_compact(pgx_dedup_stream *s);
 // a live graph's edge records on the device, in creation order with their final types (pgx_sgraph.hip; `who` names the caller in the
 // error a freed context gives); what reads them runs on ctx().stream, behind the build
 const pgx_sgraph_edge *sgraph_device_edges(const pgx_sgraph *g, const char *who, uint64_t *n);
+// live unitigs' arrays on the device (pgx_unitigs.hip): the table, the path array (creation indices, unitig after unitig) and, per path
+// slot, its unitig and the key of the node its edge enters.  Nothing is copied: the view holds while the unitigs live.
+struct UnitigsView {
+  const pgx_unitig *tab;
+  const uint32_t *paths, *slot_u;
+  const uint64_t *slot_w;
+  uint64_t n_u, m;
+  uint64_t serial;   // which unitigs these are: never given twice, whatever address a later object gets
+};
+UnitigsView unitigs_device_view(const pgx_unitigs *u, const char *who);
+bool unitigs_live(const pgx_unitigs *u, uint64_t serial);   // the unitigs of that serial: handed out by a builder, not freed, no pgx_shutdown since
 }  // namespace pgx

@@ -174,6 +174,12 @@ class LiveSet {
     std::lock_guard<std::mutex> lk(mu);
     for (T *t : live) t->drop_device_state(), t->shut = true;
   }
+  bool contains(const T *t) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (T *x : live)
+      if (x == t) return true;
+    return false;
+  }
   // the end of t (a member or not): what is enqueued may still read its buffers, so the stream drains first
   void destroy(T *t) {
     {

@@ -17,6 +17,8 @@
 // pred, and a second ranking settles the rings like paths.
 // No result depends on the order in which atomics land: they take a minimum (the first offending edge) or count.
 
+#include <atomic>
+
 #include "pgx_dedup_rows.h"
 
 typedef pgx_sgraph_edge Edge;
@@ -262,6 +264,7 @@ struct pgx_unitigs {
   DevBuf<uint64_t> line_off;     // unitigs + 1: where each line starts
   pgx_unitigs_stats_t st = {};
   uint64_t cursor = 0;           // lines handed out as text
+  uint64_t serial = 0;           // of this object among all unitigs ever built (> 0): an address may come again, a serial does not
   TextStage stage;
   bool shut = false;
   void drop_device_state() {
@@ -393,6 +396,14 @@ void require_unitigs(const pgx_unitigs *u, const char *who) {
   PGX_REQUIRE(!u->shut && ctx().ready, PGX_ESTATE, "%s: pgx_shutdown ran while the unitigs were alive (free them)", who);
 }
 
+}  // namespace
+UnitigsView unitigs_device_view(const pgx_unitigs *u, const char *who) {
+  require_unitigs(u, who);
+  return UnitigsView{u->tab.p, u->paths.p, u->slot_u.p, u->slot_w.p, u->st.unitigs, u->st.g_edges, u->serial};
+}
+bool unitigs_live(const pgx_unitigs *u, uint64_t serial) { return u && g_ut.contains(u) && u->serial == serial && !u->shut && ctx().ready; }
+namespace {
+
 // the common part of the two builders: edges() answers the device edge records once the context is known to be up
 template <class EdgesFn>
 int build_entry(const char *who, pgx_unitigs **out, EdgesFn &&edges) {
@@ -409,6 +420,8 @@ int build_entry(const char *who, pgx_unitigs **out, EdgesFn &&edges) {
       const Edge *d_edges = edges(own, &n);
       KernelTimer tm("unitigs", n);
       u = new pgx_unitigs;
+      static std::atomic<uint64_t> serials{0};
+      u->serial = ++serials;
       build_unitigs(d_edges, n, u);
     } catch (const Fail &f) {
       code = build_fail_code(f, who, "unitigs", n, "edges");

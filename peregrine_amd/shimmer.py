@@ -521,6 +521,116 @@ class Unitigs(_DeviceText):
         return out
 
 
+    def contig_paths(self) -> "ContigPaths":
+        """the final utg_data and ctg_paths of these unitigs (pgx_unitigs_contig_paths); utg_text() reads these unitigs' paths: keep them
+        open until it was drawn"""
+        c = C.c_void_p()
+        _lib.check(self._lib.pgx_unitigs_contig_paths(self._handle("pgx_unitigs_contig_paths"), C.byref(c)), "pgx_unitigs_contig_paths")
+        return ContigPaths(c, keep=self)
+
+
+CTG_UNITIG_DTYPE = np.dtype([("type", "<u4"), ("dual", "<u4")])   # pgx_ctg_unitig
+CTG_TYPES = ("simple", "spur:2", "simple_dup", "contained", "repeat_bridge", "compound")   # `type` indexes these
+CTG_NONE = 0xFFFFFFFF   # the dual of a ring
+_CTG_PATHS_STATS = ("unitigs", "simple", "spur2", "simple_dup", "contained", "repeat_bridge", "compound", "ctg_linear", "ctg_circular", "ctg_lines", "row_entries",
+                    "longest_ctg", "spur_rounds", "host_us", "device_walks")   # pgx_ctg_paths_stats_t
+
+
+class ContigPaths:
+    """The final unitigs and the contig paths of a string graph (Unitigs.contig_paths, shimmer.contig_paths): what the second half of
+    ovlp_to_graph.py writes as utg_data and ctg_paths, by the script's algorithm with every unordered container given an order (DESIGN.md
+    4.5e).  stats: the counts; table(): type and dual per unitig (the simple ones as Unitigs numbers them, then the compound ones); rows():
+    the unitig indices of every line of ctg_paths; utg_text() / ctg_text(): the two files; tiling(sg): the tiling paths, no file written."""
+
+    def __init__(self, handle, keep=None):
+        self._lib = _lib.load()
+        self.h = handle
+        self._keep = keep   # the unitigs the simple lines are read from, if they are the caller's
+        st = (C.c_uint64 * len(_CTG_PATHS_STATS))()
+        _lib.check(self._lib.pgx_ctg_paths_stats(self.h, st), "pgx_ctg_paths_stats")
+        self.stats = dict(zip(_CTG_PATHS_STATS, (int(v) for v in st)))
+
+    def _handle(self, who):
+        if not self.h:
+            raise _lib.PgxError(f"{who}: the contig paths are closed")
+        return self.h
+
+    def table(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        n = self.stats["unitigs"] - first if n is None else n
+        out = np.zeros(n, CTG_UNITIG_DTYPE)
+        _lib.check(self._lib.pgx_ctg_paths_table(self._handle("pgx_ctg_paths_table"), int(first), int(n), _ptr(out)), "pgx_ctg_paths_table")
+        return out
+
+    def rows(self) -> list:
+        """per line of ctg_paths its unitigs, as an array of indices"""
+        off, u = np.zeros(self.stats["ctg_lines"] + 1, np.uint64), np.zeros(self.stats["row_entries"], np.uint32)
+        _lib.check(self._lib.pgx_ctg_paths_rows(self._handle("pgx_ctg_paths_rows"), _ptr(off), _ptr(u)), "pgx_ctg_paths_rows")
+        return [u[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
+
+    def utg_pieces(self, max_lines: int = 1 << 20):
+        return _text_pieces(self._lib.pgx_ctg_paths_utg_text, "pgx_ctg_paths_utg_text", self._handle, max_lines)
+
+    def ctg_pieces(self, max_lines: int = 1 << 20):
+        return _text_pieces(self._lib.pgx_ctg_paths_ctg_text, "pgx_ctg_paths_ctg_text", self._handle, max_lines)
+
+    def utg_text(self, max_lines: int = 1 << 20) -> bytes:
+        """the lines of utg_data not handed out yet"""
+        return b"".join(self.utg_pieces(max_lines))
+
+    def ctg_text(self, max_lines: int = 1 << 20) -> bytes:
+        """the lines of ctg_paths not handed out yet"""
+        return b"".join(self.ctg_pieces(max_lines))
+
+    def write(self, utg_fn: str | None, ctg_fn: str | None) -> int:
+        """the two files (None: not that one); returns the bytes written"""
+        n = 0
+        for fn, pieces in ((utg_fn, self.utg_pieces), (ctg_fn, self.ctg_pieces)):
+            if fn is not None:
+                with open(fn, "wb") as f:
+                    for piece in pieces():
+                        f.write(piece)
+                        n += len(piece)
+        return n
+
+    def tiling(self, sg) -> "TilingPaths":
+        """the tiling paths of graph sg (a live StringGraph, or the path of a sg_edges_list file), these unitigs and these contig paths
+        (pgx_tiling_build on the two texts; no file is written)"""
+        utg, ctg = self.utg_text(), self.ctg_text()
+        if isinstance(sg, StringGraph):
+            return sg.tiling(utg, ctg)
+        t = C.c_void_p()
+        _lib.check(self._lib.pgx_tiling_build(str(sg).encode(), None, utg, len(utg), ctg, len(ctg), C.byref(t)), "pgx_tiling_build")
+        return TilingPaths(t)
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        self._keep = None
+        if h:
+            _lib.check(self._lib.pgx_ctg_paths_free(h), "pgx_ctg_paths_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def contig_paths(edges, device=None) -> ContigPaths:
+    """The contig paths of edge records (SGRAPH_EDGE_DTYPE) in creation order, e.g. read_sg_edges_list's, in one call (pgx_ctg_paths_build)"""
+    _lib.init(device)
+    e = np.ascontiguousarray(edges, SGRAPH_EDGE_DTYPE)
+    c = C.c_void_p()
+    _lib.check(_lib.load().pgx_ctg_paths_build(_ptr(e) if len(e) else None, len(e), C.byref(c)), "pgx_ctg_paths_build")
+    return ContigPaths(c)
+
+
 def unitigs(edges, device=None) -> Unitigs:
     """The unitigs of edge records (SGRAPH_EDGE_DTYPE) in creation order, e.g. read_sg_edges_list's; only `type` 0 (G) takes part"""
     _lib.init(device)
@@ -681,9 +791,11 @@ def graph_to_path(sg, utg_data: str, ctg_paths: str, p_out: str | None = None, a
     return dict(zip(_TILING_STATS, (int(v) for v in st)))
 
 
-def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None, utg_path: str | None = None) -> dict:
+def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None, utg_path: str | None = None, utg_data_path: str | None = None,
+                ctg_paths_path: str | None = None) -> dict:
     """cat ovlp*.dat | shmr_sgraph > sg_edges_list: the files through a graph-mode DedupStream piece by piece, the graph, its text to
-    out_path (and, with utg_path, its unitigs' lines to that file).  Returns the graph's statistics."""
+    out_path (and, with utg_path, its unitigs' lines to that file; with utg_data_path / ctg_paths_path the final utg_data / ctg_paths).
+    Returns the graph's statistics."""
     _lib.init(device)
     if isinstance(ovlp_paths, (str, bytes)):
         ovlp_paths = [ovlp_paths]
@@ -699,9 +811,13 @@ def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float =
                         break
         with ds.string_graph(min_len, min_idt) as g:
             g.write(out_path)
-            if utg_path is not None:
+            if utg_path is not None or utg_data_path is not None or ctg_paths_path is not None:
                 with g.unitigs() as u:
-                    u.write(utg_path)
+                    if utg_path is not None:
+                        u.write(utg_path)
+                    if utg_data_path is not None or ctg_paths_path is not None:
+                        with u.contig_paths() as c:
+                            c.write(utg_data_path, ctg_paths_path)
             return g.stats
 
 
