@@ -63,8 +63,17 @@ struct alignas(64) Counters {   // three cache lines: the arenas, the dirty stat
   uint32_t pad1[10];
   unsigned long long lookups, skips, evals, records;
 #ifdef PGX_BIG_STATS
-  uint32_t big_max_steps, big_long, big_long_n, big_evals;
-  unsigned long long big_pairs, pad2[1];   // pairs k_eval_big's LOOK phase looked up
+  // k_eval_big's walk, counted per evaluation and added up in the spread lines (words 3 .. 7): row passes (a row's partners, 64 at a time), rows
+  // completed, passes cut at a duplicate (two partners of the pass with the same read: the row goes on from the second one in its next pass),
+  // rows ended by a containment, rows that took more than one pass.  Here: the longest evaluation in passes, the evaluations of 64 passes and
+  // more (and the sum of their entries), all evaluations, the pairs LOOK looked up.
+  uint32_t big_max_passes, big_long, big_long_n, big_evals;
+  unsigned long long big_pairs, pad2[1];
+  // the phases in ticks of wall_clock64() (10 ns), read by thread 0 at the phase boundaries: summed over all evaluations (LOOK, WALK, COMMIT); and
+  // summed over the launches for the LONGEST evaluation of each launch -- what a pass waits for.  big_lmax holds the running launch's longest one
+  // (total << 40 | WALK << 20 | LOOK); the last workgroup of a launch to finish (big_ticket) adds it to big_cyc_long and clears it.
+  unsigned long long big_cyc[3], big_lmax, big_cyc_long[3];
+  uint32_t big_ticket, big_launches;
 #else
   unsigned long long pad2[4];
 #endif
@@ -262,6 +271,10 @@ __device__ __forceinline__ int nth128(M128 m, uint32_t nth) {   // position of t
   for (uint32_t k = 1; k < nth; ++k) w &= w - 1;
   return base + __builtin_ctzll(w);
 }
+__device__ __forceinline__ int nth64(uint64_t m, uint32_t nth) {   // the same within one word (nth >= 1, nth <= popcount(m))
+  for (uint32_t k = 1; k < nth; ++k) m &= m - 1;
+  return __builtin_ctzll(m);
+}
 __device__ __forceinline__ M128 upto128(int stop) {   // bits 0 .. stop (stop >= 127: all)
   M128 m;
   m.lo = stop >= 63 ? ~0ULL : ((2ULL << stop) - 1ULL);
@@ -292,36 +305,45 @@ __device__ __forceinline__ M128 or128(M128 a, M128 b) { return M128{a.lo | b.lo,
 // count towards bestn: every row scans most of its partners.  With a wavefront per bucket (k_eval_rows: four rows x 16 partners,
 // a row that needs more continued alone, 64 partners per step) that is 100-200 dependent steps of ~20 us -- 3.4 ms per
 // evaluation, and a sparse pass lasts as long as its largest bucket: 0.47 s of a 1.07 s step at C4 scale went there
-// (profiles/r03a_kernel_stats_bench_c4s.txt), and the ~15 tail sweeps of a human-scale chunk are little else.  Here eight
-// wavefronts take FOUR rows x 128 partners per step (a bucket holds at most 128 entries, so a row is always complete within its
-// step): the rows are committed in order through masks exchanged in LDS, exactly like k_eval_rows' four-row form; a partner that an
-// earlier row of the step found contained is dropped from the later rows' masks in place (round 4).
-// The steps themselves touch LDS only.  What a step needs to know of a (row, partner) pair -- is it in the pair table under an earlier
-// bucket and with which type; if not, is its alignment filed, settled and accepted, and of which type, or which type is guessed -- depends
-// on the bucket's entries and on tables that nothing changes while the evaluation kernels run.  A bucket has at most 128 entries, 8,128
-// pairs: LOOK finds all of that for every pair first, LOOK_NB pairs per lane with their probes in flight together, and leaves a byte per
-// pair (FACT_*).  The walk notes what it visited and inserted in two 128-bit masks per row, and COMMIT, again parallel over the pairs,
-// registers the visited ones as readers and writes the inserted ones as the bucket's item list.  (Before, every step paid the chain
-// pair probe -> memo probe -> result -> slot -> reader header -> count, each as long as the unluckiest of 512 lanes made it.)
+// (profiles/r03a_kernel_stats_bench_c4s.txt), and the ~15 tail sweeps of a human-scale chunk are little else.  Here a workgroup of
+// eight wavefronts takes a bucket through three phases:
+// LOOK (eight wavefronts).  What the walk needs to know of a (row, partner) pair -- is it in the pair table under an earlier bucket and
+// with which type; if not, is its alignment filed, settled and accepted, and of which type, or which type is guessed -- depends on the
+// bucket's entries and on tables that nothing changes while the evaluation kernels run.  A bucket has at most 128 entries, 8,128 pairs:
+// LOOK finds all of that for every pair first, LOOK_NB pairs per lane with their probes in flight together, and leaves a byte per pair
+// (FACT_*).  (Before, every step paid the chain pair probe -> memo probe -> result -> slot -> reader header -> count, each as long as the
+// unluckiest of 512 lanes made it.)
+// WALK (wavefront 0 alone; the others wait at the barrier in front of COMMIT).  The rows depend on each other in order -- the contained
+// flags, the pair set of a bucket that holds a read twice, best-n counting -- so the walk is sequential over the rows, and it touches LDS
+// only: ONE row at a time, 64 partners per pass, lane l at partner first + l.  The pass's ballots (a bit of the fact or a type each) arrive
+// in scalar registers, and the row's stop, its cut, the flags, the counters follow from them as 64-bit scalar arithmetic; a row of more than
+// 64 remaining partners takes another pass only when this one neither reached best-n nor ended the row.  One wavefront's LDS instructions
+// execute in program order, so the walk has no barrier.  (Through the previous form eight wavefronts took FOUR rows x 128 partners per step,
+// committed in order through ballots exchanged in LDS, with two or three barriers a step and the masks' arithmetic repeated in every lane:
+// ~2.8 us per step of 2.4 rows, 80 % of a launch's longest evaluation -- profiles/eval_big_walk.txt.)  The walk notes what it visited and
+// inserted in two 128-bit masks per row and hands num / lookups / skips / the guess flags on in LDS.
+// COMMIT (eight wavefronts), again parallel over the pairs, registers the visited ones as readers and writes the inserted ones as the
+// bucket's item list.
 constexpr int LOOK_NB = 4;   // pairs a lane looks up together
 constexpr uint8_t FACT_VALID = 1, FACT_PRESENT = 2, FACT_ACCEPTED = 4, FACT_GUESSED = 8, FACT_UNFILED = 16;   // (rid1 != rid0; owned by an earlier bucket; ...; mslot == NONE)
 constexpr int FACT_TYPE_SHIFT = 5;   // two bits: the owner's type when present, else the classified or guessed one
 #ifndef PGX_BIG_NW
 #define PGX_BIG_NW 8
 #endif
-constexpr int BIG_NW = PGX_BIG_NW;              // wavefronts per bucket: rows slot = wave / 2, partner half = wave % 2
-constexpr int BIG_NR = BIG_NW / 2;              // rows of a step
+constexpr int BIG_NW = PGX_BIG_NW;              // wavefronts of LOOK and COMMIT (the walk between them is wavefront 0's)
+constexpr int BIG_NR = BIG_NW / 2;              // rows COMMIT takes at a time: row slot = wave / 2, partner half = wave % 2
 constexpr uint32_t BIG_WG = 512;                // workgroups of a launch (persistent: they stride over the list / the range, 512 entries at a time; 1024 / 2048: c4s 302-305 ms against 306, c4 unchanged)
 // Buckets that hold a read TWICE (tandem arrays, low-complexity runs: the same shimmer pair several times within a read) can
 // meet a read pair more than once within one evaluation, and the second meeting must see the first one's insertion.  The
 // narrower kernels therefore run them one partner at a time -- up to 5,000 dependent steps for a 100-entry bucket, and those
 // few hundred buckets were what a sparse pass at C4 scale really waited for (3.5 ms per pass, 136 passes per step).  Here the
-// pairs this evaluation has inserted so far sit in an LDS set that every probe consults, and duplicates WITHIN a step are
-// found by letting the would-be inserters claim their pair in a second LDS table: the step is cut in front of the first lane (in
-// walk order) whose pair an earlier lane of the same step claims, the cut row is continued alone from that partner in the next
-// step -- when the insertion is in the set -- and everything before the cut is exact.  Progress per step >= one new pair, so a
-// bucket of d distinct read pairs takes at most ~d steps instead of rows x partners.
-constexpr uint32_t SET_CAP = 2048, CLAIM_CAP = 1024;   // LDS tables of k_eval_big (open addressing, power-of-two sizes)
+// pairs this evaluation has inserted so far sit in an LDS set -- those that CAN be met again, one of whose reads stands in the bucket
+// twice (a table made while the entries are staged says which entries those are, and links each to the earlier ones of its read); only such
+// pairs are looked for there.  With a row per pass the only duplicates that can meet WITHIN a pass are two partners of the row with the same
+// read: the row is cut in front of the first lane that found its pair absent while a lower lane of the pass, holding the same read, would
+// insert it; the next pass starts at that partner -- when the insertion is in the set -- and everything before the cut is exact.  Progress
+// per pass >= one new pair.  (The four-row step needed a second LDS table in which the would-be inserters of a step claimed their pairs.)
+constexpr uint32_t SET_CAP = 2048;   // LDS pair set of k_eval_big (open addressing, a power of two)
 constexpr uint32_t CB = 4096;  // buckets per block of the count kernels (256 lanes x 16)
 
 // ---- the kernels (defined in pgx_replay_eval.hip / pgx_replay_tables.hip, launched by pgx_replay.hip) ----

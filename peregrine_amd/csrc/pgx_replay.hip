@@ -282,7 +282,8 @@ struct Walk {
     // (round 4: 48 -- with k_eval_big's walk a third shorter the long buckets WITHOUT a repeated read are better off there too: k_eval_rows 38 -> 22 ms
     //  per c4s step, hidden behind k_eval_big as it is: 360 -> 354 ms; from 24 entries on k_eval_big doubles, 411 ms.  Sixteen wavefronts = eight
     //  rows a step (-DPGX_BIG_NW=16): k_eval_big 56 -> 186 ms.)
-    // (k_eval_big now looks a bucket's pairs up once and walks them from LDS, pgx_replay.h; the thresholds are those measured before that)
+    // (k_eval_big now looks a bucket's pairs up once and walks them on one wavefront, pgx_replay.h; swept again on c4s, profiles/eval_big_walk.txt:
+    //  32 / 12, 48 / 6 and 32 / 6 within 1 ms of 48 / 12, 24 -> + 30 ms, 16 -> + 137 ms: a pass still waits for k_eval_big, so the thresholds stay)
     r.big_min = (uint32_t)std::max(0, env_int("PGX_REPLAY_BIG", 48));
     r.dup_min = (uint32_t)std::max(0, env_int("PGX_REPLAY_DUP", 12));
     r.predict = std::max(END_FUZZ * 2 - 8, 1), r.predict2 = END_FUZZ * 2 - 8;
@@ -335,8 +336,15 @@ struct Walk {
 #ifdef PGX_BIG_STATS
     unsigned long long b3 = 0, b4 = 0, b5 = 0, b6 = 0, b7 = 0;
     for (uint32_t i = 0; i < SPREAD; ++i) b3 += hs[i * 8 + 3], b4 += hs[i * 8 + 4], b5 += hs[i * 8 + 5], b6 += hs[i * 8 + 6], b7 += hs[i * 8 + 7];
-    fprintf(stderr, "[pgx]   k_eval_big so far: %u evaluations, %llu steps, %llu rows committed; steps cut at a duplicate %llu, ended by a containment %llu, all rows %llu; longest %u steps, %u evaluations of >= 64 steps (entries %u); %llu pairs looked up\n",
-            hc->big_evals, b3, b4, b5, b6, b7, hc->big_max_steps, hc->big_long, hc->big_long_n, hc->big_pairs);
+    fprintf(stderr, "[pgx]   k_eval_big so far: %u evaluations, %llu row passes, %llu rows committed; passes cut at a duplicate %llu, rows ended by a containment %llu, rows of more than one pass %llu; longest %u passes, %u evaluations of >= 64 passes (entries %u); %llu pairs looked up\n",
+            hc->big_evals, b3, b4, b5, b6, b7, hc->big_max_passes, hc->big_long, hc->big_long_n, hc->big_pairs);
+    {   // the phases (Counters): 10 ns ticks -> ms
+      const unsigned long long *a = hc->big_cyc, *l = hc->big_cyc_long;
+      const double sa = (double)(a[0] + a[1] + a[2]), sl = (double)(l[0] + l[1] + l[2]);
+      fprintf(stderr, "[pgx]   k_eval_big phases, all evaluations: LOOK %.2f ms, WALK %.2f, COMMIT %.2f (%.0f / %.0f / %.0f %%); the longest evaluation of each of %u launches: LOOK %.2f ms, WALK %.2f, COMMIT %.2f (%.0f / %.0f / %.0f %%)\n",
+              a[0] * 1e-5, a[1] * 1e-5, a[2] * 1e-5, sa ? 100 * a[0] / sa : 0, sa ? 100 * a[1] / sa : 0, sa ? 100 * a[2] / sa : 0, hc->big_launches,
+              l[0] * 1e-5, l[1] * 1e-5, l[2] * 1e-5, sl ? 100 * l[0] / sl : 0, sl ? 100 * l[1] / sl : 0, sl ? 100 * l[2] / sl : 0);
+    }
 #endif
 #ifdef PGX_SETTLE_STATS
     unsigned long long c3 = 0, c4 = 0, c5 = 0, c6 = 0;

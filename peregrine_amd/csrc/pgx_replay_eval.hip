@@ -571,18 +571,21 @@ template __global__ void k_eval_rows<64, 16>(R r, uint32_t lo, uint32_t hi, uint
 // LOOK: every (row, partner) pair of the bucket is looked up once -- pair table, memo, settled result or guess -- LOOK_NB pairs per lane at a
 // time, the probes of all of them issued before any is tested; what the walk needs of a pair is one byte in LDS.  Nothing the lookups read
 // changes while the evaluation kernels run (owners: k_update; memo: k_file; results: the alignment launches; `settled`: the host).
-// WALK: the step loop, four rows x 128 partners per step, on LDS alone; what it visits and inserts is noted in two masks per row.
+// WALK: wavefront 0 alone, on LDS alone and without a barrier: a row at a time, 64 partners per pass, the pass's ballots in scalar registers and
+// the row's stop and cut scalar arithmetic; what it visits and inserts is noted in two masks per row.  The other wavefronts wait in front of COMMIT.
 // COMMIT: the visited pairs register as readers, the inserted ones become the bucket's item list, in walk order (row, then partner).
+// The walk's one exchange between lanes (the pair set of a bucket that holds a read twice: a pass's insertions are probed by the next) goes through
+// LDS within ONE wavefront, whose LDS instructions execute in program order: all it needs is that the compiler keeps that order (as PH_SYNC in
+// pgx_align.hip).  What a pass costs and where the time of a launch goes: profiles/eval_big_walk.txt.
+#define BIG_WAVE_SYNC() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"), __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront")
 __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint32_t hi, uint32_t nlist) {
-  enum { MV = 0, MP, MPO, MA, MAO, MAC, MAP, MGU, MUF, MDF, NM };
   __shared__ uint32_t s_rid[128], s_pos[128], s_rl[128];
   __shared__ uint8_t s_dir[128];
-  __shared__ uint64_t s_m[BIG_NW][NM];
   __shared__ uint32_t s_fresh, s_abort, s_bail;
+  __shared__ uint32_t s_walk[4];                      // what the walk hands to COMMIT and the final write: num, lookups, skips, any_guess | any_unfiled << 1
   __shared__ unsigned long long s_setk[SET_CAP];      // pairs inserted by this evaluation (key + 1; 0: empty) ...
   __shared__ uint8_t s_sett[SET_CAP];                 // ... and their types
-  __shared__ unsigned long long s_clk[CLAIM_CAP];     // this step's claims: pair (key + 1) ...
-  __shared__ uint32_t s_clw[CLAIM_CAP];               // ... and the lowest walk index claiming it
+  __shared__ uint16_t s_same[128];                    // dup buckets, per entry: the nearest EARLIER entry of the same read (+ 1; 0: none) | 0x100: the read stands in the bucket more than once
   __shared__ uint8_t s_fact[128 * 128];               // LOOK's byte per pair, [row][partner] (FACT_*)
   __shared__ M128 s_vis[128], s_ins[128];             // per row: the partners (bit = entry index) the walk visited / inserted
   __shared__ uint32_t s_rbase[128], s_wsum[2];        // insertion ordinal of a row's first insertion; the scan's per-wavefront sums
@@ -622,15 +625,28 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
     if (threadIdx.x < 128) s_vis[threadIdx.x] = M128{0, 0}, s_ins[threadIdx.x] = M128{0, 0};
     if (dup) {
       for (uint32_t i = threadIdx.x; i < SET_CAP; i += blockDim.x) s_setk[i] = 0;
-      for (uint32_t i = threadIdx.x; i < CLAIM_CAP; i += blockDim.x) s_clk[i] = 0, s_clw[i] = 0xFFFFFFFFu;
     }
     __syncthreads();   // (entries staged; everybody has read ever[] / dirty[] / bflags[] before thread 0 changes them)
+    if (dup) {   // which entries share their read with another one (only pairs with such an entry can be met twice in one evaluation)
+      for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+        const uint32_t me = s_rid[i];
+        uint32_t prev = 0, more = 0;
+        for (uint32_t k = 0; k < n; ++k) {
+          const bool same = s_rid[k] == me && k != i;
+          more |= same ? 0x100u : 0u;
+          if (same && k < i) prev = k + 1;
+        }
+        s_same[i] = (uint16_t)(prev | more);
+      }
+    }
     if (threadIdx.x == 0) {
       r.dirty[j] = 0, r.evaluated[j] = 1, r.ever[j] = 1, r.parity[j] ^= 1, r.ohead[j] = r.ihead[j];
       atomicAdd(&r.spread[(blockIdx.x % SPREAD) * 8], 1ULL);
     }
 #ifdef PGX_BIG_STATS
-    uint32_t st_steps = 0, st_rows = 0, st_cut = 0, st_cont = 0, st_full = 0, st_pairs = 0;
+    uint32_t st_passes = 0, st_rows = 0, st_cut = 0, st_cont = 0, st_multi = 0, st_pairs = 0;   // (Counters, pgx_replay.h)
+    unsigned long long st_t0 = 0, st_t1 = 0, st_t2 = 0;
+    if (threadIdx.x == 0) st_t0 = wall_clock64();
 #endif
     // ---- LOOK: the triangle of pairs (row i, partner p > i), folded into n / 2 lines of n (row f in front, row n - 2 - f behind it) ----
     {
@@ -734,212 +750,154 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       }
     }
     __syncthreads();   // (the facts are there)
-    // ---- workgroup-uniform state (every thread holds a copy and updates it identically) ----
-    uint64_t clo = 0, chi = 0;   // "contained" flags of the bucket's entries
-    auto cget = [&](uint32_t i) { return (((i < 64 ? clo : chi) >> (i & 63)) & 1) != 0; };
-    auto cset = [&](uint32_t i) {
-      if (i < 64) clo |= 1ULL << i;
-      else chi |= 1ULL << (i - 64);
-    };
-    uint32_t head = NIL, num = 0, lookups = 0, skips = 0;
-    bool any_guess = false, any_unfiled = false;
-    int done_to = (int)n - 1;   // rows >= done_to are finished (the first row is n - 2)
-    bool row_open = false;       // one row (cur_row) is being continued alone, from partner pbase, with `got` overlaps counted so far
-    int cur_row = 0;
-    uint32_t pbase = 0, got = 0;
-    // ---- WALK: no global access from here to the end of the loop ----
-    for (;;) {
-      // the rows of this step: the open row alone, or the next (up to four) rows that are not contained
-      int a[BIG_NR], nrows = 0;
-#pragma unroll
-      for (int k = 0; k < BIG_NR; ++k) a[k] = -1;
-      if (row_open) {
-        a[0] = cur_row, nrows = 1;
-      } else {   // (a[] and proc[] are only ever indexed by unrolled loops: they stay in registers)
-        int x = done_to;
-#pragma unroll
-        for (int k = 0; k < BIG_NR; ++k) {
-          if (x >= 0) {
-            do --x;
-            while (x >= 0 && cget((uint32_t)x));
-          }
-          if (x >= 0) a[k] = x, nrows = k + 1;
-        }
-      }
-      if (nrows == 0 || r.bestn == 0) break;
-      // ---- this step's (row, partner) of the lane: slot q = wave / 2 takes row a[q], partners first + (wave % 2) * 64 + lane ----
-      const int q = w >> 1, off = (w & 1) * 64 + lane;   // off: partner offset within the row's 128 (= its bit in the row's masks)
-      int myrow = -1;
-#pragma unroll
-      for (int k = 0; k < BIG_NR; ++k)
-        if (k == q) myrow = a[k];
-      const uint32_t first = row_open ? pbase : (uint32_t)(myrow + 1);
-      const uint32_t pi = first + (uint32_t)off;
-      const uint32_t wi = (uint32_t)(q * 128 + off);     // position in walk order
-      bool valid = q < nrows && pi < n && !cget(pi);
-      uint32_t fact = 0;
-      unsigned long long pair = 0;
-      if (valid) {
-        fact = s_fact[myrow * 128 + (int)pi];
-        const uint32_t rid0 = s_rid[myrow], rid1 = s_rid[pi];
-        pair = rid0 < rid1 ? ((unsigned long long)rid0 << 32 | rid1) : ((unsigned long long)rid1 << 32 | rid0);
-        valid = (fact & FACT_VALID) != 0;
-      }
-      bool present = false, accepted = false, guessed = false, unfiled = true;
-      uint32_t ptype = 0, type = 0;
-      if (valid) {
-        present = (fact & FACT_PRESENT) != 0;
-        ptype = present ? fact >> FACT_TYPE_SHIFT : 0;
-        if (!present && dup) {   // inserted earlier in THIS evaluation?
-          for (uint32_t i = (uint32_t)mix64(pair) & (SET_CAP - 1);; i = (i + 1) & (SET_CAP - 1)) {
-            const unsigned long long kk = s_setk[i];
-            if (kk == 0) break;
-            if (kk == pair + 1) {
-              present = true, ptype = s_sett[i];
-              break;
-            }
-          }
-        }
-        if (!present) accepted = (fact & FACT_ACCEPTED) != 0, guessed = (fact & FACT_GUESSED) != 0, unfiled = (fact & FACT_UNFILED) != 0, type = fact >> FACT_TYPE_SHIFT;
-      }
-      const bool ins0 = valid && !present && accepted;
-      uint32_t my_claim = NONE;
-      if (dup) {   // would-be inserters claim their pair: the lowest walk index wins
-        if (ins0) {
-          for (uint32_t i = (uint32_t)(mix64(pair) >> 20) & (CLAIM_CAP - 1);; i = (i + 1) & (CLAIM_CAP - 1)) {
-            unsigned long long kk = s_clk[i];
-            if (kk == 0) kk = atomicCAS(&s_clk[i], 0ULL, (unsigned long long)pair + 1), kk = kk ? kk : pair + 1;
-            if (kk == pair + 1) {
-              atomicMin(&s_clw[i], wi);
-              my_claim = i;
-              break;
-            }
-          }
-        }
-      }
-      {
-        const uint64_t mv = __ballot(valid), mp = __ballot(valid && present), mpo = __ballot(valid && present && ptype == T_OVERLAP);
-        const uint64_t ma = __ballot(ins0), mao = __ballot(ins0 && type == T_OVERLAP), mac = __ballot(ins0 && type == T_CONTAINED);
-        const uint64_t map = __ballot(ins0 && type == T_CONTAINS), mgu = __ballot(ins0 && guessed), muf = __ballot(ins0 && unfiled);
-        if (lane == 0)
-          s_m[w][MV] = mv, s_m[w][MP] = mp, s_m[w][MPO] = mpo, s_m[w][MA] = ma, s_m[w][MAO] = mao, s_m[w][MAC] = mac, s_m[w][MAP] = map,
-          s_m[w][MGU] = mgu, s_m[w][MUF] = muf, s_m[w][MDF] = 0;
-      }
-      __syncthreads();
-      if (dup) {   // a lane whose pair a LOWER lane of this step would insert is FLAGGED: its row is cut in front of it (below).  That
-                   // holds for EVERY lane that found the pair absent, also one whose own alignment is rejected: sequentially it would
-                   // have found the pair seen and skipped it.
-        bool dflag = false;
-        if (my_claim != NONE) {
-          dflag = s_clw[my_claim] < wi;
-        } else if (valid && !present) {
-          for (uint32_t i = (uint32_t)(mix64(pair) >> 20) & (CLAIM_CAP - 1);; i = (i + 1) & (CLAIM_CAP - 1)) {
-            const unsigned long long kk = s_clk[i];
-            if (kk == 0) break;
-            if (kk == pair + 1) {
-              dflag = s_clw[i] < wi;
-              break;
-            }
-          }
-        }
-        const uint64_t mdf = __ballot(dflag);
-        if (lane == 0) s_m[w][MDF] = mdf;
-        __syncthreads();
-      }
-      // ---- the sequential semantics over this step: the rows in order, each over its 128 partners, lowest first (uniform) ----
-      M128 proc[BIG_NR];
-#pragma unroll
-      for (int k = 0; k < BIG_NR; ++k) proc[k] = M128{0, 0};
-      int committed = 0;         // rows completed in this step
-      bool open_next = false;    // the row after them was cut: it is continued alone
-      int open_row = 0;
-      uint32_t open_pbase = 0, open_got = 0;
-#pragma unroll
-      for (int k = 0; k < BIG_NR; ++k) {
-        if (k >= nrows) break;
-        // A partner that an EARLIER row of this step found contained (or that was such a row) is not examined by this row: its lane is dropped
-        // from the row's masks right here.  (Round 3 ended the step at the first row that changed a flag and looked at the rows below again
-        // in the next one.  Rows themselves are never flagged by an earlier row of the step: a row's partners lie above it.)
-        const uint32_t first_k = row_open ? pbase : (uint32_t)(a[k] + 1);
-        const M128 gone = shr128(M128{clo, chi}, first_k);
-        const M128 inc = andn128(M128{s_m[2 * k][MPO] | s_m[2 * k][MAO], s_m[2 * k + 1][MPO] | s_m[2 * k + 1][MAO]}, gone);
-        const M128 ac = andn128(M128{s_m[2 * k][MAC], s_m[2 * k + 1][MAC]}, gone), ap = andn128(M128{s_m[2 * k][MAP], s_m[2 * k + 1][MAP]}, gone);
-        // the row's cut: its first flagged lane.  (Round 3 took ONE cut for the step, the lowest flagged lane of all rows -- which most often lay
-        // beyond the stop of its row, among lanes the walk never visits, and still ended the step there: 69 % of all steps ended with rows left,
-        // 1.5 of 4 rows committed per step, profiles/r04w_big_stats_c4s.txt.  A flag whose lower claimant turns out unvisited is void but harmless:
-        // the lane is looked at again in the next step.)
-        const M128 df = andn128(M128{s_m[2 * k][MDF], s_m[2 * k + 1][MDF]}, gone);
-        const int cut = any128(df) ? ctz128(df) : 128;   // first offset of the row that may not be processed
-        if (cut == 0) break;                             // the cut lies in front of this row
-        const uint32_t need = r.bestn - (row_open ? got : 0u);   // >= 1
-        int stop = 128;
-        if ((uint32_t)popc128(inc) >= need) stop = nth128(inc, need);
-        if (any128(ac)) stop = min(stop, ctz128(ac));
-        const bool complete = stop < cut || (cut == 128);   // the row ends before the cut (or there is none in it)
-        proc[k] = andn128(complete ? upto128(stop) : upto128(cut - 1), gone);
-        const M128 apk = and128(ap, proc[k]);
-        for (uint64_t m = apk.lo; m; m &= m - 1) cset(first_k + (uint32_t)__builtin_ctzll(m));   // partners found contained
-        for (uint64_t m = apk.hi; m; m &= m - 1) cset(first_k + 64u + (uint32_t)__builtin_ctzll(m));
-        const bool rowc = any128(and128(ac, proc[k]));
-        if (rowc) cset((uint32_t)a[k]);
-        if (!complete) {
-          open_next = true, open_row = a[k], open_pbase = first_k + (uint32_t)cut, open_got = (row_open ? got : 0u) + (uint32_t)popc128(and128(inc, proc[k]));
-          break;
-        }
-        ++committed;
-      }
 #ifdef PGX_BIG_STATS
-      ++st_steps, st_rows += (uint32_t)committed, st_cut += open_next ? 1u : 0u, st_full += (committed == nrows) ? 1u : 0u;
-      st_cont += (!open_next && committed < nrows) ? 1u : 0u;
+    if (threadIdx.x == 0) st_t1 = wall_clock64();
 #endif
-      // what the walk really visited and inserted of each row, for COMMIT: thread k notes row a[k] (offsets -> entry indices)
-#pragma unroll
-      for (int k = 0; k < BIG_NR; ++k)
-        if ((int)threadIdx.x == k && k < nrows && any128(proc[k])) {
-          const uint32_t first_k = row_open ? pbase : (uint32_t)(a[k] + 1);
-          const M128 v = shl128(and128(M128{s_m[2 * k][MV], s_m[2 * k + 1][MV]}, proc[k]), first_k);
-          const M128 in = shl128(and128(M128{s_m[2 * k][MA], s_m[2 * k + 1][MA]}, proc[k]), first_k);
-          s_vis[a[k]] = or128(s_vis[a[k]], v), s_ins[a[k]] = or128(s_ins[a[k]], in);
+    // ---- WALK: wavefront 0, no global access and no barrier from here to its end ----
+    // The rows in order (n - 2 downwards, skipping those an earlier row flagged contained), each over its partners in ascending order, 64 per pass:
+    // lane l looks at partner first + l.  The state is uniform -- ballots and what follows from them -- and lives in scalar registers.  A row
+    // takes another pass when this one neither reached best-n nor ended the row, or when it was cut at a duplicate; `got` carries over.
+    if (__builtin_amdgcn_readfirstlane(w) == 0) {
+      __builtin_amdgcn_s_setprio(3);   // (the launch waits for this one wavefront: it goes first where the narrow kernel's wavefronts share the CU)
+      uint64_t clo = 0, chi = 0;   // "contained" flags of the bucket's entries
+      uint32_t num = 0, lookups = 0, skips = 0;
+      bool any_guess = false, any_unfiled = false, bail = false;
+      uint32_t set_n = 0;          // pairs in the LDS set so far
+      int row = (int)n - 1;        // rows >= row are finished (the first row is n - 2)
+      while (r.bestn != 0 && !bail) {
+        {   // the next row below that is not contained
+          const M128 below{row >= 64 ? ~0ULL : (1ULL << row) - 1ULL, row > 64 ? (1ULL << (row - 64)) - 1ULL : 0ULL};   // (selects, not branches; row <= 127)
+          const M128 open = andn128(below, M128{clo, chi});
+          if (!any128(open)) break;
+          row = open.hi ? 127 - __builtin_clzll(open.hi) : 63 - __builtin_clzll(open.lo);
         }
-#pragma unroll
-      for (int k = 0; k < BIG_NR; ++k)
-        if (k == committed - 1) done_to = a[k];
-      row_open = open_next;
-      if (open_next) cur_row = open_row, pbase = open_pbase, got = open_got;
-      // per wavefront: what the walk really visits
-      uint64_t myproc = 0;
-#pragma unroll
-      for (int ww = 0; ww < BIG_NW; ++ww) {
-        const int k = ww >> 1;
-        const uint64_t pw = (ww & 1) ? proc[k].hi : proc[k].lo;
-        if (ww == w) myproc = pw;
-        num += (uint32_t)__popcll(s_m[ww][MA] & pw);
-        skips += (uint32_t)__popcll(s_m[ww][MP] & pw);
-        lookups += (uint32_t)__popcll(s_m[ww][MV] & ~s_m[ww][MP] & pw);
-        any_guess |= (s_m[ww][MGU] & pw) != 0, any_unfiled |= (s_m[ww][MUF] & pw) != 0;
-      }
-      if (dup) {
-        const bool my_ins = ins0 && ((myproc >> lane) & 1);
-        if (my_claim != NONE) s_clk[my_claim] = 0, s_clw[my_claim] = 0xFFFFFFFFu;   // (the claim table is empty again for the next step)
-        if (my_ins) {   // this evaluation's insertions, for the probes of the steps to come
-          uint32_t tries = 0;
-          for (uint32_t i = (uint32_t)mix64(pair) & (SET_CAP - 1);; i = (i + 1) & (SET_CAP - 1)) {
-            const unsigned long long kk = atomicCAS(&s_setk[i], 0ULL, (unsigned long long)pair + 1);
-            if (kk == 0 || kk == pair + 1) {
-              s_sett[i] = (uint8_t)type;
-              break;
-            }
-            if (++tries >= SET_CAP) {   // the set is full (not with <= 128 entries and bestn <= ~8; kept as a guard): leave the bucket to k_eval_rows
-              s_bail = 1;
-              break;
+        uint32_t first = (uint32_t)row + 1, got = 0;
+        M128 vis{0, 0}, ins{0, 0};   // the row's partners (bit = entry index) visited / inserted, over all its passes
+        const uint32_t row_twice = dup ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s_same[row]) & 0x100u : 0u;   // the row's read stands in the bucket again
+#ifdef PGX_BIG_STATS
+        uint32_t row_passes = 0;
+#endif
+        for (;;) {
+          const uint32_t pi = first + (uint32_t)lane;
+          // partners of this pass that an earlier row flagged contained: not looked at.  (bits first .. first + 63 of the flags; 1 <= first <= 127)
+          const uint64_t gone = first < 64 ? clo >> first | (chi << 1) << (63 - first) : chi >> (first - 64);
+          uint32_t fact = 0, same = 0;
+          if (pi < n) {
+            fact = s_fact[row * 128 + (int)pi];
+            if (dup) same = s_same[pi];
+          }
+          // the pair can be met twice in this evaluation only if one of its reads stands in the bucket twice: only such pairs are looked for in the
+          // set, and noted there when inserted
+          const bool twice = pi < n && ((row_twice | same) & 0x100u) != 0;
+          unsigned long long pair = 0;
+          if (twice) {
+            const uint32_t rid0 = s_rid[row], rid1 = s_rid[pi];
+            pair = rid0 < rid1 ? ((unsigned long long)rid0 << 32 | rid1) : ((unsigned long long)rid1 << 32 | rid0);
+          }
+          if (set_n) {   // a pair LOOK found absent: inserted earlier in THIS evaluation?  Then it is present, with the type noted in the set
+            if (twice && (fact & (FACT_VALID | FACT_PRESENT)) == FACT_VALID) {
+              for (uint32_t i = (uint32_t)mix64(pair) & (SET_CAP - 1);; i = (i + 1) & (SET_CAP - 1)) {
+                const unsigned long long kk = s_setk[i];
+                if (kk == 0) break;
+                if (kk == pair + 1) {
+                  fact = FACT_VALID | FACT_PRESENT | (uint32_t)s_sett[i] << FACT_TYPE_SHIFT;
+                  break;
+                }
+              }
             }
           }
+          // a ballot per bit of the fact and per type (one compare each), combined as scalars
+          const uint32_t ty = fact >> FACT_TYPE_SHIFT;
+          const uint64_t mv = __ballot((fact & FACT_VALID) != 0) & ~gone;        // looked at
+          const uint64_t mp = __ballot((fact & FACT_PRESENT) != 0) & mv;         // seen: skipped
+          const uint64_t ma = __ballot((fact & FACT_ACCEPTED) != 0) & mv & ~mp;  // would be inserted
+          const uint64_t mto = __ballot(ty == T_OVERLAP), mtc = __ballot(ty == T_CONTAINED), mtp = __ballot(ty == T_CONTAINS);
+          const uint64_t mgu = __ballot((fact & FACT_GUESSED) != 0), muf = __ballot((fact & FACT_UNFILED) != 0);
+          const uint64_t inc = (mp | ma) & mto;   // counts towards best-n
+          const uint64_t ac = ma & mtc;           // the row's read is contained: the row ends there
+          const uint64_t ap = ma & mtp;           // the partner is contained
+          // two partners of the pass with the same read (dup buckets): a lane that found its pair absent is flagged when a LOWER lane of the pass
+          // would insert the same pair -- that is, holds the same read: s_same leads from an entry to the earlier ones of its read.  That holds
+          // also for a lane whose own alignment is rejected: sequentially it would have found the pair seen.  The row is cut in front of the
+          // first flagged lane, which the next pass looks at again and then finds in the set.
+          uint64_t df = 0;
+          const uint64_t absent = mv & ~mp;
+          if (dup && ma && (absent & (absent - 1))) {
+            bool dflag = false;
+            if ((absent >> lane) & 1) {
+              for (uint32_t p = same & 0xFFu; p > first; p = s_same[p - 1] & 0xFFu)   // (entry p - 1 >= first: lane p - 1 - first of this pass)
+                if ((ma >> (p - 1 - first)) & 1) {
+                  dflag = true;
+                  break;
+                }
+            }
+            df = __ballot(dflag);
+          }
+          const int cut = df ? (int)__builtin_ctzll(df) : 64;   // first lane that may not be processed (>= 1: lane 0 has no lower lane)
+          const uint32_t need = r.bestn - got;                  // >= 1
+          int stop = 64;
+          if ((uint32_t)__popcll(inc) >= need) stop = nth64(inc, need);
+          if (ac) stop = min(stop, (int)__builtin_ctzll(ac));
+          const bool ends = stop < cut;   // the row ends within this pass, in front of the cut
+          const int last = ends ? stop : cut - 1;
+          const uint64_t proc = last >= 63 ? ~0ULL : (2ULL << last) - 1ULL;   // the lanes the walk really processes
+          const uint64_t pv = mv & proc, pins = ma & proc, apk = ap & proc;
+          num += (uint32_t)__popcll(pins), skips += (uint32_t)__popcll(mp & proc), lookups += (uint32_t)__popcll(pv & ~mp);
+          got += (uint32_t)__popcll(inc & proc);
+          any_guess |= (mgu & pins) != 0, any_unfiled |= (muf & pins) != 0;
+          auto up = [&](uint64_t m) { return first < 64 ? M128{m << first, (m >> 1) >> (63 - first)} : M128{0, m << (first - 64)}; };   // lanes -> entry indices
+          vis = or128(vis, up(pv)), ins = or128(ins, up(pins));
+          {   // partners found contained
+            const M128 c = up(apk);
+            clo |= c.lo, chi |= c.hi;
+          }
+          if (ac & proc) {   // the row's own read
+            if (row < 64) clo |= 1ULL << row;
+            else chi |= 1ULL << (row - 64);
+          }
+#ifdef PGX_BIG_STATS
+          ++st_passes, ++row_passes, st_cut += (!ends && cut < 64) ? 1u : 0u, st_cont += (ac & proc) ? 1u : 0u;
+#endif
+          const uint64_t pset = __ballot(twice) & pins;
+          if (pset) {   // this evaluation's insertions that can be met again, for the probes of the passes to come
+            bool full = false;
+            set_n += (uint32_t)__popcll(pset);
+            if ((pset >> lane) & 1) {
+              uint32_t tries = 0;
+              for (uint32_t i = (uint32_t)mix64(pair) & (SET_CAP - 1);; i = (i + 1) & (SET_CAP - 1)) {
+                const unsigned long long kk = atomicCAS(&s_setk[i], 0ULL, (unsigned long long)pair + 1);
+                if (kk == 0 || kk == pair + 1) {
+                  s_sett[i] = (uint8_t)ty;
+                  break;
+                }
+                if (++tries >= SET_CAP) {   // the set is full (not with <= 128 entries and bestn <= ~8; kept as a guard): leave the bucket to k_eval_rows
+                  full = true;
+                  break;
+                }
+              }
+            }
+            BIG_WAVE_SYNC();
+            bail = __ballot(full) != 0;
+          }
+          first += (uint32_t)(cut < 64 ? cut : 64);
+          if (ends || bail || first >= n) break;
         }
+        if (lane == 0 && any128(vis)) s_vis[row] = vis, s_ins[row] = ins;   // (the row is complete: its masks, once)
+#ifdef PGX_BIG_STATS
+        ++st_rows, st_multi += row_passes > 1 ? 1u : 0u;
+#endif
       }
-      __syncthreads();   // (nobody reads this step's masks any more; the set holds this step's insertions; the rows' masks are noted)
-      if (s_bail) break;
+      __builtin_amdgcn_s_setprio(0);
+      if (lane == 0) s_walk[0] = num, s_walk[1] = lookups, s_walk[2] = skips, s_walk[3] = (any_guess ? 1u : 0u) | (any_unfiled ? 2u : 0u), s_bail = bail ? 1u : 0u;
     }
+    __syncthreads();   // (the walk is over: the rows' masks and s_walk are there)
+    const uint32_t num = s_walk[0], lookups = s_walk[1], skips = s_walk[2];
+    const bool any_guess = (s_walk[3] & 1) != 0, any_unfiled = (s_walk[3] & 2) != 0;
+    uint32_t head = NIL;
     // ---- COMMIT (not on the guard path: nothing has been written for the bucket then) ----
+#ifdef PGX_BIG_STATS
+    if (threadIdx.x == 0) st_t2 = wall_clock64();
+#endif
     bool p_reg = false;          // this lane has a registration whose list position (p_idx) has not been looked at yet
     uint32_t p_idx = 0, p_slot = 0;
     auto resolve_pending = [&]() {   // as in k_eval_rows; an exhausted arena raises s_abort instead of returning
@@ -1046,13 +1004,16 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
       for (int o = 32; o; o >>= 1) st_pairs += (uint32_t)__shfl_xor((int)st_pairs, o, 64);
       if (lane == 0) atomicAdd(&r.c->big_pairs, (unsigned long long)st_pairs);
     }
-    if (threadIdx.x == 0) {   // [3] steps, [4] rows committed, [5] steps cut at a duplicate, [6] steps ended by a containment, [7] steps that committed all their rows
+    if (threadIdx.x == 0) {   // [3] row passes, [4] rows completed, [5] passes cut at a duplicate, [6] rows ended by a containment, [7] rows of more than one pass
       unsigned long long *line = r.spread + (blockIdx.x % SPREAD) * 8;
-      atomicAdd(line + 3, (unsigned long long)st_steps), atomicAdd(line + 4, (unsigned long long)st_rows), atomicAdd(line + 5, (unsigned long long)st_cut);
-      atomicAdd(line + 6, (unsigned long long)st_cont), atomicAdd(line + 7, (unsigned long long)st_full);
-      atomicMax(&r.c->big_max_steps, st_steps);
-      if (st_steps >= 64) atomicAdd(&r.c->big_long, 1u), atomicAdd(&r.c->big_long_n, n);
+      atomicAdd(line + 3, (unsigned long long)st_passes), atomicAdd(line + 4, (unsigned long long)st_rows), atomicAdd(line + 5, (unsigned long long)st_cut);
+      atomicAdd(line + 6, (unsigned long long)st_cont), atomicAdd(line + 7, (unsigned long long)st_multi);
+      atomicMax(&r.c->big_max_passes, st_passes);
+      if (st_passes >= 64) atomicAdd(&r.c->big_long, 1u), atomicAdd(&r.c->big_long_n, n);
       atomicAdd(&r.c->big_evals, 1u);
+      const unsigned long long t3 = wall_clock64(), tl = st_t1 - st_t0, tw = st_t2 - st_t1, tc = t3 - st_t2;   // the phases, and the launch's longest evaluation
+      atomicAdd(&r.c->big_cyc[0], tl), atomicAdd(&r.c->big_cyc[1], tw), atomicAdd(&r.c->big_cyc[2], tc);
+      atomicMax(&r.c->big_lmax, (t3 - st_t0) << 40 | (tw & 0xFFFFF) << 20 | (tl & 0xFFFFF));
     }
 #endif
     if (threadIdx.x == 0) {
@@ -1068,7 +1029,21 @@ __global__ __launch_bounds__(64 * BIG_NW) void k_eval_big(R r, uint32_t lo, uint
   if (s_abort) break;
   }
   if (lane == 0) r.wcur[wave_id] = make_uint4(rcur, rend, icur, iend);
+#ifdef PGX_BIG_STATS
+  if (threadIdx.x == 0) {   // the last workgroup of the launch adds the launch's longest evaluation to the sums
+    __threadfence();
+    if (atomicAdd(&r.c->big_ticket, 1u) == gridDim.x - 1) {
+      const unsigned long long m = atomicExch(&r.c->big_lmax, 0ULL);
+      if (m) {
+        const unsigned long long tl = m & 0xFFFFF, tw = (m >> 20) & 0xFFFFF;
+        r.c->big_cyc_long[0] += tl, r.c->big_cyc_long[1] += tw, r.c->big_cyc_long[2] += (m >> 40) - tl - tw, r.c->big_launches += 1;
+      }
+      r.c->big_ticket = 0;
+    }
+  }
+#endif
 }
+#undef BIG_WAVE_SYNC
 
 }  // namespace rp
 }  // namespace pgx
