@@ -532,6 +532,30 @@ int pgx_tiling_contigs(const pgx_tiling *t, int which, const char *seqdb_prefix,
 int pgx_tiling_free(pgx_tiling *t);
 int pgx_tiling_chunk(const char *sg_edges_list_fn, const char *utg_data_fn, const char *ctg_paths_fn, const char *p_out, const char *a_out, pgx_tiling_stats_t *stats);
 
+/* ---- consensus call: the second half of pg_asm_cns.py's inner loop (py/scripts/pg_asm_cns.py:149-242), get_align_tags and
+ * get_cns_from_align_tags of falcon/falcon.c:67-122,277-397, for a batch of pieces at once.  An alignment is what falcon.align answers for
+ * one read against a piece: the two alignment strings (str_len bytes each at str_off of q_str and of t_str, over ACGTNacgtn and '-'), its
+ * start pair and the offset of the aligned template part in the piece.  The consensus of a piece is a function of the multiset of its
+ * alignments: rows may come in any order.  Where the reference has no answer the call refuses with PGX_EINVAL and names the piece: no
+ * alignment path scoring above zero (the reference reads through an end iterator), a tag at or past the template's end, a negative
+ * t_offset, more than 65,535 alignments in a piece (its counters are 16-bit), a byte outside ACGTNacgtn- in an alignment string. ---- */
+typedef struct { uint32_t piece; int32_t t_offset, s1, s2; uint64_t str_off; uint32_t str_len, pad; } pgx_cns_aln;   /* 32 bytes */
+/* one column of an alignment as the reference tags it (align_tag_t): its own position and the previous column's */
+typedef struct { int32_t t_pos, p_t_pos; uint8_t delta, q_base, p_delta, p_q_base; } pgx_cns_tag;                  /* 12 bytes */
+typedef struct {
+  uint64_t n_aln, n_tags, n_edges, n_nodes, text_bytes;
+  double gpu_ms, tags_ms, sort_ms, score_ms, back_ms;   /* the whole call on the device; its tag, sort, scoring and back-track parts */
+} pgx_cns_stats;
+/* *text (pgx_free): the pieces' consensus sequences back to back, piece p at [piece_off[p], piece_off[p + 1]) (n_piece + 1 entries);
+ * lower case where the coverage is at most min_cov.  All arrays are the host's. */
+int pgx_cns_call(const pgx_cns_aln *alns, size_t n_aln, const char *q_str, const char *t_str, size_t str_bytes, const uint32_t *piece_tlen,
+                 size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats);
+/* the same with the rows and both strings in device memory (what an aligner on the device leaves); piece_tlen and the results are the host's */
+int pgx_cns_call_dev(const pgx_cns_aln *d_alns, size_t n_aln, const char *d_q_str, const char *d_t_str, size_t str_bytes, const uint32_t *piece_tlen,
+                     size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats);
+/* the tags alone: *tags (pgx_free) holds alignment a's at [tag_off[a], tag_off[a + 1]) (n_aln + 1 entries); `piece` is not read */
+int pgx_cns_tags(const pgx_cns_aln *alns, size_t n_aln, const char *q_str, const char *t_str, size_t str_bytes, pgx_cns_tag **tags, uint64_t *tag_off);
+
 /* host utility: the order in which klib khash (src/khash.h:232-336, integer hash :373) iterates n DISTINCT 64-bit keys
  * inserted in the given order -- the order shmr_overlap visits its tables in (src/shmr_overlap.c:206-215).  out receives
  * the n keys in ascending slot order.  Runs on the host (it is the routine the overlap stage uses for its outer table). */

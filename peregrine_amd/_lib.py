@@ -17,6 +17,9 @@ ALIGN_KEY_DTYPE = np.dtype([("rid0", "<u4"), ("rid1", "<u4"), ("q_off", "<u4"), 
 ALIGN_KEY2_DTYPE = np.dtype([("rid0", "<u4"), ("rid1", "<u4"), ("q_off", "<u4"), ("t_off", "<u4"), ("dir0", "u1"), ("dir1", "u1"), ("pad", "u1", 2)])
 TILE_ROW_DTYPE = np.dtype([("ctg", "<u4"), ("rid0", "<u4"), ("rid1", "<u4"), ("s", "<i4"), ("e", "<i4"), ("strand0", "u1"), ("strand1", "u1"),
                            ("pad", "u1", 2)])
+CNS_ALN_DTYPE = np.dtype([("piece", "<u4"), ("t_offset", "<i4"), ("s1", "<i4"), ("s2", "<i4"), ("str_off", "<u8"), ("str_len", "<u4"), ("pad", "<u4")])
+CNS_TAG_DTYPE = np.dtype([("t_pos", "<i4"), ("p_t_pos", "<i4"), ("delta", "u1"), ("q_base", "u1"), ("p_delta", "u1"), ("p_q_base", "u1")])
+assert CNS_ALN_DTYPE.itemsize == 32 and CNS_TAG_DTYPE.itemsize == 12
 assert MATCH_DTYPE.itemsize == 32 and ALIGN_KEY_DTYPE.itemsize == 16 and ALIGN_KEY2_DTYPE.itemsize == 20 and TILE_ROW_DTYPE.itemsize == 24
 
 
@@ -65,6 +68,14 @@ class OverlapStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CnsStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_aln", "n_tags", "n_edges", "n_nodes", "text_bytes")] + \
+               [(n, C.c_double) for n in ("gpu_ms", "tags_ms", "sort_ms", "score_ms", "back_ms")]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/pgx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "pgx_init", "pgx_shutdown", "pgx_last_error", "pgx_device_count", "pgx_version", "pgx_free",
@@ -85,6 +96,7 @@ EXPORTS = [
     "pgx_seqdb_upload_dev", "pgx_index_resident_dev", "pgx_pairs_prepare_dev", "pgx_pairs_scatter_dev", "pgx_overlap_records_dev",
     "pgx_overlap_resident_dev", "pgx_copy_dev", "pgx_seqdb_adopt_dev", "pgx_stream_wait", "pgx_stream_signal",
     "pgx_align_batch2", "pgx_contigs_resident", "pgx_contigs_chunk",
+    "pgx_cns_call", "pgx_cns_call_dev", "pgx_cns_tags",
     "build_shimmer_map4py", "get_shimmers_for_read", "get_mmer_count", "get_shimmer_hits", "pgx_shimmer_map_free",
 ]
 
@@ -188,6 +200,10 @@ def load():
         lib.pgx_align_batch2.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         lib.pgx_contigs_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_contigs_chunk.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
+        lib.pgx_cns_call.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+        lib.pgx_cns_call_dev.argtypes = lib.pgx_cns_call.argtypes
+        lib.pgx_cns_tags.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.pgx_timing_get.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_khash_slot_order.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         lib.pgx_khash_slot_order_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]

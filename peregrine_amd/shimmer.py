@@ -885,6 +885,61 @@ def path_to_contig(seqdb_prefix: str, tiling_path: str, out: str | None = None, 
     return dict(contigs=int(nc.value), bases=int(nb.value))
 
 
+def _cns_rows(pieces):
+    """pieces: [(t_len, [(q, t, s1, s2, t_offset), ...]), ...] -> the rows of pgx_cns_aln, both string buffers, the template lengths"""
+    n = sum(len(alns) for _, alns in pieces)
+    rows = np.zeros(n, _lib.CNS_ALN_DTYPE)
+    qs, ts, i, off = [], [], 0, 0
+    for p, (_, alns) in enumerate(pieces):
+        for q, t, s1, s2, t_offset in alns:
+            if len(q) != len(t):
+                raise ValueError(f"piece {p}: alignment strings of {len(q)} and {len(t)} bytes")
+            rows[i] = (p, t_offset, s1, s2, off, len(q), 0)
+            qs.append(bytes(q)); ts.append(bytes(t))
+            i, off = i + 1, off + len(q)
+    q_str, t_str = np.frombuffer(b"".join(qs), np.uint8), np.frombuffer(b"".join(ts), np.uint8)
+    return rows, q_str, t_str, np.array([t_len for t_len, _ in pieces], np.uint32)
+
+
+def consensus(pieces, min_cov: int = 1, device=None, stats: dict | None = None, on_device: bool = False):
+    """get_cns_from_align_tags over get_align_tags (falcon/falcon.c) for a batch of pieces (pgx_cns_call): pieces is a list of
+    (template length, [(q_aln_str, t_aln_str, s1, s2, t_offset), ...]) -- what falcon.align answered for every read of the piece, the
+    back-bone included -- and the answer one `bytes` per piece, the reference's consensus.  A piece the reference has no answer for raises
+    (PGX_EINVAL, the piece named).  stats: filled with pgx_cns_stats.  on_device: upload the inputs with torch and enter through
+    pgx_cns_call_dev, as an aligner on the device would."""
+    _lib.init(device)
+    rows, q_str, t_str, tlen = _cns_rows(pieces)
+    off = np.zeros(len(pieces) + 1, np.uint64)
+    st = _lib.CnsStats()
+    if on_device:
+        import torch
+        dev = torch.device("cuda", _lib._inited)
+        d = [torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev) for a in (rows, q_str, t_str)]
+        torch.cuda.synchronize(dev)
+        args, fn, name = [C.c_void_p(x.data_ptr() if x.numel() else 0) for x in d], _lib.load().pgx_cns_call_dev, "pgx_cns_call_dev"
+    else:
+        args, fn, name = [_ptr(rows), _ptr(q_str), _ptr(t_str)], _lib.load().pgx_cns_call, "pgx_cns_call"
+    text = C.c_void_p()
+    _lib.check(fn(args[0], len(rows), args[1], args[2], len(q_str), _ptr(tlen), len(pieces), int(min_cov), C.byref(text), _ptr(off), C.byref(st)), name)
+    data = C.string_at(text.value, int(off[-1]))
+    _lib.load().pgx_free(text)
+    if stats is not None:
+        stats.update(st.asdict())
+    return [data[int(off[p]):int(off[p + 1])] for p in range(len(pieces))]
+
+
+def align_tags(alns, device=None):
+    """get_align_tags (falcon/falcon.c:67-122) for a batch of alignments (pgx_cns_tags): alns is a list of (q_aln_str, t_aln_str, s1, s2,
+    t_offset); the answer one array of _lib.CNS_TAG_DTYPE rows per alignment."""
+    _lib.init(device)
+    rows, q_str, t_str, _ = _cns_rows([(0, list(alns))])
+    off = np.zeros(len(rows) + 1, np.uint64)
+    tags = C.c_void_p()
+    _lib.check(_lib.load().pgx_cns_tags(_ptr(rows), len(rows), _ptr(q_str), _ptr(t_str), len(q_str), C.byref(tags), _ptr(off)), "pgx_cns_tags")
+    allt = _lib.take(tags.value, int(off[-1]), _lib.CNS_TAG_DTYPE)
+    return [allt[int(off[a]):int(off[a + 1])] for a in range(len(rows))]
+
+
 def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None):
     """in-memory form of shmr_map (pgx_map): arrays in, text out"""
     _lib.init(device)
