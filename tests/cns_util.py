@@ -185,14 +185,122 @@ def synthetic_piece(rng, t_len, n_reads, rate=0.12, min_frac=0.3):
     return t_len, alns
 
 
+LETTERS = b"ACGTNacgtn"
+
+
+def wide_position(T, at, K, n_full):
+    """a piece (template, alignments) with exactly K distinct insertion nodes after template base at - 1: n_full back-bone copies and ten
+    reads, read r inserting K // 10 + (r < K % 10) bases of which the one at delta d + 1 is LETTERS[(d + r) % 10] (ten different letters
+    per delta).  The nodes (at - 1, 0) and (at, 0) are then K + 1 apart in key order.  With n_full = 12 the direct edge between the two
+    scores 12 - 9 = 3 and every insertion edge 2 - 21: the consensus is the template."""
+    alns = [build(T, 0, 0, [("=", len(T))]) for _ in range(n_full)]
+    for r in range(10):
+        ins = bytes(LETTERS[(d + r) % 10] for d in range(K // 10 + (r < K % 10)))
+        alns.append(build(T, 0, 0, [("=", at), ("I", ins), ("=", len(T) - at)]))
+    return T, alns
+
+
+def distinct_keys(alns):
+    """the sorted distinct tag keys of a piece's alignments (the nodes of the rule, in its order) as uint64"""
+    tags = [align_tags(*a) for a in alns]
+    tags = np.concatenate(tags) if tags else np.zeros(0, TAG_DTYPE)
+    pos = tags["t_pos"].astype(np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    return np.unique(pos << np.uint64(32) | tags["delta"].astype(np.uint64) << np.uint64(8) | tags["q_base"].astype(np.uint64))
+
+
+def node_distance(alns, key_a, key_b):
+    """how many places the node key_b = (t_pos, delta, base) lies after key_a among the piece's nodes in key order: the difference of
+    node indices that the scoring ring and the back-track window see"""
+    keys = distinct_keys(alns).tolist()
+    return keys.index(tag_key(*key_b)) - keys.index(tag_key(*key_a))
+
+
+# ---- rows as the library takes them -------------------------------------------------------------------------------------------------------
+FILLER = b"\x00.X*\xff"
+LAYOUTS = ("packed", "interleaved", "scattered", "shared")
+
+
+def rows_of(pieces, layout="packed", rng=None):
+    """pieces: [(t_len, [alignment, ...]), ...] -> (rows, q_str, t_str, piece_tlen) in the dtypes of pgx_cns_call.
+      packed       rows piece by piece, the strings back to back in row order (what shimmer._cns_rows makes)
+      interleaved  the rows in a random permutation across all pieces, the strings back to back in that order
+      scattered    rows piece by piece; the strings in a random order of their own with runs of 1 .. 70 bytes of FILLER before, between
+                   and after them, the same bytes at the same places of both buffers
+      shared       interleaved, and alignments of a piece with the same two strings point at one copy of them"""
+    from peregrine_amd import _lib
+    assert layout in LAYOUTS
+    items = [(p, a) for p, (_, alns) in enumerate(pieces) for a in alns]
+    order = np.arange(len(items)) if layout in ("packed", "scattered") else rng.permutation(len(items))
+    rows = np.zeros(len(items), _lib.CNS_ALN_DTYPE)
+    slots, slot_of, seen = [], [], {}
+    for i in order.tolist():
+        p, (q, t, s1, s2, t_offset) = items[i]
+        q, t = bytes(q), bytes(t)
+        assert len(q) == len(t)
+        key = (p, q, t) if layout == "shared" else len(slot_of)
+        if key not in seen:
+            seen[key] = len(slots)
+            slots.append((q, t))
+        slot_of.append(seen[key])
+    fill = lambda: rng.choice(np.frombuffer(FILLER, np.uint8), int(rng.integers(1, 71))).tobytes() if layout == "scattered" else b""
+    qs, ts, at = bytearray(), bytearray(), [0] * len(slots)
+    for s in (rng.permutation(len(slots)) if layout == "scattered" else np.arange(len(slots))).tolist():
+        f = fill()
+        qs += f; ts += f
+        at[s] = len(qs)
+        qs += slots[s][0]; ts += slots[s][1]
+    f = fill()
+    qs += f; ts += f
+    for r, i in enumerate(order.tolist()):
+        p, (q, t, s1, s2, t_offset) = items[i]
+        rows[r] = (p, t_offset, s1, s2, at[slot_of[r]], len(q), 0)
+    return rows, np.frombuffer(bytes(qs), np.uint8), np.frombuffer(bytes(ts), np.uint8), np.array([t_len for t_len, _ in pieces], np.uint32)
+
+
+def call_rows(rows, q_str, t_str, piece_tlen, min_cov=1, entry="pgx_cns_call", stats=None, null_text=False):
+    """pgx_cns_call or pgx_cns_call_dev (`entry` names it) on raw rows, as shimmer.consensus calls them: the consensus of every piece as
+    bytes, or _lib.PgxError.  The number of pieces is len(piece_tlen), the string bytes len(q_str): rows may name anything.  For the device
+    entry the rows and both strings are uploaded with torch.  null_text: pass no place for the text (an argument error)."""
+    import ctypes as C
+    from peregrine_amd import _lib
+    assert entry in ("pgx_cns_call", "pgx_cns_call_dev")
+    _lib.init()
+    rows = np.ascontiguousarray(rows, _lib.CNS_ALN_DTYPE)
+    q_str, t_str = np.ascontiguousarray(q_str, np.uint8), np.ascontiguousarray(t_str, np.uint8)
+    tlen = np.ascontiguousarray(piece_tlen, np.uint32)
+    assert len(q_str) == len(t_str)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    if entry == "pgx_cns_call_dev":
+        import torch
+        dev = torch.device("cuda", _lib._inited)
+        held = [torch.from_numpy(a.view(np.uint8).copy()).to(dev) for a in (rows, q_str, t_str)]
+        torch.cuda.synchronize(dev)
+        args = [C.c_void_p(x.data_ptr() if x.numel() else 0) for x in held]
+    else:
+        args = [ptr(rows), ptr(q_str), ptr(t_str)]
+    off = np.zeros(len(tlen) + 1, np.uint64)
+    st = _lib.CnsStats()
+    text = C.c_void_p()
+    rc = getattr(_lib.load(), entry)(args[0], len(rows), args[1], args[2], len(q_str), ptr(tlen), len(tlen), int(min_cov),
+                                     None if null_text else C.byref(text), ptr(off), C.byref(st))
+    _lib.check(rc, entry)
+    data = C.string_at(text.value, int(off[-1]))
+    _lib.load().pgx_free(text)
+    if stats is not None:
+        stats.update(st.asdict())
+    return [data[int(off[p]):int(off[p + 1])] for p in range(len(tlen))]
+
+
 # ---- the fixture ------------------------------------------------------------------------------------------------------------------------------
 def pack_cases(cases):
-    """cases: [(name, min_cov, [(template, [alignment, ...]), ...])] -> the input arrays of the fixture"""
-    names, min_cov, case_piece_off, tmpl, tmpl_off, piece_aln_off = [], [], [0], [], [0], [0]
+    """cases: [(name, min_cov, [(template, [alignment, ...]), ...])] -> the input arrays of the fixture.  A piece given as (template,
+    [alignment, ...], repeat) stands for its alignments `repeat` times over and is stored once (piece_repeat)."""
+    names, min_cov, case_piece_off, tmpl, tmpl_off, piece_aln_off, piece_repeat = [], [], [0], [], [0], [0], []
     t_offset, s1, s2, reads, read_off, ops, ops_off = [], [], [], [], [0], [], [0]
     for name, mc, pieces in cases:
         names.append(name); min_cov.append(mc)
-        for template, alns in pieces:
+        for template, alns, *rep in pieces:
+            piece_repeat.append(rep[0] if rep else 1)
             tmpl.append(np.frombuffer(template, np.uint8)); tmpl_off.append(tmpl_off[-1] + len(template))
             for q, t, a1, a2, off in alns:
                 r = bytes(q).replace(b"-", b"")
@@ -206,6 +314,7 @@ def pack_cases(cases):
     cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
     return dict(names=np.array(names), min_cov=np.array(min_cov, np.int32), case_piece_off=np.array(case_piece_off, np.int64),
                 tmpl=cat(tmpl, np.uint8), tmpl_off=np.array(tmpl_off, np.int64), piece_aln_off=np.array(piece_aln_off, np.int64),
+                piece_repeat=np.array(piece_repeat, np.int32),
                 aln_t_offset=np.array(t_offset, np.int32), aln_s1=np.array(s1, np.int32), aln_s2=np.array(s2, np.int32),
                 reads=cat(reads, np.uint8), read_off=np.array(read_off, np.int64), ops=cat(ops, np.uint32), ops_off=np.array(ops_off, np.int64))
 
@@ -222,6 +331,18 @@ def pack_tags(tag_lists):
 class Case:
     def __init__(self, name, min_cov, pieces, cns, tags):
         self.name, self.min_cov, self.pieces, self.cns, self.tags = name, min_cov, pieces, cns, tags   # pieces: [(t_len, [alignment])]
+
+
+def batches_by_min_cov(cases, skip=("edge_full_count",)):
+    """all pieces of the cases in one batch per min_cov: {min_cov: (pieces, the reference's consensus of each)}.  skip: cases left out
+    (the 65,535 alignments of edge_full_count run alone: in every batch they would only slow it)"""
+    out = {}
+    for c in cases:
+        if c.name not in skip:
+            pieces, want = out.setdefault(c.min_cov, ([], []))
+            pieces += c.pieces
+            want += c.cns
+    return out
 
 
 _cases = None
@@ -242,13 +363,15 @@ def load_cases():
         pieces, want, wtags = [], [], []
         for p in range(int(g["case_piece_off"][ci]), int(g["case_piece_off"][ci + 1])):
             template = tmpl[int(g["tmpl_off"][p]):int(g["tmpl_off"][p + 1])]
-            alns = []
+            alns, ptags = [], []
             for a in range(int(g["piece_aln_off"][p]), int(g["piece_aln_off"][p + 1])):
                 q, t = expand(template, reads[int(g["read_off"][a]):int(g["read_off"][a + 1])], g["aln_s2"][a], g["aln_t_offset"][a],
                               ops[int(g["ops_off"][a]):int(g["ops_off"][a + 1])])
                 alns.append((q, t, int(g["aln_s1"][a]), int(g["aln_s2"][a]), int(g["aln_t_offset"][a])))
-                wtags.append(tags[int(g["tag_off"][a]):int(g["tag_off"][a + 1])])
-            pieces.append((len(template), alns))
+                ptags.append(tags[int(g["tag_off"][a]):int(g["tag_off"][a + 1])])
+            rep = int(g["piece_repeat"][p])            # the stored alignments stand for `rep` times as many (the same objects over again)
+            pieces.append((len(template), alns * rep))
+            wtags += ptags * rep
             want.append(cns[int(g["cns_off"][p]):int(g["cns_off"][p + 1])])
         out.append(Case(name, int(g["min_cov"][ci]), pieces, want, wtags))
     _cases = out

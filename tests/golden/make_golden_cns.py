@@ -14,6 +14,13 @@ the refusal conditions, so that no stored answer rests on undefined behaviour; a
               with more nodes than the scoring kernel's LDS ring holds
   batch64     64 pieces of 60 .. 2,000 bases in one case
   big8192     one piece of 8,400 bases with 12 reads
+  edge_*      (a generator of their own, seed + 1, so that the cases above never move) two nodes 1023, 1024, 1025 and 2047, 2048, 2049
+              apart in key order (the scoring ring holds 1024, the back-track window 2048); every pair of the ten letters tied at one
+              column, every letter against a gap, every letter inserted; the cut on the last and the first lane of a chunk of columns;
+              empty alignments, insertions only, rows of zero tags, insertion runs that end a chunk, one column on the last base, negative
+              s2; min_cov 3, 65535 and 2^31 - 1, a lower-case and an all-N template; one piece of 65,535 identical alignments (stored
+              once with its repeat count); the same distances of 2047, 2048 and 2049 between the END node and its predecessor, where
+              the back-track's first window begins
 
     python tests/golden/make_golden_cns.py [path/to/reference/falcon]
 """
@@ -166,6 +173,55 @@ def hand_cases(rng):
     return cases
 
 
+def edge_cases(rng, cov12):
+    """the edges of the kernels' windows at their exact values, the order of ties, rows that yield no tags: alignment strings as data"""
+    T = CU.random_template(rng, 120)
+    full = lambda t=T: CU.build(t, 0, 0, [("=", len(t))])
+    acgt = lambda n: rng.choice(np.frombuffer(b"ACGT", np.uint8), n).tobytes()
+    cases = []
+    # the nodes (59, 0) and (60, 0) exactly this far apart in key order: the scoring ring holds 1024, the back-track window 2048
+    for what, dist in (("ring", 1023), ("ring", 1024), ("ring", 1025), ("back", 2047), ("back", 2048), ("back", 2049)):
+        cases.append((f"edge_{what}_{dist}", 1, [CU.wide_position(T, 60, dist - 1, 12)]))
+    # ties, settled by the ASCII order of the letters: every pair of letters at one column, every letter against a gap, every letter inserted
+    T100 = CU.random_template(rng, 100)
+    L = CU.LETTERS
+    at = lambda x: CU.build(T100, 0, 0, [("=", 50), ("X", bytes([x])), ("=", 49)])
+    ties = [(T100, [at(L[i]), at(L[j])]) for i in range(10) for j in range(i + 1, 10)]
+    ties += [(T100, [at(x), CU.build(T100, 0, 0, [("=", 50), ("D", 1), ("=", 49)])]) for x in L]
+    ties += [(T100, [CU.build(T100, 0, 0, [("=", 50), ("I", bytes([x])), ("=", 50)]), CU.build(T100, 0, 0, [("=", 100)])]) for x in L]
+    cases.append(("edge_ties", 0, ties))
+    # the cut at delta 255 on columns 255, 256, 319 and 320: the last and the first lane of a chunk of 64 columns
+    cut = []
+    for c in (1, 2, 65, 66):
+        ins = [acgt(255), acgt(255)]
+        cut.append((T, [full(), full()] + [CU.build(T, 0, 0, [("=", c), ("I", i), ("=", 120 - c)]) for i in ins]))
+    cases.append(("edge_cut_lanes", 1, cut))
+    # rows of no or few tags, insertion runs that end a chunk, starts before and at the ends of the template
+    n = len(T)
+    strings = [full(), full(), (b"", b"", 0, 0, 0), (b"", b"", 0, 0, 3), (b"ACGT", b"----", 0, 10, 0),
+               CU.build(T, 0, 0, [("=", 63), ("I", acgt(70))]), CU.build(T, 0, 0, [("=", 64), ("I", acgt(64))]),
+               CU.build(T, 0, 0, [("I", b"AC"), ("=", 30)])]
+    strings += [CU.build(T, off, s2, [("I", b"AC"), ("=", 30)]) for off, s2 in ((7, 3), (7, 0), (0, 9))]
+    strings += [CU.build(T, 0, 0, [("D", 3), ("=", 30)]), CU.build(T, n - 1, 0, [("=", 1)]), CU.build(T, 0, n - 1, [("=", 1)]),
+                CU.build(T, 10, -3, [("=", 40)]), (T[n - 3:], T[n - 3:], 0, -3, 0)]
+    cases.append(("edge_strings", 1, [(T, strings)]))
+    # min_cov beyond 2, at the reference's 16 bits and at the largest the fixture stores; lower-case and all-N templates
+    for mc in (3, 65535, 2**31 - 1):                                                  # cov12: hand_min_cov*'s piece
+        cases.append((f"edge_min_cov_max_{mc}", mc, cov12))
+    low = T.lower()
+    cases.append(("edge_min_cov_max_lower", 0, [(low, [full(low), full(low), CU.build(low, 0, 0, [("=", 40), ("X", b"n"), ("=", 79)])])]))
+    allN = b"N" * 200
+    cases.append(("edge_min_cov_max_allN", 1, [(allN, [full(allN), full(allN), CU.build(allN, 0, 0, [("=", 80), ("D", 2), ("=", 118)])])]))
+    # as many alignments as the reference's 16-bit counters hold, stored once
+    T8 = CU.random_template(rng, 8)
+    cases.append(("edge_full_count", 1, [(T8, [full(T8)], CU.MAX_ALNS)]))
+    # the back-track's window hangs from the node the walk stands on, first the end node: the wide position before the template's LAST
+    # base makes the end node (119, 0) the one that jumps, its predecessor (118, 0) the window's lowest slot at 2047 and outside from 2048
+    for dist in (2047, 2048, 2049):
+        cases.append((f"edge_back_end_{dist}", 1, [CU.wide_position(T, len(T) - 1, dist - 1, 12)]))
+    return cases
+
+
 def all_cases(lib):
     rng = np.random.default_rng(SEED)
     cases = []
@@ -182,6 +238,8 @@ def all_cases(lib):
     sizes = np.concatenate([[60, 2000], rng.integers(60, 2001, 62)])
     cases.append(("batch64", 1, [real_piece(lib, rng, CU.random_template(rng, int(n)), int(rng.integers(1, 5)), 0.08, offsets=True) for n in sizes]))
     cases.append(("big8192", 1, [real_piece(lib, rng, CU.random_template(rng, 8400), 12, 0.10, offsets=True)]))
+    # a generator of its own: the cases above keep their inputs whatever is added here
+    cases += edge_cases(np.random.default_rng(SEED + 1), next(pieces for name, _, pieces in cases if name == "hand_min_cov0"))
     return cases
 
 
@@ -192,14 +250,16 @@ def main():
         cns, tags, seconds = [], [], {}
         for name, mc, pieces in cases:
             seconds[name] = 0.0
-            for pi, (template, alns) in enumerate(pieces):
+            for pi, (template, unit, *rep) in enumerate(pieces):
+                alns = unit * (rep[0] if rep else 1)                               # (template, alignments, repeat): stored once
                 mine = CU.consensus(len(template), alns, mc, f"{name}[{pi}]")      # raises Refused: no such case is stored
                 mine_tags = [CU.align_tags(*a) for a in alns]
                 seq, ref_tags, dt = ref_piece(lib, len(template), alns, mc)
                 assert seq == mine, (name, pi, seq[:80], mine[:80])
                 assert all(np.array_equal(a, b) for a, b in zip(ref_tags, mine_tags)), (name, pi)
-                cns.append(seq); tags += ref_tags; seconds[name] = round(seconds[name] + dt, 6)
-            print(f"{name}: {len(pieces)} piece(s), {sum(len(a) for _, a in pieces)} alignments, {seconds[name]:.4f} s", flush=True)
+                assert all(np.array_equal(a, b) for a, b in zip(ref_tags, ref_tags[:len(unit)] * (len(alns) // len(unit)))), (name, pi)
+                cns.append(seq); tags += ref_tags[:len(unit)]; seconds[name] = round(seconds[name] + dt, 6)
+            print(f"{name}: {len(pieces)} piece(s), {sum(len(p[1]) for p in pieces)} alignments, {seconds[name]:.4f} s", flush=True)
         bench_rng = np.random.default_rng(BENCH["seed"])
         bench_s, bench_tags = [], []
         for _ in range(BENCH["pieces"]):

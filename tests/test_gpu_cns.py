@@ -18,13 +18,9 @@ def cases():
 
 @pytest.fixture(scope="module")
 def everything(cases):
-    """all pieces of the fixture in one batch, per min_cov: (pieces, expected)"""
-    out = {}
-    for c in cases:
-        pieces, want = out.setdefault(c.min_cov, ([], []))
-        pieces += c.pieces
-        want += c.cns
-    return out
+    """all pieces of the fixture in one batch, per min_cov: (pieces, expected); the 65,535 alignments of edge_full_count run alone (case by
+    case), here they would only slow the shuffles"""
+    return CU.batches_by_min_cov(cases)
 
 
 def test_tags_equal_the_reference_field_by_field(cases):
