@@ -556,6 +556,39 @@ int pgx_cns_call_dev(const pgx_cns_aln *d_alns, size_t n_aln, const char *d_q_st
 /* the tags alone: *tags (pgx_free) holds alignment a's at [tag_off[a], tag_off[a + 1]) (n_aln + 1 entries); `piece` is not read */
 int pgx_cns_tags(const pgx_cns_aln *alns, size_t n_aln, const char *q_str, const char *t_str, size_t str_bytes, pgx_cns_tag **tags, uint64_t *tag_off);
 
+/* ---- falcon.align: the first half of that loop, the banded O(ND) aligner with trace-back of falcon/DW_banded.c:104-315, for a batch of
+ * requests over one pool of bytes.  Bytes are compared as bytes ('a' != 'A', 'N' == 'N').  A request that does not align -- the band grew
+ * wider than 2 * band, or 0.3 * (q_len + t_len) steps did not reach an end of either sequence -- answers all zero, as the reference does.
+ * band <= 4096 (the front keeps 2 * band + 4 diagonals, rounded up to a power of two, in LDS: at most 16,384 slots, 64 KiB).
+ * What is NOT here is the script itself, pg_asm_cns.py as a drop-in: contig chunking, read grouping and the stitching of the pieces. ---- */
+typedef struct { uint64_t q_off, t_off; uint32_t q_len, t_len, band, want_str; } pgx_faln_req;                       /* 32 bytes */
+typedef struct { int32_t aln_str_size, dist, aln_q_s, aln_q_e, aln_t_s, aln_t_e; uint64_t str_off; } pgx_faln_res;  /* 32 bytes */
+typedef struct {
+  uint64_t n_req, n_aligned, n_cells, str_bytes;   /* requests, those that reached an end, trace cells kept (4 bytes each), bytes per string buffer */
+  double gpu_ms, count_ms, fill_ms, back_ms;       /* the aligner on the device; its counting pass, filling pass and trace-back */
+} pgx_faln_stats;
+/* falcon.align for n requests over one pool of bytes (host arrays).  *q_str, *t_str (pgx_free): request r's strings at
+ * [str_off, str_off + aln_str_size) of both where want_str != 0 and it aligned; otherwise it owns no bytes. */
+int pgx_falcon_align(const pgx_faln_req *reqs, size_t n, const char *seq, size_t seq_bytes, pgx_faln_res *res,
+                     char **q_str, char **t_str, uint64_t *str_bytes, pgx_faln_stats *stats);
+
+typedef struct { uint64_t seq_off; uint32_t t_len, pad; } pgx_cns_piece;                                      /* 16 bytes */
+typedef struct { uint64_t seq_off; uint32_t seq_len, piece; int32_t read_shift; uint32_t pad; } pgx_cns_read; /* 24 bytes */
+typedef struct {
+  pgx_faln_stats align;                            /* the back-bones' and the reads' alignments */
+  uint64_t n_pieces, n_reads, n_accepted, n_rejected, n_by_rule, n_called;   /* reads by the acceptance rule; pieces answered by the
+                                                                                 low-coverage rule and by the consensus call */
+  pgx_cns_stats call;
+} pgx_cns_pieces_stats;
+/* pg_asm_cns.py:143-244 for a batch of pieces: text / piece_off as pgx_cns_call; read_used[r] (may be NULL) = 1 where read r was accepted.
+ * Per piece the back-bone (the template against itself, band 50), then every read at band 150: a read with read_shift < 0 without its
+ * first -read_shift bases against the template, one with read_shift >= 0 against the template from read_shift on; accepted where the
+ * aligned query span comes within 48 of the query (or, read_shift >= 0, of what is left of the template).  A piece whose accepted reads
+ * cover fewer than 3 * t_len template bases answers its template in lower case; the others go through the consensus call, whose
+ * refusals pass through (PGX_EINVAL, the piece named).  A read clipped to nothing is skipped.  PGX_EINVAL also for t_len == 0. */
+int pgx_cns_pieces(const pgx_cns_piece *pieces, size_t n_piece, const pgx_cns_read *reads, size_t n_read, const char *seq, size_t seq_bytes,
+                   uint32_t min_cov, char **text, uint64_t *piece_off, uint8_t *read_used, pgx_cns_pieces_stats *stats);
+
 /* host utility: the order in which klib khash (src/khash.h:232-336, integer hash :373) iterates n DISTINCT 64-bit keys
  * inserted in the given order -- the order shmr_overlap visits its tables in (src/shmr_overlap.c:206-215).  out receives
  * the n keys in ascending slot order.  Runs on the host (it is the routine the overlap stage uses for its outer table). */

@@ -19,7 +19,13 @@ TILE_ROW_DTYPE = np.dtype([("ctg", "<u4"), ("rid0", "<u4"), ("rid1", "<u4"), ("s
                            ("pad", "u1", 2)])
 CNS_ALN_DTYPE = np.dtype([("piece", "<u4"), ("t_offset", "<i4"), ("s1", "<i4"), ("s2", "<i4"), ("str_off", "<u8"), ("str_len", "<u4"), ("pad", "<u4")])
 CNS_TAG_DTYPE = np.dtype([("t_pos", "<i4"), ("p_t_pos", "<i4"), ("delta", "u1"), ("q_base", "u1"), ("p_delta", "u1"), ("p_q_base", "u1")])
+FALN_REQ_DTYPE = np.dtype([("q_off", "<u8"), ("t_off", "<u8"), ("q_len", "<u4"), ("t_len", "<u4"), ("band", "<u4"), ("want_str", "<u4")])
+FALN_RES_DTYPE = np.dtype([("aln_str_size", "<i4"), ("dist", "<i4"), ("aln_q_s", "<i4"), ("aln_q_e", "<i4"), ("aln_t_s", "<i4"), ("aln_t_e", "<i4"),
+                           ("str_off", "<u8")])
+CNS_PIECE_DTYPE = np.dtype([("seq_off", "<u8"), ("t_len", "<u4"), ("pad", "<u4")])
+CNS_READ_DTYPE = np.dtype([("seq_off", "<u8"), ("seq_len", "<u4"), ("piece", "<u4"), ("read_shift", "<i4"), ("pad", "<u4")])
 assert CNS_ALN_DTYPE.itemsize == 32 and CNS_TAG_DTYPE.itemsize == 12
+assert FALN_REQ_DTYPE.itemsize == 32 and FALN_RES_DTYPE.itemsize == 32 and CNS_PIECE_DTYPE.itemsize == 16 and CNS_READ_DTYPE.itemsize == 24
 assert MATCH_DTYPE.itemsize == 32 and ALIGN_KEY_DTYPE.itemsize == 16 and ALIGN_KEY2_DTYPE.itemsize == 20 and TILE_ROW_DTYPE.itemsize == 24
 
 
@@ -76,6 +82,24 @@ class CnsStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class FalnStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_req", "n_aligned", "n_cells", "str_bytes")] + \
+               [(n, C.c_double) for n in ("gpu_ms", "count_ms", "fill_ms", "back_ms")]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class CnsPiecesStats(C.Structure):
+    _fields_ = [("align", FalnStats)] + [(n, C.c_uint64) for n in ("n_pieces", "n_reads", "n_accepted", "n_rejected", "n_by_rule", "n_called")] + \
+               [("call", CnsStats)]
+
+    def asdict(self):
+        out = {n: getattr(self, n) for n, t in self._fields_ if t is C.c_uint64}
+        out["align"], out["call"] = self.align.asdict(), self.call.asdict()
+        return out
+
+
 # every symbol include/pgx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "pgx_init", "pgx_shutdown", "pgx_last_error", "pgx_device_count", "pgx_version", "pgx_free",
@@ -96,7 +120,7 @@ EXPORTS = [
     "pgx_seqdb_upload_dev", "pgx_index_resident_dev", "pgx_pairs_prepare_dev", "pgx_pairs_scatter_dev", "pgx_overlap_records_dev",
     "pgx_overlap_resident_dev", "pgx_copy_dev", "pgx_seqdb_adopt_dev", "pgx_stream_wait", "pgx_stream_signal",
     "pgx_align_batch2", "pgx_contigs_resident", "pgx_contigs_chunk",
-    "pgx_cns_call", "pgx_cns_call_dev", "pgx_cns_tags",
+    "pgx_cns_call", "pgx_cns_call_dev", "pgx_cns_tags", "pgx_falcon_align", "pgx_cns_pieces",
     "build_shimmer_map4py", "get_shimmers_for_read", "get_mmer_count", "get_shimmer_hits", "pgx_shimmer_map_free",
 ]
 
@@ -204,6 +228,9 @@ def load():
                                      C.c_void_p]
         lib.pgx_cns_call_dev.argtypes = lib.pgx_cns_call.argtypes
         lib.pgx_cns_tags.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.pgx_falcon_align.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_cns_pieces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
         lib.pgx_timing_get.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_khash_slot_order.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         lib.pgx_khash_slot_order_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]

@@ -307,8 +307,9 @@ struct Events {
 };
 
 // the first pass over the alignments and its verdict: ntag, and -- piece_tlen != nullptr -- naln
+// names: the caller's number of every piece, where the pieces here are a selection of the caller's (nullptr: their own)
 void scan_and_check(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, const uint8_t *d_q, const uint8_t *d_t, size_t str_bytes, const uint32_t *d_tlen,
-                    uint32_t n_piece, DevBuf<uint32_t> &ntag, DevBuf<uint32_t> &err) {
+                    uint32_t n_piece, DevBuf<uint32_t> &ntag, DevBuf<uint32_t> &err, const uint32_t *names = nullptr) {
   hipStream_t st = ctx().stream;
   DevBuf<uint32_t> naln(d_tlen ? n_piece : 0);
   err.alloc(E_SLOTS);
@@ -322,6 +323,8 @@ void scan_and_check(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, co
   uint32_t h[E_SLOTS];
   err.download(h, E_SLOTS);
   sync();
+  for (int e : {E_OFFSET, E_MANY, E_BYTE, E_TPOS})
+    if (names && h[e] != UINT32_MAX) h[e] = names[h[e]];
   PGX_REQUIRE(h[E_PIECE] == UINT32_MAX, PGX_EARG, "%s: alignment %u names a piece beyond the %u given", who, h[E_PIECE], n_piece);
   PGX_REQUIRE(h[E_RANGE] == UINT32_MAX, PGX_EARG, "%s: the strings of alignment %u lie outside the %zu bytes given", who, h[E_RANGE], str_bytes);
   PGX_REQUIRE(h[E_OFFSET] == UINT32_MAX, PGX_EINVAL, "%s: piece %u: an alignment with a negative t_offset", who, h[E_OFFSET]);
@@ -336,14 +339,16 @@ void check_args(const char *who, const void *alns, size_t n_aln, const void *q, 
   PGX_REQUIRE(n_aln < (1ull << 31), PGX_EARG, "%s: too many alignments for one call", who);
 }
 
+}  // namespace
+
 void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, const uint8_t *d_q, const uint8_t *d_t, size_t str_bytes, const uint32_t *piece_tlen,
-                  size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats) {
+                  size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats, const uint32_t *names) {
   PGX_REQUIRE(text && piece_off && (n_piece == 0 || piece_tlen), PGX_EARG, "%s: null argument", who);
   check_args(who, d_alns, n_aln, d_q, d_t, str_bytes);
   PGX_REQUIRE(n_piece <= MAX_PIECES, PGX_EARG, "%s: more than %u pieces in one call", who, MAX_PIECES);
   std::vector<uint64_t> cov_off(n_piece + 1, 0);
   for (size_t p = 0; p < n_piece; ++p) {
-    PGX_REQUIRE(piece_tlen[p] <= (uint32_t)INT32_MAX, PGX_EARG, "%s: piece %zu: a template of %u bases", who, p, piece_tlen[p]);
+    PGX_REQUIRE(piece_tlen[p] <= (uint32_t)INT32_MAX, PGX_EARG, "%s: piece %zu: a template of %u bases", who, names ? (size_t)names[p] : p, piece_tlen[p]);
     cov_off[p + 1] = cov_off[p] + piece_tlen[p];
   }
   *text = nullptr;
@@ -363,7 +368,7 @@ void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, cons
   DevBuf<uint64_t> d_cov_off(np + 1);
   d_tlen.upload(piece_tlen, np);
   d_cov_off.upload(cov_off.data(), np + 1);
-  scan_and_check(who, d_alns, n_aln, d_q, d_t, str_bytes, d_tlen.p, np, ntag, err);
+  scan_and_check(who, d_alns, n_aln, d_q, d_t, str_bytes, d_tlen.p, np, ntag, err, names);
   PrimWs ws;
   DevBuf<uint64_t> tag_off(n_aln + 1);
   const uint64_t n_tag64 = scan_to_total(ntag.p, tag_off.p, n_aln, &ws);
@@ -418,7 +423,8 @@ void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, cons
   PGX_HIP(hipMemcpyAsync(&no_end, err.p + E_NOEND, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   DevBuf<uint64_t> d_off(np + 1);
   const uint64_t total = scan_to_total(len.p, d_off.p, np, &ws);   // (synchronises)
-  PGX_REQUIRE(no_end == UINT32_MAX, PGX_EINVAL, "%s: piece %u: no alignment path scores above zero, the reference has no consensus for it", who, no_end);
+  PGX_REQUIRE(no_end == UINT32_MAX, PGX_EINVAL, "%s: piece %u: no alignment path scores above zero, the reference has no consensus for it", who,
+              names ? names[no_end] : no_end);
   DevBuf<char> d_text(total ? total : 1);
   hipLaunchKernelGGL(k_cns_text, dim3(np), dim3(256), 0, st, rev.p, pnode.p, len.p, d_off.p, d_text.p);
   ev.mark(5);
@@ -438,7 +444,6 @@ void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, cons
   }
 }
 
-}  // namespace
 }  // namespace pgx
 
 using namespace pgx;
@@ -450,7 +455,7 @@ int pgx_cns_call_dev(const pgx_cns_aln *d_alns, size_t n_aln, const char *d_q_st
   return guarded([&] {
     require_ready();
     cns_call_dev("pgx_cns_call_dev", d_alns, n_aln, (const uint8_t *)d_q_str, (const uint8_t *)d_t_str, str_bytes, piece_tlen, n_piece, min_cov, text, piece_off,
-                 stats);
+                 stats, nullptr);
   });
 }
 
@@ -465,7 +470,7 @@ int pgx_cns_call(const pgx_cns_aln *alns, size_t n_aln, const char *q_str, const
     d_alns.upload(alns, n_aln);
     d_q.upload((const uint8_t *)q_str, str_bytes);
     d_t.upload((const uint8_t *)t_str, str_bytes);
-    cns_call_dev("pgx_cns_call", d_alns.p, n_aln, d_q.p, d_t.p, str_bytes, piece_tlen, n_piece, min_cov, text, piece_off, stats);
+    cns_call_dev("pgx_cns_call", d_alns.p, n_aln, d_q.p, d_t.p, str_bytes, piece_tlen, n_piece, min_cov, text, piece_off, stats, nullptr);
   });
 }
 

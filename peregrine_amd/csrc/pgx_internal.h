@@ -693,6 +693,10 @@ T *host_copy(const std::vector<T> &v) {
   if (v.size()) memcpy(p, v.data(), v.size() * sizeof(T));
   return p;
 }
+// The consensus call on rows and strings in device memory (pgx_cns.hip; include/pgx.h: pgx_cns_call_dev; piece_tlen and the results are the
+// host's).  names: where the pieces are a selection of the caller's, the caller's number of each, which the refusals then name (or nullptr).
+void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, const uint8_t *d_q, const uint8_t *d_t, size_t str_bytes, const uint32_t *piece_tlen,
+                  size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats, const uint32_t *names);
 // n bytes of text as a NUL-terminated string of the caller's (pgx_free); src == nullptr: room for n bytes, still to be filled
 inline char *caller_text(const char *src, size_t n) {
   char *t = (char *)malloc(n + 1);

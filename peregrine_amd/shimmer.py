@@ -940,6 +940,78 @@ def align_tags(alns, device=None):
     return [allt[int(off[a]):int(off[a + 1])] for a in range(len(rows))]
 
 
+def _pool(seqs):
+    """byte strings back to back, each stored once (by identity): the pool and where each begins"""
+    parts, where, at = [], {}, 0
+    for s in seqs:
+        if id(s) not in where:
+            where[id(s)] = at
+            parts.append(bytes(s))
+            at += len(s)
+    return np.frombuffer(b"".join(parts), np.uint8), where
+
+
+def falcon_align(pairs, band: int = 150, want_str=True, device=None, stats: dict | None = None):
+    """falcon.align (falcon/DW_banded.c) for a batch of pairs (pgx_falcon_align): pairs is a list of (q_bytes, t_bytes) or (q_bytes,
+    t_bytes, band); the answer one (aln_str_size, dist, aln_q_s, aln_q_e, aln_t_s, aln_t_e, q_aln_str, t_aln_str) per pair, the fields of the
+    reference's `alignment` in its order.  A pair that does not align answers zeros and empty strings.  want_str: one flag for all pairs or
+    one per pair; without it the strings are empty and aln_str_size is (q_e + t_e + dist) / 2.  stats: filled with pgx_faln_stats."""
+    _lib.init(device)
+    pairs = list(pairs)
+    want = [bool(want_str)] * len(pairs) if np.ndim(want_str) == 0 else [bool(w) for w in want_str]
+    if len(want) != len(pairs):
+        raise ValueError(f"{len(want)} want_str flags for {len(pairs)} pairs")
+    seq, where = _pool(s for pr in pairs for s in pr[:2])
+    reqs = np.zeros(len(pairs), _lib.FALN_REQ_DTYPE)
+    for i, pr in enumerate(pairs):
+        reqs[i] = (where[id(pr[0])], where[id(pr[1])], len(pr[0]), len(pr[1]), pr[2] if len(pr) > 2 else band, want[i])
+    res = np.zeros(len(pairs), _lib.FALN_RES_DTYPE)
+    q_str, t_str, nb, st = C.c_void_p(), C.c_void_p(), C.c_uint64(0), _lib.FalnStats()
+    _lib.check(_lib.load().pgx_falcon_align(_ptr(reqs), len(reqs), _ptr(seq), len(seq), _ptr(res), C.byref(q_str), C.byref(t_str), C.byref(nb), C.byref(st)),
+               "pgx_falcon_align")
+    qs, ts = C.string_at(q_str.value, nb.value), C.string_at(t_str.value, nb.value)
+    _lib.load().pgx_free(q_str)
+    _lib.load().pgx_free(t_str)
+    if stats is not None:
+        stats.update(st.asdict())
+    out = []
+    for r, w in zip(res.tolist(), want):
+        n = r[0] if w else 0
+        out.append((*r[:6], qs[r[6]:r[6] + n], ts[r[6]:r[6] + n]))
+    return out
+
+
+def consensus_reads(pieces, min_cov: int = 1, device=None, stats: dict | None = None, used: list | None = None):
+    """pg_asm_cns.py:143-244 for a batch of pieces (pgx_cns_pieces): pieces is a list of (template_bytes, [(read_bytes, read_shift), ...]);
+    every read is aligned to its template on the GPU (the back-bone too), kept or dropped by the script's rule, and the pieces answered
+    by the consensus call or, where fewer than 3 template lengths aligned, by the template in lower case.  One `bytes` per piece.
+    used: a list that receives one bool array per piece (which reads were accepted); stats: filled with pgx_cns_pieces_stats."""
+    _lib.init(device)
+    pieces = [(t, list(reads)) for t, reads in pieces]
+    seq, where = _pool([t for t, _ in pieces] + [r for _, reads in pieces for r, _ in reads])
+    pc = np.zeros(len(pieces), _lib.CNS_PIECE_DTYPE)
+    rd = np.zeros(sum(len(reads) for _, reads in pieces), _lib.CNS_READ_DTYPE)
+    i = 0
+    for p, (t, reads) in enumerate(pieces):
+        pc[p] = (where[id(t)], len(t), 0)
+        for r, shift in reads:
+            rd[i] = (where[id(r)], len(r), p, shift, 0)
+            i += 1
+    off = np.zeros(len(pieces) + 1, np.uint64)
+    flags = np.zeros(len(rd), np.uint8)
+    text, st = C.c_void_p(), _lib.CnsPiecesStats()
+    _lib.check(_lib.load().pgx_cns_pieces(_ptr(pc), len(pc), _ptr(rd), len(rd), _ptr(seq), len(seq), int(min_cov), C.byref(text), _ptr(off), _ptr(flags),
+                                          C.byref(st)), "pgx_cns_pieces")
+    data = C.string_at(text.value, int(off[-1]))
+    _lib.load().pgx_free(text)
+    if stats is not None:
+        stats.update(st.asdict())
+    if used is not None:
+        ends = np.cumsum([len(reads) for _, reads in pieces]).tolist()
+        used[:] = [flags[e - len(reads):e].astype(bool) for e, (_, reads) in zip(ends, pieces)]
+    return [data[int(off[p]):int(off[p + 1])] for p in range(len(pieces))]
+
+
 def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None):
     """in-memory form of shmr_map (pgx_map): arrays in, text out"""
     _lib.init(device)
