@@ -218,9 +218,6 @@ struct Head {   // the head of a line that is made of `s~via~t` pieces
 struct Piece {
   uint32_t u, head, last;   // the entry; its line's Head if it starts the line (NONE otherwise); whether it ends the line
 };
-constexpr uint32_t PIECE_MAX = 256;   // a contig line's head (id 10, type 12, a triple 41, a name 13, two numbers of <= 20, 6 blanks) + a triple + 1 = 161
-constexpr uint32_t CP_TILE = 8192, CP_THREADS = 256;
-
 template <bool WRITE>
 __device__ inline void put(LineOut<WRITE> &o, const char *s) {
   for (; *s; ++s) o.ch(*s);
@@ -243,52 +240,45 @@ __device__ inline void put_entry_head(LineOut<WRITE> &o, const Ent &e) {   // "s
   put_node(o, e.s), o.ch(' '), put_node(o, e.via), o.ch(' '), put_node(o, e.t), o.ch(' '), put_type(o, e.type), o.ch(' ');
   o.i64(e.len), o.ch(' '), o.i64(e.score), o.ch(' ');
 }
-// what the format kernels read
+// the piece source of both texts (pgx_text.h's piece scheme lays them out and formats them)
 struct TextSrc {
   const Ent *ent;
   const pgx_unitig *tab;        // the slot pieces (utg_data's simple lines): pieces [0, m_slots)
   const uint32_t *slot_u;
   const uint64_t *slot_w;
   uint32_t m_slots;
-  const Piece *piece;           // the triple pieces: pieces [m_slots, n_pieces)
+  const Piece *triples;         // the triple pieces: pieces [m_slots, n)
   const Head *head;
-  uint32_t n_pieces;
-};
-template <bool WRITE>
-__device__ inline uint32_t format_piece(const TextSrc &src, uint32_t j, char *dst) {
-  LineOut<WRITE> o{dst, 0};
-  if (j < src.m_slots) {
-    const uint32_t u = src.slot_u[j];
-    const uint64_t first = src.tab[u].first;
-    if (j == first) put_entry_head(o, src.ent[u]), put_node(o, src.ent[u].s), o.ch('~');
-    put_node(o, src.slot_w[j]);
-    o.ch(j == first + src.tab[u].n_edges - 1 ? '\n' : '~');
+  uint32_t n;
+  static constexpr uint32_t MAX = 256;   // a contig line's head (id 10, type 12, a triple 41, a name 13, two numbers of <= 20, 6 blanks) + a triple + 1 = 161
+  template <bool WRITE>
+  __device__ uint32_t piece(uint32_t j, char *dst) const {
+    LineOut<WRITE> o{dst, 0};
+    if (j < m_slots) {
+      const uint32_t u = slot_u[j];
+      const uint64_t first = tab[u].first;
+      if (j == first) put_entry_head(o, ent[u]), put_node(o, ent[u].s), o.ch('~');
+      put_node(o, slot_w[j]);
+      o.ch(j == first + tab[u].n_edges - 1 ? '\n' : '~');
+      return o.n;
+    }
+    const Piece p = triples[j - m_slots];
+    if (p.head != NONE) {
+      const Head h = head[p.head];
+      if (h.kind == 0) {
+        put_entry_head(o, ent[h.u0]);
+      } else {
+        if (h.kind == 3) o.i64((int64_t)h.id, 6);
+        else o.u32(h.id, 6), o.ch(h.kind == 1 ? 'F' : 'R');
+        put(o, h.circular ? " ctg_circular " : " ctg_linear ");
+        put_triple(o, ent[h.u0]), o.ch(' '), put_node(o, h.end), o.ch(' '), o.i64(h.len), o.ch(' '), o.i64(h.score), o.ch(' ');
+      }
+    }
+    put_triple(o, ent[p.u]);
+    o.ch(p.last ? '\n' : '|');
     return o.n;
   }
-  const Piece p = src.piece[j - src.m_slots];
-  if (p.head != NONE) {
-    const Head h = src.head[p.head];
-    if (h.kind == 0) {
-      put_entry_head(o, src.ent[h.u0]);
-    } else {
-      if (h.kind == 3) o.i64((int64_t)h.id, 6);
-      else o.u32(h.id, 6), o.ch(h.kind == 1 ? 'F' : 'R');
-      put(o, h.circular ? " ctg_circular " : " ctg_linear ");
-      put_triple(o, src.ent[h.u0]), o.ch(' '), put_node(o, h.end), o.ch(' '), o.i64(h.len), o.ch(' '), o.i64(h.score), o.ch(' ');
-    }
-  }
-  put_triple(o, src.ent[p.u]);
-  o.ch(p.last ? '\n' : '|');
-  return o.n;
-}
-__global__ void k_cp_piece_len(TextSrc src, uint32_t *__restrict__ len) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < src.n_pieces) len[j] = format_piece<false>(src, j, nullptr);
-}
-__global__ void k_cp_line_off(const uint32_t *__restrict__ line_piece, const uint64_t *__restrict__ poff, uint32_t n_lines, uint64_t *__restrict__ line_off) {
-  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l <= n_lines) line_off[l] = poff[line_piece[l]];
-}
+};
 // the first piece of every line of utg_data: a simple unitig's first slot, a compound line's first triple piece, and the end
 __global__ void k_cp_utg_line_piece(const pgx_unitig *__restrict__ tab, uint32_t n_u, const uint32_t *__restrict__ sub_off, uint32_t n_c, uint32_t m_slots,
                                     uint32_t *__restrict__ line_piece) {
@@ -296,40 +286,10 @@ __global__ void k_cp_utg_line_piece(const pgx_unitig *__restrict__ tab, uint32_t
   if (l > n_u + n_c) return;
   line_piece[l] = l < n_u ? (uint32_t)tab[l].first : m_slots + sub_off[l - n_u];
 }
-// A workgroup per tile of CP_TILE output bytes, as k_ut_format: the pieces that cover the tile are found by binary search of the pieces'
-// offsets, each is formatted whole into LDS (PIECE_MAX bytes of margin on either side), and the tile streams out.
-__global__ __launch_bounds__(CP_THREADS) void k_cp_format(TextSrc src, const uint64_t *__restrict__ poff, uint64_t base, uint64_t total, char *__restrict__ text) {
-  __shared__ __attribute__((aligned(16))) char tile[PIECE_MAX + CP_TILE + PIECE_MAX];
-  const uint64_t t0 = (uint64_t)blockIdx.x * CP_TILE, lo = base + t0, hi = base + min(total, t0 + CP_TILE);
-  uint32_t a = 0, b = src.n_pieces;   // the last piece that starts at or before lo (poff[0 .. n] ascending, poff[n] > lo)
-  while (a < b) {
-    const uint32_t mid = a + ((b - a) >> 1);
-    if (poff[mid + 1] <= lo) a = mid + 1;
-    else b = mid;
-  }
-  for (uint32_t j = a + threadIdx.x; j < src.n_pieces; j += CP_THREADS) {
-    const uint64_t at = poff[j];
-    if (at >= hi) break;
-    format_piece<true>(src, j, tile + PIECE_MAX + (int64_t)(at - lo));   // (at - lo > -PIECE_MAX: the piece reaches past lo)
-  }
-  __syncthreads();
-  tile_out<CP_THREADS>(tile + PIECE_MAX, text + t0, 0, (uint32_t)(hi - lo));
-}
 }  // namespace
 }  // namespace pgx
 
 using namespace pgx;
-
-namespace pgx {
-namespace {
-// a text whose pieces and lines are laid out: where each starts in the whole file
-struct TextPlan {
-  DevBuf<uint64_t> poff, line_off;   // pieces + 1, lines + 1
-  uint64_t n_lines = 0, cursor = 0;
-  void release() { poff.release(), line_off.release(); }
-};
-}  // namespace
-}  // namespace pgx
 
 struct pgx_ctg_paths {
   pgx_unitigs *u = nullptr;      // the unitigs whose slot arrays the simple lines of utg_data are read from
@@ -798,18 +758,6 @@ void contig_walks(Cascade &cs, CPath *c_path, uint64_t *device_walks) {
   }
 }
 
-// lays a text out: the lengths of its pieces, their scan, the lines' offsets
-void plan_text(const TextSrc &src, const uint32_t *d_line_piece, uint64_t n_lines, TextPlan *plan, PrimWs *tmp) {
-  hipStream_t st = ctx().stream;
-  plan->n_lines = n_lines, plan->cursor = 0;
-  plan->poff.alloc((size_t)src.n_pieces + 1), plan->line_off.alloc(n_lines + 1);
-  DevBuf<uint32_t> plen(src.n_pieces);
-  if (src.n_pieces) LAUNCH(k_cp_piece_len, src.n_pieces, src, plen.p);
-  (void)scan_to_total(plen.p, plan->poff.p, src.n_pieces, tmp);
-  LAUNCH(k_cp_line_off, n_lines + 1, d_line_piece, plan->poff.p, (uint32_t)n_lines, plan->line_off.p);
-  PGX_HIP(hipGetLastError());
-}
-
 void build_ctg_paths(pgx_unitigs *u, pgx_ctg_paths *c) {
   hipStream_t st = ctx().stream;
   PrimWs tmp;
@@ -972,65 +920,28 @@ void require_cp(const pgx_ctg_paths *c, const char *who) {
 }
 
 int build_entry(const char *who, pgx_unitigs *u, bool owns, pgx_ctg_paths **out) {
-  pgx_ctg_paths *c = nullptr;
-  const int rc = guarded([&] {
-    PGX_REQUIRE(out, PGX_EARG, "%s: null argument", who);
-    *out = nullptr;
-    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "%s: no device context (pgx_init has not been called, or found no HIP device)", who);
-    PGX_REQUIRE(u, PGX_EARG, "%s: null argument", who);
-    int code = PGX_OK;
-    uint64_t n = 0;
-    try {
-      MemTag tag("ctg_paths");
-      n = unitigs_device_view(u, who).n_u;
-      KernelTimer tm("ctg_paths", n);
-      c = new pgx_ctg_paths;
-      build_ctg_paths(u, c);
-    } catch (const Fail &f) {
-      code = build_fail_code(f, who, "contig paths", n, "unitigs");
-    }
-    timing_flush();
-    if (code != PGX_OK) return code;
+  return live_build(who, g_cp, out, [&] { PGX_REQUIRE(u, PGX_EARG, "%s: null argument", who); }, [&](pgx_ctg_paths *c, uint64_t *n) {
+    MemTag tag("ctg_paths");
+    *n = unitigs_device_view(u, who).n_u;
+    KernelTimer tm("ctg_paths", *n);
+    build_ctg_paths(u, c);
     c->owns_u = owns;
-    g_cp.add(c);
-    *out = c;
-    return (int)PGX_OK;
-  });
-  if (rc != PGX_OK) delete c;
-  return rc;
+  }, "contig paths", "unitigs");
 }
 
 int text_entry(const char *who, pgx_ctg_paths *c, bool utg, uint64_t max_lines, char **text, size_t *text_len, int *done) {
   return text_call(text, text_len, done, [&] {
     require_cp(c, who);
-    PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "%s: null argument or max_lines == 0", who);
-    hipStream_t st = ctx().stream;
     TextPlan &plan = utg ? c->utg : c->ctg;
-    const uint64_t nl = text_lines(max_lines, plan.n_lines - plan.cursor);
-    if (nl == 0) {
-      text_hand_out(c->stage, nullptr, 0, text, text_len);
-    } else {
-      TextSrc src{c->ent.p, nullptr, nullptr, nullptr, 0, c->ctg_piece.p, c->ctg_head.p, c->n_ctg_pieces};
-      if (utg) {
-        PGX_REQUIRE(unitigs_live(c->u, c->u_serial), PGX_ESTATE, "%s: the unitigs these contig paths were made of are gone (utg_data reads their paths)", who);
-        const UnitigsView v = unitigs_device_view(c->u, who);
-        src = TextSrc{c->ent.p, v.tab, v.slot_u, v.slot_w, c->m_slots, c->utg_piece.p, c->utg_head.p, c->n_utg_pieces};
-      }
-      KernelTimer tm("ctg_paths", nl), tm_text("ctg_paths_text", nl);
-      MemTag tag("ctg_paths");
-      uint64_t range[2];
-      PGX_HIP(hipMemcpyAsync(&range[0], plan.line_off.p + plan.cursor, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      PGX_HIP(hipMemcpyAsync(&range[1], plan.line_off.p + plan.cursor + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      pgx::sync();
-      const uint64_t total = range[1] - range[0];
-      char *d_text = ws<char>("cp.text", total + 16);
-      hipLaunchKernelGGL(k_cp_format, dim3(cdiv(total, CP_TILE)), dim3(CP_THREADS), 0, st, src, plan.poff.p, range[0], total, d_text);
-      PGX_HIP(hipGetLastError());
-      text_hand_out(c->stage, d_text, total, text, text_len);
+    TextSrc src{c->ent.p, nullptr, nullptr, nullptr, 0, c->ctg_piece.p, c->ctg_head.p, c->n_ctg_pieces};
+    // utg_data reads the unitigs' slot arrays -- where text_next will format something: it refuses its arguments, and hands out the empty
+    // text behind the last line, before it looks at the source
+    if (utg && text && text_len && done && max_lines && plan.cursor < plan.n_lines) {
+      PGX_REQUIRE(unitigs_live(c->u, c->u_serial), PGX_ESTATE, "%s: the unitigs these contig paths were made of are gone (utg_data reads their paths)", who);
+      const UnitigsView v = unitigs_device_view(c->u, who);
+      src = TextSrc{c->ent.p, v.tab, v.slot_u, v.slot_w, c->m_slots, c->utg_piece.p, c->utg_head.p, c->n_utg_pieces};
     }
-    plan.cursor += nl;
-    if (plan.cursor == plan.n_lines) *done = 1;
-    timing_flush();
+    text_next(who, plan, src, c->stage, TextNames{"ctg_paths", "ctg_paths_text", "ctg_paths", "cp.text"}, max_lines, text, text_len, done);
   });
 }
 }  // namespace

@@ -160,6 +160,7 @@ static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) 
 // unitigs).  T supplies `bool shut` and drop_device_state(), which releases what the object holds on the device (idempotent).  The
 // shutdown rule: pgx_shutdown drops the device state of every member and marks it `shut` -- the caller still holds the handle, whose
 // entry points then refuse it, and destroys it whenever it likes.  Use: LiveSet<T> g_set; ShutdownHook g_hook([] { g_set.shutdown(); });
+// Members are made by live_build (below, behind the timers it flushes).
 template <class T>
 class LiveSet {
   std::mutex mu;
@@ -263,6 +264,36 @@ struct KernelTimer {
   hipEvent_t e0, e1;
 };
 void timing_flush();  // resolve pending events into the totals (synchronises the stream)
+
+// The entry point that builds a member of a LiveSet, once.  In this order: `out` is checked and cleared; no device context is refused;
+// pre() throws the stage's own refusals of its arguments and their state; build(obj, &n) fills a new T inside the stage's own MemTag and
+// KernelTimer scopes, and keeps n -- the size of its input, in `units` -- current for the message of a device that ran out of memory
+// (build_fail_code); the timers are flushed; the object joins the set and goes to *out.  After any failure the object is deleted.
+template <class T, class Pre, class Build>
+int live_build(const char *who, LiveSet<T> &set, T **out, Pre &&pre, Build &&build, const char *what, const char *units) {
+  T *obj = nullptr;
+  const int rc = guarded([&] {
+    PGX_REQUIRE(out, PGX_EARG, "%s: null argument", who);
+    *out = nullptr;
+    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "%s: no device context (pgx_init has not been called, or found no HIP device)", who);
+    pre();
+    int code = PGX_OK;
+    uint64_t n = 0;
+    try {
+      obj = new T;
+      build(obj, &n);
+    } catch (const Fail &f) {
+      code = build_fail_code(f, who, what, n, units);
+    }
+    timing_flush();
+    if (code != PGX_OK) return code;
+    set.add(obj);
+    *out = obj;
+    return (int)PGX_OK;
+  });
+  if (rc != PGX_OK) delete obj;
+  return rc;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // resident read database

@@ -559,11 +559,7 @@ const pgx_sgraph_edge *sgraph_device_edges(const pgx_sgraph *g, const char *who,
 }  // namespace pgx
 
 extern "C" int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min_idt, uint32_t flags, pgx_sgraph **out) {
-  pgx_sgraph *g = nullptr;
-  const int rc = guarded([&] {
-    PGX_REQUIRE(out, PGX_EARG, "pgx_sgraph_build: null argument");
-    *out = nullptr;
-    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "pgx_sgraph_build: no device context (pgx_init has not been called, or found no HIP device)");
+  auto pre = [&] {
     PGX_REQUIRE(s, PGX_EARG, "pgx_sgraph_build: null argument");
     PGX_REQUIRE(!s->shut, PGX_ESTATE, "pgx_sgraph_build: pgx_shutdown ran while the stream was open (close it)");
     PGX_REQUIRE(!s->failed, PGX_ESTATE, "pgx_sgraph_build: the stream returned an error before (close it)");
@@ -575,24 +571,14 @@ extern "C" int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min
     PGX_REQUIRE(!(flags & PGX_SGRAPH_LFC), PGX_EINVAL, "pgx_sgraph_build: --lfc is not offered (pg_run.py leaves it off)");
     PGX_REQUIRE(flags == 0, PGX_EINVAL, "pgx_sgraph_build: unknown flag bits 0x%x", flags);
     PGX_REQUIRE(!(min_idt != min_idt), PGX_EARG, "pgx_sgraph_build: min_idt is not a number");
-    int code = PGX_OK;
-    try {
-      KernelTimer tm("sgraph", s->store_n);
-      if (!s->draining) graph_compact(s);
-      PGX_REQUIRE(s->store_n <= (uint64_t)INT32_MAX, PGX_EINVAL, "pgx_sgraph_build: %llu kept rows, more than 2^31 - 1", (unsigned long long)s->store_n);
-      g = new pgx_sgraph;
-      build_graph(s->store.p, (uint32_t)s->store_n, min_len, min_idt, g);
-    } catch (const Fail &f) {
-      code = build_fail_code(f, "pgx_sgraph_build", "graph", s->store_n, "rows");   // (the stream is untouched: pgx_dedup_drain still has its rows)
-    }
-    timing_flush();
-    if (code != PGX_OK) return code;
-    g_graphs.add(g);
-    *out = g;
-    return (int)PGX_OK;
-  });
-  if (rc != PGX_OK) delete g;
-  return rc;
+  };
+  // (after a failure the stream is untouched: pgx_dedup_drain still has its rows)
+  return live_build("pgx_sgraph_build", g_graphs, out, pre, [&](pgx_sgraph *g, uint64_t *n) {
+    KernelTimer tm("sgraph", *n = s->store_n);
+    if (!s->draining) graph_compact(s), *n = s->store_n;
+    PGX_REQUIRE(s->store_n <= (uint64_t)INT32_MAX, PGX_EINVAL, "pgx_sgraph_build: %llu kept rows, more than 2^31 - 1", (unsigned long long)s->store_n);
+    build_graph(s->store.p, (uint32_t)s->store_n, min_len, min_idt, g);
+  }, "graph", "rows");
 }
 
 extern "C" int pgx_sgraph_stats(const pgx_sgraph *g, pgx_sgraph_stats_t *out) {

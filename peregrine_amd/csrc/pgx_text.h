@@ -1,7 +1,12 @@
 // pgx_text.h -- everything about device text, once: the pieces of a line as glibc prints them (LineOut), the stream-out of a tile of
-// text from LDS (tile_out), the pinned staging that device text leaves through (TextStage), and the host side of an entry point that
-// hands text out (text_call, text_hand_out).  Used by the stages that write their text on the device: pgx_dedup.hip, pgx_sgraph.hip,
-// pgx_unitigs.hip.
+// text from LDS (tile_out), the pinned staging that device text leaves through (TextStage), the host side of an entry point that hands
+// text out (text_call, text_hand_out), and the piece scheme whole (k_piece_len, k_piece_format, TextPlan, plan_text, text_next).
+// The stages that write their text on the device tile it in one of two ways:
+//   * tiles of lines: a workgroup formats 256 lines into LDS behind a pad to the global address's phase (k_format of pgx_dedup.hip,
+//     k_sg_format of pgx_sgraph.hip).  The two kernels are their stages' own; they share LineOut, tile_out and the host side.
+//   * tiles of bytes over pieces: a workgroup serves TEXT_TILE bytes of the file and finds the pieces that touch them by searching the
+//     pieces' offsets (pgx_unitigs.hip, pgx_ctgpaths.hip, pgx_tiling.hip).  A stage supplies a piece source; the kernels, the layout and
+//     the hand-out are here.
 #pragma once
 #include <algorithm>
 
@@ -143,5 +148,102 @@ int text_call(char **text, size_t *text_len, int *done, F &&body) {
     if (text_len) *text_len = 0;
   }
   return rc;
+}
+
+// ---- tiles of bytes over pieces -------------------------------------------------------------------------------------------------------
+// A text is a sequence of pieces: piece j occupies the bytes [poff[j], poff[j + 1]) of the whole file.  A line starts at the first byte
+// of some piece (a line is one piece or several).  No piece is longer than its source's bound.
+// A piece source is a trivially copyable struct that goes to the kernels by value and supplies
+//   uint32_t n                                                       the number of pieces
+//   static constexpr uint32_t MAX                                    an upper bound of a piece's length, a multiple of 16
+//   template <bool WRITE> __device__ uint32_t piece(j, dst) const    prints piece j through LineOut<WRITE>, returns its length
+constexpr uint32_t TEXT_TILE = 8192, TEXT_THREADS = 256;
+template <class Src>
+__global__ void k_piece_len(Src src, uint32_t *__restrict__ len) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < src.n) len[j] = src.template piece<false>(j, nullptr);
+}
+template <class Index>
+__global__ void k_line_off(const Index *__restrict__ first_piece, const uint64_t *__restrict__ poff, uint32_t n_lines, uint64_t *__restrict__ line_off) {
+  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l <= n_lines) line_off[l] = poff[first_piece[l]];
+}
+// A workgroup per tile of TEXT_TILE output bytes: text[t * TEXT_TILE ..) holds the characters base + t * TEXT_TILE .. of the whole file.
+// The pieces that cover the tile are found by binary search of the pieces' offsets (as k_stitch finds its segments); each is formatted
+// whole into LDS, which has Src::MAX bytes of margin on either side for the pieces that straddle the tile's ends, and the tile streams
+// out (tile_out from its byte 0: text is 16-byte aligned, TEXT_TILE and Src::MAX are multiples of 16).
+template <class Src>
+__global__ __launch_bounds__(TEXT_THREADS) void k_piece_format(Src src, const uint64_t *__restrict__ poff, uint64_t base, uint64_t total, char *__restrict__ text) {
+  static_assert(Src::MAX % 16 == 0, "the margin keeps the tile 16-byte aligned in LDS");
+  __shared__ __attribute__((aligned(16))) char tile[Src::MAX + TEXT_TILE + Src::MAX];
+  const uint64_t t0 = (uint64_t)blockIdx.x * TEXT_TILE, lo = base + t0, hi = base + min(total, t0 + TEXT_TILE);
+  // the last piece that starts at or before lo (poff[0 .. n] ascending, poff[n] > lo)
+  uint32_t a = 0, b = src.n;
+  while (a < b) {
+    const uint32_t mid = a + ((b - a) >> 1);
+    if (poff[mid + 1] <= lo) a = mid + 1;
+    else b = mid;
+  }
+  for (uint32_t j = a + threadIdx.x; j < src.n; j += TEXT_THREADS) {
+    const uint64_t at = poff[j];
+    if (at >= hi) break;
+    src.template piece<true>(j, tile + Src::MAX + (int64_t)(at - lo));   // (at - lo > -Src::MAX: the piece reaches past lo)
+  }
+  __syncthreads();
+  tile_out<TEXT_THREADS>(tile + Src::MAX, text + t0, 0, (uint32_t)(hi - lo));
+}
+
+// a text whose pieces and lines are laid out: where each starts in the whole file, and how many lines have been handed out
+struct TextPlan {
+  DevBuf<uint64_t> poff, line_off;   // pieces + 1; lines + 1, or none where every piece is a line
+  uint64_t n_lines = 0, cursor = 0;
+  const uint64_t *line_offs() const { return line_off.p ? line_off.p : poff.p; }
+  void release() { poff.release(), line_off.release(); }
+};
+// lays a text out: the lengths of its pieces, their scan, the lines' offsets.  d_first_piece: lines + 1 entries, the first piece of each
+// line and the number of pieces behind the last; a typed nullptr where every piece is a line.  No piece: no launch, poff[0] = 0.
+template <class Src, class Index>
+void plan_text(const Src &src, const Index *d_first_piece, uint64_t n_lines, TextPlan *plan, PrimWs *tmp) {
+  hipStream_t st = ctx().stream;
+  plan->n_lines = n_lines, plan->cursor = 0;
+  plan->poff.alloc((size_t)src.n + 1);
+  DevBuf<uint32_t> plen(src.n);
+  if (src.n) LAUNCH(k_piece_len<Src>, src.n, src, plen.p);
+  (void)scan_to_total(plen.p, plan->poff.p, src.n, tmp);
+  if (d_first_piece) {
+    plan->line_off.alloc(n_lines + 1);
+    LAUNCH(k_line_off<Index>, n_lines + 1, d_first_piece, plan->poff.p, (uint32_t)n_lines, plan->line_off.p);
+  }
+  PGX_HIP(hipGetLastError());
+}
+// what a stage calls its timers (the stage's total, its text), its MemTag and the workspace its text is formatted into
+struct TextNames {
+  const char *stage, *text, *tag, *ws;
+};
+// The body of an entry point that hands out the next lines of a planned text, [cursor, cursor + max_lines), inside text_call: two offsets
+// come down, the tiles between them are formatted and handed out through `stage`; *done when the last line has left.
+template <class Src>
+void text_next(const char *who, TextPlan &plan, const Src &src, TextStage &stage, const TextNames &names, uint64_t max_lines, char **text, size_t *text_len, int *done) {
+  PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "%s: null argument or max_lines == 0", who);
+  hipStream_t st = ctx().stream;
+  const uint64_t nl = text_lines(max_lines, plan.n_lines - plan.cursor);
+  if (nl == 0) {
+    text_hand_out(stage, nullptr, 0, text, text_len);
+  } else {
+    KernelTimer tm(names.stage, nl), tm_text(names.text, nl);
+    MemTag tag(names.tag);
+    uint64_t range[2];
+    PGX_HIP(hipMemcpyAsync(&range[0], plan.line_offs() + plan.cursor, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    PGX_HIP(hipMemcpyAsync(&range[1], plan.line_offs() + plan.cursor + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    pgx::sync();
+    const uint64_t total = range[1] - range[0];
+    char *d_text = ws<char>(names.ws, total + 16);
+    hipLaunchKernelGGL(k_piece_format<Src>, dim3(cdiv(total, TEXT_TILE)), dim3(TEXT_THREADS), 0, st, src, plan.poff.p, range[0], total, d_text);
+    PGX_HIP(hipGetLastError());
+    text_hand_out(stage, d_text, total, text, text_len);
+  }
+  plan.cursor += nl;
+  if (plan.cursor == plan.n_lines) *done = 1;
+  timing_flush();
 }
 }  // namespace pgx

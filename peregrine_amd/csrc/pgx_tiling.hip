@@ -344,54 +344,34 @@ __global__ void k_tl_rows(const uint64_t *__restrict__ path_row0, const uint32_t
 // ---------------------------------------------------------------------------------------------------------
 // the text: '%s %s %s %s %d %d %d %0.2f %d %d\n' % (ctg_id, v, w, rid, s, t, aln_score, idt, ctg_length, |s - t|), a line per row
 // ---------------------------------------------------------------------------------------------------------
-constexpr uint32_t TL_LINE_MAX = 256;   // CTG_NAME_MAX + 2 names of <= 13 + a rid of <= 11 + 2 numbers of <= 11 + a score of <= 20 + an identity of <= 24 + a length
-                                        // of <= 20 + a difference of <= 10 + 9 blanks + '\n' = 239
-template <bool WRITE>
-__device__ inline uint32_t format_line(uint32_t r, const pgx_tile_row *__restrict__ rows, const RowInfo *__restrict__ info, const uint64_t *__restrict__ cum,
-                                       const uint64_t *__restrict__ path_row0, const uint32_t *__restrict__ name_off, const char *__restrict__ names, char *dst) {
-  LineOut<WRITE> o{dst, 0};
-  const pgx_tile_row row = rows[r];
-  const RowInfo ri = info[r];
-  const uint32_t a = name_off[ri.path], b = name_off[ri.path + 1];
-  if (WRITE)
-    for (uint32_t k = a; k < b; ++k) dst[k - a] = names[k];
-  o.n = b - a;
-  o.ch(' '), o.node(row.rid0, row.strand0 == 0), o.ch(' '), o.node(row.rid1, row.strand1 == 0), o.ch(' '), o.rid((int32_t)ri.label), o.ch(' ');
-  o.i32(row.s), o.ch(' '), o.i32(row.e), o.ch(' '), o.i64(ri.score), o.ch(' ');
-  const uint64_t ah = ri.hund < 0 ? 0ULL - (uint64_t)ri.hund : (uint64_t)ri.hund, whole = ah / 100u;
-  if (ri.hund < 0) o.ch('-');
-  o.u64(whole), o.ch('.'), o.u32((uint32_t)(ah - whole * 100u), 2), o.ch(' ');
-  o.u64(cum[r] - cum[path_row0[ri.path]]), o.ch(' '), o.u32(ri.dl), o.ch('\n');
-  return o.n;
-}
-__global__ void k_tl_line_len(const pgx_tile_row *__restrict__ rows, const RowInfo *__restrict__ info, const uint64_t *__restrict__ cum, const uint64_t *__restrict__ path_row0,
-                              const uint32_t *__restrict__ name_off, uint32_t n_rows, uint32_t *__restrict__ len) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n_rows) len[r] = format_line<false>(r, rows, info, cum, path_row0, name_off, nullptr, nullptr);
-}
-// A workgroup per tile of TL_TILE output bytes, as k_ut_format: the lines that cover the tile are found by binary search of the lines'
-// offsets, each is formatted whole into LDS (a margin of TL_LINE_MAX on either side takes the lines that straddle the tile's ends), and
-// the tile streams out with 16-byte stores.
-constexpr uint32_t TL_TILE = 8192, TL_THREADS = 256;
-__global__ __launch_bounds__(TL_THREADS) void k_tl_format(const uint64_t *__restrict__ loff, const pgx_tile_row *__restrict__ rows, const RowInfo *__restrict__ info,
-                                                          const uint64_t *__restrict__ cum, const uint64_t *__restrict__ path_row0, const uint32_t *__restrict__ name_off,
-                                                          const char *__restrict__ names, uint32_t n_rows, uint64_t base, uint64_t total, char *__restrict__ text) {
-  __shared__ __attribute__((aligned(16))) char tile[TL_LINE_MAX + TL_TILE + TL_LINE_MAX];
-  const uint64_t t0 = (uint64_t)blockIdx.x * TL_TILE, lo = base + t0, hi = base + min(total, t0 + TL_TILE);
-  uint32_t a = 0, b = n_rows;   // the last line that starts at or before lo (loff[0 .. n_rows] ascending, loff[n_rows] > lo)
-  while (a < b) {
-    const uint32_t mid = a + ((b - a) >> 1);
-    if (loff[mid + 1] <= lo) a = mid + 1;
-    else b = mid;
+// A piece is a line: the piece source of pgx_text.h's piece scheme, which lays the text out and formats it.
+struct RowLines {
+  const pgx_tile_row *__restrict__ rows;
+  const RowInfo *__restrict__ info;
+  const uint64_t *__restrict__ cum, *__restrict__ row0;
+  const uint32_t *__restrict__ name_off;
+  const char *__restrict__ names;
+  uint32_t n;                            // rows
+  static constexpr uint32_t MAX = 256;   // CTG_NAME_MAX + 2 names of <= 13 + a rid of <= 11 + 2 numbers of <= 11 + a score of <= 20 + an identity of <= 24 + a length
+                                         // of <= 20 + a difference of <= 10 + 9 blanks + '\n' = 239
+  template <bool WRITE>
+  __device__ uint32_t piece(uint32_t r, char *dst) const {
+    LineOut<WRITE> o{dst, 0};
+    const pgx_tile_row row = rows[r];
+    const RowInfo ri = info[r];
+    const uint32_t a = name_off[ri.path], b = name_off[ri.path + 1];
+    if (WRITE)
+      for (uint32_t k = a; k < b; ++k) dst[k - a] = names[k];
+    o.n = b - a;
+    o.ch(' '), o.node(row.rid0, row.strand0 == 0), o.ch(' '), o.node(row.rid1, row.strand1 == 0), o.ch(' '), o.rid((int32_t)ri.label), o.ch(' ');
+    o.i32(row.s), o.ch(' '), o.i32(row.e), o.ch(' '), o.i64(ri.score), o.ch(' ');
+    const uint64_t ah = ri.hund < 0 ? 0ULL - (uint64_t)ri.hund : (uint64_t)ri.hund, whole = ah / 100u;
+    if (ri.hund < 0) o.ch('-');
+    o.u64(whole), o.ch('.'), o.u32((uint32_t)(ah - whole * 100u), 2), o.ch(' ');
+    o.u64(cum[r] - cum[row0[ri.path]]), o.ch(' '), o.u32(ri.dl), o.ch('\n');
+    return o.n;
   }
-  for (uint32_t j = a + threadIdx.x; j < n_rows; j += TL_THREADS) {
-    const uint64_t at = loff[j];
-    if (at >= hi) break;
-    format_line<true>(j, rows, info, cum, path_row0, name_off, names, tile + TL_LINE_MAX + (int64_t)(at - lo));   // (at - lo > -TL_LINE_MAX: the line reaches past lo)
-  }
-  __syncthreads();
-  tile_out<TL_THREADS>(tile + TL_LINE_MAX, text + t0, 0, (uint32_t)(hi - lo));
-}
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // host: the parsed sg_edges_list on the device
@@ -777,18 +757,20 @@ struct pgx_tiling {
   struct Set {
     DevBuf<pgx_tile_row> rows;
     DevBuf<RowInfo> info;
-    DevBuf<uint64_t> cum, loff, row0;   // rows + 1: running |s - t| and where each line starts; paths + 1: the first row of each path
+    DevBuf<uint64_t> cum, row0;   // rows + 1: running |s - t|; paths + 1: the first row of each path
     DevBuf<uint32_t> name_off;
     DevBuf<char> names;
     std::string distinct;   // the contigs' names, a line each
     std::vector<std::string> ctg_names;
-    uint64_t n_rows = 0, n_ctg = 0, cursor = 0;
+    TextPlan text;                // a line per row
+    uint64_t n_rows = 0, n_ctg = 0;
+    RowLines lines() const { return RowLines{rows.p, info.p, cum.p, row0.p, name_off.p, names.p, (uint32_t)n_rows}; }
   } set[2];
   pgx_tiling_stats_t st = {};
   TextStage stage;
   bool shut = false;
   void drop_device_state() {
-    for (Set &s : set) s.rows.release(), s.info.release(), s.cum.release(), s.loff.release(), s.row0.release(), s.name_off.release(), s.names.release();
+    for (Set &s : set) s.rows.release(), s.info.release(), s.cum.release(), s.text.release(), s.row0.release(), s.name_off.release(), s.names.release();
     stage.drop();
   }
 };
@@ -815,7 +797,7 @@ void build_set(const PathSet &ps, const DevBuf<uint64_t> &d_pool, uint64_t pool_
   DevBuf<uint32_t> seg_n(n_seg), path_ctg(n_path), dl(n_rows), err(2);
   DevBuf<uint64_t> node_off((size_t)n_seg + 1);
   out.row0.alloc((size_t)n_path + 1), out.name_off.alloc((size_t)n_path + 1), out.names.alloc(ps.names.size() + 1);
-  out.rows.alloc(n_rows), out.info.alloc(n_rows), out.cum.alloc(n_rows + 1), out.loff.alloc(n_rows + 1);
+  out.rows.alloc(n_rows), out.info.alloc(n_rows), out.cum.alloc(n_rows + 1);
   std::vector<uint32_t> h_seg_n(n_seg);
   for (uint32_t i = 0; i < n_seg; ++i) h_seg_n[i] = ps.seg[i].n;
   seg.upload(ps.seg.data(), n_seg), seg_n.upload(h_seg_n.data(), n_seg), path_ctg.upload(ps.ctg.data(), n_path);
@@ -847,12 +829,7 @@ void build_set(const PathSet &ps, const DevBuf<uint64_t> &d_pool, uint64_t pool_
     PGX_REQUIRE(false, PGX_EINVAL, "%s: line %llu: the edge %s %s of its path is not a G edge of the edge table", ctg_name, (unsigned long long)ps.src_line[p], a, b);
   }
   (void)scan_to_total(dl.p, out.cum.p, n_rows, &tmp);
-  {
-    DevBuf<uint32_t> len(n_rows);
-    LAUNCH(k_tl_line_len, n_rows, out.rows.p, out.info.p, out.cum.p, out.row0.p, out.name_off.p, (uint32_t)n_rows, len.p);
-    PGX_HIP(hipGetLastError());
-    (void)scan_to_total(len.p, out.loff.p, n_rows, &tmp);
-  }
+  plan_text(out.lines(), (const uint32_t *)nullptr, n_rows, &out.text, &tmp);   // (no first pieces: a piece per line)
 }
 
 struct Inputs {
@@ -1182,56 +1159,16 @@ void require_tiling(const pgx_tiling *t, int which, const char *who) {
 }
 
 int tiling_entry(const char *who, const Inputs &in, pgx_tiling **out) {
-  pgx_tiling *t = nullptr;
-  const int rc = guarded([&] {
-    PGX_REQUIRE(out, PGX_EARG, "%s: null argument", who);
-    *out = nullptr;
-    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "%s: no device context (pgx_init has not been called, or found no HIP device)", who);
+  auto pre = [&] {
     PGX_REQUIRE((in.sg_fn != nullptr) != (in.g != nullptr), PGX_EARG, "%s: one of a sg_edges_list file and a string graph", who);
     PGX_REQUIRE((in.utg || !in.utg_len) && (in.ctg || !in.ctg_len), PGX_EARG, "%s: null argument", who);
-    int code = PGX_OK;
-    try {
-      MemTag tag("tiling");
-      KernelTimer tm("tiling", 0);
-      t = new pgx_tiling;
-      build_tiling(in, t);
-    } catch (const Fail &f) {
-      code = build_fail_code(f, who, "tiling paths", in.utg_len + in.ctg_len, "bytes of unitigs and contig paths");
-    }
-    timing_flush();
-    if (code != PGX_OK) return code;
-    g_tl.add(t);
-    *out = t;
-    return (int)PGX_OK;
-  });
-  if (rc != PGX_OK) delete t;
-  return rc;
-}
-
-// the next lines of set `which`, as pgx_unitigs_text
-void tiling_text(pgx_tiling *t, int which, uint64_t max_lines, char **text, size_t *text_len, int *done) {
-  hipStream_t st = ctx().stream;
-  pgx_tiling::Set &s = t->set[which];
-  const uint64_t nl = text_lines(max_lines, s.n_rows - s.cursor);
-  if (nl == 0) {
-    text_hand_out(t->stage, nullptr, 0, text, text_len);
-  } else {
-    KernelTimer tm("tiling", nl), tm_text("tiling_text", nl);
+  };
+  return live_build(who, g_tl, out, pre, [&](pgx_tiling *t, uint64_t *n) {
+    *n = in.utg_len + in.ctg_len;
     MemTag tag("tiling");
-    uint64_t range[2];
-    PGX_HIP(hipMemcpyAsync(&range[0], s.loff.p + s.cursor, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    PGX_HIP(hipMemcpyAsync(&range[1], s.loff.p + s.cursor + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    pgx::sync();
-    const uint64_t total = range[1] - range[0];
-    char *d_text = ws<char>("tl.text", total + 16);
-    hipLaunchKernelGGL(k_tl_format, dim3(cdiv(total, TL_TILE)), dim3(TL_THREADS), 0, st, s.loff.p, s.rows.p, s.info.p, s.cum.p, s.row0.p, s.name_off.p, s.names.p,
-                       (uint32_t)s.n_rows, range[0], total, d_text);
-    PGX_HIP(hipGetLastError());
-    text_hand_out(t->stage, d_text, total, text, text_len);
-  }
-  s.cursor += nl;
-  if (s.cursor == s.n_rows) *done = 1;
-  timing_flush();
+    KernelTimer tm("tiling", 0);
+    build_tiling(in, t);
+  }, "tiling paths", "bytes of unitigs and contig paths");
 }
 }  // namespace
 }  // namespace pgx
@@ -1308,8 +1245,8 @@ extern "C" int pgx_tiling_names(const pgx_tiling *t, int which, char **text, siz
 extern "C" int pgx_tiling_text(pgx_tiling *t, int which, uint64_t max_lines, char **text, size_t *text_len, int *done) {
   return text_call(text, text_len, done, [&] {
     require_tiling(t, which, "pgx_tiling_text");
-    PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_tiling_text: null argument or max_lines == 0");
-    tiling_text(t, which, max_lines, text, text_len, done);
+    pgx_tiling::Set &s = t->set[which];
+    text_next("pgx_tiling_text", s.text, s.lines(), t->stage, TextNames{"tiling", "tiling_text", "tiling", "tl.text"}, max_lines, text, text_len, done);
   });
 }
 

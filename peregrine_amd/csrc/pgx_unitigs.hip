@@ -198,58 +198,32 @@ __global__ void k_ut_firsts(const uint64_t *__restrict__ off, uint32_t n_u, pgx_
 // ---------------------------------------------------------------------------------------------------------
 // the text: 's via t simple length score n0~n1~...~nk', a line per unitig.  A line is cut into pieces, one per path slot: the node the
 // slot's edge enters and what follows it ('~', or '\n' behind the line's last); the first slot's piece starts with the line's head and
-// the path's first node.  No piece is longer than PIECE_MAX.
+// the path's first node.  The piece source of pgx_text.h's piece scheme, which lays the text out and formats it.
 // ---------------------------------------------------------------------------------------------------------
-constexpr uint32_t PIECE_MAX = 128;   // 5 names of <= 13, " simple ", two numbers of <= 20, 4 blanks, 2 separators = 119
-template <bool WRITE>
-__device__ inline uint32_t format_piece(uint64_t slot, uint32_t u, uint64_t w, const pgx_unitig *__restrict__ tab, char *dst) {
-  LineOut<WRITE> o{dst, 0};
-  const uint64_t first = tab[u].first;
-  const uint32_t n_edges = tab[u].n_edges;
-  if (slot == first) {
-    const pgx_unitig t = tab[u];
-    o.node(t.s_rid, t.s_end), o.ch(' '), o.node(t.via_rid, t.via_end), o.ch(' '), o.node(t.t_rid, t.t_end);
-    for (const char *c = " simple "; *c; ++c) o.ch(*c);
-    o.i64(t.length), o.ch(' '), o.i64(t.score), o.ch(' ');
-    o.node(t.s_rid, t.s_end), o.ch('~');
+struct SlotPieces {
+  const uint32_t *__restrict__ slot_u;
+  const uint64_t *__restrict__ slot_w;
+  const pgx_unitig *__restrict__ tab;
+  uint32_t n;                                  // path slots
+  static constexpr uint32_t MAX = 128;   // 5 names of <= 13, " simple ", two numbers of <= 20, 4 blanks, 2 separators = 119
+  template <bool WRITE>
+  __device__ uint32_t piece(uint32_t j, char *dst) const {
+    LineOut<WRITE> o{dst, 0};
+    const uint32_t u = slot_u[j];
+    const uint64_t slot = j, w = slot_w[j], first = tab[u].first;
+    const uint32_t n_edges = tab[u].n_edges;
+    if (slot == first) {
+      const pgx_unitig t = tab[u];
+      o.node(t.s_rid, t.s_end), o.ch(' '), o.node(t.via_rid, t.via_end), o.ch(' '), o.node(t.t_rid, t.t_end);
+      for (const char *c = " simple "; *c; ++c) o.ch(*c);
+      o.i64(t.length), o.ch(' '), o.i64(t.score), o.ch(' ');
+      o.node(t.s_rid, t.s_end), o.ch('~');
+    }
+    o.node((uint32_t)(w >> 1), (uint32_t)(w & 1));
+    o.ch(slot == first + n_edges - 1 ? '\n' : '~');
+    return o.n;
   }
-  o.node((uint32_t)(w >> 1), (uint32_t)(w & 1));
-  o.ch(slot == first + n_edges - 1 ? '\n' : '~');
-  return o.n;
-}
-__global__ void k_ut_piece_len(const uint32_t *__restrict__ slot_u, const uint64_t *__restrict__ slot_w, const pgx_unitig *__restrict__ tab, uint32_t m,
-                               uint32_t *__restrict__ len) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < m) len[j] = format_piece<false>(j, slot_u[j], slot_w[j], tab, nullptr);
-}
-__global__ void k_ut_line_off(const uint64_t *__restrict__ off, const uint64_t *__restrict__ poff, uint32_t n_u, uint64_t *__restrict__ line_off) {
-  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (u <= n_u) line_off[u] = poff[off[u]];
-}
-// A workgroup per tile of UT_TILE output bytes: text[t * UT_TILE ..) holds the characters base + t * UT_TILE .. of the whole file.  The
-// pieces that cover the tile are found by binary search of the pieces' offsets (as k_stitch finds its segments); each is formatted whole
-// into LDS, which has PIECE_MAX bytes of margin on either side for the pieces that straddle the tile's ends, and the tile streams out
-// (tile_out from its byte 0: text is 16-byte aligned, UT_TILE and PIECE_MAX are multiples of 16).
-constexpr uint32_t UT_TILE = 8192, UT_THREADS = 256;
-__global__ __launch_bounds__(UT_THREADS) void k_ut_format(const uint64_t *__restrict__ poff, const uint32_t *__restrict__ slot_u, const uint64_t *__restrict__ slot_w,
-                                                          const pgx_unitig *__restrict__ tab, uint32_t m, uint64_t base, uint64_t total, char *__restrict__ text) {
-  __shared__ __attribute__((aligned(16))) char tile[PIECE_MAX + UT_TILE + PIECE_MAX];
-  const uint64_t t0 = (uint64_t)blockIdx.x * UT_TILE, lo = base + t0, hi = base + min(total, t0 + UT_TILE);
-  // the last piece that starts at or before lo (poff[0 .. m] ascending, poff[m] > lo)
-  uint32_t a = 0, b = m;
-  while (a < b) {
-    const uint32_t mid = a + ((b - a) >> 1);
-    if (poff[mid + 1] <= lo) a = mid + 1;
-    else b = mid;
-  }
-  for (uint32_t j = a + threadIdx.x; j < m; j += UT_THREADS) {
-    const uint64_t at = poff[j];
-    if (at >= hi) break;
-    format_piece<true>(j, slot_u[j], slot_w[j], tab, tile + PIECE_MAX + (int64_t)(at - lo));   // (at - lo > -PIECE_MAX: the piece reaches past lo)
-  }
-  __syncthreads();
-  tile_out<UT_THREADS>(tile + PIECE_MAX, text + t0, 0, (uint32_t)(hi - lo));
-}
+};
 }  // namespace
 }  // namespace pgx
 
@@ -260,15 +234,13 @@ struct pgx_unitigs {
   DevBuf<uint32_t> paths;        // creation indices, unitig after unitig
   DevBuf<uint32_t> slot_u;       // per path slot: its unitig
   DevBuf<uint64_t> slot_w;       // ... and the key of the node its edge enters
-  DevBuf<uint64_t> poff;         // g_edges + 1: where each slot's piece of text starts in the whole file
-  DevBuf<uint64_t> line_off;     // unitigs + 1: where each line starts
+  TextPlan text;                 // a piece per path slot, a line per unitig
   pgx_unitigs_stats_t st = {};
-  uint64_t cursor = 0;           // lines handed out as text
   uint64_t serial = 0;           // of this object among all unitigs ever built (> 0): an address may come again, a serial does not
   TextStage stage;
   bool shut = false;
   void drop_device_state() {
-    tab.release(), paths.release(), slot_u.release(), slot_w.release(), poff.release(), line_off.release();
+    tab.release(), paths.release(), slot_u.release(), slot_w.release(), text.release();
     stage.drop();
   }
 };
@@ -277,6 +249,8 @@ namespace pgx {
 namespace {
 LiveSet<pgx_unitigs> g_ut;
 ShutdownHook g_ut_hook([] { g_ut.shutdown(); });
+std::atomic<uint64_t> g_ut_serials{0};
+SlotPieces slot_pieces(const pgx_unitigs *u) { return SlotPieces{u->slot_u.p, u->slot_w.p, u->tab.p, (uint32_t)u->st.g_edges}; }
 
 // pointer doubling over pred until every edge has reached the start of its path, max_rounds at the most; returns the edges that still
 // have a pointer.  The answer is in *cur.
@@ -361,7 +335,7 @@ void build_unitigs(const Edge *d_edges, uint64_t n64, pgx_unitigs *u) {
     LAUNCH(k_ut_first_flags, m, pred.p, m, flag.p);
     n_u = select_indices(flag.p, m, firsts.p, &tmp);
   }
-  u->tab.alloc(n_u), u->paths.alloc(m), u->slot_u.alloc(m), u->slot_w.alloc(m), u->poff.alloc((size_t)m + 1), u->line_off.alloc((size_t)n_u + 1);
+  u->tab.alloc(n_u), u->paths.alloc(m), u->slot_u.alloc(m), u->slot_w.alloc(m);
   DevBuf<uint32_t> n_edges(n_u);
   PGX_HIP(hipMemsetAsync(uid_of.p, 0xFF, (size_t)m * sizeof(uint32_t), st));
   PGX_HIP(hipMemsetAsync(n_edges.p, 0, (size_t)n_u * sizeof(uint32_t), st));
@@ -376,13 +350,7 @@ void build_unitigs(const Edge *d_edges, uint64_t n64, pgx_unitigs *u) {
   LAUNCH(k_ut_scatter, m, cur, uid_of.p, off.p, gsel.p, wk.p, m, n_u, u->paths.p, u->slot_u.p, u->slot_w.p, cnt.p + 7);
   // ---- where the text of every piece and line starts
   part.reset(), part.reset(new KernelTimer("unitigs_text", m));
-  {
-    DevBuf<uint32_t> plen(m);
-    LAUNCH(k_ut_piece_len, m, u->slot_u.p, u->slot_w.p, u->tab.p, m, plen.p);
-    (void)scan_to_total(plen.p, u->poff.p, m, &tmp);
-  }
-  LAUNCH(k_ut_line_off, (size_t)n_u + 1, off.p, u->poff.p, n_u, u->line_off.p);
-  PGX_HIP(hipGetLastError());
+  plan_text(slot_pieces(u), off.p, n_u, &u->text, &tmp);
   uint32_t h[3];
   PGX_HIP(hipMemcpyAsync(h, cnt.p + 5, sizeof(h), hipMemcpyDeviceToHost, st));
   pgx::sync();
@@ -407,33 +375,14 @@ namespace {
 // the common part of the two builders: edges() answers the device edge records once the context is known to be up
 template <class EdgesFn>
 int build_entry(const char *who, pgx_unitigs **out, EdgesFn &&edges) {
-  pgx_unitigs *u = nullptr;
-  const int rc = guarded([&] {
-    PGX_REQUIRE(out, PGX_EARG, "%s: null argument", who);
-    *out = nullptr;
-    PGX_REQUIRE(ctx().ready, PGX_ESTATE, "%s: no device context (pgx_init has not been called, or found no HIP device)", who);
-    int code = PGX_OK;
-    uint64_t n = 0;
-    try {
-      MemTag tag("unitigs");
-      DevBuf<Edge> own;
-      const Edge *d_edges = edges(own, &n);
-      KernelTimer tm("unitigs", n);
-      u = new pgx_unitigs;
-      static std::atomic<uint64_t> serials{0};
-      u->serial = ++serials;
-      build_unitigs(d_edges, n, u);
-    } catch (const Fail &f) {
-      code = build_fail_code(f, who, "unitigs", n, "edges");
-    }
-    timing_flush();
-    if (code != PGX_OK) return code;
-    g_ut.add(u);
-    *out = u;
-    return (int)PGX_OK;
-  });
-  if (rc != PGX_OK) delete u;
-  return rc;
+  return live_build(who, g_ut, out, [] {}, [&](pgx_unitigs *u, uint64_t *n) {
+    MemTag tag("unitigs");
+    DevBuf<Edge> own;
+    const Edge *d_edges = edges(own, n);
+    KernelTimer tm("unitigs", *n);
+    u->serial = ++g_ut_serials;
+    build_unitigs(d_edges, *n, u);
+  }, "unitigs", "edges");
 }
 }  // namespace
 }  // namespace pgx
@@ -487,28 +436,7 @@ extern "C" int pgx_unitigs_paths(const pgx_unitigs *u, uint64_t first, uint64_t 
 extern "C" int pgx_unitigs_text(pgx_unitigs *u, uint64_t max_lines, char **text, size_t *text_len, int *done) {
   return text_call(text, text_len, done, [&] {
     require_unitigs(u, "pgx_unitigs_text");
-    PGX_REQUIRE(text && text_len && done && max_lines, PGX_EARG, "pgx_unitigs_text: null argument or max_lines == 0");
-    hipStream_t st = ctx().stream;
-    const uint64_t nl = text_lines(max_lines, u->st.unitigs - u->cursor);
-    if (nl == 0) {
-      text_hand_out(u->stage, nullptr, 0, text, text_len);
-    } else {
-      KernelTimer tm("unitigs", nl), tm_text("unitigs_text", nl);
-      MemTag tag("unitigs");
-      uint64_t range[2];
-      PGX_HIP(hipMemcpyAsync(&range[0], u->line_off.p + u->cursor, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      PGX_HIP(hipMemcpyAsync(&range[1], u->line_off.p + u->cursor + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      pgx::sync();
-      const uint64_t total = range[1] - range[0];
-      char *d_text = ws<char>("ut.text", total + 16);
-      hipLaunchKernelGGL(k_ut_format, dim3(cdiv(total, UT_TILE)), dim3(UT_THREADS), 0, st, u->poff.p, u->slot_u.p, u->slot_w.p, u->tab.p, (uint32_t)u->st.g_edges,
-                         range[0], total, d_text);
-      PGX_HIP(hipGetLastError());
-      text_hand_out(u->stage, d_text, total, text, text_len);
-    }
-    u->cursor += nl;
-    if (u->cursor == u->st.unitigs) *done = 1;
-    timing_flush();
+    text_next("pgx_unitigs_text", u->text, slot_pieces(u), u->stage, TextNames{"unitigs", "unitigs_text", "unitigs", "ut.text"}, max_lines, text, text_len, done);
   });
 }
 

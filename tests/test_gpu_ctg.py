@@ -96,6 +96,56 @@ def test_sizes_at_which_the_kernels_can_go_wrong(name):
     assert texts[0] == texts[1] == texts[2]                      # ... and across runs
 
 
+# ctg_paths is written in tiles of 8,192 bytes, 16 bytes a store and the bytes behind the last whole 16 one by one (the piece scheme that
+# utg_data of the unitigs has its tail cases for in test_gpu_utg.py).  The whole text's last tile as the cases above do not show it: one of
+# 1 .. 15 bytes (no 16-byte store at all), and one that ends exactly on a 16-byte store (no byte-wise tail).
+TAIL_CASES = {"tail_1_15": lambda length: 1 <= length % 8192 <= 15,
+              "tail_16s": lambda length: length > 8192 and length % 8192 != 0 and length % 16 == 0}
+
+
+def contigs_for_tail(n_unitigs: int, n_short: int) -> np.ndarray:
+    """chain_with_tips(n_unitigs) and n_short further chains of one unitig, each a contig of its own: ctg_paths grows by a triple on both
+    of the long contig's lines with every unitig, and by two short lines with every further chain"""
+    parts = [CU.chain_with_tips(n_unitigs)]
+    for k in range(n_short):
+        g = CU.Graph(base=300000 + 10 * k)
+        g.chain([1, 2, 3, 4])
+        parts.append(CU.edges_of_g_lines(g.lines))
+    return np.concatenate(parts)
+
+
+def shape_for_tail(accept):
+    """(edges, the restatement's result) of the first contigs_for_tail(n, k), 100 <= n < 260 and k < 8, whose ctg_paths has a length that
+    accept() takes (None: there is none).  The restatement is run where a straight line through its lengths at n = 100 and 101 comes
+    within 4 bytes of such a length (the digits of the summed lengths and scores move the real one by a few bytes); the caller holds the
+    chosen text against accept() again."""
+    base = [len(CU.contig_paths(contigs_for_tail(100, k)).ctg_text) for k in range(8)]
+    step = len(CU.contig_paths(contigs_for_tail(101, 0)).ctg_text) - base[0]
+    for n in range(100, 260):
+        for k in range(8):
+            if any(accept(base[k] + (n - 100) * step + d) for d in range(-4, 5)):
+                edges = contigs_for_tail(n, k)
+                want = CU.contig_paths(edges)
+                if accept(len(want.ctg_text)):
+                    return edges, want
+    return None
+
+
+@pytest.mark.parametrize("name", sorted(TAIL_CASES))
+def test_ctg_paths_whose_last_tile_is_a_tail_case(name):
+    found = shape_for_tail(TAIL_CASES[name])
+    assert found is not None
+    edges, want = found
+    assert TAIL_CASES[name](len(want.ctg_text))                  # before anything runs on the GPU: the case is a tail case
+    lines = want.ctg_text.count(b"\n")
+    for max_lines in (1, 7, 1 << 20):
+        with shimmer.contig_paths(edges) as c:
+            parts = list(c.ctg_pieces(max_lines))
+            assert all(0 < p.count(b"\n") <= max_lines and p.endswith(b"\n") for p in parts) and len(parts) == -(-lines // max_lines)
+            assert b"".join(parts) == want.ctg_text              # byte for byte the restatement's
+            assert c.utg_text(max_lines) == want.utg_text
+
+
 def test_the_empty_graph_and_a_graph_without_g_edges():
     none = CU.fixture_edges(Z, "spur")
     none["type"] = SG.TR

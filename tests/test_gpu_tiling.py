@@ -245,6 +245,51 @@ def test_a_long_line_in_a_later_piece_is_named_after_what_comes_before_it(tmp_pa
     assert not (tmp_path / "p").exists()
 
 
+# The primary file is written in tiles of 8,192 bytes, 16 bytes a store and the bytes behind the last whole 16 one by one (the piece scheme
+# that utg_data of the unitigs has its tail cases for in test_gpu_utg.py).  The whole text's last tile as the cases above do not show it: one
+# of 1 .. 15 bytes (no 16-byte store at all), and one that ends exactly on a 16-byte store (no byte-wise tail).
+TAIL_CASES = {"tail_1_15": lambda length: 1 <= length % 8192 <= 15,
+              "tail_16s": lambda length: length > 8192 and length % 8192 != 0 and length % 16 == 0}
+
+
+def chain_files(n_rows, score):
+    """one contig of one simple unitig of n_rows edges, all of one length, score and identity: a primary file of n_rows lines, in which only
+    the running length's digits -- and with `score` the score's -- change the length of a line"""
+    b = TU.Builder(96)
+    nodes = [TU.key(r, TU.E) for r in range(1, n_rows + 2)]
+    b.contig("000000F", [b.simple(nodes, length=1000, score=score, s=100, idt="99.50")], nodes[-1])
+    return b.files()
+
+
+def chain_for_tail(accept):
+    """(n_rows, score) of the first chain_files, score a power of ten times 7 and n_rows <= 400, whose primary file has a length that accept()
+    takes (None: there is none).  The first n lines of a longer chain's file are the file of the chain of n rows, so one run of the rule per
+    score gives every length; the caller holds the chosen chain's own file against accept() again."""
+    for score in (7, 70, 700, 7000, 70000):
+        total = 0
+        for n, line in enumerate(TU.tiling_rule(*chain_files(400, score))[0].split(b"\n")[:-1], 1):
+            total += len(line) + 1
+            if accept(total):
+                return n, score
+    return None
+
+
+@pytest.mark.parametrize("name", sorted(TAIL_CASES))
+def test_a_primary_file_whose_last_tile_is_a_tail_case(name, tmp_path):
+    found = chain_for_tail(TAIL_CASES[name])
+    assert found is not None
+    n_rows, score = found
+    want = TU.tiling_rule(*chain_files(n_rows, score))[0]
+    assert TAIL_CASES[name](len(want)) and want.count(b"\n") == n_rows   # before anything runs on the GPU: the case is a tail case
+    inputs = put(str(tmp_path), *chain_files(n_rows, score))
+    for max_lines in (1, 7, 1 << 20):
+        with shimmer.graph_to_path(*inputs) as t:
+            parts = list(t.text("p", max_lines))
+            assert all(0 < x.count(b"\n") <= max_lines and x.endswith(b"\n") for x in parts) and len(parts) == -(-n_rows // max_lines)
+            assert b"".join(parts) == want                      # byte for byte the rule's
+            assert list(t.text("a")) == []
+
+
 def test_a_pipe_is_refused(tmp_path):
     inputs = put(str(tmp_path), *_base().files())
     fifo = str(tmp_path / "fifo")
