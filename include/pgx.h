@@ -560,7 +560,7 @@ int pgx_cns_tags(const pgx_cns_aln *alns, size_t n_aln, const char *q_str, const
  * requests over one pool of bytes.  Bytes are compared as bytes ('a' != 'A', 'N' == 'N').  A request that does not align -- the band grew
  * wider than 2 * band, or 0.3 * (q_len + t_len) steps did not reach an end of either sequence -- answers all zero, as the reference does.
  * band <= 4096 (the front keeps 2 * band + 4 diagonals, rounded up to a power of two, in LDS: at most 16,384 slots, 64 KiB).
- * What is NOT here is the script itself, pg_asm_cns.py as a drop-in: contig chunking, read grouping and the stitching of the pieces. ---- */
+ * The script itself -- contig chunking, read grouping, the stitching of the pieces -- is pgx_cns_job, further down. ---- */
 typedef struct { uint64_t q_off, t_off; uint32_t q_len, t_len, band, want_str; } pgx_faln_req;                       /* 32 bytes */
 typedef struct { int32_t aln_str_size, dist, aln_q_s, aln_q_e, aln_t_s, aln_t_e; uint64_t str_off; } pgx_faln_res;  /* 32 bytes */
 typedef struct {
@@ -588,6 +588,47 @@ typedef struct {
  * refusals pass through (PGX_EINVAL, the piece named).  A read clipped to nothing is skipped.  PGX_EINVAL also for t_len == 0. */
 int pgx_cns_pieces(const pgx_cns_piece *pieces, size_t n_piece, const pgx_cns_read *reads, size_t n_read, const char *seq, size_t seq_bytes,
                    uint32_t min_cov, char **text, uint64_t *piece_off, uint8_t *read_used, pgx_cns_pieces_stats *stats);
+
+/* ---- pg_asm_cns.py as a whole (py/scripts/pg_asm_cns.py; the rule: DESIGN.md section 4.7b).  A map row is nine integers
+ * `ctg p1 p2 read rb re strand mc0 mc1` (int64 each).  The layout: a contig's rows, sorted stably by p1, are cut into groups -- a row
+ * 50,000 and more beyond the group's left anchor closes it and is the next anchor; a group that grew to 100,000 and more is emptied; a
+ * tail of at most 1,000 goes to the group before -- and every group is a piece whose template is the contig's bases
+ * [left, left + t_len) = [left_anchor - 1000, right).  Its read entries: per (read, strand) an entry at the smallest offset p1 - rb and at
+ * every offset more than 50 above the last entry's, read_shift = offset - left, in the order the script aligns them.  Pieces come contig by
+ * contig in the order of first appearance among the rows, a contig's segments in order; piece p owns reads [read_first, read_first + n_read).
+ * Refused with PGX_EINVAL, the row or the contig and segment named: a contig the lengths lack (ctg_len[ctg] < 0 or ctg >= n_ctg) or of
+ * length 0, a template that is empty or leaves its contig, and what the tables cannot hold (|p1| or |rb| or a length of 2^29 and more, a
+ * read id beyond 32 bits, a strand other than 0 and 1). ---- */
+typedef struct { uint32_t ctg, seg; int32_t left; uint32_t t_len, n_mapped, read_first, n_read, pad; } pgx_cns_job_piece;   /* 32 bytes */
+typedef struct { uint32_t piece, read; int32_t read_shift; uint32_t strand; } pgx_cns_job_read;                             /* 16 bytes */
+/* the layout alone: rows (n_rows x 9, the chunk's) and the contig lengths by contig id in, *pieces and *reads (pgx_free) out */
+int pgx_cns_layout(const int64_t *rows, size_t n_rows, const int64_t *ctg_len, size_t n_ctg, pgx_cns_job_piece **pieces, uint64_t *n_piece,
+                   pgx_cns_job_read **reads, uint64_t *n_read);
+typedef struct {
+  uint64_t n_rows, n_contigs, n_pieces, n_reads;     /* rows kept by the chunk filter, contigs answered, pieces, read entries */
+  uint64_t n_accepted, n_by_rule, n_called;          /* entries the acceptance rule kept; pieces by the low-coverage rule / the call */
+  uint64_t n_batches, pool_bytes, text_bytes;        /* batches of pieces, ASCII pool bytes decoded over all of them, FASTA bytes */
+  double total_ms, layout_ms, decode_ms, pieces_ms, stitch_ms;   /* host clock around the parts: layout, decode, inner loop, stitch + FASTA */
+  pgx_faln_stats align;                              /* the aligner's, summed over the batches and the stitch */
+  pgx_cns_stats call;                                /* the call's, summed over the batches */
+} pgx_cns_job_stats;
+/* The script on two resident databases (their bytes in place: not released, not compacted) and ALL rows of a map: the chunk filter
+ * `my_chunk % total_chunks == ctg % total_chunks`, the layout, per batch of pieces the decode of templates and reads into an ASCII pool and
+ * pgx_cns_pieces' loop at min_cov 1, the stitch (the last 1,000 bytes of a segment against the first 1,050 of the next at band 400, no
+ * strings) and the FASTA, all on the device between the upload of the rows and the download of the text.  ctg_names / ctg_name_off: the
+ * contigs' names by contig id, name c at [ctg_name_off[c], ctg_name_off[c + 1]), n_names + 1 offsets, n_names beyond the largest contig id.
+ * *text (pgx_free): `>name\n bytes \n` per contig in the order of first appearance; *ctg_off (pgx_free): *n_ctg + 1 offsets of the
+ * contigs' records in it.  PGX_EINVAL, beyond the layout's refusals: total_chunks == 0, a read the idx lacks, a stitch whose first
+ * segment is shorter than 1,000 bytes or whose second is shorter than 1,050, and the refusals of pgx_cns_pieces and of the call, with the
+ * contig and the segment named.  PGX_CNS_JOB_BATCH=<pieces per batch>: a test hook. */
+int pgx_cns_job_resident(pgx_seqdb *reads, pgx_seqdb *ref, const int64_t *rows, size_t n_rows, uint32_t total_chunks, uint32_t my_chunk,
+                         const char *ctg_names, const uint64_t *ctg_name_off, size_t n_names, char **text, uint64_t **ctg_off, uint64_t *n_ctg,
+                         uint64_t *text_len, pgx_cns_job_stats *stats);
+/* the file level, `pg_asm_cns.py read_db_prefix ref_db_prefix read_to_contig_map total_chunks my_chunk`: <prefix>.idx / .seqdb of both
+ * databases and the map file in (parsed on the device in bounded pieces of the file; blanks are what Python's split() takes for one), the
+ * script's stdout to out_path (NULL: stdout).  PGX_EINVAL also for the first line that does not hold nine decimal integers that fit. */
+int pgx_cns_job(const char *read_db_prefix, const char *ref_db_prefix, const char *map_path, uint32_t total_chunks, uint32_t my_chunk,
+                const char *out_path, pgx_cns_job_stats *stats);
 
 /* host utility: the order in which klib khash (src/khash.h:232-336, integer hash :373) iterates n DISTINCT 64-bit keys
  * inserted in the given order -- the order shmr_overlap visits its tables in (src/shmr_overlap.c:206-215).  out receives

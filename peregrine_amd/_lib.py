@@ -24,6 +24,10 @@ FALN_RES_DTYPE = np.dtype([("aln_str_size", "<i4"), ("dist", "<i4"), ("aln_q_s",
                            ("str_off", "<u8")])
 CNS_PIECE_DTYPE = np.dtype([("seq_off", "<u8"), ("t_len", "<u4"), ("pad", "<u4")])
 CNS_READ_DTYPE = np.dtype([("seq_off", "<u8"), ("seq_len", "<u4"), ("piece", "<u4"), ("read_shift", "<i4"), ("pad", "<u4")])
+CNS_JOB_PIECE_DTYPE = np.dtype([("ctg", "<u4"), ("seg", "<u4"), ("left", "<i4"), ("t_len", "<u4"), ("n_mapped", "<u4"), ("read_first", "<u4"), ("n_read", "<u4"),
+                                ("pad", "<u4")])
+CNS_JOB_READ_DTYPE = np.dtype([("piece", "<u4"), ("read", "<u4"), ("read_shift", "<i4"), ("strand", "<u4")])
+assert CNS_JOB_PIECE_DTYPE.itemsize == 32 and CNS_JOB_READ_DTYPE.itemsize == 16
 assert CNS_ALN_DTYPE.itemsize == 32 and CNS_TAG_DTYPE.itemsize == 12
 assert FALN_REQ_DTYPE.itemsize == 32 and FALN_RES_DTYPE.itemsize == 32 and CNS_PIECE_DTYPE.itemsize == 16 and CNS_READ_DTYPE.itemsize == 24
 assert MATCH_DTYPE.itemsize == 32 and ALIGN_KEY_DTYPE.itemsize == 16 and ALIGN_KEY2_DTYPE.itemsize == 20 and TILE_ROW_DTYPE.itemsize == 24
@@ -100,6 +104,17 @@ class CnsPiecesStats(C.Structure):
         return out
 
 
+class CnsJobStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_contigs", "n_pieces", "n_reads", "n_accepted", "n_by_rule", "n_called", "n_batches", "pool_bytes",
+                                          "text_bytes")] + \
+               [(n, C.c_double) for n in ("total_ms", "layout_ms", "decode_ms", "pieces_ms", "stitch_ms")] + [("align", FalnStats), ("call", CnsStats)]
+
+    def asdict(self):
+        out = {n: getattr(self, n) for n, t in self._fields_ if t in (C.c_uint64, C.c_double)}
+        out["align"], out["call"] = self.align.asdict(), self.call.asdict()
+        return out
+
+
 # every symbol include/pgx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "pgx_init", "pgx_shutdown", "pgx_last_error", "pgx_device_count", "pgx_version", "pgx_free",
@@ -121,6 +136,7 @@ EXPORTS = [
     "pgx_overlap_resident_dev", "pgx_copy_dev", "pgx_seqdb_adopt_dev", "pgx_stream_wait", "pgx_stream_signal",
     "pgx_align_batch2", "pgx_contigs_resident", "pgx_contigs_chunk",
     "pgx_cns_call", "pgx_cns_call_dev", "pgx_cns_tags", "pgx_falcon_align", "pgx_cns_pieces",
+    "pgx_cns_layout", "pgx_cns_job_resident", "pgx_cns_job",
     "build_shimmer_map4py", "get_shimmers_for_read", "get_mmer_count", "get_shimmer_hits", "pgx_shimmer_map_free",
 ]
 
@@ -231,6 +247,10 @@ def load():
         lib.pgx_falcon_align.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_cns_pieces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
+        lib.pgx_cns_layout.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_cns_job_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_cns_job.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
         lib.pgx_timing_get.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_khash_slot_order.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         lib.pgx_khash_slot_order_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]

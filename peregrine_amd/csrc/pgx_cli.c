@@ -1,6 +1,6 @@
 /*
  * pgx_cli.c -- native drop-ins for the reference's stage executables, one multi-call binary (the tool is chosen by the
- * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map, path_to_contig.py, graph_to_path.py.  Same getopt strings, defaults
+ * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map, path_to_contig.py, graph_to_path.py, pg_asm_cns.py.  Same getopt strings, defaults
  * and output files / streams as /root/reference/src/shmr_mkseqdb.c:14-128, shmr_index.c:37-245, shmr_overlap.c:233-419,
  * shmr_dedup.c:19-104, shmr_map.c:163-373; everything else happens behind the C-ABI of include/pgx.h on the GPU.
  * Plain C against libpgx.so: this is the cgo / FFI-free form of the boundary (the Python shims in bin/ do the same).
@@ -594,6 +594,27 @@ static int main_path_to_contig(int argc, char **argv) {
   return 0;
 }
 
+/* pg_asm_cns.py <read_db_prefix> <ref_db_prefix> <read_to_contig_map> <total_chunks> <my_chunk> > cns.fa (py/scripts/pg_asm_cns.py, the
+ * last stage of pg_run.py).  Always stand-alone: both databases are loaded by this process. */
+static int parse_chunk(const char *s, uint32_t *out) {
+  char *end = NULL;
+  errno = 0;
+  const long long v = strtoll(s, &end, 10);
+  if (errno || end == s || *end || v < 0 || v > 0xFFFFFFFFll) return 0;
+  *out = (uint32_t)v;
+  return 1;
+}
+static int main_pg_asm_cns(int argc, char **argv) {
+  uint32_t total = 0, my = 0;
+  if (argc != 6 || !parse_chunk(argv[4], &total) || !parse_chunk(argv[5], &my)) {
+    fprintf(stderr, "Usage: pg_asm_cns.py read_db_prefix ref_db_prefix read_to_contig_map total_chunks my_chunk > cns.fa\n");
+    return 1;
+  }
+  if (pgx_init(device_of_env())) return fail("pg_asm_cns.py", "pgx_init");
+  if (pgx_cns_job(argv[1], argv[2], argv[3], total, my, NULL, NULL)) return fail("pg_asm_cns.py", "pgx_cns_job");
+  return 0;
+}
+
 /* graph_to_path.py [--improper-p-ctg] [--proper-a-ctg] [--seqdb-prefix P] [--sg-edges-list-fn F] [--utg-data-fn F] [--ctg-paths-fn F]
  * (py/scripts/graph_to_path.py): p_ctg_tiling_path and a_ctg_tiling_path into the working directory, nothing on stdout.  The first three
  * options change nothing in the script's tiling paths either. */
@@ -680,9 +701,10 @@ int main(int argc, char **argv) {
   else if (strcmp(tool, "shmr_map") == 0) rc = main_map(argc, argv);
   else if (strcmp(tool, "path_to_contig.py") == 0) rc = main_path_to_contig(argc, argv);
   else if (strcmp(tool, "graph_to_path.py") == 0) rc = main_graph_to_path(argc, argv);
+  else if (strcmp(tool, "pg_asm_cns.py") == 0) rc = main_pg_asm_cns(argc, argv);
   else if (strcmp(tool, "serve") == 0) rc = main_serve(argc, argv);
   else {
-    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_sgraph|shmr_map|path_to_contig.py|graph_to_path.py} [flags]   (or invoke through a link of that name)\n"
+    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_sgraph|shmr_map|path_to_contig.py|graph_to_path.py|pg_asm_cns.py} [flags]   (or invoke through a link of that name)\n"
                     "       pgx_cli serve -p seqdb_prefix [-i idle_seconds]   (keeps the read database in HBM; the drop-ins attach to it)\n");
     rc = 2;
   }

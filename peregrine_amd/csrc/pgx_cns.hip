@@ -327,10 +327,10 @@ void scan_and_check(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, co
     if (names && h[e] != UINT32_MAX) h[e] = names[h[e]];
   PGX_REQUIRE(h[E_PIECE] == UINT32_MAX, PGX_EARG, "%s: alignment %u names a piece beyond the %u given", who, h[E_PIECE], n_piece);
   PGX_REQUIRE(h[E_RANGE] == UINT32_MAX, PGX_EARG, "%s: the strings of alignment %u lie outside the %zu bytes given", who, h[E_RANGE], str_bytes);
-  PGX_REQUIRE(h[E_OFFSET] == UINT32_MAX, PGX_EINVAL, "%s: piece %u: an alignment with a negative t_offset", who, h[E_OFFSET]);
-  PGX_REQUIRE(h[E_MANY] == UINT32_MAX, PGX_EINVAL, "%s: piece %u: more than %u alignments (the reference counts them in 16 bits)", who, h[E_MANY], MAX_ALNS_PER_PIECE);
-  PGX_REQUIRE(h[E_BYTE] == UINT32_MAX, PGX_EINVAL, "%s: piece %u: an alignment string holds a byte outside ACGTNacgtn-", who, h[E_BYTE]);
-  PGX_REQUIRE(h[E_TPOS] == UINT32_MAX, PGX_EINVAL, "%s: piece %u: an alignment runs past the end of the template", who, h[E_TPOS]);
+  PGX_REQUIRE_PIECE(h[E_OFFSET] == UINT32_MAX, PGX_EINVAL, h[E_OFFSET], "%s: piece %u: an alignment with a negative t_offset", who, h[E_OFFSET]);
+  PGX_REQUIRE_PIECE(h[E_MANY] == UINT32_MAX, PGX_EINVAL, h[E_MANY], "%s: piece %u: more than %u alignments (the reference counts them in 16 bits)", who, h[E_MANY], MAX_ALNS_PER_PIECE);
+  PGX_REQUIRE_PIECE(h[E_BYTE] == UINT32_MAX, PGX_EINVAL, h[E_BYTE], "%s: piece %u: an alignment string holds a byte outside ACGTNacgtn-", who, h[E_BYTE]);
+  PGX_REQUIRE_PIECE(h[E_TPOS] == UINT32_MAX, PGX_EINVAL, h[E_TPOS], "%s: piece %u: an alignment runs past the end of the template", who, h[E_TPOS]);
 }
 
 void check_args(const char *who, const void *alns, size_t n_aln, const void *q, const void *t, size_t str_bytes) {
@@ -342,19 +342,26 @@ void check_args(const char *who, const void *alns, size_t n_aln, const void *q, 
 }  // namespace
 
 void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, const uint8_t *d_q, const uint8_t *d_t, size_t str_bytes, const uint32_t *piece_tlen,
-                  size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats, const uint32_t *names) {
-  PGX_REQUIRE(text && piece_off && (n_piece == 0 || piece_tlen), PGX_EARG, "%s: null argument", who);
+                  size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats, const uint32_t *names, DevBuf<char> *d_text_out,
+                  DevBuf<uint64_t> *d_off_out) {
+  const bool stay = d_text_out && d_off_out;   // the text and its offsets stay on the device
+  PGX_REQUIRE((stay || (text && piece_off)) && (n_piece == 0 || piece_tlen), PGX_EARG, "%s: null argument", who);
   check_args(who, d_alns, n_aln, d_q, d_t, str_bytes);
   PGX_REQUIRE(n_piece <= MAX_PIECES, PGX_EARG, "%s: more than %u pieces in one call", who, MAX_PIECES);
   std::vector<uint64_t> cov_off(n_piece + 1, 0);
   for (size_t p = 0; p < n_piece; ++p) {
-    PGX_REQUIRE(piece_tlen[p] <= (uint32_t)INT32_MAX, PGX_EARG, "%s: piece %zu: a template of %u bases", who, names ? (size_t)names[p] : p, piece_tlen[p]);
+    PGX_REQUIRE_PIECE(piece_tlen[p] <= (uint32_t)INT32_MAX, PGX_EARG, names ? (size_t)names[p] : p, "%s: piece %zu: a template of %u bases", who, names ? (size_t)names[p] : p, piece_tlen[p]);
     cov_off[p + 1] = cov_off[p] + piece_tlen[p];
   }
-  *text = nullptr;
+  if (text) *text = nullptr;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n_piece == 0) {
     PGX_REQUIRE(n_aln == 0, PGX_EARG, "%s: alignments without pieces", who);
+    if (stay) {
+      d_text_out->alloc(1), d_off_out->alloc(1);
+      PGX_HIP(hipMemsetAsync(d_off_out->p, 0, sizeof(uint64_t), ctx().stream));
+      return;
+    }
     *text = caller_text(nullptr, 0);
     piece_off[0] = 0;
     return;
@@ -423,21 +430,26 @@ void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, cons
   PGX_HIP(hipMemcpyAsync(&no_end, err.p + E_NOEND, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   DevBuf<uint64_t> d_off(np + 1);
   const uint64_t total = scan_to_total(len.p, d_off.p, np, &ws);   // (synchronises)
-  PGX_REQUIRE(no_end == UINT32_MAX, PGX_EINVAL, "%s: piece %u: no alignment path scores above zero, the reference has no consensus for it", who,
+  PGX_REQUIRE_PIECE(no_end == UINT32_MAX, PGX_EINVAL, names ? names[no_end] : no_end, "%s: piece %u: no alignment path scores above zero, the reference has no consensus for it", who,
               names ? names[no_end] : no_end);
   DevBuf<char> d_text(total ? total : 1);
   hipLaunchKernelGGL(k_cns_text, dim3(np), dim3(256), 0, st, rev.p, pnode.p, len.p, d_off.p, d_text.p);
   ev.mark(5);
-  char *out = caller_text(nullptr, total);
-  try {
-    if (total) PGX_HIP(hipMemcpyAsync(out, d_text.p, total, hipMemcpyDeviceToHost, st));
-    d_off.download(piece_off, np + 1);
+  if (stay) {
     sync();
-  } catch (...) {
-    free(out);
-    throw;
+    *d_text_out = std::move(d_text), *d_off_out = std::move(d_off);
+  } else {
+    char *out = caller_text(nullptr, total);
+    try {
+      if (total) PGX_HIP(hipMemcpyAsync(out, d_text.p, total, hipMemcpyDeviceToHost, st));
+      d_off.download(piece_off, np + 1);
+      sync();
+    } catch (...) {
+      free(out);
+      throw;
+    }
+    *text = out;
   }
-  *text = out;
   if (stats) {
     stats->n_aln = n_aln, stats->n_tags = n_tag, stats->n_edges = n_edge, stats->n_nodes = n_node, stats->text_bytes = total;
     stats->tags_ms = ev.ms(0, 1), stats->sort_ms = ev.ms(1, 2), stats->score_ms = ev.ms(2, 3), stats->back_ms = ev.ms(3, 4), stats->gpu_ms = ev.ms(0, 5);

@@ -291,12 +291,6 @@ struct Events {
   }
 };
 
-struct FalnOut {
-  DevBuf<pgx_faln_res> res;
-  DevBuf<uint8_t> q_str, t_str;
-  uint64_t str_bytes = 0;
-};
-
 // falcon.align for n > 0 requests in device memory over the device's copy of the pool (which has 16 bytes of padding behind it: a probe
 // reads 8 bytes at a time).  max_band: the widest band among them.  err: F_SLOTS slots, set to 0xFF..; ctr: C_SLOTS counters, [C_ALIGNED] 0.
 void faln_run(const char *who, const pgx_faln_req *d_reqs, size_t n, const uint8_t *d_seq, uint32_t max_band, uint32_t *d_err, uint32_t *d_ctr, FalnOut &out,
@@ -433,7 +427,136 @@ __global__ void k_cp_gather(const pgx_cns_aln *in, const uint32_t *list, uint32_
   if (i < n) out[i] = in[list[i]];
 }
 
+// which pieces enter the consensus call: those whose accepted reads cover 3 * t_len template bases and more (pg_asm_cns.py:235)
+__global__ void k_cp_called(const pgx_cns_piece *pieces, const unsigned long long *aln_base, uint32_t np, uint8_t *called) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < np) called[p] = aln_base[p] >= 3ull * pieces[p].t_len;
+}
+__global__ void k_cp_call_tables(const uint32_t *call_piece, uint32_t n_call, const pgx_cns_piece *pieces, uint32_t name_base, uint32_t *call_no, uint32_t *call_tlen,
+                                 uint32_t *call_name) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_call) return;
+  const uint32_t p = call_piece[i];
+  call_no[p] = i, call_tlen[i] = pieces[p].t_len, call_name[i] = name_base + p;
+}
+// the text: a piece of the call as the call answered it, the others their template through ASCII lower-casing
+__global__ void k_cp_out_len(const pgx_cns_piece *pieces, const uint32_t *call_no, const uint64_t *c_off, uint32_t np, uint32_t *len) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= np) return;
+  const uint32_t c = call_no[p];
+  len[p] = c == UINT32_MAX ? pieces[p].t_len : (uint32_t)(c_off[c + 1] - c_off[c]);
+}
+// a thread per 16 bytes of the text (out has 16 bytes of room behind `total`): the piece by binary search of the offsets
+__global__ void k_cp_out_text(const pgx_cns_piece *__restrict__ pieces, const uint32_t *__restrict__ call_no, const uint64_t *__restrict__ c_off,
+                              const char *__restrict__ c_text, const uint8_t *__restrict__ seq, const uint64_t *__restrict__ off, uint32_t np, uint64_t total,
+                              char *__restrict__ out) {
+  const uint64_t at = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+  if (at >= total) return;
+  uint32_t a = 0, b = np;   // the last piece that starts at or before `at` and is not empty there
+  while (a < b) {
+    const uint32_t mid = a + ((b - a) >> 1);
+    if (off[mid + 1] <= at) a = mid + 1;
+    else b = mid;
+  }
+  uint32_t p = a;
+  union {
+    uint4 v;
+    char c[16];
+  } u;
+  u.v = make_uint4(0, 0, 0, 0);
+  const uint32_t n = (uint32_t)min((uint64_t)16, total - at);
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint64_t pos = at + k;
+    while (off[p + 1] <= pos) ++p;   // (pos < total = off[np])
+    const uint64_t x = pos - off[p];
+    const uint32_t cn = call_no[p];
+    char ch;
+    if (cn == UINT32_MAX) {
+      ch = (char)seq[pieces[p].seq_off + x];
+      if (ch >= 'A' && ch <= 'Z') ch = (char)(ch + 32);
+    } else {
+      ch = c_text[c_off[cn] + x];
+    }
+    u.c[k] = ch;
+  }
+  *reinterpret_cast<uint4 *>(out + at) = u.v;
+}
+
 }  // namespace
+void faln_dev(const char *who, const pgx_faln_req *d_reqs, size_t n, const uint8_t *d_seq, uint32_t max_band, FalnOut &out, pgx_faln_stats *stats) {
+  hipStream_t st = ctx().stream;
+  DevBuf<uint32_t> err(F_SLOTS), ctr(C_SLOTS);
+  PGX_HIP(hipMemsetAsync(err.p, 0xFF, F_SLOTS * sizeof(uint32_t), st));
+  PGX_HIP(hipMemsetAsync(ctr.p, 0, C_SLOTS * sizeof(uint32_t), st));
+  faln_run(who, d_reqs, n, d_seq, max_band, err.p, ctr.p, out, stats);
+}
+
+// name_base: the caller's number of piece 0 (the refusals name name_base + p)
+void cns_pieces_dev(const char *who, const pgx_cns_piece *d_pieces, uint32_t np, const pgx_cns_read *d_reads, uint32_t nr, const uint8_t *d_seq, uint64_t seq_bytes,
+                    uint32_t min_cov, CnsPiecesDev &res, pgx_cns_pieces_stats *stats, uint32_t name_base) {
+  hipStream_t st = ctx().stream;
+  const uint32_t n = np + nr;
+  DevBuf<uint8_t> keep(n), called(np);
+  res.used.alloc(nr ? nr : 1);
+  DevBuf<uint32_t> err(F_SLOTS), ctr(C_SLOTS);
+  DevBuf<pgx_faln_req> d_reqs(n);
+  DevBuf<CpRow> meta(n);
+  DevBuf<pgx_cns_aln> alns(n);
+  DevBuf<unsigned long long> aln_base(np);
+  PGX_HIP(hipMemsetAsync(err.p, 0xFF, F_SLOTS * sizeof(uint32_t), st));
+  PGX_HIP(hipMemsetAsync(ctr.p, 0, C_SLOTS * sizeof(uint32_t), st));
+  PGX_HIP(hipMemsetAsync(aln_base.p, 0, np * sizeof(unsigned long long), st));
+  LAUNCH(k_cp_reqs, n, d_pieces, np, d_reads, nr, seq_bytes, d_reqs.p, meta.p, err.p);
+  uint32_t h[F_SLOTS];
+  err.download(h, F_SLOTS);
+  sync();
+  PGX_REQUIRE_PIECE(h[F_PIECE_RANGE] == UINT32_MAX, PGX_EARG, name_base + h[F_PIECE_RANGE], "%s: piece %u lies outside the %zu bytes given (or is longer than 2^30)", who, name_base + h[F_PIECE_RANGE],
+              (size_t)seq_bytes);
+  PGX_REQUIRE(h[F_READ_PIECE] == UINT32_MAX, PGX_EARG, "%s: read %u names a piece beyond the %u given", who, h[F_READ_PIECE], np);
+  PGX_REQUIRE(h[F_RANGE] == UINT32_MAX, PGX_EARG, "%s: read %u lies outside the %zu bytes given", who, h[F_RANGE], (size_t)seq_bytes);
+  PGX_REQUIRE(h[F_LEN] == UINT32_MAX, PGX_EARG, "%s: read %u: query and target of 2^31 bytes and more together", who, h[F_LEN]);
+  PGX_REQUIRE_PIECE(h[F_TLEN] == UINT32_MAX, PGX_EINVAL, name_base + h[F_TLEN], "%s: piece %u: a template of no bases", who, name_base + h[F_TLEN]);
+  FalnOut out;
+  pgx_faln_stats ast = {};
+  faln_run(who, d_reqs.p, n, d_seq, CP_READ_BAND, err.p, ctr.p, out, &ast);
+  LAUNCH(k_cp_accept, n, out.res.p, meta.p, np, nr, alns.p, keep.p, res.used.p, aln_base.p, ctr.p);
+  // which pieces enter the call, their numbers in it, their template lengths (the call takes those from the host)
+  PrimWs ws;
+  DevBuf<uint32_t> call_piece(np), call_no(np), call_tlen(np), call_name(np);
+  LAUNCH(k_cp_called, np, d_pieces, aln_base.p, np, called.p);
+  PGX_HIP(hipMemsetAsync(call_no.p, 0xFF, np * sizeof(uint32_t), st));
+  const uint32_t n_call = select_indices(called.p, np, call_piece.p, &ws);
+  DevBuf<char> c_text;
+  DevBuf<uint64_t> c_off(1);
+  pgx_cns_stats cst = {};
+  if (n_call) {
+    LAUNCH(k_cp_call_tables, n_call, call_piece.p, n_call, d_pieces, name_base, call_no.p, call_tlen.p, call_name.p);
+    std::vector<uint32_t> h_tlen(n_call), h_name(n_call);
+    call_tlen.download(h_tlen.data(), n_call);
+    call_name.download(h_name.data(), n_call);
+    DevBuf<uint32_t> list(n);
+    LAUNCH(k_cp_renumber, n, alns.p, keep.p, n, call_no.p);
+    const uint32_t n_keep = select_indices(keep.p, n, list.p, &ws);   // (synchronises: the two downloads are there)
+    DevBuf<pgx_cns_aln> rows(n_keep);
+    if (n_keep) LAUNCH(k_cp_gather, n_keep, alns.p, list.p, n_keep, rows.p);
+    cns_call_dev(who, rows.p, n_keep, out.q_str.p, out.t_str.p, out.str_bytes, h_tlen.data(), n_call, min_cov, nullptr, nullptr, &cst, h_name.data(), &c_text, &c_off);
+  }
+  DevBuf<uint32_t> len(np);
+  res.off.alloc(np + 1);
+  LAUNCH(k_cp_out_len, np, d_pieces, call_no.p, c_off.p, np, len.p);
+  res.total = scan_to_total(len.p, res.off.p, np, &ws);
+  res.text.alloc(res.total + 16);
+  if (res.total) LAUNCH(k_cp_out_text, cdiv(res.total, 16), d_pieces, call_no.p, c_off.p, c_text.p, d_seq, res.off.p, np, res.total, res.text.p);
+  uint32_t hc[C_SLOTS];
+  ctr.download(hc, C_SLOTS);
+  sync();
+  if (stats) {
+    stats->align = ast, stats->call = cst;
+    stats->n_pieces = np, stats->n_reads = nr, stats->n_accepted = hc[C_ACCEPTED], stats->n_rejected = nr - hc[C_ACCEPTED];
+    stats->n_by_rule = np - n_call, stats->n_called = n_call;
+  }
+}
+
 }  // namespace pgx
 
 using namespace pgx;
@@ -504,90 +627,26 @@ int pgx_cns_pieces(const pgx_cns_piece *pieces, size_t n_piece, const pgx_cns_re
       return;
     }
     MemTag mem_tag("cns.align");
-    hipStream_t st = ctx().stream;
-    const uint32_t np = (uint32_t)n_piece, nr = (uint32_t)n_read, n = np + nr;
+    const uint32_t np = (uint32_t)n_piece, nr = (uint32_t)n_read;
     DevBuf<pgx_cns_piece> d_pieces(np);
     DevBuf<pgx_cns_read> d_reads(nr);
-    DevBuf<uint8_t> d_seq, keep(n), used(nr ? nr : 1);
-    DevBuf<uint32_t> err(F_SLOTS), ctr(C_SLOTS);
-    DevBuf<pgx_faln_req> d_reqs(n);
-    DevBuf<CpRow> meta(n);
-    DevBuf<pgx_cns_aln> alns(n);
-    DevBuf<unsigned long long> aln_base(np);
+    DevBuf<uint8_t> d_seq;
     d_pieces.upload(pieces, np);
     d_reads.upload(reads, nr);
     upload_pool(d_seq, seq, seq_bytes);
-    PGX_HIP(hipMemsetAsync(err.p, 0xFF, F_SLOTS * sizeof(uint32_t), st));
-    PGX_HIP(hipMemsetAsync(ctr.p, 0, C_SLOTS * sizeof(uint32_t), st));
-    PGX_HIP(hipMemsetAsync(aln_base.p, 0, np * sizeof(unsigned long long), st));
-    LAUNCH(k_cp_reqs, n, d_pieces.p, np, d_reads.p, nr, (uint64_t)seq_bytes, d_reqs.p, meta.p, err.p);
-    uint32_t h[F_SLOTS];
-    err.download(h, F_SLOTS);
-    sync();
-    PGX_REQUIRE(h[F_PIECE_RANGE] == UINT32_MAX, PGX_EARG, "%s: piece %u lies outside the %zu bytes given (or is longer than 2^30)", who, h[F_PIECE_RANGE], seq_bytes);
-    PGX_REQUIRE(h[F_READ_PIECE] == UINT32_MAX, PGX_EARG, "%s: read %u names a piece beyond the %u given", who, h[F_READ_PIECE], np);
-    PGX_REQUIRE(h[F_RANGE] == UINT32_MAX, PGX_EARG, "%s: read %u lies outside the %zu bytes given", who, h[F_RANGE], seq_bytes);
-    PGX_REQUIRE(h[F_LEN] == UINT32_MAX, PGX_EARG, "%s: read %u: query and target of 2^31 bytes and more together", who, h[F_LEN]);
-    PGX_REQUIRE(h[F_TLEN] == UINT32_MAX, PGX_EINVAL, "%s: piece %u: a template of no bases", who, h[F_TLEN]);
-    FalnOut out;
-    pgx_faln_stats ast = {};
-    faln_run(who, d_reqs.p, n, d_seq.p, CP_READ_BAND, err.p, ctr.p, out, &ast);
-    LAUNCH(k_cp_accept, n, out.res.p, meta.p, np, nr, alns.p, keep.p, used.p, aln_base.p, ctr.p);
-    // the one small copy back: the aligned template bases per piece settle which pieces enter the call (and the flags are an answer)
-    std::vector<unsigned long long> h_base(np);
-    std::vector<uint8_t> h_used(nr);
-    uint32_t hc[C_SLOTS];
-    aln_base.download(h_base.data(), np);
-    used.download(h_used.data(), nr);
-    ctr.download(hc, C_SLOTS);
-    sync();
-    std::vector<uint32_t> call_no(np, UINT32_MAX), call_piece, call_tlen;
-    for (uint32_t p = 0; p < np; ++p)
-      if (h_base[p] >= 3ull * pieces[p].t_len) call_no[p] = (uint32_t)call_piece.size(), call_piece.push_back(p), call_tlen.push_back(pieces[p].t_len);
-    const size_t n_call = call_piece.size();
-    char *c_text = nullptr;
-    std::vector<uint64_t> c_off(n_call + 1, 0);
-    pgx_cns_stats cst = {};
-    if (n_call) {
-      DevBuf<uint32_t> d_no(np), list(n);
-      d_no.upload(call_no.data(), np);
-      LAUNCH(k_cp_renumber, n, alns.p, keep.p, n, d_no.p);
-      const uint32_t n_keep = select_indices(keep.p, n, list.p);
-      DevBuf<pgx_cns_aln> rows(n_keep);
-      if (n_keep) LAUNCH(k_cp_gather, n_keep, alns.p, list.p, n_keep, rows.p);
-      cns_call_dev(who, rows.p, n_keep, out.q_str.p, out.t_str.p, out.str_bytes, call_tlen.data(), n_call, min_cov, &c_text, c_off.data(), &cst, call_piece.data());
-    }
-    // the text: a piece of the call as the call answered it, the others their template through ASCII lower-casing
-    uint64_t total = 0;
-    for (uint32_t p = 0; p < np; ++p) {
-      piece_off[p] = total;
-      total += call_no[p] == UINT32_MAX ? pieces[p].t_len : c_off[call_no[p] + 1] - c_off[call_no[p]];
-    }
-    piece_off[np] = total;
-    char *o = nullptr;
+    CnsPiecesDev out;
+    cns_pieces_dev(who, d_pieces.p, np, d_reads.p, nr, d_seq.p, seq_bytes, min_cov, out, stats, 0);
+    char *o = caller_text(nullptr, out.total);
     try {
-      o = caller_text(nullptr, total);
+      if (out.total) PGX_HIP(hipMemcpyAsync(o, out.text.p, out.total, hipMemcpyDeviceToHost, ctx().stream));
+      out.off.download(piece_off, np + 1);
+      if (read_used) out.used.download(read_used, nr);
+      sync();
     } catch (...) {
-      free(c_text);
+      free(o);
       throw;
     }
-    for (uint32_t p = 0; p < np; ++p) {
-      char *dst = o + piece_off[p];
-      if (call_no[p] == UINT32_MAX) {
-        const char *src = seq + pieces[p].seq_off;
-        for (uint32_t i = 0; i < pieces[p].t_len; ++i) dst[i] = (src[i] >= 'A' && src[i] <= 'Z') ? (char)(src[i] + 32) : src[i];
-      } else {
-        memcpy(dst, c_text + c_off[call_no[p]], c_off[call_no[p] + 1] - c_off[call_no[p]]);
-      }
-    }
-    free(c_text);
     *text = o;
-    if (read_used && nr) memcpy(read_used, h_used.data(), nr);
-    if (stats) {
-      stats->align = ast, stats->call = cst;
-      stats->n_pieces = np, stats->n_reads = nr, stats->n_accepted = hc[C_ACCEPTED], stats->n_rejected = nr - hc[C_ACCEPTED];
-      stats->n_by_rule = np - n_call, stats->n_called = n_call;
-    }
   });
 }
 

@@ -34,6 +34,7 @@ namespace pgx {
 void set_error(const char *fmt, ...);
 struct Fail {
   int code;
+  int64_t piece = -1;   // a refusal that names a piece of a consensus batch: the caller's number of it (PGX_REQUIRE_PIECE)
 };
 #define PGX_HIP(call)                                                                         \
   do {                                                                                        \
@@ -49,6 +50,14 @@ struct Fail {
       pgx::set_error(__VA_ARGS__);   \
       throw pgx::Fail{code};         \
     }                                \
+  } while (0)
+// ... of a piece: the Fail carries the piece's number, so that a caller whose pieces are something else's (a contig's segments) can say so
+#define PGX_REQUIRE_PIECE(cond, code, piece_no, ...) \
+  do {                                               \
+    if (!(cond)) {                                   \
+      pgx::set_error(__VA_ARGS__);                   \
+      throw pgx::Fail{code, (int64_t)(piece_no)};    \
+    }                                                \
   } while (0)
 // The epilogue of a C entry point: runs body (which returns nothing -- PGX_OK is answered -- or the code to answer); a Fail becomes its
 // code, an allocation failure PGX_ENOMEM with a message.  No C++ exception of the library's own leaves an extern "C" function.
@@ -726,8 +735,28 @@ T *host_copy(const std::vector<T> &v) {
 }
 // The consensus call on rows and strings in device memory (pgx_cns.hip; include/pgx.h: pgx_cns_call_dev; piece_tlen and the results are the
 // host's).  names: where the pieces are a selection of the caller's, the caller's number of each, which the refusals then name (or nullptr).
+// d_text_out and d_off_out both given: the text and its n_piece + 1 offsets stay on the device instead (text, piece_off are not written).
 void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, const uint8_t *d_q, const uint8_t *d_t, size_t str_bytes, const uint32_t *piece_tlen,
-                  size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats, const uint32_t *names);
+                  size_t n_piece, uint32_t min_cov, char **text, uint64_t *piece_off, pgx_cns_stats *stats, const uint32_t *names, DevBuf<char> *d_text_out = nullptr,
+                  DevBuf<uint64_t> *d_off_out = nullptr);
+// falcon.align for n > 0 checked requests in device memory over a device pool with 16 bytes of padding behind it (pgx_cns_align.hip): the
+// answers, without strings unless a request wants them.  max_band: the widest band among them.
+struct FalnOut {
+  DevBuf<pgx_faln_res> res;
+  DevBuf<uint8_t> q_str, t_str;
+  uint64_t str_bytes = 0;
+};
+void faln_dev(const char *who, const pgx_faln_req *d_reqs, size_t n, const uint8_t *d_seq, uint32_t max_band, FalnOut &out, pgx_faln_stats *stats);
+// pgx_cns_pieces on pieces, reads and a pool that are on the device already (the pool with 16 bytes of padding behind its seq_bytes): the
+// pieces' text stays there, piece p at text[off[p], off[p + 1]).  name_base: the caller's number of piece 0 (the refusals name name_base + p).
+struct CnsPiecesDev {
+  DevBuf<char> text;       // 16 bytes of room behind the last piece
+  DevBuf<uint64_t> off;    // n_piece + 1
+  DevBuf<uint8_t> used;    // per read: accepted
+  uint64_t total = 0;
+};
+void cns_pieces_dev(const char *who, const pgx_cns_piece *d_pieces, uint32_t n_piece, const pgx_cns_read *d_reads, uint32_t n_read, const uint8_t *d_seq,
+                    uint64_t seq_bytes, uint32_t min_cov, CnsPiecesDev &out, pgx_cns_pieces_stats *stats, uint32_t name_base);
 // n bytes of text as a NUL-terminated string of the caller's (pgx_free); src == nullptr: room for n bytes, still to be filled
 inline char *caller_text(const char *src, size_t n) {
   char *t = (char *)malloc(n + 1);

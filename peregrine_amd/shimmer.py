@@ -1012,6 +1012,52 @@ def consensus_reads(pieces, min_cov: int = 1, device=None, stats: dict | None = 
     return [data[int(off[p]):int(off[p + 1])] for p in range(len(pieces))]
 
 
+def cns_layout(rows, ctg_len, device=None):
+    """the layout of pg_asm_cns.py:53-139 (pgx_cns_layout): rows is an (n, 9) integer array of map rows `ctg p1 p2 read rb re strand mc0 mc1`
+    that passed the chunk filter, ctg_len the contig lengths by contig id (negative: the idx lacks it).  The answer: (pieces, reads) as
+    _lib.CNS_JOB_PIECE_DTYPE and _lib.CNS_JOB_READ_DTYPE arrays, in the order the script answers its segments and aligns their reads."""
+    _lib.init(device)
+    rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 9)
+    lens = np.ascontiguousarray(ctg_len, np.int64)
+    pieces, reads, n_piece, n_read = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.load().pgx_cns_layout(_ptr(rows), len(rows), _ptr(lens), len(lens), C.byref(pieces), C.byref(n_piece), C.byref(reads), C.byref(n_read)),
+               "pgx_cns_layout")
+    return _lib.take(pieces.value, n_piece.value, _lib.CNS_JOB_PIECE_DTYPE), _lib.take(reads.value, n_read.value, _lib.CNS_JOB_READ_DTYPE)
+
+
+def cns_job_resident(reads: "ResidentDB", ref: "ResidentDB", rows, total_chunks: int, my_chunk: int, ctg_names, stats: dict | None = None):
+    """pg_asm_cns.py on two resident databases and all rows of a map (pgx_cns_job_resident): rows is an (n, 9) integer array, ctg_names the
+    contigs' names by contig id (a list of str; '' for an id the idx lacks).  The answer: (FASTA bytes, the offsets of the contigs' records
+    in it).  stats: filled with pgx_cns_job_stats."""
+    rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 9)
+    enc = [n.encode() for n in ctg_names]
+    name_off = np.concatenate([[0], np.cumsum([len(n) for n in enc])]).astype(np.uint64)
+    names = np.frombuffer(b"".join(enc), np.uint8)
+    text, off, n_ctg, n_text, st = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0), _lib.CnsJobStats()
+    _lib.check(_lib.load().pgx_cns_job_resident(reads.h, ref.h, _ptr(rows), len(rows), int(total_chunks), int(my_chunk), _ptr(names), _ptr(name_off), len(enc),
+                                                C.byref(text), C.byref(off), C.byref(n_ctg), C.byref(n_text), C.byref(st)), "pgx_cns_job_resident")
+    data = C.string_at(text.value, n_text.value)
+    offs = np.frombuffer(C.string_at(off.value, 8 * (n_ctg.value + 1)), np.uint64).copy()
+    _lib.load().pgx_free(text)
+    _lib.load().pgx_free(off)
+    if stats is not None:
+        stats.update(st.asdict())
+    return data, offs
+
+
+def pg_asm_cns(read_prefix: str, ref_prefix: str, map_path: str, total_chunks: int, my_chunk: int, out: str | None = None, device=None) -> dict:
+    """pg_asm_cns.py read_db_prefix ref_db_prefix read_to_contig_map total_chunks my_chunk (pgx_cns_job): the polished contigs of the
+    chunk as FASTA, byte for byte the script's stdout, written to `out` (None: this process's stdout).  Returns pgx_cns_job_stats."""
+    _lib.init(device)
+    if out is None:
+        import sys
+        sys.stdout.flush()
+    st = _lib.CnsJobStats()
+    _lib.check(_lib.load().pgx_cns_job(read_prefix.encode(), ref_prefix.encode(), map_path.encode(), int(total_chunks), int(my_chunk),
+                                       out.encode() if out is not None else None, C.byref(st)), "pgx_cns_job")
+    return st.asdict()
+
+
 def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None):
     """in-memory form of shmr_map (pgx_map): arrays in, text out"""
     _lib.init(device)
