@@ -405,6 +405,37 @@ int pgx_map(const pgx_mm128 *ref_mmers, size_t n_ref, const pgx_mm128 *mmers, si
 /* file level: -r refdb_prefix (unused, as in the reference) -m ref_shimmer_prefix -p seqdb_prefix -l shimmer_prefix */
 int pgx_map_chunk(const char *refdb_prefix, const char *ref_shimmer_prefix, const char *seqdb_prefix,
                   const char *shimmer_prefix, const pgx_map_params *p, char **text, size_t *text_len, uint64_t *n_lines);
+/* pgx_map / pgx_map_chunk answering the rows in place of the text: *rows (pgx_free) holds *n_rows x 9 int64, a line's nine numbers in the
+ * order the text has them -- what pgx_map_merge_rows and pgx_cns_job_resident take, so a resident caller never forms the text. */
+int pgx_map_rows(const pgx_mm128 *ref_mmers, size_t n_ref, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts,
+                 size_t n_counts, const uint32_t *rlen_by_rid, uint32_t n_rid, const pgx_map_params *p, int64_t **rows,
+                 uint64_t *n_rows);
+int pgx_map_rows_chunk(const char *refdb_prefix, const char *ref_shimmer_prefix, const char *seqdb_prefix,
+                       const char *shimmer_prefix, const pgx_map_params *p, int64_t **rows, uint64_t *n_rows);
+
+/* ---- map merge (replaces `cat map-*.dat | sort -k 1 -g -k 2 -g`, pg_run.py:491-496, the step between shmr_map and pg_asm_cns.py) ----
+ * The order is that of `LC_ALL=C sort -k 1 -g -k 2 -g` on shmr_map's lines (nine canonical decimals below 2^32, single blanks): by field
+ * 0 as a number, by field 1 as a number, then by the whole line bytewise -- fields 2 .. 8 compared as decimal STRINGS ("100" before
+ * "99", "7" before "70").  Rows equal under all three are identical lines.  One stable 64-bit radix sort by (field 0, field 1), then the
+ * runs of equal keys by the string rule: a run of up to 64 rows on a wavefront, one of up to 1,024 on a workgroup, longer ones through
+ * an LSD sort of their rows alone.  n < 2^31 rows; no host spill: rows that do not fit the device answer
+ * PGX_ENOMEM.  PGX_MERGE_RUN_MAX=<rows> (1 .. 1,024) shrinks the workgroup's bound -- below 64 the wavefront's too; 1 sends every tie run
+ * through the LSD sort -- and PGX_MERGE_PIECE=<bytes> the pieces of the file level: test hooks. */
+typedef struct {
+  uint64_t n_rows, n_runs, n_tie_runs, longest_run;   /* runs of equal (field 0, field 1); those of two rows and more; the longest */
+  uint64_t rows_wave, rows_group, rows_lsd;           /* rows of tie runs by the path that ordered them */
+  double parse_ms, key_ms, sort_ms, ties_ms, format_ms;   /* host clock: text to rows, keys, the radix sort, the runs + gather, rows to text */
+} pgx_map_merge_stats;                                /* 96 bytes */
+/* rows: n x 9 uint32 in device memory, any order; the merged rows to d_out (device, n x 9, not d_rows) */
+int pgx_map_merge_dev(const uint32_t *d_rows, uint64_t n, uint32_t *d_out, pgx_map_merge_stats *stats);
+/* the host form, n x 9 int64 in, n x 9 int64 out (the caller's array; may be `rows`).  A value outside [0, 2^32): PGX_EINVAL, the row named. */
+int pgx_map_merge_rows(const int64_t *rows, size_t n, int64_t *out, pgx_map_merge_stats *stats);
+/* the file level: the map chunk files, one after the other in the given order ("-": stdin), to one merged file (out_path NULL: stdout).
+ * Parsed on the device in bounded pieces of each file, the rows kept there as 9 x u32, the text formatted there in bounded pieces.
+ * PGX_EINVAL, the file and the 0-based line named and NOTHING written: a line that is not nine canonical decimals (0|[1-9][0-9]*) below
+ * 2^32 separated by single blanks -- a sign, a leading zero, a tab, a '\r', a blank line, eight or ten fields.  A file's last line may
+ * lack its '\n' (the output ends every line with one); empty files and no rows at all give an empty output. */
+int pgx_map_merge(const char *const *paths, size_t n_paths, const char *out_path, pgx_map_merge_stats *stats);
 
 /* ---- batch level ---- */
 int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, pgx_mm128 **out,

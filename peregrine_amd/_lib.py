@@ -115,6 +115,14 @@ class CnsJobStats(C.Structure):
         return out
 
 
+class MapMergeStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_runs", "n_tie_runs", "longest_run", "rows_wave", "rows_group", "rows_lsd")] + \
+               [(n, C.c_double) for n in ("parse_ms", "key_ms", "sort_ms", "ties_ms", "format_ms")]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/pgx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "pgx_init", "pgx_shutdown", "pgx_last_error", "pgx_device_count", "pgx_version", "pgx_free",
@@ -131,7 +139,7 @@ EXPORTS = [
     "pgx_sgraph_parse", "pgx_tiling_build", "pgx_tiling_stats", "pgx_tiling_rows", "pgx_tiling_names", "pgx_tiling_text", "pgx_tiling_contigs", "pgx_tiling_free", "pgx_tiling_chunk",
     "pgx_sketch_batch", "pgx_reduce_batch", "pgx_count_batch", "pgx_align_batch",
     "decode_biseq", "encode_biseq", "mm_sketch", "mm_reduce", "ovlp_match", "free_ovlp_match", "read_mmlist", "write_mmlist",
-    "pgx_map", "pgx_map_chunk", "pgx_khash_slot_order", "pgx_khash_slot_order_ex",
+    "pgx_map", "pgx_map_chunk", "pgx_map_rows", "pgx_map_rows_chunk", "pgx_map_merge_dev", "pgx_map_merge_rows", "pgx_map_merge", "pgx_khash_slot_order", "pgx_khash_slot_order_ex",
     "pgx_seqdb_upload_dev", "pgx_index_resident_dev", "pgx_pairs_prepare_dev", "pgx_pairs_scatter_dev", "pgx_overlap_records_dev",
     "pgx_overlap_resident_dev", "pgx_copy_dev", "pgx_seqdb_adopt_dev", "pgx_stream_wait", "pgx_stream_signal",
     "pgx_align_batch2", "pgx_contigs_resident", "pgx_contigs_chunk",
@@ -257,6 +265,12 @@ def load():
         lib.pgx_map.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_map_chunk.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_map_rows.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_map_rows_chunk.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_map_merge_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.pgx_map_merge_rows.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.pgx_map_merge.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p, C.c_void_p]
         lib.build_shimmer_map4py.restype = None
         lib.build_shimmer_map4py.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.get_shimmers_for_read.restype = None

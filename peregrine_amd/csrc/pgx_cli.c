@@ -1,6 +1,6 @@
 /*
  * pgx_cli.c -- native drop-ins for the reference's stage executables, one multi-call binary (the tool is chosen by the
- * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map, path_to_contig.py, graph_to_path.py, pg_asm_cns.py.  Same getopt strings, defaults
+ * name it is invoked under): shmr_mkseqdb, shmr_index, shmr_overlap, shmr_dedup, shmr_map, shmr_map_merge, path_to_contig.py, graph_to_path.py, pg_asm_cns.py.  Same getopt strings, defaults
  * and output files / streams as /root/reference/src/shmr_mkseqdb.c:14-128, shmr_index.c:37-245, shmr_overlap.c:233-419,
  * shmr_dedup.c:19-104, shmr_map.c:163-373; everything else happens behind the C-ABI of include/pgx.h on the GPU.
  * Plain C against libpgx.so: this is the cgo / FFI-free form of the boundary (the Python shims in bin/ do the same).
@@ -615,6 +615,33 @@ static int main_pg_asm_cns(int argc, char **argv) {
   return 0;
 }
 
+/* shmr_map_merge [FILE...] [-o OUT]: the map chunk files in the order of `LC_ALL=C sort -k 1 -g -k 2 -g` over their lines, the step between
+ * shmr_map and pg_asm_cns.py (pg_run.py:491-496).  Without files it reads stdin, so `cat map-*.dat | shmr_map_merge > out` works too. */
+static int main_map_merge(int argc, char **argv) {
+  const char *out = NULL, *in_stdin = "-";
+  const char **paths = malloc(sizeof(char *) * (size_t)(argc > 1 ? argc : 1));
+  size_t n = 0;
+  int bad = paths == NULL;
+  for (int i = 1; i < argc && !bad; ++i) {
+    if (strcmp(argv[i], "-o") == 0) {
+      if (i + 1 < argc && !out) out = argv[++i];
+      else bad = 1;
+    } else if (argv[i][0] == '-' && argv[i][1]) {
+      bad = 1;
+    } else {
+      paths[n++] = argv[i];
+    }
+  }
+  if (bad) {
+    fprintf(stderr, "usage: shmr_map_merge [FILE...] [-o OUT]   (no FILE: stdin; no -o: stdout)\n");
+    return 1;
+  }
+  if (n == 0) paths[n++] = in_stdin;
+  if (pgx_init(device_of_env())) return fail("shmr_map_merge", "pgx_init");
+  if (pgx_map_merge(paths, n, out, NULL)) return fail("shmr_map_merge", "pgx_map_merge");
+  return 0;
+}
+
 /* graph_to_path.py [--improper-p-ctg] [--proper-a-ctg] [--seqdb-prefix P] [--sg-edges-list-fn F] [--utg-data-fn F] [--ctg-paths-fn F]
  * (py/scripts/graph_to_path.py): p_ctg_tiling_path and a_ctg_tiling_path into the working directory, nothing on stdout.  The first three
  * options change nothing in the script's tiling paths either. */
@@ -702,9 +729,10 @@ int main(int argc, char **argv) {
   else if (strcmp(tool, "path_to_contig.py") == 0) rc = main_path_to_contig(argc, argv);
   else if (strcmp(tool, "graph_to_path.py") == 0) rc = main_graph_to_path(argc, argv);
   else if (strcmp(tool, "pg_asm_cns.py") == 0) rc = main_pg_asm_cns(argc, argv);
+  else if (strcmp(tool, "shmr_map_merge") == 0) rc = main_map_merge(argc, argv);
   else if (strcmp(tool, "serve") == 0) rc = main_serve(argc, argv);
   else {
-    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_sgraph|shmr_map|path_to_contig.py|graph_to_path.py|pg_asm_cns.py} [flags]   (or invoke through a link of that name)\n"
+    fprintf(stderr, "usage: pgx_cli {shmr_mkseqdb|shmr_index|shmr_overlap|shmr_dedup|shmr_sgraph|shmr_map|shmr_map_merge|path_to_contig.py|graph_to_path.py|pg_asm_cns.py} [flags]   (or invoke through a link of that name)\n"
                     "       pgx_cli serve -p seqdb_prefix [-i idle_seconds]   (keeps the read database in HBM; the drop-ins attach to it)\n");
     rc = 2;
   }

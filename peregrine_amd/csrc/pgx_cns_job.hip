@@ -542,10 +542,12 @@ __global__ void k_job_ctg_off(const uint32_t *first_piece, uint32_t n_used, cons
 }
 
 // ---- map text -> rows ----------------------------------------------------------------------------------------------------------------
-__global__ void k_par_newlines(const char *text, uint32_t n, uint8_t *flag) {
+}  // namespace
+__global__ void k_par_newlines(const char *text, uint32_t n, uint8_t *flag) {   // (pgx_internal.h: the map merge finds its lines with it too)
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) flag[i] = text[i] == '\n';
 }
+namespace {
 // an optional '-' and 1 .. 18 digits
 __device__ inline bool parse_int(const char *p, uint32_t n, int64_t *out) {
   const bool neg = n && p[0] == '-';

@@ -757,6 +757,11 @@ struct CnsPiecesDev {
 };
 void cns_pieces_dev(const char *who, const pgx_cns_piece *d_pieces, uint32_t n_piece, const pgx_cns_read *d_reads, uint32_t n_read, const uint8_t *d_seq,
                     uint64_t seq_bytes, uint32_t min_cov, CnsPiecesDev &out, pgx_cns_pieces_stats *stats, uint32_t name_base);
+// the line select of the device parsers of map text (pgx_cns_job.hip): flag[i] = text[i] is a newline
+__global__ void k_par_newlines(const char *text, uint32_t n, uint8_t *flag);
+// the merge of shmr_map's rows (pgx_mapmerge.hip): n > 0 rows (9 x u32, device) in the order of `LC_ALL=C sort -k 1 -g -k 2 -g` over their
+// lines to d_out (not d_rows); the times are added to *ms
+void map_merge_dev(const uint32_t *d_rows, uint32_t n, uint32_t *d_out, pgx_map_merge_stats *ms);
 // n bytes of text as a NUL-terminated string of the caller's (pgx_free); src == nullptr: room for n bytes, still to be filled
 inline char *caller_text(const char *src, size_t n) {
   char *t = (char *)malloc(n + 1);

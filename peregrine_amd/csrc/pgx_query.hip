@@ -175,10 +175,10 @@ inline char *put_u32(char *w, uint32_t v) {  // decimal, no padding
   return w;
 }
 
-void run_map(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts, size_t n_counts,
-             const uint32_t *rlen_by_rid, uint32_t n_rid, const pgx_map_params *p, std::string &text, uint64_t &n_lines) {
-  text.clear();
-  n_lines = 0;
+// the rows of shmr_map in the order it prints them, left on the device (total == 0: none, d_rows untouched)
+void run_map_dev(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts, size_t n_counts,
+                 const uint32_t *rlen_by_rid, uint32_t n_rid, const pgx_map_params *p, DevBuf<MapRow> &d_rows, uint32_t &total) {
+  total = 0;
   PGX_REQUIRE(p && p->total_chunk > 0 && p->mychunk > 0 && p->mychunk <= p->total_chunk, PGX_EARG,
               "need 0 < mychunk <= total_chunk (shmr_map.c:247-248)");
   PGX_REQUIRE(n_ref > 0, PGX_EARG, "no reference shimmers (shmr_map.c:83)");
@@ -212,11 +212,23 @@ void run_map(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t 
   running_max(chain_in.p, chain.p, n);
   hipLaunchKernelGGL(k_ref_hits, dim3(cdiv(n, 256)), dim3(256), 0, st, d_ref.p, n, chain.p, first.p, gkey0.p, ng, gbucket.p, bkey1.p,
                      bstart.p, bucket.p, rows.p);
-  const uint32_t total = scan_to_total(rows.p, off.p, n);
+  total = scan_to_total(rows.p, off.p, n);
   if (total == 0) return;
-  DevBuf<MapRow> d_rows(total);
+  d_rows.alloc(total);
   hipLaunchKernelGGL(k_ref_rows, dim3(cdiv(n, 256)), dim3(256), 0, st, d_ref.p, n, chain.p, bucket.p, rows.p, off.p, cnt.p, bstart.p,
                      y0.p, y1.p, dir.p, d_rows.p);
+  PGX_HIP(hipGetLastError());
+  sync();   // (the tables above go back to the block cache with this scope)
+}
+
+void run_map(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts, size_t n_counts,
+             const uint32_t *rlen_by_rid, uint32_t n_rid, const pgx_map_params *p, std::string &text, uint64_t &n_lines) {
+  text.clear();
+  n_lines = 0;
+  DevBuf<MapRow> d_rows;
+  uint32_t total = 0;
+  run_map_dev(ref, n_ref, mmers, n_mm, counts, n_counts, rlen_by_rid, n_rid, p, d_rows, total);
+  if (total == 0) return;
   HostArray<MapRow> h(total);
   d_rows.download(h.data(), total);
   sync();
@@ -233,6 +245,48 @@ void run_map(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t 
   }
   text.resize((size_t)(w - text.data()));
   n_lines = total;
+}
+
+// what the file level of shmr_map reads behind its prefixes (shmr_map.c:285-345): the contigs' shimmers, the reads' lengths, shimmers and counts
+struct MapFiles {
+  std::vector<pgx_mm128> ref, mm;
+  std::vector<pgx_mm_count> mc;
+  std::vector<uint32_t> rl;
+  MapFiles(const char *who, const char *ref_shimmer_prefix, const char *seqdb_prefix, const char *shimmer_prefix) {
+    PGX_REQUIRE(ref_shimmer_prefix && seqdb_prefix && shimmer_prefix, PGX_EARG, "%s: null argument", who);
+    read_counted(std::string(ref_shimmer_prefix) + "-[0-9]*-of-[0-9]*.dat", ref);
+    rlen_by_rid_of(seqdb_prefix, rl);
+    read_counted(std::string(shimmer_prefix) + "-[0-9]*-of-[0-9]*.dat", mm);
+    read_counted(std::string(shimmer_prefix) + "-MC-[0-9]*-of-[0-9]*.dat", mc);
+  }
+};
+
+// the rows-out path beside run_map: the same rows as n x 9 int64, the form pgx_cns_job_resident and pgx_map_merge_rows take
+__global__ void k_map_rows_wide(const uint32_t *__restrict__ in, uint64_t n_vals, int64_t *__restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n_vals) out[t] = in[t];
+}
+void run_map_rows(const pgx_mm128 *ref, size_t n_ref, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts, size_t n_counts,
+                  const uint32_t *rlen_by_rid, uint32_t n_rid, const pgx_map_params *p, int64_t **rows, uint64_t *n_rows) {
+  static_assert(sizeof(MapRow) == 9 * sizeof(uint32_t), "a MapRow is nine numbers");
+  hipStream_t st = ctx().stream;
+  DevBuf<MapRow> d_rows;
+  uint32_t total = 0;
+  run_map_dev(ref, n_ref, mmers, n_mm, counts, n_counts, rlen_by_rid, n_rid, p, d_rows, total);
+  const uint64_t nv = (uint64_t)total * 9;
+  int64_t *out = (int64_t *)out_alloc(nv ? nv * sizeof(int64_t) : 1);
+  try {
+    if (total) {
+      DevBuf<int64_t> wide(nv);
+      LAUNCH(k_map_rows_wide, nv, (const uint32_t *)d_rows.p, nv, wide.p);
+      wide.download(out, nv);
+      sync();
+    }
+  } catch (...) {
+    out_free(out);
+    throw;
+  }
+  *rows = out, *n_rows = total;
 }
 
 }  // namespace
@@ -264,17 +318,32 @@ int pgx_map_chunk(const char *refdb_prefix, const char *ref_shimmer_prefix, cons
                   const pgx_map_params *p, char **text, size_t *text_len, uint64_t *n_lines) {
   return guarded([&]() -> int {
     require_ready();
-    PGX_REQUIRE(ref_shimmer_prefix && seqdb_prefix && shimmer_prefix, PGX_EARG, "pgx_map_chunk: null argument");
     (void)refdb_prefix;  // the reference maps the two seqdb files but never reads them (shmr_map.c:60-78)
-    std::vector<pgx_mm128> ref, mm;
-    std::vector<pgx_mm_count> mc;
-    std::vector<uint32_t> rl;
-    read_counted(std::string(ref_shimmer_prefix) + "-[0-9]*-of-[0-9]*.dat", ref);
-    rlen_by_rid_of(seqdb_prefix, rl);
-    read_counted(std::string(shimmer_prefix) + "-[0-9]*-of-[0-9]*.dat", mm);
-    read_counted(std::string(shimmer_prefix) + "-MC-[0-9]*-of-[0-9]*.dat", mc);
-    return pgx_map(ref.data(), ref.size(), mm.data(), mm.size(), mc.data(), mc.size(), rl.data(), (uint32_t)rl.size(), p, text,
+    const MapFiles f("pgx_map_chunk", ref_shimmer_prefix, seqdb_prefix, shimmer_prefix);
+    return pgx_map(f.ref.data(), f.ref.size(), f.mm.data(), f.mm.size(), f.mc.data(), f.mc.size(), f.rl.data(), (uint32_t)f.rl.size(), p, text,
                    text_len, n_lines);
+  });
+}
+
+int pgx_map_rows(const pgx_mm128 *ref_mmers, size_t n_ref, const pgx_mm128 *mmers, size_t n_mm, const pgx_mm_count *counts,
+                 size_t n_counts, const uint32_t *rlen_by_rid, uint32_t n_rid, const pgx_map_params *p, int64_t **rows, uint64_t *n_rows) {
+  return guarded([&] {
+    require_ready();
+    PGX_REQUIRE(rows && n_rows && (n_ref == 0 || ref_mmers) && (n_mm == 0 || mmers) && (n_counts == 0 || counts) && (n_rid == 0 || rlen_by_rid),
+                PGX_EARG, "pgx_map_rows: null argument");
+    *rows = nullptr, *n_rows = 0;
+    run_map_rows(ref_mmers, n_ref, mmers, n_mm, counts, n_counts, rlen_by_rid, n_rid, p, rows, n_rows);
+    timing_flush();
+  });
+}
+
+int pgx_map_rows_chunk(const char *refdb_prefix, const char *ref_shimmer_prefix, const char *seqdb_prefix, const char *shimmer_prefix,
+                       const pgx_map_params *p, int64_t **rows, uint64_t *n_rows) {
+  return guarded([&]() -> int {
+    require_ready();
+    (void)refdb_prefix;
+    const MapFiles f("pgx_map_rows_chunk", ref_shimmer_prefix, seqdb_prefix, shimmer_prefix);
+    return pgx_map_rows(f.ref.data(), f.ref.size(), f.mm.data(), f.mm.size(), f.mc.data(), f.mc.size(), f.rl.data(), (uint32_t)f.rl.size(), p, rows, n_rows);
   });
 }
 

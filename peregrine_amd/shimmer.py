@@ -8,6 +8,7 @@ libpgx.so on the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -1056,6 +1057,85 @@ def pg_asm_cns(read_prefix: str, ref_prefix: str, map_path: str, total_chunks: i
     _lib.check(_lib.load().pgx_cns_job(read_prefix.encode(), ref_prefix.encode(), map_path.encode(), int(total_chunks), int(my_chunk),
                                        out.encode() if out is not None else None, C.byref(st)), "pgx_cns_job")
     return st.asdict()
+
+
+def map_merge(rows_or_paths, out: str | None = None, device=None, stats: dict | None = None):
+    """The step between shmr_map and pg_asm_cns.py, `cat map-*.dat | LC_ALL=C sort -k 1 -g -k 2 -g` (pg_run.py:491-496), on the GPU: by
+    field 0 and field 1 as numbers, then by the whole line bytewise -- fields 2 .. 8 as decimal strings.
+    An (n, 9) integer array of rows (pgx_map_merge_rows): the merged rows come back as an (n, 9) int64 array; `out` is not used.
+    A path or a list of paths ("-": stdin) of map chunk files (pgx_map_merge): one merged file is written to `out` (None: this process's
+    stdout), and the stats come back.  stats: filled with pgx_map_merge_stats either way."""
+    _lib.init(device)
+    st = _lib.MapMergeStats()
+    if isinstance(rows_or_paths, np.ndarray):
+        rows = np.ascontiguousarray(rows_or_paths, np.int64).reshape(-1, 9)
+        merged = np.empty_like(rows)
+        _lib.check(_lib.load().pgx_map_merge_rows(_ptr(rows), len(rows), _ptr(merged), C.byref(st)), "pgx_map_merge_rows")
+        if stats is not None:
+            stats.update(st.asdict())
+        return merged
+    paths = [rows_or_paths] if isinstance(rows_or_paths, (str, bytes, os.PathLike)) else list(rows_or_paths)
+    arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+    if out is None:
+        import sys
+        sys.stdout.flush()
+    _lib.check(_lib.load().pgx_map_merge(arr, len(paths), os.fsencode(out) if out is not None else None, C.byref(st)), "pgx_map_merge")
+    if stats is not None:
+        stats.update(st.asdict())
+    return st.asdict()
+
+
+def map_rows(ref_shimmer_prefix: str = "ref-L2", seqdb_prefix: str = "seq_dataset", shimmer_prefix: str = "shimmer-L2", refdb_prefix: str = "ref",
+             total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None) -> np.ndarray:
+    """shmr_map answering its rows in place of its text (pgx_map_rows_chunk): an (n, 9) int64 array, a line's nine numbers a row, in the
+    order shmr_map prints them -- what map_merge and cns_job_resident take."""
+    _lib.init(device)
+    p = _lib.MapParams(total_chunk, mychunk, mc_lower, mc_upper)
+    rows, n = C.c_void_p(), C.c_uint64(0)
+    _lib.check(_lib.load().pgx_map_rows_chunk(refdb_prefix.encode(), ref_shimmer_prefix.encode(), seqdb_prefix.encode(), shimmer_prefix.encode(), C.byref(p),
+                                              C.byref(rows), C.byref(n)), "pgx_map_rows_chunk")
+    return _lib.take(rows.value, n.value * 9, np.dtype(np.int64)).reshape(-1, 9)
+
+
+def map_rows_of(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None) -> np.ndarray:
+    """in-memory form of map_rows (pgx_map_rows): arrays in, rows out"""
+    _lib.init(device)
+    rf = np.ascontiguousarray(ref_mmers, MM_DTYPE)
+    mm = np.ascontiguousarray(mmers, MM_DTYPE)
+    mc = np.ascontiguousarray(counts, MC_DTYPE)
+    rl = np.ascontiguousarray(rlen_by_rid, np.uint32)
+    p = _lib.MapParams(total_chunk, mychunk, mc_lower, mc_upper)
+    rows, n = C.c_void_p(), C.c_uint64(0)
+    _lib.check(_lib.load().pgx_map_rows(_ptr(rf), len(rf), _ptr(mm), len(mm), _ptr(mc), len(mc), _ptr(rl), len(rl), C.byref(p), C.byref(rows), C.byref(n)),
+               "pgx_map_rows")
+    return _lib.take(rows.value, n.value * 9, np.dtype(np.int64)).reshape(-1, 9)
+
+
+def consensus_branch(read_prefix: str, read_index_prefix: str, ctg_prefix: str, ctg_index_prefix: str, mapping_nchunk: int, cns_nchunk: int,
+                     mc_lower=1, mc_upper=240, out: str | None = None, device=None):
+    """The consensus branch of pg_run.py (:389-545) behind the contigs' index, in one process: both databases are loaded once; map_rows for
+    the chunks 1 .. mapping_nchunk, map_merge, and cns_job_resident for my = 1 .. cns_nchunk -- the order in which pg_run.py:540-545
+    concatenates its chunk files (my == cns_nchunk is chunk 0).  Neither the map text nor the merged file is formed.  The concatenated
+    FASTA is returned, or written to `out`."""
+    from .formats import read_seqdb
+    _lib.init(device)
+    read_db, ctg_db = read_seqdb(read_prefix), read_seqdb(ctg_prefix)
+    names = [""] * (int(ctg_db.rid.max()) + 1 if ctg_db.n_reads else 0)
+    for r, nm in zip(ctg_db.rid, ctg_db.names):
+        names[int(r)] = nm
+    rdb, cdb = ResidentDB(read_db), ResidentDB(ctg_db)
+    try:
+        parts = [map_rows(ctg_index_prefix, read_prefix, read_index_prefix, ctg_prefix, mapping_nchunk, c, mc_lower, mc_upper)
+                 for c in range(1, int(mapping_nchunk) + 1)]
+        rows = map_merge(np.concatenate(parts) if parts else np.zeros((0, 9), np.int64))
+        fasta = b"".join(cns_job_resident(rdb, cdb, rows, cns_nchunk, my, names)[0] for my in range(1, int(cns_nchunk) + 1))
+    finally:
+        rdb.close(), cdb.close()
+    if out is not None:
+        with open(out, "wb") as f:
+            f.write(fasta)
+        return len(fasta)
+    return fasta
 
 
 def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None):
