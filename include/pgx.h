@@ -62,7 +62,7 @@ void pgx_free(void *p);              /* releases any host array returned by this
 
 /* per-kernel device time (HIP events on the library's stream), accumulated since the last reset.
  * names: "sketch", "sketch_general", "sketch_redo", "sketch_nreads", "sketch_gather", "pack", "reduce", "count", "pairs", "replay_dense" / "replay_rows" / "replay_update" (k_eval, k_eval_rows, k_update of the device replay; only with PGX_REPLAY_TIMING=1), "align" (k_align_ph), "align1" (k_align1: launches of
- * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map", "sgraph" (the string graph: build and text; its parts also as "sgraph_edges", "sgraph_adj", "sgraph_tr", "sgraph_spur",
+ * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map", "sgraph" (the string graph: build and text; its parts also as "sgraph_edges", "sgraph_adj", "sgraph_tr", "sgraph_chimer", "sgraph_spur",
  * "sgraph_best", "sgraph_text"), "unitigs" (its parts: "unitigs_links", "unitigs_rank", "unitigs_paths", "unitigs_text"), "ctg_paths" (its parts:
  * "ctg_paths_graph", "ctg_paths_clean", "ctg_paths_walk", "ctg_paths_text"). */
 int pgx_timing_get(const char *kernel, double *total_ms, uint64_t *launches, uint64_t *units);
@@ -301,9 +301,9 @@ int pgx_dedup_graph_stats(pgx_dedup_stream *s, uint64_t *n_contained_reads, uint
  *   pgx_sgraph_build : on a graph-mode stream after its last feed.  Runs the stream's final compaction if no drain has run yet (feeds are
  *                      refused afterwards, as after a drain); the rows stay with the stream, which can still be drained or closed, before
  *                      or after pgx_sgraph_free: the graph owns its arrays.  PGX_ESTATE: a plain or failed stream, or one whose last
- *                      line was drained (the rows are gone).  PGX_EINVAL, with a message that says why: any bit of `flags` (the chimer
- *                      bridge step and --lfc are not offered: the first pops from a set of objects, so the script's own output changes
- *                      with the hash seed); more than 2^31 - 1 kept rows; a kept row with m_size == 0 (its identity prints as nan or
+ *                      line was drained (the rows are gone).  PGX_EINVAL, with a message that says why: any bit of `flags` but
+ *                      PGX_SGRAPH_CHIMER_ORDERED (the chimer bridge step as the script runs it and --lfc are not offered: the first pops
+ *                      from a set of objects, so the script's own output changes with the hash seed); more than 2^31 - 1 kept rows; a kept row with m_size == 0 (its identity prints as nan or
  *                      inf; the message names the row).  PGX_ENOMEM: no device memory -- the stream stays usable for pgx_dedup_drain.
  *                      A line whose first field is negative (a read id of 2^31 and more as rid0) would end the script's file; such rows
  *                      are built like any other here.
@@ -313,16 +313,36 @@ int pgx_dedup_graph_stats(pgx_dedup_stream *s, uint64_t *n_contained_reads, uint
  *                      *text malloc'd (pgx_free), *done != 0 with the last of them (at once for an empty graph).
  *   pgx_sgraph_free  : releases the graph (NULL is accepted).
  * PGX_SGRAPH_DEG_MAX (a test hook, read by every build): the most out-edges of a node whose transitive reduction runs from LDS tables
- * (default and maximum 256); nodes with more run the same pass on tables in HBM. */
-#define PGX_SGRAPH_CHIMER_BRIDGE 1u  /* ask for the chimer bridge step: refused */
-#define PGX_SGRAPH_LFC 2u            /* ask for --lfc: refused */
-enum { PGX_SGRAPH_G = 0, PGX_SGRAPH_TR = 1, PGX_SGRAPH_S = 2, PGX_SGRAPH_R = 3 };
+ * (default and maximum 256); nodes with more run the same pass on tables in HBM.
+ *
+ * PGX_SGRAPH_CHIMER_ORDERED: the script's chimer bridge step (mark_chimer_edges, :127-195 -- what the script does WITHOUT
+ * --disable_chimer_bridge_removal, which is how pg_run.py runs it) between the transitive reduction and the first spur pass, with one
+ * thing added to the script's algorithm: bfs_nodes (:107-125) pops from its pool the node with the smallest (rid as unsigned, end), B
+ * before E, where the script pops from a set of objects.  The result is one of the script's own possible answers, and the script's
+ * answer wherever the script has only one.  The rule: on the marks the reduction left, node n is a candidate iff some unreduced edge
+ * u -> n has a tail with at least 2 unreduced out-edges and some unreduced edge n -> x a head with at least 2 unreduced in-edges.
+ * With O the heads of all of n's out-edges and T the heads of all out-edges of the tails of n's in-edges, without n (edges in any
+ * state), n is chosen iff O and T are disjoint and so are the unions of flow(v, n) over O and over T; flow(s, n): A = pool = {s}; at
+ * most 4 times, while the pool is not empty, its smallest node p leaves it and every head w != n of p's out-edges that is not in A
+ * enters A, and the pool too if w has out-edges.  Every edge of a chosen node that the reduction left unreduced is reduced with type
+ * C, and so is its reverse; the later passes run on those marks.  A C edge prints `C`; pgx_sgraph_stats_t counts no C edges, so
+ * n_g + n_tr + n_s + n_r falls short of `edges` by their number.  Accepted alone: with bit 1 or 2 those bits' refusals win.
+ *   pgx_sgraph_chimer_stats : the step's counts; zeros for a graph built without the flag.
+ *   pgx_sgraph_chimer_nodes : the chimers_nodes file (:854-856) as *text (pgx_free), *len bytes: for every chosen node, in node creation
+ *                             order, its name and then its reverse end's, a line each.  The script's line order is that of a set of
+ *                             objects: only the sorted lines compare.  Empty without the flag.
+ * PGX_SGRAPH_CHIMER_LDS (a test hook, read by every build): the most nodes of a candidate's table in LDS (default and maximum 1024);
+ * candidates whose flows reach more run the same tests on tables in HBM. */
+#define PGX_SGRAPH_CHIMER_BRIDGE 1u   /* ask for the chimer bridge step as the script runs it (no single answer): refused */
+#define PGX_SGRAPH_LFC 2u             /* ask for --lfc: refused */
+#define PGX_SGRAPH_CHIMER_ORDERED 4u  /* the chimer bridge step with bfs_nodes' pool popped smallest (rid, end) first */
+enum { PGX_SGRAPH_G = 0, PGX_SGRAPH_TR = 1, PGX_SGRAPH_S = 2, PGX_SGRAPH_R = 3, PGX_SGRAPH_C = 4 };
 typedef struct {
   uint32_t v_rid, w_rid;     /* the edge leaves node (v_rid, v_end) and enters (w_rid, w_end) */
   uint32_t label_rid;
   int32_t sp, tp;            /* the label's coordinates; the edge's length is |sp - tp| */
   uint8_t v_end, w_end;      /* 0: B, 1: E */
-  uint8_t type;              /* PGX_SGRAPH_G .. _R */
+  uint8_t type;              /* PGX_SGRAPH_G .. _C */
   uint8_t pad;
   int64_t score;             /* m_size */
   int64_t idt_tenths;        /* identity in tenths, as the dedup line prints it */
@@ -340,6 +360,14 @@ int pgx_sgraph_stats(const pgx_sgraph *g, pgx_sgraph_stats_t *out);
 int pgx_sgraph_edges(const pgx_sgraph *g, uint64_t first, uint64_t n, pgx_sgraph_edge *out);
 int pgx_sgraph_text(pgx_sgraph *g, uint64_t max_lines, char **text, size_t *text_len, int *done);
 int pgx_sgraph_free(pgx_sgraph *g);
+typedef struct {
+  uint64_t candidates;   /* nodes the step tests */
+  uint64_t past_test1;   /* of them with O and T disjoint */
+  uint64_t chosen;       /* of those with disjoint flows: the chimer nodes */
+  uint64_t c_edges;      /* edges of type C */
+} pgx_sgraph_chimer_stats_t;
+int pgx_sgraph_chimer_stats(const pgx_sgraph *g, pgx_sgraph_chimer_stats_t *out);
+int pgx_sgraph_chimer_nodes(const pgx_sgraph *g, char **text, size_t *len);
 
 /* ---- unitigs (phase 1 of unitig construction in py/scripts/ovlp_to_graph.py: identify_simple_paths, :1033-1144): every maximal simple
  * path of the string graph's G edges as one unitig, and the `simple` lines of utg_data (:1478-1487).  Only edges of type G take part;

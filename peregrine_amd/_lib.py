@@ -133,7 +133,7 @@ EXPORTS = [
     "pgx_overlap_resident", "pgx_overlap_chunk", "pgx_index_chunk_db", "pgx_overlap_chunk_db", "pgx_overlap_chunk_db_begin", "pgx_output_finish", "pgx_index_overlap_resident", "pgx_mkseqdb", "pgx_dedup",
     "pgx_dedup_open", "pgx_dedup_feed", "pgx_dedup_feed_dev", "pgx_dedup_close",
     "pgx_dedup_open_graph", "pgx_dedup_drain", "pgx_dedup_graph_stats",
-    "pgx_sgraph_build", "pgx_sgraph_stats", "pgx_sgraph_edges", "pgx_sgraph_text", "pgx_sgraph_free",
+    "pgx_sgraph_build", "pgx_sgraph_stats", "pgx_sgraph_edges", "pgx_sgraph_text", "pgx_sgraph_free", "pgx_sgraph_chimer_stats", "pgx_sgraph_chimer_nodes",
     "pgx_sgraph_unitigs", "pgx_unitigs_build", "pgx_unitigs_stats", "pgx_unitigs_table", "pgx_unitigs_paths", "pgx_unitigs_text", "pgx_unitigs_free",
     "pgx_unitigs_contig_paths", "pgx_ctg_paths_build", "pgx_ctg_paths_stats", "pgx_ctg_paths_table", "pgx_ctg_paths_rows", "pgx_ctg_paths_utg_text", "pgx_ctg_paths_ctg_text", "pgx_ctg_paths_free",
     "pgx_sgraph_parse", "pgx_tiling_build", "pgx_tiling_stats", "pgx_tiling_rows", "pgx_tiling_names", "pgx_tiling_text", "pgx_tiling_contigs", "pgx_tiling_free", "pgx_tiling_chunk",
@@ -217,6 +217,8 @@ def load():
         lib.pgx_sgraph_edges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
         lib.pgx_sgraph_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_sgraph_free.argtypes = [C.c_void_p]
+        lib.pgx_sgraph_chimer_stats.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pgx_sgraph_chimer_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_sgraph_unitigs.argtypes = [C.c_void_p, C.c_void_p]
         lib.pgx_unitigs_build.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         lib.pgx_unitigs_stats.argtypes = [C.c_void_p, C.c_void_p]

@@ -395,6 +395,8 @@ struct sgraph_opts {
   double min_idt;
   const char *utg;   /* --utg FILE: the unitigs' lines go there (NULL: none are made) */
   const char *utg_data, *ctg_paths;   /* --utg-data FILE, --ctg-paths FILE: the final utg_data and ctg_paths (NULL: not written) */
+  int chimer_ordered;                 /* --chimer_bridge_ordered: PGX_SGRAPH_CHIMER_ORDERED */
+  const char *chimers_nodes;          /* --chimers-nodes FILE: the chimers_nodes file (NULL: not written) */
 };
 /* What every hand-out of text ends with: the status of the call `what` reported, or its text written to f (named fname in the
  * complaint); the text is freed either way.  Returns the exit code so far. */
@@ -448,6 +450,20 @@ static int write_unitigs(const char *tool, pgx_sgraph *g, const struct sgraph_op
   pgx_unitigs_free(u);
   return rc;
 }
+/* the chimers_nodes file of g to the file at path */
+static int write_chimers_nodes(const char *tool, const pgx_sgraph *g, const char *path) {
+  FILE *f = fopen(path, "wb");
+  if (!f) {
+    perror(path);
+    return 1;
+  }
+  char *text = NULL;
+  size_t len = 0;
+  const int status = pgx_sgraph_chimer_nodes(g, &text, &len);
+  int rc = put_text(tool, "pgx_sgraph_chimer_nodes", status, text, len, f, path);
+  if (fclose(f) && !rc) rc = 1, perror(path);
+  return rc;
+}
 static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg) {
   size_t piece = (size_t)16 << 20;
   const char *pe = getenv("PGX_DEDUP_PIECE");
@@ -491,8 +507,9 @@ static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg
     if (!more) break;
   }
   pgx_sgraph *g = NULL;
-  if (sg && ds && !rc && pgx_sgraph_build(ds, sg->min_len, sg->min_idt, 0, &g)) rc = fail(tool, "pgx_sgraph_build");
+  if (sg && ds && !rc && pgx_sgraph_build(ds, sg->min_len, sg->min_idt, sg->chimer_ordered ? PGX_SGRAPH_CHIMER_ORDERED : 0, &g)) rc = fail(tool, "pgx_sgraph_build");
   if (g) rc = write_pieces(tool, "pgx_sgraph_text", next_sgraph_text, g, piece, stdout, "stdout");
+  if (g && sg->chimers_nodes && !rc) rc = write_chimers_nodes(tool, g, sg->chimers_nodes);
   if (g && (sg->utg || sg->utg_data || sg->ctg_paths) && !rc) rc = write_unitigs(tool, g, sg, piece);
   pgx_sgraph_free(g);
   if (graph && !sg && ds && !rc) rc = write_pieces(tool, "pgx_dedup_drain", next_drain_text, ds, piece, stdout, "stdout");
@@ -508,9 +525,10 @@ static int main_dedup(int argc, char **argv) {
 }
 
 /* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
- * --disable_chimer_bridge_removal and without --lfc -- the only setting offered */
+ * --disable_chimer_bridge_removal and without --lfc; --chimer_bridge_ordered [--chimers-nodes FILE] runs the chimer bridge step too, under the
+ * stated pop order (pgx.h, PGX_SGRAPH_CHIMER_ORDERED) */
 static int main_sgraph(int argc, char **argv) {
-  struct sgraph_opts o = {4000, 96.0, NULL, NULL, NULL};
+  struct sgraph_opts o = {4000, 96.0, NULL, NULL, NULL, 0, NULL};
   for (int i = 1; i < argc; ++i) {
     const char *a = argv[i], *v = NULL;
     const int len_opt = strncmp(a, "--min_len", 9) == 0 && (a[9] == 0 || a[9] == '='), idt_opt = strncmp(a, "--min_idt", 9) == 0 && (a[9] == 0 || a[9] == '=');
@@ -537,19 +555,31 @@ static int main_sgraph(int argc, char **argv) {
         fprintf(stderr, "shmr_sgraph: %.*s needs a file name\n", (int)nl, a);
         return 2;
       }
+    } else if (strcmp(a, "--chimer_bridge_ordered") == 0) {
+      o.chimer_ordered = 1;
+    } else if (strncmp(a, "--chimers-nodes", 15) == 0 && (a[15] == 0 || a[15] == '=')) {
+      o.chimers_nodes = a[15] ? a + 16 : (i + 1 < argc ? argv[++i] : NULL);
+      if (!o.chimers_nodes || !*o.chimers_nodes) {
+        fprintf(stderr, "shmr_sgraph: --chimers-nodes needs a file name\n");
+        return 2;
+      }
     } else if (strcmp(a, "--lfc") == 0) {
       fprintf(stderr, "shmr_sgraph: --lfc is not offered (pg_run.py leaves it off)\n");
       return 2;
     } else if (strcmp(a, "--disable_chimer_bridge_removal") == 0) {
       /* what this tool always does */
     } else if (strcmp(a, "--chimer_bridge_removal") == 0) {
-      fprintf(stderr, "shmr_sgraph: the chimer bridge step is not offered (it pops from a set of objects: the script's own output changes with the hash seed); "
-                      "compare with ovlp_to_graph.py --disable_chimer_bridge_removal\n");
+      fprintf(stderr, "shmr_sgraph: the chimer bridge step as the script runs it is not offered (it pops from a set of objects: the script's own output changes "
+                      "with the hash seed); --chimer_bridge_ordered runs it under a stated pop order, or compare with ovlp_to_graph.py --disable_chimer_bridge_removal\n");
       return 2;
     } else {
-      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] < ovlp.dat > sg_edges_list\n");
+      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal | --chimer_bridge_ordered [--chimers-nodes FILE]] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] < ovlp.dat > sg_edges_list\n");
       return 2;
     }
+  }
+  if (o.chimers_nodes && !o.chimer_ordered) {
+    fprintf(stderr, "shmr_sgraph: --chimers-nodes needs --chimer_bridge_ordered\n");
+    return 2;
   }
   return dedup_stdin("shmr_sgraph", 1, &o);
 }

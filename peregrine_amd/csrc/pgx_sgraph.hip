@@ -1,6 +1,7 @@
 // pgx_sgraph.hip -- the string graph: what generate_string_graph of the reference (py/scripts/ovlp_to_graph.py:658-905) does with
 // disable_chimer_bridge_removal=True and lfc=False, on the rows a graph-mode dedup stream keeps in HBM (pgx_dedup.hip), down to the
-// sg_edges_list text.  What the kernels rely on ("string graph"):
+// sg_edges_list text; with PGX_SGRAPH_CHIMER_ORDERED also the chimer bridge step (mark_chimer_edges, :127-195) between the transitive
+// reduction and the first spur pass, with bfs_nodes' pool popped smallest (rid, end) first.  What the kernels rely on ("string graph"):
 //   * the stream's pairs are unique, so the loader's overlap_set rejects nothing and no add_edge meets an edge that exists;
 //   * a row that passes the filter and its geometry case adds exactly two edges, 2k and 2k + 1, each other's reverse (e ^ 1);
 //   * nodes are (rid, end) numbered in creation order -- only the spur pass depends on the numbering;
@@ -24,7 +25,7 @@ constexpr uint32_t FUZZ = 500;
 constexpr uint32_t DEG_CAP = 256;      // most out-edges of a node whose transitive reduction runs from LDS
 constexpr uint32_t TAB_SLOTS = 512;    // its neighbour table (open addressing, load <= 1/2)
 constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
-enum : uint8_t { T_G = PGX_SGRAPH_G, T_TR = PGX_SGRAPH_TR, T_S = PGX_SGRAPH_S, T_R = PGX_SGRAPH_R };
+enum : uint8_t { T_G = PGX_SGRAPH_G, T_TR = PGX_SGRAPH_TR, T_S = PGX_SGRAPH_S, T_R = PGX_SGRAPH_R, T_C = PGX_SGRAPH_C };
 
 // ---------------------------------------------------------------------------------------------------------
 // rows -> edges
@@ -283,6 +284,259 @@ __global__ __launch_bounds__(64) void k_sg_tr_global(const uint32_t *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// chimer bridge step (mark_chimer_edges, :127-195; PGX_SGRAPH_CHIMER_ORDERED).  It reads the marks as the transitive reduction left them
+// (only to find the candidates) and adjacency in any state; what it decides goes to a byte per candidate, and a kernel of its own marks
+// the chosen nodes' edges afterwards.  So a candidate's answer depends on no other candidate's, and the candidates run side by side:
+// one wavefront (a workgroup of 64) per candidate n.
+//   test 1   O = the heads of n's out-edges, T = the heads of the out-edges of the tails of n's in-edges, without n: O and T disjoint
+//   test 2   the union of flow(v, n) over O and the union over T are disjoint.  flow(s, n) is bfs_nodes with depth 5: A = pool = {s};
+//            at most 4 times the pool's smallest (rid as unsigned, end) leaves it and every head w != n of its out-edges that is not in
+//            A enters A, and the pool too if w has out-edges.  The pop order is this library's: the script pops from a set of objects.
+// One table node -> (generation << 2 | sides) serves both tests: side 1 = reached from O, side 2 = from T, generation = the flow that
+// saw the node last, so "w is in A" is "w's generation is this flow's" and the two unions meet where a node has both sides.  The pool
+// holds ranks in the (rid, end) order (krank), so a pop is a minimum.  Where the table lives is the policy: ChLds (a hash table of
+// CH_SLOTS in LDS; a candidate whose flows outgrow it is handed on) or ChGlobal (any size: the workgroup's own slice of an array in
+// HBM with an entry per node, valid where its upper half is the candidate's tag).
+// ---------------------------------------------------------------------------------------------------------
+// an edge's mark where other lanes or workgroups of the same kernel may be storing to it
+__device__ inline uint8_t type_now(const uint8_t *type, uint32_t e) { return __hip_atomic_load(&type[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline void type_set(uint8_t *type, uint32_t e, uint8_t t) { __hip_atomic_store(&type[e], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+constexpr uint32_t CH_SLOTS = 2048;           // ChLds: open addressing
+constexpr uint32_t CH_NODES = CH_SLOTS / 2;   // the most nodes it takes (load <= 1/2), and the pool's size: a flow's pool is part of its A
+enum : uint8_t { CH_CHOSEN = 1, CH_PAST1 = 2, CH_OVER = 4 };
+enum { FL_OK = 0, FL_MEET = 1, FL_FULL = 2 };
+
+// node keys (rid << 1 | end) by dense id (every edge of a node stores the same value), and the identity list for the sort by key
+__global__ void k_sg_node_keys(const uint32_t *__restrict__ node_of, const Edge *__restrict__ edges, uint32_t n_e, uint64_t *__restrict__ nkey,
+                               uint32_t *__restrict__ iota) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_e) return;
+  const Edge ed = edges[e];
+  const uint32_t v = node_of[2 * (size_t)e], w = node_of[2 * (size_t)e + 1];
+  nkey[v] = (uint64_t)ed.v_rid << 1 | ed.v_end, iota[v] = v;
+  nkey[w] = (uint64_t)ed.w_rid << 1 | ed.w_end, iota[w] = w;
+}
+__global__ void k_sg_kranks(const uint32_t *__restrict__ by_rank, uint32_t n_nodes, uint32_t *__restrict__ krank) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_nodes) krank[by_rank[i]] = i;
+}
+// multi[v]: bit 0 = at least 2 unreduced out-edges, bit 1 = at least 2 unreduced in-edges
+__global__ void k_sg_multi(uint32_t n_nodes, const uint32_t *__restrict__ out_off, const uint32_t *__restrict__ out_e, const uint32_t *__restrict__ in_off,
+                           const uint32_t *__restrict__ in_e, const uint8_t *__restrict__ type, uint8_t *__restrict__ multi) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_nodes) return;
+  uint32_t lo = 0, li = 0;   // (whole lists, no early exit: the counts are read after the loops)
+  for (uint32_t k = out_off[v]; k < out_off[v + 1]; ++k) lo += type[out_e[k]] == T_G;
+  for (uint32_t k = in_off[v]; k < in_off[v + 1]; ++k) li += type[in_e[k]] == T_G;
+  multi[v] = (uint8_t)((lo >= 2) | (li >= 2) << 1);
+}
+// a candidate: an unreduced in-edge from a node with 2 and more unreduced out-edges, and an unreduced out-edge into a node with 2 and more
+// unreduced in-edges (:129-154)
+__global__ void k_sg_chimer_cands(uint32_t n_nodes, const uint32_t *__restrict__ out_off, const uint32_t *__restrict__ out_e, const uint32_t *__restrict__ out_w,
+                                  const uint32_t *__restrict__ in_off, const uint32_t *__restrict__ in_e, const uint32_t *__restrict__ node_of,
+                                  const uint8_t *__restrict__ type, const uint8_t *__restrict__ multi, uint8_t *__restrict__ flag) {
+  const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= n_nodes) return;
+  uint32_t a = 0, b = 0;
+  for (uint32_t k = in_off[n]; k < in_off[n + 1]; ++k) a += type[in_e[k]] == T_G && (multi[node_of[2 * (size_t)in_e[k]]] & 1);
+  for (uint32_t k = out_off[n]; k < out_off[n + 1]; ++k) b += type[out_e[k]] == T_G && (multi[out_w[k]] & 2);
+  flag[n] = a != 0 && b != 0;
+}
+
+struct ChLds {
+  uint32_t *tkey;   // CH_SLOTS node ids, ~0 = empty
+  uint32_t *tval;   // generation << 2 | sides
+  uint32_t *pool;   // CH_NODES
+  uint32_t lim;     // the most nodes the table may take (PGX_SGRAPH_CHIMER_LDS; <= CH_NODES)
+  uint32_t cnt;     // nodes in it (the same in every lane)
+  __device__ void reset(uint32_t lane) {
+    for (uint32_t s = lane; s < CH_SLOTS; s += 64) tkey[s] = ~0u;
+    cnt = 0;
+    __syncthreads();
+  }
+  __device__ bool room(uint32_t need) const { return cnt + need <= lim; }
+  __device__ void grew(uint32_t k) { cnt += k; }
+  __device__ static uint32_t home(uint32_t x) { return (x * 0x9E3779B1u) >> 21; }   // (top 11 bits: CH_SLOTS == 2048)
+  __device__ uint32_t claim(uint32_t x, bool &fresh) {   // x's slot, made if there is none (room() said there is space)
+    for (uint32_t s = home(x);; s = (s + 1) & (CH_SLOTS - 1)) {
+      const uint32_t k = atomicCAS(&tkey[s], ~0u, x);
+      if (k == ~0u || k == x) {
+        fresh = k == ~0u;
+        return s;
+      }
+    }
+  }
+  __device__ bool has(uint32_t x) const {
+    for (uint32_t s = home(x);; s = (s + 1) & (CH_SLOTS - 1)) {
+      const uint32_t k = tkey[s];
+      if (k == x) return true;
+      if (k == ~0u) return false;
+    }
+  }
+  __device__ uint32_t get(uint32_t s) const { return tval[s]; }
+  __device__ void set(uint32_t s, uint32_t v) { tval[s] = v; }
+  __device__ uint32_t pool_get(uint32_t i) const { return pool[i]; }
+  __device__ void pool_set(uint32_t i, uint32_t v) { pool[i] = v; }
+};
+static_assert(CH_SLOTS == 2048, "the table's hash takes the top 11 bits");
+struct ChGlobal {
+  uint64_t *tab;    // an entry per node: tag << 32 | generation << 2 | sides (zero before the launch; a tag is never 0)
+  uint32_t *pool;   // 4 * the largest out-degree + 1
+  uint64_t tag;     // the candidate's, in the upper half
+  // (device-scope accesses, as NbGlobal's: what a lane wrote before the barrier is what every lane reads after it)
+  __device__ uint64_t ld(uint32_t x) const { return __hip_atomic_load(&tab[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ void reset(uint32_t) {}
+  __device__ bool room(uint32_t) const { return true; }
+  __device__ void grew(uint32_t) {}
+  __device__ uint32_t claim(uint32_t x, bool &fresh) {   // (the caller sets a fresh entry at once)
+    fresh = (ld(x) & 0xFFFFFFFF00000000ULL) != tag;
+    return x;
+  }
+  __device__ bool has(uint32_t x) const { return (ld(x) & 0xFFFFFFFF00000000ULL) == tag; }
+  __device__ uint32_t get(uint32_t s) const { return (uint32_t)ld(s); }
+  __device__ void set(uint32_t s, uint32_t v) { __hip_atomic_store(&tab[s], tag | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ uint32_t pool_get(uint32_t i) const { return __hip_atomic_load(&pool[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ void pool_set(uint32_t i, uint32_t v) { __hip_atomic_store(&pool[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+struct ChGraph {   // what the tests read: adjacency in any state, and the (rid, end) order
+  const uint32_t *out_off, *out_w, *in_off, *in_e, *node_of, *krank, *by_rank;
+};
+// one step of a flow: the active lanes' nodes (all different: a node's out-edges have different heads) enter A unless they are in it,
+// and the pool if they have out-edges (the start node: always)
+template <class Tab>
+__device__ inline int flow_add(Tab &tab, const ChGraph &G, bool active, uint32_t w, uint32_t side, uint32_t gen, bool start, uint32_t &pool_n, uint32_t lane) {
+  if (!tab.room((uint32_t)__popcll(__ballot(active)))) return FL_FULL;
+  bool fresh = false, push = false, meet = false;
+  if (active) {
+    const uint32_t s = tab.claim(w, fresh), v = fresh ? 0u : tab.get(s);
+    if (fresh || (v >> 2) != gen) {
+      const uint32_t nv = gen << 2 | (v & 3u) | side;
+      tab.set(s, nv);
+      meet = (nv & 3u) == 3u;
+      push = start || G.out_off[w + 1] != G.out_off[w];
+    }
+  }
+  tab.grew((uint32_t)__popcll(__ballot(fresh)));
+  const uint64_t pb = __ballot(push);
+  if (push) tab.pool_set(pool_n + (uint32_t)__popcll(pb & ((1ULL << lane) - 1)), G.krank[w]);
+  pool_n += (uint32_t)__popcll(pb);
+  __syncthreads();
+  return __ballot(meet) ? FL_MEET : FL_OK;
+}
+// the pool's smallest rank leaves it; ~0: the pool is empty.  (The ranks in a pool are all different, so one lane holds the minimum.)
+template <class Tab>
+__device__ inline uint32_t pool_pop(Tab &tab, uint32_t pool_n, uint32_t lane) {
+  uint32_t best = ~0u, at = 0;
+  for (uint32_t i = lane; i < pool_n; i += 64) {
+    const uint32_t r = tab.pool_get(i);
+    if (r < best) best = r, at = i;
+  }
+  uint32_t mn = best;
+  for (int s = 32; s; s >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, s));
+  if (mn != ~0u && best == mn) tab.pool_set(at, ~0u);
+  __syncthreads();
+  return mn;
+}
+// flow(s, n) into the table as generation gen of `side`; FL_MEET as soon as a node has both sides (the answer is then known)
+template <class Tab>
+__device__ inline int flow(Tab &tab, const ChGraph &G, uint32_t s, uint32_t n, uint32_t side, uint32_t gen, uint32_t lane) {
+  uint32_t pool_n = 0;
+  int r = flow_add(tab, G, lane == 0, s, side, gen, true, pool_n, lane);
+  for (int pop = 0; pop < 4 && r == FL_OK; ++pop) {
+    const uint32_t mn = pool_pop(tab, pool_n, lane);
+    if (mn == ~0u) break;
+    const uint32_t p = G.by_rank[mn], po = G.out_off[p], pd = G.out_off[p + 1] - po;
+    for (uint32_t k0 = 0; k0 < pd && r == FL_OK; k0 += 64) {
+      const uint32_t k = k0 + lane, w = k < pd ? G.out_w[po + k] : n;
+      r = flow_add(tab, G, w != n, w, side, gen, false, pool_n, lane);
+    }
+  }
+  return r;
+}
+// the two tests of candidate n: CH_PAST1 / CH_CHOSEN, or CH_OVER alone where the table is full (every branch is wave-uniform)
+template <class Tab>
+__device__ inline uint8_t chimer_node(Tab &tab, const ChGraph &G, uint32_t n, uint32_t lane) {
+  tab.reset(lane);
+  const uint32_t no = G.out_off[n], nd = G.out_off[n + 1] - no, io = G.in_off[n], id = G.in_off[n + 1] - io;
+  for (uint32_t k0 = 0; k0 < nd; k0 += 64) {   // O, as side 1 of generation 0 (no flow's)
+    const uint32_t k = k0 + lane;
+    if (!tab.room((uint32_t)__popcll(__ballot(k < nd)))) return CH_OVER;
+    bool fresh = false;
+    if (k < nd) tab.set(tab.claim(G.out_w[no + k], fresh), 1u);
+    tab.grew((uint32_t)__popcll(__ballot(fresh)));
+  }
+  __syncthreads();
+  for (uint32_t i = 0; i < id; ++i) {   // test 1: no member of T is in the table
+    const uint32_t u = G.node_of[2 * (size_t)G.in_e[io + i]], uo = G.out_off[u], ud = G.out_off[u + 1] - uo;
+    bool hit = false;
+    for (uint32_t k = lane; k < ud; k += 64) {
+      const uint32_t w = G.out_w[uo + k];
+      hit |= w != n && tab.has(w);
+    }
+    if (__ballot(hit)) return 0;
+  }
+  uint32_t gen = 0;   // (at most one flow per edge: below 2^30)
+  for (uint32_t k = 0; k < nd; ++k) {
+    const int r = flow(tab, G, G.out_w[no + k], n, 1u, ++gen, lane);
+    if (r != FL_OK) return r == FL_FULL ? CH_OVER : CH_PAST1;
+  }
+  for (uint32_t i = 0; i < id; ++i) {
+    const uint32_t u = G.node_of[2 * (size_t)G.in_e[io + i]], uo = G.out_off[u], ud = G.out_off[u + 1] - uo;
+    for (uint32_t k = 0; k < ud; ++k) {
+      const uint32_t w = G.out_w[uo + k];
+      if (w == n) continue;
+      const int r = flow(tab, G, w, n, 2u, ++gen, lane);   // (a member of T that two tails share runs twice, to the same end)
+      if (r != FL_OK) return r == FL_FULL ? CH_OVER : CH_PAST1;
+    }
+  }
+  return CH_PAST1 | CH_CHOSEN;
+}
+// every candidate, a workgroup per candidate, grid-stride
+__global__ __launch_bounds__(64) void k_sg_chimer_lds(const uint32_t *__restrict__ cand, uint32_t n_cand, uint32_t lim, ChGraph G, uint8_t *__restrict__ res) {
+  __shared__ uint32_t tkey[CH_SLOTS], tval[CH_SLOTS], pool[CH_NODES];
+  ChLds tab{tkey, tval, pool, lim, 0};
+  for (uint32_t q = blockIdx.x; q < n_cand; q += gridDim.x) {
+    const uint8_t r = chimer_node(tab, G, cand[q], threadIdx.x);
+    if (threadIdx.x == 0) res[q] = r;
+    __syncthreads();   // the tables are reused by the workgroup's next candidate
+  }
+}
+// the listed candidates (their flows outgrew the LDS table), on the workgroup's slices of tabs and pools
+__global__ __launch_bounds__(64) void k_sg_chimer_global(const uint32_t *__restrict__ cand, const uint32_t *__restrict__ list, uint32_t n_list, ChGraph G,
+                                                         uint64_t *__restrict__ tabs, uint32_t n_nodes, uint32_t *__restrict__ pools, uint32_t pool_size,
+                                                         uint8_t *__restrict__ res) {
+  for (uint32_t j = blockIdx.x; j < n_list; j += gridDim.x) {
+    const uint32_t q = list[j];
+    ChGlobal tab{tabs + (size_t)blockIdx.x * n_nodes, pools + (size_t)blockIdx.x * pool_size, (uint64_t)(q + 1) << 32};
+    const uint8_t r = chimer_node(tab, G, cand[q], threadIdx.x);
+    if (threadIdx.x == 0) res[q] = r;
+    __syncthreads();
+  }
+}
+// flag[q] = res[q] has `bit`; cnt[0] += the candidates past test 1 (bit == CH_CHOSEN only: the last call)
+__global__ void k_sg_chimer_flags(const uint8_t *__restrict__ res, uint32_t n, uint8_t bit, uint8_t *__restrict__ flag, uint32_t *__restrict__ cnt) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint8_t r = q < n ? res[q] : 0;
+  if (q < n) flag[q] = (r & bit) != 0;
+  const uint64_t b = __ballot(bit == CH_CHOSEN && (r & CH_PAST1));
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(cnt, (uint32_t)__popcll(b));
+}
+// the chosen nodes' keys, and their edges that the reduction left unreduced become C, each with its reverse (:173-193; a thread per node.
+// An edge reads G or, where another chosen node got there first, C: both end as C.  TR stays.)
+__global__ void k_sg_chimer_mark(const uint32_t *__restrict__ cand, const uint32_t *__restrict__ chosen, uint32_t n_chosen, const uint64_t *__restrict__ nkey,
+                                 const uint32_t *__restrict__ out_off, const uint32_t *__restrict__ out_e, const uint32_t *__restrict__ in_off,
+                                 const uint32_t *__restrict__ in_e, uint8_t *type, uint64_t *__restrict__ ckey) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_chosen) return;
+  const uint32_t n = cand[chosen[j]];
+  ckey[j] = nkey[n];
+  for (uint32_t k = out_off[n]; k < out_off[n + 1]; ++k)
+    if (type_now(type, out_e[k]) != T_TR) type_set(type, out_e[k], T_C), type_set(type, out_e[k] ^ 1u, T_C);
+  for (uint32_t k = in_off[n]; k < in_off[n + 1]; ++k)
+    if (type_now(type, in_e[k]) != T_TR) type_set(type, in_e[k], T_C), type_set(type, in_e[k] ^ 1u, T_C);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // spur pass, best overlap
 // ---------------------------------------------------------------------------------------------------------
 // a node the spur pass can act on: an out-edge into a node without out-edges, or an in-edge from a node without in-edges (the degrees
@@ -299,8 +553,6 @@ __global__ void k_sg_spur_flags(uint32_t n_nodes, const uint32_t *__restrict__ o
   }
   flag[v] = c;
 }
-__device__ inline uint8_t type_now(const uint8_t *type, uint32_t e) { return __hip_atomic_load(&type[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void type_set(uint8_t *type, uint32_t e, uint8_t t) { __hip_atomic_store(&type[e], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // one side of mark_spur_edge at node v: with more than one unreduced edge in the list, every unreduced one whose far node is a dead end
 // goes, with its reverse.  far_off: the far node's degree table (out-degrees for the out side, in-degrees for the in side).
 __device__ inline void spur_side(const uint32_t *__restrict__ lst, uint32_t d, uint32_t far_slot, const uint32_t *__restrict__ node_of,
@@ -357,7 +609,7 @@ __global__ void k_sg_finish(Edge *__restrict__ edges, const uint8_t *__restrict_
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   const uint8_t t = e < n_e ? type[e] : 0xFF;
   if (e < n_e) edges[e].type = t;
-  for (uint8_t q = 0; q < 4; ++q) {
+  for (uint8_t q = 0; q < 5; ++q) {   // (by_type[4]: the C edges)
     const uint64_t b = __ballot(t == q);
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(&by_type[q], (uint32_t)__popcll(b));
   }
@@ -386,7 +638,7 @@ __device__ inline uint32_t format_edge(const Edge &e, char *dst) {
   o.ch(' ');
   if (e.type == T_G) o.ch('G');
   else if (e.type == T_TR) o.ch('T'), o.ch('R');
-  else o.ch(e.type == T_S ? 'S' : 'R');
+  else o.ch(e.type == T_S ? 'S' : e.type == T_R ? 'R' : 'C');
   o.ch('\n');
   return o.n;
 }
@@ -414,6 +666,8 @@ using namespace pgx;
 struct pgx_sgraph {
   DevBuf<Edge> edges;            // creation order, types final (MemTag "sgraph")
   pgx_sgraph_stats_t st = {};
+  pgx_sgraph_chimer_stats_t ch = {};   // zeros without PGX_SGRAPH_CHIMER_ORDERED
+  std::vector<uint64_t> chimers;       // the chosen nodes' keys (rid << 1 | end) in creation order
   uint64_t cursor = 0;           // edges handed out as text
   TextStage stage;
   bool shut = false;             // pgx_shutdown ran: the device state is gone
@@ -434,17 +688,73 @@ uint32_t deg_cap() {   // PGX_SGRAPH_DEG_MAX: a test hook that shrinks the LDS p
   return (uint32_t)std::min<long>(std::max<long>(c, 0), (long)DEG_CAP);
 }
 
+uint32_t chimer_lds() {   // PGX_SGRAPH_CHIMER_LDS: a test hook that shrinks the LDS table of the chimer bridge step, as PGX_SGRAPH_DEG_MAX does
+  const char *v = getenv("PGX_SGRAPH_CHIMER_LDS");
+  const long c = v ? atol(v) : (long)CH_NODES;
+  return (uint32_t)std::min<long>(std::max<long>(c, 0), (long)CH_NODES);
+}
+
+// the chimer bridge step on the marks the transitive reduction left in `type`; fills g->ch and g->chimers.  The host learns three
+// counts (candidates, candidates beyond the LDS table, chosen nodes) and the chosen nodes' keys: no round trip per candidate.
+void chimer_pass(pgx_sgraph *g, uint32_t n_nodes, uint32_t n_e, uint32_t max_deg, const Edge *edges, const uint32_t *node_of, const uint32_t *out_off,
+                 const uint32_t *out_e, const uint32_t *out_w, const uint32_t *in_off, const uint32_t *in_e, uint8_t *type, uint32_t *d_past1, PrimWs *tmp) {
+  hipStream_t st = ctx().stream;
+  DevBuf<uint8_t> multi(n_nodes), flag(n_nodes);
+  DevBuf<uint32_t> cand(n_nodes);
+  LAUNCH(k_sg_multi, n_nodes, n_nodes, out_off, out_e, in_off, in_e, type, multi.p);
+  LAUNCH(k_sg_chimer_cands, n_nodes, n_nodes, out_off, out_e, out_w, in_off, in_e, node_of, type, multi.p, flag.p);
+  const uint32_t n_cand = select_indices(flag.p, n_nodes, cand.p, tmp);
+  g->ch.candidates = n_cand;
+  if (n_cand == 0) return;
+  multi.release();
+  // ---- the (rid, end) order: by_rank[i] = the node with the i-th smallest key, krank its inverse
+  DevBuf<uint64_t> nkey(n_nodes), nkey_s(n_nodes);
+  DevBuf<uint32_t> iota(n_nodes), by_rank(n_nodes), krank(n_nodes);
+  LAUNCH(k_sg_node_keys, n_e, node_of, edges, n_e, nkey.p, iota.p);
+  sort_pairs(nkey.p, nkey_s.p, iota.p, by_rank.p, n_nodes, 0, 33, tmp);
+  LAUNCH(k_sg_kranks, n_nodes, by_rank.p, n_nodes, krank.p);
+  nkey_s.release(), iota.release();
+  // ---- the tests
+  const ChGraph G{out_off, out_w, in_off, in_e, node_of, krank.p, by_rank.p};
+  DevBuf<uint8_t> res(n_cand);
+  DevBuf<uint32_t> list(n_cand);
+  hipLaunchKernelGGL(k_sg_chimer_lds, dim3(std::min<uint32_t>(n_cand, (uint32_t)ctx().num_cu * 32u)), dim3(64), 0, st, cand.p, n_cand, chimer_lds(), G, res.p);
+  LAUNCH(k_sg_chimer_flags, n_cand, res.p, n_cand, (uint8_t)CH_OVER, flag.p, d_past1);
+  const uint32_t n_over = select_indices(flag.p, n_cand, list.p, tmp);
+  if (n_over) {   // a table with an entry per node for each workgroup: as many workgroups as 1 GiB of tables allows
+    const uint32_t wgs = (uint32_t)std::min<uint64_t>({(uint64_t)n_over, 64, std::max<uint64_t>(1, (1ULL << 27) / n_nodes)});
+    const uint32_t pool_size = 4 * max_deg + 1;
+    DevBuf<uint64_t> tabs((size_t)wgs * n_nodes);
+    DevBuf<uint32_t> pools((size_t)wgs * pool_size);
+    PGX_HIP(hipMemsetAsync(tabs.p, 0, (size_t)wgs * n_nodes * sizeof(uint64_t), st));
+    hipLaunchKernelGGL(k_sg_chimer_global, dim3(wgs), dim3(64), 0, st, cand.p, list.p, n_over, G, tabs.p, n_nodes, pools.p, pool_size, res.p);
+    PGX_HIP(hipGetLastError());
+    pgx::sync();   // (the tables go back behind the kernel)
+  }
+  // ---- the chosen nodes in creation order, their edges
+  LAUNCH(k_sg_chimer_flags, n_cand, res.p, n_cand, (uint8_t)CH_CHOSEN, flag.p, d_past1);
+  const uint32_t n_chosen = select_indices(flag.p, n_cand, list.p, tmp);
+  g->ch.chosen = n_chosen;
+  if (n_chosen == 0) return;
+  DevBuf<uint64_t> ckey(n_chosen);
+  LAUNCH(k_sg_chimer_mark, n_chosen, cand.p, list.p, n_chosen, nkey.p, out_off, out_e, in_off, in_e, type, ckey.p);
+  PGX_HIP(hipGetLastError());
+  g->chimers.resize(n_chosen);
+  ckey.download(g->chimers.data(), n_chosen);
+  pgx::sync();
+}
+
 // the passes over n_rows rows at d_rows; fills g
-void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min_idt, pgx_sgraph *g) {
+void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min_idt, bool chimer, pgx_sgraph *g) {
   hipStream_t st = ctx().stream;
   MemTag tag("sgraph");
   PrimWs tmp;
   g->st.rows_in = n_rows;
   if (n_rows == 0) return;
-  // ---- filter and geometry (the parts are timed one by one as well: "sgraph_edges", "_adj", "_tr", "_spur", "_best")
+  // ---- filter and geometry (the parts are timed one by one as well: "sgraph_edges", "_adj", "_tr", "_chimer", "_spur", "_best")
   std::unique_ptr<KernelTimer> part(new KernelTimer("sgraph_edges", n_rows));
-  DevBuf<uint32_t> cnt(8);   // [0] rows past the filter, [1] first row that cannot be built, [2] largest out-degree, [4 .. 8) edges by type
-  PGX_HIP(hipMemsetAsync(cnt.p, 0, 8 * sizeof(uint32_t), st));
+  DevBuf<uint32_t> cnt(12);   // [0] rows past the filter, [1] first row that cannot be built, [2] largest out-degree, [4 .. 9) edges by type, [9] candidates past test 1
+  PGX_HIP(hipMemsetAsync(cnt.p, 0, 12 * sizeof(uint32_t), st));
   PGX_HIP(hipMemsetAsync(cnt.p + 1, 0xFF, sizeof(uint32_t), st));
   DevBuf<uint8_t> flag(n_rows);
   DevBuf<uint32_t> sel(n_rows);
@@ -524,6 +834,11 @@ void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min
     pgx::sync();   // (big and marks go back to the block cache behind the kernel anyway: one stream)
   }
   vw_key.release(), vw_pos.release();
+  // ---- chimer bridge step
+  if (chimer) {
+    part.reset(), part.reset(new KernelTimer("sgraph_chimer", n_e));
+    chimer_pass(g, n_nodes, n_e, max_deg, edges, node_of.p, out_off.p, out_e.p, out_w.p, in_off.p, in_e.p, type.p, cnt.p + 9, &tmp);
+  }
   // ---- spur, best overlap, spur
   part.reset(), part.reset(new KernelTimer("sgraph_spur", n_e));
   DevBuf<uint32_t> cand(n_nodes);
@@ -539,11 +854,12 @@ void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min
   part.reset();
   LAUNCH(k_sg_finish, n_e, edges, type.p, n_e, cnt.p + 4);
   PGX_HIP(hipGetLastError());
-  uint32_t by_type[4];
+  uint32_t by_type[6];   // ([5]: the candidates past test 1)
   PGX_HIP(hipMemcpyAsync(by_type, cnt.p + 4, sizeof(by_type), hipMemcpyDeviceToHost, st));
   pgx::sync();
   g->st.edges = n_e, g->st.nodes = n_nodes, g->st.max_out_degree = max_deg, g->st.spur_candidates = n_cand;
   g->st.n_g = by_type[T_G], g->st.n_tr = by_type[T_TR], g->st.n_s = by_type[T_S], g->st.n_r = by_type[T_R];
+  g->ch.c_edges = by_type[T_C], g->ch.past_test1 = by_type[5];
 }
 
 void require_graph(const pgx_sgraph *g, const char *who) {
@@ -566,10 +882,11 @@ extern "C" int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min
     PGX_REQUIRE(s->graph, PGX_ESTATE, "pgx_sgraph_build: not a graph-mode stream (pgx_dedup_open_graph)");
     PGX_REQUIRE(!s->released, PGX_ESTATE, "pgx_sgraph_build: the stream's last line was drained: its rows are gone");
     PGX_REQUIRE(!(flags & PGX_SGRAPH_CHIMER_BRIDGE), PGX_EINVAL,
-                "pgx_sgraph_build: the chimer bridge step is not offered (it pops from a set of objects: the script's own output changes with the hash "
-                "seed); run ovlp_to_graph.py with --disable_chimer_bridge_removal to compare");
+                "pgx_sgraph_build: the chimer bridge step as the script runs it is not offered (it pops from a set of objects: the script's own output "
+                "changes with the hash seed); PGX_SGRAPH_CHIMER_ORDERED runs the step with a stated pop order, or run ovlp_to_graph.py with "
+                "--disable_chimer_bridge_removal to compare");
     PGX_REQUIRE(!(flags & PGX_SGRAPH_LFC), PGX_EINVAL, "pgx_sgraph_build: --lfc is not offered (pg_run.py leaves it off)");
-    PGX_REQUIRE(flags == 0, PGX_EINVAL, "pgx_sgraph_build: unknown flag bits 0x%x", flags);
+    PGX_REQUIRE((flags & ~PGX_SGRAPH_CHIMER_ORDERED) == 0, PGX_EINVAL, "pgx_sgraph_build: unknown flag bits 0x%x", flags & ~PGX_SGRAPH_CHIMER_ORDERED);
     PGX_REQUIRE(!(min_idt != min_idt), PGX_EARG, "pgx_sgraph_build: min_idt is not a number");
   };
   // (after a failure the stream is untouched: pgx_dedup_drain still has its rows)
@@ -577,7 +894,7 @@ extern "C" int pgx_sgraph_build(pgx_dedup_stream *s, int64_t min_len, double min
     KernelTimer tm("sgraph", *n = s->store_n);
     if (!s->draining) graph_compact(s), *n = s->store_n;
     PGX_REQUIRE(s->store_n <= (uint64_t)INT32_MAX, PGX_EINVAL, "pgx_sgraph_build: %llu kept rows, more than 2^31 - 1", (unsigned long long)s->store_n);
-    build_graph(s->store.p, (uint32_t)s->store_n, min_len, min_idt, g);
+    build_graph(s->store.p, (uint32_t)s->store_n, min_len, min_idt, (flags & PGX_SGRAPH_CHIMER_ORDERED) != 0, g);
   }, "graph", "rows");
 }
 
@@ -585,6 +902,29 @@ extern "C" int pgx_sgraph_stats(const pgx_sgraph *g, pgx_sgraph_stats_t *out) {
   return guarded([&] {
     PGX_REQUIRE(g && out, PGX_EARG, "pgx_sgraph_stats: null argument");
     *out = g->st;
+  });
+}
+
+extern "C" int pgx_sgraph_chimer_stats(const pgx_sgraph *g, pgx_sgraph_chimer_stats_t *out) {
+  return guarded([&] {
+    PGX_REQUIRE(g && out, PGX_EARG, "pgx_sgraph_chimer_stats: null argument");
+    *out = g->ch;
+  });
+}
+
+// the chimers_nodes file (:854-856): a chosen node's name, then its reverse end's; formatted on the host from the keys the build kept
+extern "C" int pgx_sgraph_chimer_nodes(const pgx_sgraph *g, char **text, size_t *len) {
+  return text_call(text, len, nullptr, [&] {
+    PGX_REQUIRE(g && text && len, PGX_EARG, "pgx_sgraph_chimer_nodes: null argument");
+    std::string s;
+    char line[32];
+    for (const uint64_t key : g->chimers)
+      for (const uint64_t k : {key, key ^ 1u}) {
+        snprintf(line, sizeof line, "%09d:%c\n", (int)(int32_t)(uint32_t)(k >> 1), (k & 1) ? 'E' : 'B');
+        s += line;
+      }
+    *text = caller_text(s.data(), s.size());
+    *len = s.size();
   });
 }
 

@@ -368,11 +368,15 @@ class DedupStream:
         _lib.check(self._lib.pgx_dedup_graph_stats(self._handle("pgx_dedup_graph_stats"), C.byref(nc), C.byref(nk), C.byref(nt)), "pgx_dedup_graph_stats")
         return dict(contained_reads=int(nc.value), lines_kept=int(nk.value), lines_total=int(nt.value))
 
-    def string_graph(self, min_len: int = 4000, min_idt: float = 96.0, chimer_bridge_removal: bool = False, lfc: bool = False) -> "StringGraph":
+    def string_graph(self, min_len: int = 4000, min_idt: float = 96.0, chimer_bridge_removal: bool = False, lfc: bool = False,
+                     chimer_ordered: bool = False) -> "StringGraph":
         """graph_ready streams, after the last feed: the string graph of the kept lines (pgx_sgraph_build), what ovlp_to_graph.py's
-        generate_string_graph builds with --disable_chimer_bridge_removal and without --lfc.  Either option set is refused, not approximated.
-        The stream can still be drained or closed; feeds are refused afterwards, as after a drain."""
-        flags = (SGRAPH_CHIMER_BRIDGE if chimer_bridge_removal else 0) | (SGRAPH_LFC if lfc else 0)
+        generate_string_graph builds with --disable_chimer_bridge_removal and without --lfc.  chimer_ordered runs the script's chimer
+        bridge step too, with bfs_nodes' pool popped smallest (rid, end) first (SGRAPH_CHIMER_ORDERED): one of the script's own possible
+        answers, and the script's answer wherever it has only one.  chimer_bridge_removal (the step as the script runs it, which has no
+        single answer) and lfc are refused, not approximated.  The stream can still be drained or closed; feeds are refused afterwards,
+        as after a drain."""
+        flags = (SGRAPH_CHIMER_BRIDGE if chimer_bridge_removal else 0) | (SGRAPH_LFC if lfc else 0) | (SGRAPH_CHIMER_ORDERED if chimer_ordered else 0)
         g = C.c_void_p()
         _lib.check(self._lib.pgx_sgraph_build(self._handle("pgx_sgraph_build"), int(min_len), float(min_idt), flags, C.byref(g)), "pgx_sgraph_build")
         return StringGraph(g)
@@ -401,9 +405,11 @@ class DedupStream:
 
 
 SGRAPH_CHIMER_BRIDGE, SGRAPH_LFC = 1, 2   # pgx_sgraph_build's flags: both are refused
+SGRAPH_CHIMER_ORDERED = 4                 # the chimer bridge step under the stated pop order
 SGRAPH_EDGE_DTYPE = np.dtype([("v_rid", "<u4"), ("w_rid", "<u4"), ("label_rid", "<u4"), ("sp", "<i4"), ("tp", "<i4"), ("v_end", "u1"), ("w_end", "u1"),
                               ("type", "u1"), ("pad", "u1"), ("score", "<i8"), ("idt_tenths", "<i8")])   # pgx_sgraph_edge
-SGRAPH_TYPES = ("G", "TR", "S", "R")
+SGRAPH_TYPES = ("G", "TR", "S", "R", "C")
+_SGRAPH_CHIMER_STATS = ("candidates", "past_test1", "chosen", "c_edges")   # pgx_sgraph_chimer_stats_t
 _SGRAPH_STATS = ("rows_in", "rows_pass", "edges", "nodes", "n_g", "n_tr", "n_s", "n_r", "max_out_degree", "spur_candidates")
 
 
@@ -463,11 +469,30 @@ class StringGraph(_DeviceText):
     _STATS, _CLOSED = _SGRAPH_STATS, "the graph is closed"
 
     def edges(self, first: int = 0, n: int | None = None) -> np.ndarray:
-        """edge records (SGRAPH_EDGE_DTYPE) in creation order: edge e's reverse is e ^ 1; `type` indexes SGRAPH_TYPES"""
+        """edge records (SGRAPH_EDGE_DTYPE) in creation order: edge e's reverse is e ^ 1; `type` indexes SGRAPH_TYPES (C only in a graph
+        built with chimer_ordered; `stats` counts no C edges)"""
         n = self.stats["edges"] - first if n is None else n
         out = np.zeros(n, SGRAPH_EDGE_DTYPE)
         _lib.check(self._lib.pgx_sgraph_edges(self._handle("pgx_sgraph_edges"), int(first), int(n), _ptr(out)), "pgx_sgraph_edges")
         return out
+
+    @property
+    def chimer_stats(self) -> dict:
+        """the chimer bridge step's counts (pgx_sgraph_chimer_stats): candidates, of them past test 1, chosen nodes, C edges; zeros for a
+        graph built without chimer_ordered"""
+        st = (C.c_uint64 * len(_SGRAPH_CHIMER_STATS))()
+        _lib.check(self._lib.pgx_sgraph_chimer_stats(self._handle("pgx_sgraph_chimer_stats"), st), "pgx_sgraph_chimer_stats")
+        return dict(zip(_SGRAPH_CHIMER_STATS, (int(v) for v in st)))
+
+    def chimers_nodes(self) -> bytes:
+        """the chimers_nodes file (pgx_sgraph_chimer_nodes): for every chosen node, in node creation order, its name and then its reverse
+        end's, a line each (the script's line order is a set's: compare the sorted lines)"""
+        text, n = C.c_void_p(), C.c_size_t(0)
+        _lib.check(self._lib.pgx_sgraph_chimer_nodes(self._handle("pgx_sgraph_chimer_nodes"), C.byref(text), C.byref(n)), "pgx_sgraph_chimer_nodes")
+        try:
+            return C.string_at(text.value, n.value) if n.value else b""
+        finally:
+            self._lib.pgx_free(text)
 
     def unitigs(self) -> "Unitigs":
         """the maximal simple paths of the graph's G edges (pgx_sgraph_unitigs); they own their arrays: the graph may be closed first"""
@@ -483,15 +508,16 @@ class StringGraph(_DeviceText):
         return TilingPaths(t)
 
 
-def string_graph(records, min_len: int = 4000, min_idt: float = 96.0, device=None, piece: int = 0) -> StringGraph:
+def string_graph(records, min_len: int = 4000, min_idt: float = 96.0, device=None, piece: int = 0, chimer_ordered: bool = False) -> StringGraph:
     """The string graph of `records` (OVLP_DTYPE) in one call: a graph-mode dedup stream fed the records (in pieces of `piece`, 0: one
-    feed), then DedupStream.string_graph.  The stream is closed; the graph stays."""
+    feed), then DedupStream.string_graph (chimer_ordered: with the chimer bridge step under the stated pop order).  The stream is closed;
+    the graph stays."""
     recs = np.ascontiguousarray(records, OVLP_DTYPE)
     piece = piece or max(len(recs), 1)
     with DedupStream(device=device, graph_ready=True) as ds:
         for a in range(0, len(recs), piece):
             ds.feed(recs[a:a + piece])
-        return ds.string_graph(min_len, min_idt)
+        return ds.string_graph(min_len, min_idt, chimer_ordered=chimer_ordered)
 
 
 UNITIG_DTYPE = np.dtype([("s_rid", "<u4"), ("t_rid", "<u4"), ("via_rid", "<u4"), ("s_end", "u1"), ("t_end", "u1"), ("via_end", "u1"), ("circular", "u1"),
@@ -793,10 +819,13 @@ def graph_to_path(sg, utg_data: str, ctg_paths: str, p_out: str | None = None, a
 
 
 def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None, utg_path: str | None = None, utg_data_path: str | None = None,
-                ctg_paths_path: str | None = None) -> dict:
+                ctg_paths_path: str | None = None, chimer_ordered: bool = False, chimers_nodes_path: str | None = None) -> dict:
     """cat ovlp*.dat | shmr_sgraph > sg_edges_list: the files through a graph-mode DedupStream piece by piece, the graph, its text to
     out_path (and, with utg_path, its unitigs' lines to that file; with utg_data_path / ctg_paths_path the final utg_data / ctg_paths).
-    Returns the graph's statistics."""
+    chimer_ordered: with the chimer bridge step under the stated pop order (DedupStream.string_graph); chimers_nodes_path, valid only with
+    it, takes the chimers_nodes file.  Returns the graph's statistics."""
+    if chimers_nodes_path is not None and not chimer_ordered:
+        raise ValueError("chimers_nodes_path needs chimer_ordered")
     _lib.init(device)
     if isinstance(ovlp_paths, (str, bytes)):
         ovlp_paths = [ovlp_paths]
@@ -810,8 +839,11 @@ def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float =
                         ds.feed(recs)
                     if len(recs) < piece:
                         break
-        with ds.string_graph(min_len, min_idt) as g:
+        with ds.string_graph(min_len, min_idt, chimer_ordered=chimer_ordered) as g:
             g.write(out_path)
+            if chimers_nodes_path is not None:
+                with open(chimers_nodes_path, "wb") as f:
+                    f.write(g.chimers_nodes())
             if utg_path is not None or utg_data_path is not None or ctg_paths_path is not None:
                 with g.unitigs() as u:
                     if utg_path is not None:
