@@ -144,6 +144,17 @@ int pgx_index_chunk(const char *seqdb_prefix, const char *out_prefix, const pgx_
  * seq_dataset_path: text file with one FASTA/FASTQ(.gz) path per whitespace-separated token; writes <prefix>.seqdb and
  * <prefix>.idx byte-identical to the reference's.  The two-strand encoding runs on the GPU. */
 int pgx_mkseqdb(const char *seq_dataset_path, const char *seqdb_prefix, uint64_t *n_reads, uint64_t *n_bases);
+/* A FASTA text to a resident database, on the GPU (record grammar, compaction and two-strand encoding: pgx_fasta.hip).
+ * text: FASTA at a host pointer (on_device == 0) or a device pointer (!= 0; what the caller's stream enqueued comes first after
+ * pgx_stream_wait).  *out: a database whose rid are 0 .. n-1 in text order, bytes in place, equal in every field and byte to
+ * pgx_seqdb_load of the files pgx_mkseqdb writes from the same text.  *names (pgx_free): the names, a line each, in rid order.
+ * PGX_EINVAL: no record in the text; a line behind the first header's that starts with '+' (a FASTQ record: the message carries the
+ * smallest such byte offset); a record of 2^32 bases or more.  PGX_ENOMEM: the text does not fit beside its database. */
+int pgx_seqdb_from_fasta(const char *text, size_t len, int on_device, pgx_seqdb **out, char **names, size_t *names_len,
+                         uint64_t *n_reads, uint64_t *n_bases);
+/* <prefix>.seqdb / <prefix>.idx of a database whose bytes are in place (PGX_ESTATE once released or compacted), idx lines
+ * "%09d %s %u %lu\n" with the names given: byte for byte shmr_mkseqdb's two files. */
+int pgx_seqdb_save(pgx_seqdb *db, const char *names, size_t names_len, const char *seqdb_prefix);
 
 /* ---- overlap stage (replaces shmr_overlap) ---- */
 typedef struct {

@@ -796,10 +796,11 @@ static void upload_file_pieces(const char *path, uint8_t *d_dst, size_t nbytes) 
   cleanup();
 }
 
-// seqdb: host bytes, device bytes (from_device), or -- file != nullptr -- the path of the .seqdb file (nbytes = its size)
+// seqdb: host bytes, device bytes (from_device), or -- file != nullptr -- the path of the .seqdb file (nbytes = its size); take: a block
+// of the library's own that holds the bytes in place already (nbytes + 1024 of it at least) and becomes the database's, without a copy
 static int seqdb_upload_impl(const uint8_t *seqdb, size_t nbytes, const uint32_t *rid, const uint32_t *rlen,
                              const uint64_t *roff, uint32_t nreads, pgx_seqdb **out, bool from_device, const char *file = nullptr,
-                             bool adopt = false) {
+                             bool adopt = false, DevBuf<uint8_t> *take = nullptr) {
   return guarded([&]() -> int {
     require_ready();
     PGX_REQUIRE(out && (nreads == 0 || (rid && rlen && roff)), PGX_EARG, "pgx_seqdb_upload: null argument");
@@ -823,7 +824,9 @@ static int seqdb_upload_impl(const uint8_t *seqdb, size_t nbytes, const uint32_t
       db->rlen_by_rid[rid[i]] = rlen[i], db->roff_by_rid[rid[i]] = roff[i], db->max_rlen = std::max(db->max_rlen, rlen[i]);
     db->nbytes = nbytes;
     try {
-      if (adopt) {
+      if (take) {
+        db->d_seq = std::move(*take);
+      } else if (adopt) {
         db->borrowed = true;
         db->d_seq.p = const_cast<uint8_t *>(seqdb), db->d_seq.n = nbytes + 1024;
       } else {
@@ -831,7 +834,7 @@ static int seqdb_upload_impl(const uint8_t *seqdb, size_t nbytes, const uint32_t
         db->d_seq.alloc(nbytes + 1024);
       }
       PGX_HIP(hipMemsetAsync(db->d_seq.p + nbytes, 0, 1024, ctx().stream));
-      if (adopt) {
+      if (adopt || take) {
       } else if (nbytes && file) upload_file_pieces(file, db->d_seq.p, nbytes);
       else if (nbytes) PGX_HIP(hipMemcpyAsync(db->d_seq.p, seqdb, nbytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx().stream));
       db->d_roff.alloc(nr ? nr : 1);
@@ -864,6 +867,14 @@ int pgx_seqdb_adopt_dev(uint8_t *d_seqdb, size_t nbytes, size_t capacity, const 
     return PGX_EARG;
   }
   return seqdb_upload_impl(d_seqdb, nbytes, rid, rlen, roff, nreads, out, true, nullptr, true);
+}
+extern "C++" int pgx::seqdb_take_dev(DevBuf<uint8_t> &&bytes, size_t nbytes, const uint32_t *rid, const uint32_t *rlen, const uint64_t *roff,
+                                     uint32_t nreads, pgx_seqdb **out) {
+  if (!bytes.p || bytes.n < nbytes + 1024) {
+    pgx::set_error("seqdb_take_dev: the block is shorter than nbytes + 1024");
+    return PGX_EARG;
+  }
+  return seqdb_upload_impl(bytes.p, nbytes, rid, rlen, roff, nreads, out, true, nullptr, false, &bytes);
 }
 // event hand-over between the library's stream and another runtime's
 static int stream_order(hipStream_t first, hipStream_t then) {

@@ -383,6 +383,12 @@ struct pgx_seqdb {
 
 namespace pgx {
 
+// A database over bytes that a stage of the library made in place (pgx_fasta.hip): `bytes` holds nbytes of seqdb and 1 KiB of room behind
+// them, and becomes the database's d_seq -- the constructor pgx_seqdb_upload_dev and pgx_seqdb_adopt_dev end in, without their copy.  After
+// a failure the block is released.
+int seqdb_take_dev(DevBuf<uint8_t> &&bytes, size_t nbytes, const uint32_t *rid, const uint32_t *rlen, const uint64_t *roff, uint32_t nreads,
+                   pgx_seqdb **out);
+
 // ---------------------------------------------------------------------------------------------------------
 // device stages (pgx_kernels.hip).  All take/return device pointers and run on ctx().stream.
 // ---------------------------------------------------------------------------------------------------------

@@ -53,6 +53,13 @@ def _text_pieces(fn, name, handle, max_lines):
             yield data
 
 
+def _rlen_by_rid(rid, rlen) -> np.ndarray:
+    """the idx columns as the array the map stage indexes by rid (0 for a rid the idx lacks)"""
+    out = np.zeros(int(rid.max()) + 1 if len(rid) else 0, np.uint32)
+    out[rid] = rlen
+    return out
+
+
 class ResidentDB:
     """A read database uploaded once to HBM (pgx_seqdb)."""
 
@@ -67,6 +74,7 @@ class ResidentDB:
         _lib.check(self._lib.pgx_seqdb_upload(_ptr(seq), seq.size, _ptr(rid), _ptr(rlen), _ptr(roff), len(rid),
                                               C.byref(self.h)), "pgx_seqdb_upload")
         self.n_reads, self.n_bases = len(rid), int(rlen.sum(dtype=np.uint64))
+        self.rlen_by_rid = _rlen_by_rid(rid, rlen)
 
     @classmethod
     def from_device(cls, d_seqdb: int, nbytes: int, rid, rlen, roff, device: int | None = None):
@@ -81,6 +89,7 @@ class ResidentDB:
         _lib.check(self._lib.pgx_seqdb_upload_dev(C.c_void_p(d_seqdb), nbytes, _ptr(rid), _ptr(rlen), _ptr(roff), len(rid),
                                                   C.byref(self.h)), "pgx_seqdb_upload_dev")
         self.n_reads, self.n_bases = len(rid), int(rlen.sum(dtype=np.uint64))
+        self.rlen_by_rid = _rlen_by_rid(rid, rlen)
         return self
 
     @classmethod
@@ -101,7 +110,39 @@ class ResidentDB:
                                                  _ptr(rlen), _ptr(roff), len(rid), C.byref(self.h)), "pgx_seqdb_adopt_dev")
         self._adopted = seq_tensor
         self.n_reads, self.n_bases = len(rid), int(rlen.sum(dtype=np.uint64))
+        self.rlen_by_rid = _rlen_by_rid(rid, rlen)
         return self
+
+    @classmethod
+    def from_fasta(cls, text, device: int | None = None):
+        """The database of a FASTA text, made on the GPU (pgx_seqdb_from_fasta): `text` is bytes, or a contiguous torch uint8 device tensor
+        (what torch's current stream enqueued comes first).  rid are 0 .. n-1 in text order; `.names` holds the records' names in that
+        order; every field and byte is what shmr_mkseqdb and a load of its files give.  FASTQ records, a text without a record and a
+        record of 2^32 bases are refused (PgxError)."""
+        self = cls.__new__(cls)
+        _lib.init(device)
+        self._lib = _lib.load()
+        self.h = C.c_void_p()
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(text, np.uint8)
+            ptr, n, on_dev = _ptr(buf) if len(buf) else None, len(buf), 0
+        else:
+            assert text.is_cuda and text.is_contiguous() and text.element_size() == 1, "a contiguous uint8 device tensor"
+            _lib.stream_wait()
+            ptr, n, on_dev = C.c_void_p(text.data_ptr()), int(text.numel()), 1
+        names, nl, nr, nb = C.c_void_p(), C.c_size_t(0), C.c_uint64(0), C.c_uint64(0)
+        _lib.check(self._lib.pgx_seqdb_from_fasta(ptr, n, on_dev, C.byref(self.h), C.byref(names), C.byref(nl), C.byref(nr), C.byref(nb)),
+                   "pgx_seqdb_from_fasta")
+        self._names = C.string_at(names.value, nl.value)
+        self._lib.pgx_free(names)
+        self.names = self._names.decode("latin-1").split("\n")[:-1]
+        self.n_reads, self.n_bases = int(nr.value), int(nb.value)
+        self.rlen_by_rid = None   # (the lengths stay with the library)
+        return self
+
+    def save(self, prefix: str):
+        """<prefix>.seqdb and <prefix>.idx of a from_fasta database whose bytes are in place (pgx_seqdb_save): shmr_mkseqdb's two files"""
+        _lib.check(self._lib.pgx_seqdb_save(self.h, self._names, len(self._names), os.fsencode(prefix)), "pgx_seqdb_save")
 
     # ---- multi-GPU hand-over on device pointers (include/pgx.h, SURVEY 8e) ------------------------------------------
     def index_dev(self, total_chunk=1, mychunk=1, levels=2, reduction=6, window=80, kmer=16):
@@ -1168,6 +1209,110 @@ def consensus_branch(read_prefix: str, read_index_prefix: str, ctg_prefix: str, 
             f.write(fasta)
         return len(fasta)
     return fasta
+
+
+def polish(rdb: "ResidentDB", read_top, read_counts, contig_fasta, mapping_nchunk: int, cns_nchunk: int, levels=2, reduction=6, window=80, kmer=16,
+           mc_lower=1, mc_upper=240, out: str | None = None, stats: dict | None = None):
+    """The consensus branch of pg_run.py (:401-545) on a read database that is resident already, with its top-level shimmer list and
+    counts (all index chunks, concatenated in chunk order), and the contigs as FASTA text (bytes, or a torch uint8 device tensor): the
+    contig database straight from the text (ResidentDB.from_fasta), its index with -t 1 -c 1, map_rows_of for the chunks
+    1 .. mapping_nchunk, map_merge, cns_job_resident for my = 1 .. cns_nchunk in consensus_branch's order.  No contig file, index file
+    or map text is formed.  The concatenated FASTA is returned, or written to `out` (its length returned)."""
+    import time
+    if rdb.rlen_by_rid is None:
+        raise _lib.PgxError("polish: the read database carries no read lengths on the host (a from_fasta database)")
+    t = [time.perf_counter()]
+    cdb = ResidentDB.from_fasta(contig_fasta)
+    try:
+        t.append(time.perf_counter())
+        ix = cdb.index(1, 1, levels, reduction, window, kmer)
+        t.append(time.perf_counter())
+        parts = [map_rows_of(ix.top, read_top, read_counts, rdb.rlen_by_rid, mapping_nchunk, c, mc_lower, mc_upper) for c in range(1, int(mapping_nchunk) + 1)]
+        t.append(time.perf_counter())
+        rows = map_merge(np.concatenate(parts) if parts else np.zeros((0, 9), np.int64))
+        t.append(time.perf_counter())
+        fasta = b"".join(cns_job_resident(rdb, cdb, rows, cns_nchunk, my, cdb.names)[0] for my in range(1, int(cns_nchunk) + 1))
+        t.append(time.perf_counter())
+        if stats is not None:
+            stats.update(contigs=cdb.n_reads, contig_bases=cdb.n_bases, map_rows=len(rows),
+                         ms={k: (b - a) * 1e3 for k, a, b in zip(("contig_db", "contig_index", "map", "map_merge", "consensus"), t, t[1:])})
+    finally:
+        cdb.close()
+    if out is not None:
+        with open(out, "wb") as f:
+            f.write(fasta)
+        return len(fasta)
+    return fasta
+
+
+def assemble(seqdb_prefix: str, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: int = 0, cns_nchunk: int = 0, min_len: int = 4000,
+             min_idt: float = 96.0, with_alt: bool = False, levels=2, reduction=6, window=80, kmer=16, bestn=4, mc_lower=2, mc_upper=240,
+             align_bandwidth=100, ovlp_upper=120, chimer_ordered: bool = True, out_dir: str | None = None, device=None) -> dict:
+    """pg_run.py from the read database on (:227-386 and, with cns_nchunk > 0, :389-565) in one process, on one ResidentDB loaded once:
+    every index chunk; every overlap chunk on the concatenated lists and counts; the chunks' records through one graph-mode
+    DedupStream in chunk order; the string graph (chimer_ordered: the chimer bridge step, which pg_run.py leaves on, under the stated
+    pop order), unitigs, contig paths, tiling paths; the contigs of p (and of a with with_alt) laid out from the rows; polish() on the
+    primary FASTA.  mc_lower / mc_upper go to the overlap and to the map stage alike, as pg_run.py passes them.
+    Returns dict(p_ctg, a_ctg, p_ctg_cns, stats): FASTA bytes (a_ctg / p_ctg_cns None when not asked for) and the stages' statistics
+    with their wall times.  With out_dir, p_ctg.fa, a_ctg.fa and p_ctg_cns.fa are written there.  Every handle is closed, also when
+    a stage raises."""
+    import contextlib
+    import time
+    from .formats import read_seqdb
+    _lib.init(device)
+    stats, ms = {}, {}
+    clock = [time.perf_counter()]
+
+    def lap(name):
+        clock.append(time.perf_counter())
+        ms[name] = (clock[-1] - clock[-2]) * 1e3
+
+    def fasta_of(t, which):
+        rows, names = t.rows(which), t.names(which)
+        if not len(rows):
+            return b""
+        data, off = rdb.contigs(rows)
+        return b"".join(b">" + names[c].encode() + b"\n" + data[int(off[c]):int(off[c + 1])] + b"\n" for c in range(len(off) - 1))
+
+    with contextlib.ExitStack() as es:
+        rdb = ResidentDB(read_seqdb(seqdb_prefix), device)
+        es.callback(rdb.close)
+        lap("load")
+        ixs = [rdb.index(index_nchunk, c, levels, reduction, window, kmer) for c in range(1, int(index_nchunk) + 1)]
+        top = np.concatenate([ix.top for ix in ixs]) if ixs else np.zeros(0, MM_DTYPE)
+        counts = np.concatenate([ix.top_mc for ix in ixs]) if ixs else np.zeros(0, MC_DTYPE)
+        stats["index"] = [dict(bases=ix.bases, reads=ix.reads, shimmers=len(ix.top)) for ix in ixs]
+        lap("index")
+        ds = es.enter_context(DedupStream(device=device, graph_ready=True))
+        stats["overlap"] = []
+        for c in range(1, int(ovlp_nchunk) + 1):
+            recs, st = rdb.overlap(top, counts, ovlp_nchunk, c, bestn, mc_lower, mc_upper, align_bandwidth, ovlp_upper)
+            ds.feed(recs)
+            stats["overlap"].append(st)
+        lap("overlap")
+        g = es.enter_context(ds.string_graph(min_len, min_idt, chimer_ordered=chimer_ordered))
+        stats["dedup"], stats["graph"] = ds.stats, g.stats
+        u = es.enter_context(g.unitigs())
+        cp = es.enter_context(u.contig_paths())
+        t = es.enter_context(cp.tiling(g))
+        stats["tiling"] = t.stats
+        lap("graph")
+        p_ctg = fasta_of(t, 0)
+        a_ctg = fasta_of(t, 1) if with_alt else None
+        lap("contigs")
+        cns = None
+        if int(cns_nchunk) > 0:
+            stats["polish"] = {}
+            cns = b"" if not p_ctg else polish(rdb, top, counts, p_ctg, mapping_nchunk, cns_nchunk, levels, reduction, window, kmer, mc_lower, mc_upper, stats=stats["polish"])
+            lap("polish")
+    stats["ms"] = ms
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, data in (("p_ctg.fa", p_ctg), ("a_ctg.fa", a_ctg), ("p_ctg_cns.fa", cns)):
+            if data is not None:
+                with open(os.path.join(out_dir, name), "wb") as f:
+                    f.write(data)
+    return dict(p_ctg=p_ctg, a_ctg=a_ctg, p_ctg_cns=cns, stats=stats)
 
 
 def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None):
