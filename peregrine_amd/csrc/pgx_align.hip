@@ -1,13 +1,14 @@
 // pgx_align.hip -- banded O(ND) furthest-reaching confirmation (ovlp_match, /root/reference/src/DWmatch.c:66-204),
-// EIGHT candidate alignments per wavefront.
+// EIGHT or SIXTEEN candidate alignments per wavefront.
 //
 // A candidate keeps on average 3.6 diagonals alive (<= 8 in 98.7 % of the steps, at most band+1 = 101), so one wavefront
 // per candidate leaves most lanes idle -- and the kernel is bound by VALU issue (profiles/r01_pmc_align.txt), so lane
-// utilisation is throughput.  Here a wavefront is eight independent 8-lane groups (GL); each group runs the reference's
+// utilisation is throughput.  Here a wavefront is 64 / GL independent groups of GL = 8 or 4 lanes; each group runs the reference's
 // d-loop for its own candidate and pulls the next one from a device-wide counter the moment it finishes (persistent groups:
 // no tail inside the wave).  Lane j of a group owns diagonal k = min_k + 2*(base+j) of the current step; wider bands take
-// several rounds of 8.  V lives in a per-group LDS ring indexed by k (only the previous step's values are ever read, so
-// 2*band+8 slots never alias live data; only V[1] needs to start at 0).
+// several rounds of GL.  V lives in a per-group LDS ring: in the grouped kernel a HALF ring indexed by (k - d) >> 1 and updated in
+// place (band + 2 slots; see k_align_ph), in the one-candidate-per-wavefront kernels a ring indexed by k (only the previous step's
+// values are ever read, so 2*band+8 slots never alias live data); only V[1] needs to start at 0.
 // Per step: start point from V[k-1], V[k+1]; a probe per lane (off-diagonal fronts stop there); long snakes are extended
 // by the whole group with coalesced loads; the order-dependent side results (first diagonal reaching an end, first
 // extension > 16, first occurrence of the strictly longest extension) are resolved lowest-k-first with ballots restricted
@@ -44,13 +45,16 @@ template <int CTRL>
 __device__ __forceinline__ int dpp_max(int v) {
   return max(v, __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true));   // (bound_ctrl: folds into one v_max_i32_dpp)
 }
-constexpr int GL = 8;   // lanes per candidate of the grouped kernel: half a DPP row, eight groups per wavefront
-// maximum over the 8 lanes of a group, result in every lane: xor-butterfly with quad_perm / row_half_mirror
-__device__ __forceinline__ int group_max8_i32(int v) {
+// GL = lanes per candidate of the grouped kernel: 8 (half a DPP row, eight groups per wavefront) or 4 (a quad, sixteen groups)
+// maximum over the GL lanes of a group, result in every lane: xor-butterfly with quad_perm, and row_half_mirror for the step from 4 to 8
+template <int GL>
+__device__ __forceinline__ int group_max_i32(int v) {
+  static_assert(GL == 4 || GL == 8, "a group is a quad or half a DPP row");
   v = dpp_max<0xB1>(v);   // quad_perm [1,0,3,2]
   v = dpp_max<0x4E>(v);   // quad_perm [2,3,0,1]
-  return dpp_max<0x141>(v);  // row_half_mirror: lanes i <-> 7-i of every 8
+  return GL == 8 ? dpp_max<0x141>(v) : v;  // row_half_mirror: lanes i <-> 7-i of every 8
 }
+template <int GL>
 __device__ __forceinline__ uint32_t group_bits(uint64_t wave_mask, int gbase) {
   return (uint32_t)(wave_mask >> gbase) & ((1u << GL) - 1u);
 }
@@ -58,11 +62,12 @@ template <int CTRL>
 __device__ __forceinline__ int dpp_min(int v) {
   return min(v, __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true));   // (one v_min_i32_dpp)
 }
-// minimum over the 8 lanes of a group, result in every lane (same butterfly as group_max8_i32)
-__device__ __forceinline__ int group_min8_i32(int v) {
+// minimum over the GL lanes of a group, result in every lane (same butterfly as group_max_i32)
+template <int GL>
+__device__ __forceinline__ int group_min_i32(int v) {
   v = dpp_min<0xB1>(v);
   v = dpp_min<0x4E>(v);
-  return dpp_min<0x141>(v);
+  return GL == 8 ? dpp_min<0x141>(v) : v;
 }
 // v_ffbl_b32 as the hardware defines it: the position of the lowest set bit, 0xFFFFFFFF for 0 (__builtin_ctz leaves 0 undefined and the
 // guarded form costs a compare and a select)
@@ -310,16 +315,19 @@ enum { PH_FETCH = 0, PH_STEP = 1, PH_ROUND = 2, PH_SNAKE = 3, PH_END = 4, PH_BAN
 // 32 % of the main diagonals' matches, one of 8 only 18 %).  seq = the two packs (pack1 = seq + pack_stride dwords); candidates
 // that meet a read with ambiguous bases (nflag) are handed on to the byte-wise launch through esc_list.
 // ROUND 6 -- a WORKGROUP of up to 16 wavefronts shares one run of the request list.  The wavefronts still run on their own (no barrier
-// inside the loop; every V ring belongs to one 8-lane group), but they take their chunks of 8 candidates from a SEGMENT of `seg`
+// inside the loop; every V ring belongs to one group), but they take their chunks of 64 / GL candidates from a SEGMENT of `seg`
 // consecutive requests that the workgroup claimed from the device-wide counter, through one packed LDS word {segment start, taken}.
 // With the requests of a launch in the order of the packs' layout (order list: dev_align sorts them by the query read's rank) the
-// 128 candidates a workgroup has in flight are neighbours in the layout -- one or two loci -- and a CU (two workgroups) touches a few
+// 128 or 256 candidates a workgroup has in flight are neighbours in the layout -- one or two loci -- and a CU (two workgroups) touches a few
 // dozen translation ranges of the 47 GB of packs instead of 512 (pgx_pack.hip; rounds 2-5: a wavefront per workgroup, chunks of 8
 // straight from the device-wide counter: every wavefront of a CU at another locus).
 // PACKED: seq = the packs, roff = d_poff (dword index of a read's forward strand; its reverse complement follows at + ceil(len / 16)).
 // VT = storage type of the V ring: uint16_t when no read is longer than 65,535 bases (x <= q_len fits), which halves the LDS of a
-// group and lets 32 instead of 19 wavefronts share a CU; int32_t otherwise (the byte form only: such databases have no packs).
-template <typename VT, bool PACKED>
+// group; int32_t otherwise (the byte form only: such databases have no packs).
+// GL = lanes per candidate, 8 or 4.  A 4-lane group takes rounds of 4 diagonals and extends a snake by 4 x SL codes per iteration; a
+// wavefront then carries 16 candidates and a chunk of the work counter is 16 requests.  With the half ring (below) a group's V is
+// 256 bytes at band 100, so 16 groups per wavefront still leave a CU its 32 wavefronts.
+template <typename VT, bool PACKED, int GL>
 __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ roff,
                                                       const uint32_t *__restrict__ rlen, const pgx_align_key *__restrict__ keys,
                                                       uint32_t n, int band, int ring, pgx_match *__restrict__ out,
@@ -337,7 +345,18 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
   VT *V = reinterpret_cast<VT *>(Vall) + ((threadIdx.x >> 6) * (64 / GL) + lane / GL) * ring;
   if (threadIdx.x == 0) s_state = (unsigned long long)seg, s_lock = 0u;   // (an exhausted segment: the first fetch claims one)
   __syncthreads();
-  const int mask = ring - 1, band_size = band * 2;
+  // The HALF RING.  The diagonals of step d all have d's parity, and a step reads only what the step before wrote, so V is kept by
+  // s(k, d) = (k - d) >> 1 modulo `ring`: the lane of diagonal k reads V_old[k-1] from slot s and V_old[k+1] from slot s + 1 and writes
+  // V_new[k] to slot s -- IN PLACE.  Within a round every read (ROUND) precedes every write (END) in program order; across the rounds of
+  // a wide step, which go up in k, the slot a lane overwrites held V_old[k-1], and the only other reader of that was the lane of k - 2,
+  // one round earlier at the latest: a later round finds both its slots as the step before left them.  (With s = (k + d) >> 1 the write
+  // would land on V_old[k+1], which the first lane of the next round still needs.)  The slots a step touches are s(min_k) .. s(max_k) + 1,
+  // nk + 1 <= band + 2 of them (STEP lets no wider band through), so ring >= band + 2 keeps them apart (dev_align).  k - d is even:
+  // the slot's offset in ring elements, times two, is (k - d) & mask2.
+  const int mask2 = (ring - 1) << 1, band_size = band * 2;
+  const auto slot = [&](int kd) -> VT & {   // kd = k - d of a diagonal of step d; kd + 2: the slot above
+    return *reinterpret_cast<VT *>(reinterpret_cast<char *>(V) + (kd & mask2) * (int)(sizeof(VT) / 2));
+  };
   constexpr int SL = PACKED ? 32 : 16;                     // codes per lane and snake iteration
   constexpr int PROBE = PACKED ? 16 : 8;                   // codes of a probe
   if (redo_list) n = *redo_n;
@@ -395,8 +414,8 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
     const uint64_t fw = ballot64(fetching);
     uint32_t na = 0;
     if (fw) {   // (wave-uniform; ~3 % of the iterations)
-      constexpr uint32_t CHUNK = 8;
-      const uint64_t need = fw & 0x0101010101010101ULL;   // the first lanes of the fetching groups
+      constexpr uint32_t CHUNK = 64 / GL;   // (a candidate for every group of the wavefront)
+      const uint64_t need = fw & (GL == 8 ? 0x0101010101010101ULL : 0x1111111111111111ULL);   // the first lanes of the fetching groups
       const uint32_t cnt = (uint32_t)__builtin_popcountll(need);
       const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));   // such lanes below this one
       const uint32_t avail = __builtin_amdgcn_readfirstlane(c_end - c_next);
@@ -460,7 +479,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
         d = 0, best_m = -1, min_k = 0, max_k = 0, longest = 0;
         started = false;
         q_bgn = t_bgn = q_m_end = t_m_end = 0;
-        if (gl == 0) V[1 & mask] = (VT)0;  // the only slot read before it is written (d = 0 reads V[k+1] = V[1])
+        if (gl == 0) slot(2) = (VT)0;  // the only slot read before it is written (d = 0 reads V[k+1] = V[1], the slot above k = 0's own)
         phase = PH_STEP;
         if (PACKED && ((nflag[key.rid0] | nflag[key.rid1]) & 1u)) {   // an ambiguous base has no 2-bit code: the byte-wise launch takes it
           if (gl == 0) esc_list[n + atomicAdd(esc_n + 1, 1u)] = a;      // (second list of the escalation block: [4 + n ..), count at [1])
@@ -472,7 +491,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
     PH_SYNC();
 
     // ---- STEP: the loop conditions of a new d (DWmatch.c:118-122,196-199) -------------------------------------------
-    // (the V ring holds every live diagonal of a band that passes the width test below: ring >= 2 band + 8 by dev_align, so the only
+    // (the V ring holds every live diagonal of a band that passes the width test below: ring >= band + 2 by dev_align, so the only
     //  hand-on left is the iteration budget -- round 2's narrow-ring launches are gone)
     if (iters > iter_budget && phase == PH_STEP && !(d >= max_d || max_k - min_k > band_size)) {   // a straggler: k_align1_list takes it, a wavefront of its own
       if (gl == 0) esc_list[atomicAdd(esc_n, 1u)] = a;
@@ -503,7 +522,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       k = min_k + 2 * j;
       // (x, y, x1, y1 of the lanes beyond the band keep whatever they held: every use below is behind `active`)
       if (active) {
-        const int va = (int)V[(k - 1) & mask], vb = (int)V[(k + 1) & mask];
+        const int va = (int)slot(k - d), vb = (int)slot(k - d + 2);
         x = (k == min_k || (k != max_k && va < vb)) ? vb : va + 1;
         y = x - k;
         x1 = x, y1 = y;
@@ -529,7 +548,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       // (a ballot of ONE integer compare is one v_cmp; of a bool the compiler materialises 0 / 1 and compares again.  Lanes outside
       //  ROUND hold 0.)  The group's mask is STATE from here on: SNAKE clears a bit per finished diagonal, no ballot of its own.
       asm volatile("" : "+v"(probe_full));   // (kept a VGPR value: as a bool the compiler carries it as a lane mask and the ballot costs a select + a compare on top)
-      const uint32_t g = group_bits(ballot64(probe_full >= PROBE), gbase);
+      const uint32_t g = group_bits<GL>(ballot64(probe_full >= PROBE), gbase);
       if (phase == PH_ROUND) gm = g, phase = g ? PH_SNAKE : PH_END;
     }
 
@@ -537,7 +556,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
     {
       const bool sn = phase == PH_SNAKE;
       if (ballot64(sn)) {
-        const int L = __builtin_ctz(gm | 0x100u);   // (groups outside SNAKE: lane 8 = the next group's lane 0, looked at and dropped)
+        const int L = __builtin_ctz(gm | (1u << GL));   // (groups outside SNAKE: lane GL = the next group's lane 0, looked at and dropped)
         const int xs = group_lane(x, gb4, L), ys = group_lane(y, gb4, L);
         const int rem = min(q_len - xs, t_len - ys);
         const int off = gl * SL;
@@ -567,7 +586,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
             e = m < SL ? off + m : GL * SL;
           }
         }
-        const int ext = group_min8_i32(e);
+        const int ext = group_min_i32<GL>(e);
         if (sn) {
           if (gl == L) x += ext, y += ext;
           if (ext < GL * SL || ext >= rem) gm &= gm - 1;  // mismatch found or an end reached: this diagonal is done
@@ -585,7 +604,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       int hl = GL;
       uint32_t hitm = 0;
       if (hitw) {   // (once per candidate)
-        hitm = group_bits(hitw, gbase);
+        hitm = group_bits<GL>(hitw, gbase);
         if (hitm) hl = __builtin_ctz(hitm);
         asm volatile("" : "+v"(hl));   // (keeps the branch: folded into selects the four instructions run in every iteration)
       }
@@ -594,7 +613,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
         const uint64_t sw = ballot64((valid && !started ? ext : 0) > 16);   // (a select + ONE compare: the compiler turns a ballot of
                                                                            // combined predicates into select 0/1 + compare on top of them)
         if (sw) {
-          const uint32_t m = group_bits(sw, gbase);
+          const uint32_t m = group_bits<GL>(sw, gbase);
           const int l = m ? __builtin_ctz(m) : 0;
           const int bx = group_lane(x1, gb4, l), by = group_lane(y1, gb4, l);
           if (m) q_bgn = bx, t_bgn = by, started = true;
@@ -602,16 +621,16 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       }
       const int ev = valid ? ext : -1;
       if (ballot64(ev > (int)longest)) {  // strictly longer extension (DWmatch.c:148-152)
-        const int mx = group_max8_i32(ev);
-        const uint32_t m = group_bits(ballot64(valid && ext == mx), gbase);
+        const int mx = group_max_i32<GL>(ev);
+        const uint32_t m = group_bits<GL>(ballot64(valid && ext == mx), gbase);
         const int l = m ? __builtin_ctz(m) : 0;
         const int ex = group_lane(x, gb4, l), ey = group_lane(y, gb4, l);
         if (e && mx >= 0 && (uint32_t)mx > longest) longest = (uint32_t)mx, q_m_end = ex, t_m_end = ey;
       }
-      if (valid) V[k & mask] = (VT)x;
+      if (valid) slot(k - d) = (VT)x;
       const int u = x + y;
       {
-        const int s = group_max8_i32(valid ? u : -1);
+        const int s = group_max_i32<GL>(valid ? u : -1);
         if (e) best_m = max(best_m, s);
       }
       bool matched = false;
@@ -636,7 +655,7 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
       // recorded new_max qualifies, and if those two still pass the FINAL threshold -- re-read from the ring in the last round, a lane each --
       // they are the scan's answer and the step is done here.  Only when a later round raised best_m past one of them (5 % of the wide
       // steps) does the step go through BAND below, a round of GL diagonals per iteration.
-      const uint32_t qm = group_bits(ballot64((e && active ? u : INT32_MIN) >= best_m - band), gbase);
+      const uint32_t qm = group_bits<GL>(ballot64((e && active ? u : INT32_MIN) >= best_m - band), gbase);
       const bool wide_step = e && !matched && nk > GL;
       if (ballot64(wide_step)) {   // (1.4 % of the steps)
         const bool last = wide_step && base + GL >= nk;
@@ -655,8 +674,8 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
           const bool some = last && new_min <= new_max;
           const int ke = gl ? new_max : new_min;
           int ue = INT32_MIN;
-          if (some && gl < 2) ue = 2 * (int)V[ke & mask] - ke;
-          const uint32_t pm = group_bits(ballot64(ue >= best_m - band), gbase);
+          if (some && gl < 2) ue = 2 * (int)slot(ke - d) - ke;
+          const uint32_t pm = group_bits<GL>(ballot64(ue >= best_m - band), gbase);
           if (last) {
             if (!some || (pm & 3u) == 3u) {
               max_k = new_max + 1, min_k = new_min - 1, ++d, phase = PH_STEP;
@@ -690,8 +709,8 @@ __global__ __launch_bounds__(1024, 8) void k_align_ph(const uint8_t *__restrict_
         const int j = bbase + gl;
         const int k2 = min_k + 2 * j;
         int u = 0;
-        if (bnd && j < nk) u = 2 * (int)V[k2 & mask] - k2;   // (nk > GL: U of the earlier rounds' diagonals is not in the registers)
-        const uint32_t m = group_bits(ballot64((bnd && j < nk ? u : INT32_MIN) >= thr), gbase);
+        if (bnd && j < nk) u = 2 * (int)slot(k2 - d) - k2;   // (nk > GL: U of the earlier rounds' diagonals is not in the registers)
+        const uint32_t m = group_bits<GL>(ballot64((bnd && j < nk ? u : INT32_MIN) >= thr), gbase);
         if (bnd) {
           if (m) {
             new_min = min(new_min, min_k + 2 * (bbase + __builtin_ctz(m)));
@@ -772,7 +791,8 @@ void dev_align_prepare(const pgx_seqdb *db) { (void)align_source(db, LONG_MAX); 
 //   large launches : k_align_ph<u16, packed> over the 2-bit packs + k_align1_list for what it hands on (reads with bytes that have no
 //                    2-bit code, stragglers past the iteration budget); without packs (no HBM for them, PGX_ALIGN_PACKED_MIN < 0)
 //                    k_align_ph<u16> on the seqdb bytes; with a read beyond 65,535 bases (16-bit V ring too narrow) k_align_ph<int32>
-//                    on the seqdb bytes
+//                    on the seqdb bytes.  Lanes per candidate: 4 in the main launch of a stage on the packs (and in the byte-wise launch
+//                    that takes what it hands on), 8 in the tail batches and in the 32-bit form
 void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int band, pgx_match *d_out, int tail_batch) {
   if (n == 0) return;
   // launches up to this many alignments take a wavefront per candidate (k_align1).  On uniform candidates the crossover is ~14 k
@@ -824,27 +844,36 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
 #endif
   uint32_t *counter = ws<uint32_t>("align.counter", n_counter);
   PGX_HIP(hipMemsetAsync(counter, 0, n_counter * sizeof(uint32_t), st));
-  // k_align_ph: workgroups of NW wavefronts (a V ring of `ring` elements per 8-lane group), as many as give a CU its 32 wavefronts.  x <= read
-  // length must fit the ring's element: 32-bit rings when a read is longer than 65,535 bases (19 wavefronts per CU at ring 256)
+  // k_align_ph: workgroups of NW wavefronts (a V half ring of `ring_ph` elements per group of `gl` lanes), as many as give a CU its 32
+  // wavefronts.  x <= read length must fit the ring's element: 32-bit rings when a read is longer than 65,535 bases.
+  // Lanes per candidate: a d-step holds 3.6 diagonals on average (<= 4 in 77 % of the steps), so 4-lane groups, sixteen candidates per
+  // wavefront, waste fewer lanes of every ROUND / END body than 8-lane groups do -- for the ordinary candidates of a stage's MAIN launch.
+  // The tail batches are mostly wide-band candidates whose launch lasts as long as its longest one, which takes twice the rounds in a
+  // 4-lane group: they stay at 8 lanes, like the 32-bit form.  PGX_ALIGN_GL = 4 / 8 overrides (never for the 32-bit form).
   const bool wide = db->max_rlen > 65535u;
-  const size_t lds_wave = (size_t)8 * ring * (wide ? sizeof(int32_t) : sizeof(uint16_t));
+  const long gl_env = getenv("PGX_ALIGN_GL") ? atol(getenv("PGX_ALIGN_GL")) : 0;
+  const int gl = wide ? 8 : (gl_env == 4 || gl_env == 8) ? (int)gl_env : (src.grouped.packed && tail_batch == 0) ? 4 : 8;
+  const size_t chunk = 64 / gl;   // the groups of a wavefront = the requests it takes at a time
+  int ring_ph = 32;   // the grouped kernel's half ring (k_align_ph: the slots of a step are nk + 1 <= band + 2)
+  while (ring_ph < band + 2) ring_ph <<= 1;
+  const size_t lds_wave = chunk * ring_ph * (wide ? sizeof(int32_t) : sizeof(uint16_t));
   const unsigned waves_cu = (unsigned)std::min<size_t>(32, (158u << 10) / lds_wave);   // 32 = all the wavefronts a CU holds; alignment kernels per c3 step
                                                                                        // with the chunked work counter: 16 -> 65.3 ms, 20 -> 55.9, 24 -> 50.1, 28 -> 46.3, 32 -> 43.7
   const long nw_env = getenv("PGX_ALIGN_NW") ? atol(getenv("PGX_ALIGN_NW")) : 0;
-  unsigned NW = 1;   // the widest workgroup that does not cost the CU wavefronts (ring 256: 16 x 2; ring 512: 19 fit -> 16 x 1)
+  unsigned NW = 1;   // the widest workgroup that does not cost the CU wavefronts (32 fit: 16 x 2; 19 fit: 16 x 1)
   for (unsigned c = 16; c >= 1; c >>= 1)
     if (c <= waves_cu && (waves_cu / c) * c > (waves_cu / NW) * NW) NW = c;
   if (waves_cu >= 16 && (waves_cu / 16) * 16 >= (waves_cu / NW) * NW) NW = 16;
   if (nw_env >= 1 && nw_env <= 16 && (unsigned)nw_env <= waves_cu) NW = (unsigned)nw_env;
   const size_t lds = lds_wave * NW;
   const unsigned wg_cu = waves_cu / NW;
-  // segment = the run of requests a workgroup's wavefronts share (a multiple of the chunk of 8): long enough that the workgroup stays at
+  // segment = the run of requests a workgroup's wavefronts share (a multiple of the chunk): long enough that the workgroup stays at
   // one place of the list, short enough that the last segments of a launch do not leave the other CUs idle
   const size_t n_wg = (size_t)ctx().num_cu * wg_cu;
   auto segment = [&](size_t cnt) {
     const long se = getenv("PGX_ALIGN_SEG") ? atol(getenv("PGX_ALIGN_SEG")) : 0;
-    size_t sg = se > 0 ? (size_t)se : std::min<size_t>(512, std::max<size_t>(8 * NW, cnt / (n_wg * 16)));
-    return (uint32_t)((sg + 7) & ~(size_t)7);
+    size_t sg = se > 0 ? (size_t)se : std::min<size_t>(64 * chunk, std::max<size_t>(chunk * NW, cnt / (n_wg * 16)));
+    return (uint32_t)((sg + chunk - 1) & ~(chunk - 1));
   };
   const uint32_t seg = segment(n);
   const unsigned grid = (unsigned)std::min<size_t>((n + seg - 1) / seg, n_wg);
@@ -873,8 +902,9 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
       order = v_out;
     }
   }
-  const auto ph_bytes = wide ? k_align_ph<int32_t, false> : k_align_ph<uint16_t, false>;   // (the packs never serve a wide launch)
-  launch_on(src.grouped, k_align_ph<uint16_t, true>, ph_bytes, dim3(grid), dim3(64 * NW), lds, db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out,
+  const auto ph_bytes = wide ? k_align_ph<int32_t, false, 8> : gl == 4 ? k_align_ph<uint16_t, false, 4> : k_align_ph<uint16_t, false, 8>;
+  const auto ph_packs = gl == 4 ? k_align_ph<uint16_t, true, 4> : k_align_ph<uint16_t, true, 8>;   // (the packs never serve a wide launch)
+  launch_on(src.grouped, ph_packs, ph_bytes, dim3(grid), dim3(64 * NW), lds, db->d_rlen.p, d_keys, (uint32_t)n, band, ring_ph, d_out,
             counter, order ? esc + 3 : nullptr, order, esc, esc ? esc + 4 : nullptr, db->d_nflag.p, seg, iter_limit);
 #ifdef PGX_ALIGN_STATS
   {
@@ -906,15 +936,15 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
         side_view_of_keys(db, d_keys, esc + 4 + n, nf, view);
         uint32_t *esc2 = ws<uint32_t>("align.esc_view", (size_t)nf + 4);
         PGX_HIP(hipMemsetAsync(esc2, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL((k_align_ph<uint16_t, false>), dim3((unsigned)std::min<size_t>(nf / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds, st, view.seq, view.off,
-                           db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out, esc + 2, esc + 1, esc + 4 + n, esc2, esc2 + 4, (const uint32_t *)nullptr,
+        hipLaunchKernelGGL(ph_bytes, dim3((unsigned)std::min<size_t>(nf / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds, st, view.seq, view.off,
+                           db->d_rlen.p, d_keys, (uint32_t)n, band, ring_ph, d_out, esc + 2, esc + 1, esc + 4 + n, esc2, esc2 + 4, (const uint32_t *)nullptr,
                            segment(nf / 16 + 1), iter_limit);
         hipLaunchKernelGGL(k_align1_list<false>, dim3(std::min<unsigned>(nf, (unsigned)ctx().num_cu * 32)), dim3(64), ring * sizeof(int32_t), st, view.seq,
                            view.off, db->d_rlen.p, d_keys, esc2, esc2 + 4, band, ring, d_out);
       }
     } else if (db->n_flagged_reads)
-      launch_on(seq_bytes(db), k_align_ph<uint16_t, true>, ph_bytes, dim3((unsigned)std::min<size_t>(n / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds,
-                db->d_rlen.p, d_keys, (uint32_t)n, band, ring, d_out, esc + 2, esc + 1, esc + 4 + n, esc, esc + 4, nullptr, segment(n / 16 + 1),
+      launch_on(seq_bytes(db), ph_packs, ph_bytes, dim3((unsigned)std::min<size_t>(n / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds,
+                db->d_rlen.p, d_keys, (uint32_t)n, band, ring_ph, d_out, esc + 2, esc + 1, esc + 4 + n, esc, esc + 4, nullptr, segment(n / 16 + 1),
                 iter_limit);
     // the stragglers of either launch, a wavefront per candidate, from the list
     const dim3 g1((unsigned)std::min<size_t>(std::max<size_t>(n / 256, 256), (size_t)ctx().num_cu * 32));
