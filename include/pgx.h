@@ -155,6 +155,30 @@ int pgx_seqdb_from_fasta(const char *text, size_t len, int on_device, pgx_seqdb 
 /* <prefix>.seqdb / <prefix>.idx of a database whose bytes are in place (PGX_ESTATE once released or compacted), idx lines
  * "%09d %s %u %lu\n" with the names given: byte for byte shmr_mkseqdb's two files. */
 int pgx_seqdb_save(pgx_seqdb *db, const char *names, size_t names_len, const char *seqdb_prefix);
+/* FASTA/FASTQ texts, in pieces and from several files, to one resident database on the GPU (pgx_reads.hip): the whole
+ * grammar of the reference's reader, its '+' branch included.  A builder is a live device object (pgx_shutdown drops its device state;
+ * its calls then answer PGX_ESTATE; close it).
+ * open:   room for reserve_bases bases is set aside (the store grows by doubling when they do not suffice).
+ * feed:   the next `len` bytes of the current file, at a host (on_device == 0) or device pointer; ends_file != 0: they are the file's last
+ *         (len may be 0).  Records whose whole parse lies inside the bytes seen are encoded into the store, rid running on across files;
+ *         the text from the first unfinished header on is kept on the device.  A record the reader calls truncated ends its FILE's
+ *         records, not the call.  PGX_EINVAL: 2^31 lines in one piece and its carry, 2^32 records, a record of 2^32 bases; and an empty
+ *         line inside a quality block behind a '\r' that the reader would strip from an earlier line (the message names its byte offset
+ *         in the file) -- nothing else that the reference reads is refused.
+ * finish: the database (as pgx_seqdb_from_fasta's: equal in every field and byte to pgx_seqdb_load of the files pgx_mkseqdb writes from
+ *         the same inputs) and the names, a line each (pgx_free).  PGX_EINVAL: no record at all.  The builder is empty afterwards.
+ * from_files: a list file as pgx_mkseqdb reads it (whitespace-separated paths, plain or .gz), each file inflated on the calling thread
+ *         and fed in pieces of PGX_FROM_READS_PIECE bytes (default 256 MiB) from a pinned buffer.
+ * read_lengths: the lengths of db's reads by rid (cap: room at rlen_by_rid, at least pgx_seqdb_reads(db)). */
+typedef struct pgx_seqdb_builder pgx_seqdb_builder;
+int pgx_seqdb_builder_open(uint64_t reserve_bases, pgx_seqdb_builder **out);
+int pgx_seqdb_builder_feed(pgx_seqdb_builder *b, const char *text, size_t len, int on_device, int ends_file);
+int pgx_seqdb_builder_finish(pgx_seqdb_builder *b, pgx_seqdb **out, char **names, size_t *names_len, uint64_t *n_reads,
+                             uint64_t *n_bases);
+void pgx_seqdb_builder_close(pgx_seqdb_builder *b);
+int pgx_seqdb_from_files(const char *seq_dataset_path, pgx_seqdb **out, char **names, size_t *names_len, uint64_t *n_reads,
+                         uint64_t *n_bases);
+int pgx_seqdb_read_lengths(const pgx_seqdb *db, uint32_t *rlen_by_rid, size_t cap);
 
 /* ---- overlap stage (replaces shmr_overlap) ---- */
 typedef struct {

@@ -129,6 +129,7 @@ EXPORTS = [
     "pgx_timing_get", "pgx_timing_reset", "pgx_mem_ledger", "pgx_results_async", "pgx_results_wait",
     "pgx_seqdb_upload", "pgx_seqdb_load", "pgx_seqdb_free", "pgx_seqdb_bases", "pgx_seqdb_reads", "pgx_seqdb_release_bytes", "pgx_seqdb_has_bytes",
     "pgx_seqdb_compact_bytes", "pgx_seqdb_side_bytes", "pgx_seqdb_read_bytes", "pgx_seqdb_from_fasta", "pgx_seqdb_save",
+    "pgx_seqdb_builder_open", "pgx_seqdb_builder_feed", "pgx_seqdb_builder_finish", "pgx_seqdb_builder_close", "pgx_seqdb_from_files", "pgx_seqdb_read_lengths",
     "pgx_index_resident", "pgx_index_result_free", "pgx_index_chunk",
     "pgx_overlap_resident", "pgx_overlap_chunk", "pgx_index_chunk_db", "pgx_overlap_chunk_db", "pgx_overlap_chunk_db_begin", "pgx_output_finish", "pgx_index_overlap_resident", "pgx_mkseqdb", "pgx_dedup",
     "pgx_dedup_open", "pgx_dedup_feed", "pgx_dedup_feed_dev", "pgx_dedup_close",
@@ -187,6 +188,13 @@ def load():
         lib.pgx_seqdb_load.argtypes = [C.c_char_p, C.c_void_p]
         lib.pgx_seqdb_from_fasta.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_seqdb_save.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p]
+        lib.pgx_seqdb_builder_open.argtypes = [C.c_uint64, C.c_void_p]
+        lib.pgx_seqdb_builder_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+        lib.pgx_seqdb_builder_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_seqdb_builder_close.argtypes = [C.c_void_p]
+        lib.pgx_seqdb_builder_close.restype = None
+        lib.pgx_seqdb_from_files.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_seqdb_read_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.pgx_index_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_index_chunk.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
         lib.pgx_overlap_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,

@@ -140,8 +140,48 @@ class ResidentDB:
         self.rlen_by_rid = None   # (the lengths stay with the library)
         return self
 
+    @classmethod
+    def from_reads(cls, source, device: int | None = None):
+        """The database of FASTA/FASTQ reads, made on the GPU (pgx_reads.hip): `source` is the path of a list file as shmr_mkseqdb reads it
+        (whitespace-separated paths, plain or .gz: pgx_seqdb_from_files), or a sequence of texts, each one file and each bytes or a
+        contiguous torch uint8 device tensor (pgx_seqdb_builder_*).  rid run on across the files; `.names`, `.n_reads`, `.n_bases` and
+        `.rlen_by_rid` are set; every field and byte is what shmr_mkseqdb and a load of its files give.  Inputs without a record are
+        refused (PgxError)."""
+        self = cls.__new__(cls)
+        _lib.init(device)
+        lib = self._lib = _lib.load()
+        self.h = C.c_void_p()
+        names, nl, nr, nb = C.c_void_p(), C.c_size_t(0), C.c_uint64(0), C.c_uint64(0)
+        if isinstance(source, (str, os.PathLike)):
+            _lib.check(lib.pgx_seqdb_from_files(os.fsencode(source), C.byref(self.h), C.byref(names), C.byref(nl), C.byref(nr), C.byref(nb)),
+                       "pgx_seqdb_from_files")
+        else:
+            b = C.c_void_p()
+            _lib.check(lib.pgx_seqdb_builder_open(0, C.byref(b)), "pgx_seqdb_builder_open")
+            try:
+                for text in source:
+                    if isinstance(text, (bytes, bytearray, memoryview)):
+                        buf = np.frombuffer(text, np.uint8)
+                        ptr, n, on_dev = _ptr(buf) if len(buf) else None, len(buf), 0
+                    else:
+                        assert text.is_cuda and text.is_contiguous() and text.element_size() == 1, "a contiguous uint8 device tensor"
+                        _lib.stream_wait()
+                        ptr, n, on_dev = C.c_void_p(text.data_ptr()), int(text.numel()), 1
+                    _lib.check(lib.pgx_seqdb_builder_feed(b, ptr, n, on_dev, 1), "pgx_seqdb_builder_feed")
+                _lib.check(lib.pgx_seqdb_builder_finish(b, C.byref(self.h), C.byref(names), C.byref(nl), C.byref(nr), C.byref(nb)),
+                           "pgx_seqdb_builder_finish")
+            finally:
+                lib.pgx_seqdb_builder_close(b)
+        self._names = C.string_at(names.value, nl.value)
+        lib.pgx_free(names)
+        self.names = self._names.decode("latin-1").split("\n")[:-1]
+        self.n_reads, self.n_bases = int(nr.value), int(nb.value)
+        self.rlen_by_rid = np.zeros(self.n_reads, np.uint32)
+        _lib.check(lib.pgx_seqdb_read_lengths(self.h, _ptr(self.rlen_by_rid), self.n_reads), "pgx_seqdb_read_lengths")
+        return self
+
     def save(self, prefix: str):
-        """<prefix>.seqdb and <prefix>.idx of a from_fasta database whose bytes are in place (pgx_seqdb_save): shmr_mkseqdb's two files"""
+        """<prefix>.seqdb and <prefix>.idx of a from_fasta / from_reads database whose bytes are in place (pgx_seqdb_save): shmr_mkseqdb's two files"""
         _lib.check(self._lib.pgx_seqdb_save(self.h, self._names, len(self._names), os.fsencode(prefix)), "pgx_seqdb_save")
 
     # ---- multi-GPU hand-over on device pointers (include/pgx.h, SURVEY 8e) ------------------------------------------
@@ -1245,7 +1285,7 @@ def polish(rdb: "ResidentDB", read_top, read_counts, contig_fasta, mapping_nchun
     return fasta
 
 
-def assemble(seqdb_prefix: str, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: int = 0, cns_nchunk: int = 0, min_len: int = 4000,
+def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: int = 0, cns_nchunk: int = 0, min_len: int = 4000,
              min_idt: float = 96.0, with_alt: bool = False, levels=2, reduction=6, window=80, kmer=16, bestn=4, mc_lower=2, mc_upper=240,
              align_bandwidth=100, ovlp_upper=120, chimer_ordered: bool = True, out_dir: str | None = None, device=None) -> dict:
     """pg_run.py from the read database on (:227-386 and, with cns_nchunk > 0, :389-565) in one process, on one ResidentDB loaded once:
@@ -1253,6 +1293,7 @@ def assemble(seqdb_prefix: str, index_nchunk: int, ovlp_nchunk: int, mapping_nch
     DedupStream in chunk order; the string graph (chimer_ordered: the chimer bridge step, which pg_run.py leaves on, under the stated
     pop order), unitigs, contig paths, tiling paths; the contigs of p (and of a with with_alt) laid out from the rows; polish() on the
     primary FASTA.  mc_lower / mc_upper go to the overlap and to the map stage alike, as pg_run.py passes them.
+    seqdb_prefix may be a ResidentDB that carries its read lengths (ResidentDB.from_reads): it is used as it is and left open.
     Returns dict(p_ctg, a_ctg, p_ctg_cns, stats): FASTA bytes (a_ctg / p_ctg_cns None when not asked for) and the stages' statistics
     with their wall times.  With out_dir, p_ctg.fa, a_ctg.fa and p_ctg_cns.fa are written there.  Every handle is closed, also when
     a stage raises."""
@@ -1275,8 +1316,11 @@ def assemble(seqdb_prefix: str, index_nchunk: int, ovlp_nchunk: int, mapping_nch
         return b"".join(b">" + names[c].encode() + b"\n" + data[int(off[c]):int(off[c + 1])] + b"\n" for c in range(len(off) - 1))
 
     with contextlib.ExitStack() as es:
-        rdb = ResidentDB(read_seqdb(seqdb_prefix), device)
-        es.callback(rdb.close)
+        if isinstance(seqdb_prefix, ResidentDB):
+            rdb = seqdb_prefix
+        else:
+            rdb = ResidentDB(read_seqdb(seqdb_prefix), device)
+            es.callback(rdb.close)
         lap("load")
         ixs = [rdb.index(index_nchunk, c, levels, reduction, window, kmer) for c in range(1, int(index_nchunk) + 1)]
         top = np.concatenate([ix.top for ix in ixs]) if ixs else np.zeros(0, MM_DTYPE)
