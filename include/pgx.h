@@ -734,9 +734,36 @@ int pgx_khash_slot_order(const uint64_t *keys, size_t n, uint64_t *out);
  * the home of every key: removed in round 4) */
 int pgx_khash_slot_order_ex(const uint64_t *keys, size_t n, int touch, uint64_t *out);
 
+/* ---- shimmer chain alignment: shmr_aln (src/shmr_align.c:21-160) for a batch of list pairs.  For a pair (list 0, list 1) the shared
+ * shimmers are chained into co-linear runs: list 1 is walked in order; a shimmer whose hash x >> 8 list 0 lacks, or holds more than
+ * max_repeat times, is skipped; each occurrence in list 0 (in list order) on the same strand is a candidate, appended to the chain opened
+ * so far whose last element lies at or before it in list 0, closer than max_dist in list 0's positions, with the smallest change of the
+ * offset |pos0 - pos1| below max_diff (the first such chain among equals), or opens a chain.  The walk ends after a shimmer whose last scan
+ * saw more than 4,800 chains of fewer than 3 elements (MAX_SMALL_ALNS).  DESIGN.md section 4.9 states the rule in full.
+ *   mm0 / off0 / n_lists0 : the lists of side 0 back to back, list l at mm0[off0[l] .. off0[l + 1]) (n_lists0 + 1 offsets from 0); side 1 alike.
+ *                           A list of side 0 is indexed once, however many pairs name it.
+ *   pairs                 : n_pairs pairs (list of side 0, list of side 1).
+ *   *pair_off, *chain_off, *idx0, *idx1 (each the caller's, pgx_free): pair p owns the chains [pair_off[p], pair_off[p + 1]) in the order
+ *                           the reference opens them, chain c the elements [chain_off[c], chain_off[c + 1]) in the order it pushes them,
+ *                           element e = (idx0[e], idx1[e]), indices into the pair's two lists.  n_pairs + 1 and n_chains + 1 offsets.
+ * PGX_ESTATE without pgx_init; PGX_EARG for a null argument, a pair that names a list out of range, offsets that do not start at 0 or
+ * decrease, a list (or a side) of 2^31 entries and more, and for direction != 0: the reference's reversed walk begins by reading
+ * mmers1->a[n], one past the list, so it has no answer to reproduce.  PGX_ENOMEM leaves nothing allocated.  After any failure the four
+ * outputs are untouched.  PGX_SHMR_ALN_LDS=<chains>: a test hook, the chains whose state the walk keeps in LDS (default and most 1024).
+ * Device memory is booked as "shmr_aln". ---- */
+typedef struct { uint32_t list0, list1; } pgx_shmr_aln_pair;
+typedef struct {
+  uint64_t n_pairs, n_lists0, n_candidates, n_chains, n_elems, n_stopped;   /* n_candidates: the bound the state was sized by; n_stopped: pairs ended by the small-chain count */
+  double gpu_ms, index_ms, walk_ms, unroll_ms;   /* host clock: the whole call; upload + index of side 0; bounds + walk; CSR + download */
+} pgx_shmr_aln_stats;
+int pgx_shmr_aln_batch(const pgx_mm128 *mm0, const uint64_t *off0, size_t n_lists0, const pgx_mm128 *mm1, const uint64_t *off1, size_t n_lists1,
+                       const pgx_shmr_aln_pair *pairs, size_t n_pairs, uint8_t direction, uint32_t max_diff, uint32_t max_dist, uint32_t max_repeat,
+                       uint64_t **pair_off, uint64_t **chain_off, uint32_t **idx0, uint32_t **idx1, pgx_shmr_aln_stats *stats);
+
 /* ---- shimmer4py surface (py/peregrine/build_shimmer4py.py:8-84), GPU-backed single-call forms ----
- * NOT exported: shmr_aln / free_shmr_alns (build_shimmer4py.py:64-77; src/shmr_align.c is the consensus stage's aligner, out of
- * scope per SURVEY.md section 2 #10) -- a caller that needs them keeps the reference's own shimmer4py for those two symbols. */
+ * NOT exported under their own names: shmr_aln / free_shmr_alns (build_shimmer4py.py:64-77; src/shmr_align.c).  Their answer is
+ * offered for a batch of list pairs by pgx_shmr_aln_batch (above), chain for chain the reference's; what it hands out is flat arrays
+ * released with pgx_free, not the reference's nested kvecs, so the two names themselves stay with the reference's own shimmer4py. */
 typedef struct { size_t n, m; pgx_mm128 *a; } mm128_v; /* kvec layout, src/shimmer.h:27-30; .a is malloc'd, caller frees */
 typedef pgx_match ovlp_match_t;
 void decode_biseq(uint8_t *src, char *seq, size_t len, uint8_t strand);

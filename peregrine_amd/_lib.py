@@ -123,6 +123,17 @@ class MapMergeStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ShmrAlnStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_pairs", "n_lists0", "n_candidates", "n_chains", "n_elems", "n_stopped")] + \
+               [(n, C.c_double) for n in ("gpu_ms", "index_ms", "walk_ms", "unroll_ms")]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+SHMR_ALN_PAIR_DTYPE = np.dtype([("list0", "<u4"), ("list1", "<u4")])
+
+
 # every symbol include/pgx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "pgx_init", "pgx_shutdown", "pgx_last_error", "pgx_device_count", "pgx_version", "pgx_free",
@@ -145,7 +156,7 @@ EXPORTS = [
     "pgx_overlap_resident_dev", "pgx_copy_dev", "pgx_seqdb_adopt_dev", "pgx_stream_wait", "pgx_stream_signal",
     "pgx_align_batch2", "pgx_contigs_resident", "pgx_contigs_chunk",
     "pgx_cns_call", "pgx_cns_call_dev", "pgx_cns_tags", "pgx_falcon_align", "pgx_cns_pieces",
-    "pgx_cns_layout", "pgx_cns_job_resident", "pgx_cns_job",
+    "pgx_cns_layout", "pgx_cns_job_resident", "pgx_cns_job", "pgx_shmr_aln_batch",
     "build_shimmer_map4py", "get_shimmers_for_read", "get_mmer_count", "get_shimmer_hits", "pgx_shimmer_map_free",
 ]
 
@@ -283,6 +294,8 @@ def load():
         lib.pgx_map_merge_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.pgx_map_merge_rows.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.pgx_map_merge.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p, C.c_void_p]
+        lib.pgx_shmr_aln_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.build_shimmer_map4py.restype = None
         lib.build_shimmer_map4py.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.get_shimmers_for_read.restype = None

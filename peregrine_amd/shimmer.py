@@ -362,6 +362,71 @@ def mm_count(mm: np.ndarray) -> np.ndarray:
     return _lib.take(out.value, n.value, MC_DTYPE)
 
 
+def _pool_lists(lists):
+    """shimmer lists back to back: (the pool, its len(lists) + 1 offsets)"""
+    lists = [np.ascontiguousarray(l, MM_DTYPE) for l in lists]
+    off = np.zeros(len(lists) + 1, np.uint64)
+    np.cumsum([len(l) for l in lists], out=off[1:])
+    return (np.concatenate(lists) if lists else np.zeros(0, MM_DTYPE)), off
+
+
+def shimmer_alns(lists0, lists1, pairs=None, max_diff=100, max_dist=1200, max_repeat=1, direction=0, device=None, stats: dict | None = None):
+    """shmr_aln (src/shmr_align.c:21-160) for a batch of list pairs on the GPU (pgx_shmr_aln_batch): the shared shimmers of lists0[a] and
+    lists1[b] chained into co-linear runs, chain for chain the reference's.  lists0, lists1: lists of MM_DTYPE arrays; a single array
+    for lists0 is that one list against every lists1[j].  pairs: (a, b) index pairs; None pairs lists0[i] with lists1[i].  Returns per
+    pair the list of its chains, each an (idx0, idx1) pair of uint32 arrays of equal length, indices into the pair's two lists.
+    direction must be 0: the reference's reversed walk reads one entry past its second list and has no answer to reproduce."""
+    _lib.init(device)
+    one = isinstance(lists0, np.ndarray)
+    lists0 = [lists0] if one else list(lists0)
+    lists1 = list(lists1)
+    if pairs is None:
+        if not one and len(lists0) != len(lists1):
+            raise ValueError(f"{len(lists0)} lists against {len(lists1)}: give pairs")
+        pairs = [(0 if one else i, i) for i in range(len(lists1))]
+    pr = np.zeros(len(pairs), _lib.SHMR_ALN_PAIR_DTYPE)
+    if len(pairs):
+        p = np.asarray(pairs, np.int64).reshape(-1, 2)
+        if p.min() < 0 or p.max() >= 2**32:
+            raise _lib.PgxError(f"pgx_shmr_aln_batch: a pair names a list out of range ({len(lists0)}, {len(lists1)} lists)")
+        pr["list0"], pr["list1"] = p[:, 0], p[:, 1]
+    mm0, off0 = _pool_lists(lists0)
+    mm1, off1 = _pool_lists(lists1)
+    po, co, i0, i1 = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    st = _lib.ShmrAlnStats()
+    _lib.check(_lib.load().pgx_shmr_aln_batch(_ptr(mm0), _ptr(off0), len(lists0), _ptr(mm1), _ptr(off1), len(lists1), _ptr(pr), len(pr), int(direction),
+                                              int(max_diff), int(max_dist), int(max_repeat), C.byref(po), C.byref(co), C.byref(i0), C.byref(i1), C.byref(st)),
+               "pgx_shmr_aln_batch")
+    pair_off = _lib.take(po.value, len(pr) + 1, np.dtype("<u8")).astype(np.int64)
+    n_chains = int(pair_off[-1])
+    chain_off = _lib.take(co.value, n_chains + 1, np.dtype("<u8")).astype(np.int64)
+    n_elems = int(chain_off[-1])
+    idx0, idx1 = _lib.take(i0.value, n_elems, np.dtype("<u4")), _lib.take(i1.value, n_elems, np.dtype("<u4"))
+    if stats is not None:
+        stats.update(st.asdict())
+    co_l = chain_off.tolist()
+    return [[(idx0[co_l[c]:co_l[c + 1]], idx1[co_l[c]:co_l[c + 1]]) for c in range(a, b)] for a, b in zip(pair_off[:-1].tolist(), pair_off[1:].tolist())]
+
+
+def mmer2tuple(mmer):
+    """py/peregrine/utils.py:17-25 on one MM_DTYPE entry: (mmer, span, rid, pos_end, direction)"""
+    x, y = int(mmer["x"]), int(mmer["y"])
+    return (x >> 8, x & 0xFF, y >> 32, ((y & 0xFFFFFFFF) >> 1) + 1, y & 1)
+
+
+def get_shimmer_alns(shimmers0, shimmers1, direction=0, max_diff=100, max_dist=1200, max_repeat=1):
+    """py/peregrine/utils.py:52-73 on two MM_DTYPE arrays: per chain (the list of (mmer2tuple, mmer2tuple) pairs, np.max(d), np.mean(d),
+    np.min(d)).  As in the script, all three numbers come from the LAST pair's d = pos_end0 - pos_end1 alone (it reduces the scalar d,
+    not the offsets it collected), so they are equal."""
+    shimmers0, shimmers1 = np.ascontiguousarray(shimmers0, MM_DTYPE), np.ascontiguousarray(shimmers1, MM_DTYPE)
+    aln_chains = []
+    for idx0, idx1 in shimmer_alns(shimmers0, [shimmers1], None, max_diff, max_dist, max_repeat, direction)[0]:
+        chain = [(mmer2tuple(shimmers0[a]), mmer2tuple(shimmers1[b])) for a, b in zip(idx0.tolist(), idx1.tolist())]
+        d = chain[-1][0][3] - chain[-1][1][3]
+        aln_chains.append((chain, np.max(d), np.mean(d), np.min(d)))
+    return aln_chains
+
+
 # ---- file-level stages: drop-ins for the two executables -------------------------------------------------------
 def shmr_index(seqdb_prefix: str, out_prefix: str = "shimmer", total_chunk=1, mychunk=1, levels=2, reduction=6,
                write_l0=1, window=80, kmer=16, device=None) -> dict:
