@@ -92,7 +92,7 @@ void pgx_seqdb_free(pgx_seqdb *db);
  * the database, or here): the index stage's closed-form kernels and every alignment kernel of the default path read the packs.  Refused --
  * PGX_ESTATE, bytes kept -- for a database with a read that holds an ambiguous base (sketched run by run / aligned nibble by nibble from the
  * bytes: src/mm_sketch.c:112-113, src/DWmatch.c:136-137) or a read longer than 65,535 bases.  Afterwards the entry points that need bytes (w / k
- * other than 80 / 16, want_l0, pgx_sketch_batch) return PGX_ESTATE; a buffer handed over with pgx_seqdb_adopt_dev is no longer referenced.
+ * other than 80 / 16, want_l0, PGX_INDEX_HPC, pgx_sketch_batch) return PGX_ESTATE; a buffer handed over with pgx_seqdb_adopt_dev is no longer referenced.
  * A database with ambiguous bases gives its bytes back through pgx_seqdb_compact_bytes instead. */
 int pgx_seqdb_release_bytes(pgx_seqdb *db);
 int pgx_seqdb_has_bytes(const pgx_seqdb *db);
@@ -121,8 +121,14 @@ typedef struct {
   int reduction;     /* -r (<256) */
   int window;        /* -w (24..255) */
   int kmer;          /* -k (12..28) */
-  int want_l0;       /* -m : also return / write the L0 list and its counts */
+  int want_l0;       /* -m : also return / write the L0 list and its counts; | PGX_INDEX_HPC: see below */
 } pgx_index_params;
+/* -H : homopolymer-compressed shimmers, mm_sketch's is_hpc = 1 (src/mm_sketch.c:89-99): minimizers of the compressed read, positions and
+ * spans in raw coordinates.  A flag OR-ed into want_l0 (whose own values stay 0, 1, or "another number": general path, no L0 files), so the
+ * struct keeps its size and callers built against an older header need no recompile.  (A want_l0 with bit 8 set -- 256, any negative number
+ * -- therefore no longer means "another number": pass 2 for that.)  With it the stage takes the general path (sketch,
+ * reduce x levels, count) and reads the seqdb's bytes: PGX_ESTATE once they are released or compacted.  Files keep their names and formats. */
+#define PGX_INDEX_HPC 0x100
 
 typedef struct {
   pgx_mm128 *l0; size_t n_l0;           /* only when want_l0 */
@@ -501,6 +507,8 @@ int pgx_map_merge_rows(const int64_t *rows, size_t n, int64_t *out, pgx_map_merg
 int pgx_map_merge(const char *const *paths, size_t n_paths, const char *out_path, pgx_map_merge_stats *stats);
 
 /* ---- batch level ---- */
+/* pgx_sketch_batch with mm_sketch's is_hpc = 1 (any 0 < k <= 28, 0 < w < 256): same arguments, same ownership */
+int pgx_sketch_batch_hpc(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, pgx_mm128 **out, size_t *n_out);
 int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, pgx_mm128 **out,
                      size_t *n_out);  /* read_slots index the idx-file order; output in that order */
 int pgx_reduce_batch(const pgx_mm128 *in, size_t n, int rs, pgx_mm128 **out, size_t *n_out);

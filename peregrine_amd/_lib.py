@@ -41,6 +41,14 @@ class IndexParams(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("total_chunk", "mychunk", "levels", "reduction", "window", "kmer", "want_l0")]
 
 
+INDEX_HPC = 0x100   # PGX_INDEX_HPC: OR-ed into IndexParams.want_l0, homopolymer-compressed shimmers (mm_sketch's is_hpc = 1)
+
+
+def want_l0_word(want_l0, hpc=False) -> int:
+    """IndexParams.want_l0 of a -m value (1: L0 lists too; another non-zero number: the general path without them) and the hpc flag"""
+    return (1 if want_l0 == 1 else 2 if want_l0 else 0) | (INDEX_HPC if hpc else 0)
+
+
 class IndexResult(C.Structure):
     _fields_ = [("l0", C.c_void_p), ("n_l0", C.c_size_t), ("l0_mc", C.c_void_p), ("n_l0_mc", C.c_size_t),
                 ("top", C.c_void_p), ("n_top", C.c_size_t), ("top_mc", C.c_void_p), ("n_top_mc", C.c_size_t),
@@ -149,7 +157,7 @@ EXPORTS = [
     "pgx_sgraph_unitigs", "pgx_unitigs_build", "pgx_unitigs_stats", "pgx_unitigs_table", "pgx_unitigs_paths", "pgx_unitigs_text", "pgx_unitigs_free",
     "pgx_unitigs_contig_paths", "pgx_ctg_paths_build", "pgx_ctg_paths_stats", "pgx_ctg_paths_table", "pgx_ctg_paths_rows", "pgx_ctg_paths_utg_text", "pgx_ctg_paths_ctg_text", "pgx_ctg_paths_free",
     "pgx_sgraph_parse", "pgx_tiling_build", "pgx_tiling_stats", "pgx_tiling_rows", "pgx_tiling_names", "pgx_tiling_text", "pgx_tiling_contigs", "pgx_tiling_free", "pgx_tiling_chunk",
-    "pgx_sketch_batch", "pgx_reduce_batch", "pgx_count_batch", "pgx_align_batch",
+    "pgx_sketch_batch", "pgx_sketch_batch_hpc", "pgx_reduce_batch", "pgx_count_batch", "pgx_align_batch",
     "decode_biseq", "encode_biseq", "mm_sketch", "mm_reduce", "ovlp_match", "free_ovlp_match", "read_mmlist", "write_mmlist",
     "pgx_map", "pgx_map_chunk", "pgx_map_rows", "pgx_map_rows_chunk", "pgx_map_merge_dev", "pgx_map_merge_rows", "pgx_map_merge", "pgx_khash_slot_order", "pgx_khash_slot_order_ex",
     "pgx_seqdb_upload_dev", "pgx_index_resident_dev", "pgx_pairs_prepare_dev", "pgx_pairs_scatter_dev", "pgx_overlap_records_dev",
@@ -265,6 +273,7 @@ def load():
         lib.pgx_tiling_free.argtypes = [C.c_void_p]
         lib.pgx_tiling_chunk.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p]
         lib.pgx_sketch_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        lib.pgx_sketch_batch_hpc.argtypes = lib.pgx_sketch_batch.argtypes
         lib.pgx_reduce_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         lib.pgx_count_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.pgx_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]

@@ -1005,11 +1005,10 @@ uint64_t pgx_seqdb_bases(const pgx_seqdb *db) { return db ? db->bases : 0; }
 uint32_t pgx_seqdb_reads(const pgx_seqdb *db) { return db ? (uint32_t)db->rid.size() : 0; }
 
 // ---- batch level -----------------------------------------------------------------------------------------
-int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, pgx_mm128 **out,
-                     size_t *n_out) {
+static int sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, bool hpc, pgx_mm128 **out, size_t *n_out) {
   return guarded([&]() -> int {
     require_ready();
-    PGX_REQUIRE(db && out && n_out, PGX_EARG, "pgx_sketch_batch: null argument");
+    PGX_REQUIRE(db && out && n_out && (n == 0 || read_slots), PGX_EARG, "pgx_sketch_batch: null argument");
     PGX_REQUIRE(w > 0 && w < 256 && k > 0 && k <= 28, PGX_EARG, "need 0<w<256, 0<k<=28 (src/mm_sketch.c:77-78)");
     std::vector<ReadDesc> reads(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -1020,7 +1019,7 @@ int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int 
     }
     DevBuf<pgx_mm128> d;
     size_t m = 0;
-    dev_sketch(db, reads, w, k, d, m, nullptr);
+    dev_sketch(db, reads, w, k, d, m, nullptr, hpc);
     std::vector<pgx_mm128> h(m);
     d.download(h.data(), m);
     pgx::sync();
@@ -1028,6 +1027,12 @@ int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int 
     *n_out = m;
     return PGX_OK;
   });
+}
+int pgx_sketch_batch(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, pgx_mm128 **out, size_t *n_out) {
+  return sketch_batch(db, read_slots, n, w, k, false, out, n_out);
+}
+int pgx_sketch_batch_hpc(pgx_seqdb *db, const uint32_t *read_slots, uint32_t n, int w, int k, pgx_mm128 **out, size_t *n_out) {
+  return sketch_batch(db, read_slots, n, w, k, true, out, n_out);
 }
 
 int pgx_reduce_batch(const pgx_mm128 *in, size_t n, int rs, pgx_mm128 **out, size_t *n_out) {

@@ -294,8 +294,8 @@ static int main_mkseqdb(int argc, char **argv) {
 static int run_index_args(int argc, char **argv, pgx_seqdb *db, const char *served_prefix, char *msg, size_t cap) {
   const char *p = "seq_dataset", *o = "shimmer";
   pgx_index_params ip = {1, 1, 2, 6, 80, 16, 1}; /* -t -c -l -r -w -k -m : shmr_index.c:21-23,49-55 */
-  int c;
-  while ((c = getopt(argc, argv, "p:o:t:c:l:r:m:w:k:")) != -1) {
+  int c, m = 1, hpc = 0; /* -H: homopolymer-compressed shimmers (minimap2's letter; free in the reference's getopt string) */
+  while ((c = getopt(argc, argv, "p:o:t:c:l:r:m:w:k:H")) != -1) {
     switch (c) {
       case 'p': p = optarg; break;
       case 'o': o = optarg; break;
@@ -303,12 +303,14 @@ static int run_index_args(int argc, char **argv, pgx_seqdb *db, const char *serv
       case 'c': ip.mychunk = atoi(optarg); break;
       case 'l': ip.levels = atoi(optarg); break;
       case 'r': ip.reduction = atoi(optarg); break;
-      case 'm': ip.want_l0 = atoi(optarg); break;
+      case 'm': m = atoi(optarg); break;
+      case 'H': hpc = 1; break;
       case 'w': ip.window = atoi(optarg); break;
       case 'k': ip.kmer = atoi(optarg); break;
       default: return 1; /* the reference returns 1 on a missing option argument (:93-107) */
     }
   }
+  ip.want_l0 = (m == 1 ? 1 : m ? 2 : 0) | (hpc ? PGX_INDEX_HPC : 0); /* (only 1 writes L0 files: shmr_index.c:165; another number: no fused path) */
   if (!db) {
     const int served = try_server("shmr_index", p, argc, argv);
     if (served >= 0) return served;

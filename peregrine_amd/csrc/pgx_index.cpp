@@ -23,7 +23,14 @@ T *download_list(const DevBuf<T> &d, size_t n) {
   return h;
 }
 
-void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, DeviceIndex *keep = nullptr, bool host_arrays = true) {
+// want_l0 without the flag it carries
+int want_l0_of(const pgx_index_params *p) { return p->want_l0 & ~PGX_INDEX_HPC; }
+
+void run_index(pgx_seqdb *db, const pgx_index_params *given, pgx_index_result *out, DeviceIndex *keep = nullptr, bool host_arrays = true) {
+  const bool hpc = (given->want_l0 & PGX_INDEX_HPC) != 0;   // homopolymer-compressed shimmers: never the fused kernels
+  pgx_index_params plain = *given;
+  plain.want_l0 = want_l0_of(given);
+  const pgx_index_params *p = &plain;
   ++index_generation();   // every index-stage call rewrites the "ix.*" workspaces: views of them handed out earlier are stale now
   memset(out, 0, sizeof(*out));
   if (keep) keep->valid = false;
@@ -64,14 +71,15 @@ void run_index(pgx_seqdb *db, const pgx_index_params *p, pgx_index_result *out, 
   if (trace) fprintf(stderr, "[pgx] index: read selection %.2f ms\n", wall_ms() - t0);
 
   // The final-level list on the device: the fused path (closed-form kernels fused with the per-read reduce: pg_run.py's defaults) where it
-  // takes the chunk, else -- other (w, k), or the level-0 list is wanted too -- sketch, then one list-wide reduce per level.
+  // takes the chunk, else -- other (w, k), the level-0 list is wanted too, or homopolymer-compressed shimmers (hpc) -- sketch, then one
+  // list-wide reduce per level.
   const pgx_mm128 *d_top = nullptr;
   size_t ntop = 0;
   DevBuf<pgx_mm128> l0, l1, l2;
-  const bool fused = !p->want_l0 && dev_index_fused(db, reads, p->window, p->kmer, p->reduction, p->levels, &d_top, &ntop, &plan, &out->reads_literal);
+  const bool fused = !p->want_l0 && !hpc && dev_index_fused(db, reads, p->window, p->kmer, p->reduction, p->levels, &d_top, &ntop, &plan, &out->reads_literal);
   if (!fused) {
     size_t n0 = 0, n1 = 0, n2 = 0;
-    dev_sketch(db, reads, p->window, p->kmer, l0, n0, &out->reads_literal);
+    dev_sketch(db, reads, p->window, p->kmer, l0, n0, &out->reads_literal, hpc);
     PGX_REQUIRE(n0 < (1ULL << 31), PGX_EARG, "chunk too large: %zu L0 minimizers (use more index chunks)", n0);
     if (p->want_l0) {
       DevBuf<pgx_mm_count> mc;
@@ -178,7 +186,7 @@ int pgx_index_resident_dev(pgx_seqdb *db, const pgx_index_params *p, pgx_index_r
     require_ready();
     PGX_REQUIRE(db && stats && d_top && n_top && d_mc && n_mc, PGX_EARG, "pgx_index_resident_dev: null argument");
     check_params(p);
-    PGX_REQUIRE(!p->want_l0, PGX_EARG, "pgx_index_resident_dev returns the final level only");
+    PGX_REQUIRE(!want_l0_of(p), PGX_EARG, "pgx_index_resident_dev returns the final level only");
     held = DeviceIndex();
     held_top.release();
     run_index(db, p, stats, &held, false);
@@ -206,7 +214,7 @@ int pgx_index_chunk_db(pgx_seqdb *db, const char *out_prefix, const pgx_index_pa
     DeviceIndex dev;
     run_index(db, p, &res, &dev, true);
     // file names and order of writing as in shmr_index.c:165-233
-    if (p->want_l0 == 1) {
+    if (want_l0_of(p) == 1) {
       write_counted(level_path(out_prefix, 0, false, p->mychunk, p->total_chunk), res.l0, res.n_l0, sizeof(pgx_mm128));
       write_counted(level_path(out_prefix, 0, true, p->mychunk, p->total_chunk), res.l0_mc, res.n_l0_mc, sizeof(pgx_mm_count));
     }

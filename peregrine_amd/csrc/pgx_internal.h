@@ -394,7 +394,7 @@ int seqdb_take_dev(DevBuf<uint8_t> &&bytes, size_t nbytes, const uint32_t *rid, 
 // ---------------------------------------------------------------------------------------------------------
 // L0 minimizers of the given reads (device array of ReadDesc, in output order). Returns device list.
 void dev_sketch(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, int k, DevBuf<pgx_mm128> &out,
-                size_t &n_out, uint32_t *n_literal);
+                size_t &n_out, uint32_t *n_literal, bool hpc = false);   // hpc: mm_sketch's is_hpc = 1 (pgx_sketch_hpc.hip)
 // fused index path: k_sketch_blk, or k_sketch_wave -> per-read reduce x levels in LDS; redo passes for the reads they flag; ordered
 // gather.  Returns false (and leaves the outputs untouched) when the chunk needs the general path (other w/k ...).
 // plan: the database's selection of `reads`, whose descriptors and slab offsets stay on the device with it (nullptr: uploaded for this call only)
@@ -412,6 +412,9 @@ void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint
 void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list, int w,
                            int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
                            const uint8_t *bytes = nullptr);
+void launch_sketch_hpc(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list, int w, int k,
+                       pgx_mm128 *d_slab, const uint64_t *d_slab_off, int off_by_list, uint32_t *d_counts, uint32_t *d_flags,
+                       uint32_t *d_need);
 bool sketch_blk_supported(int w, int k, int rs, int levels);
 void launch_sketch_blk(const pgx_seqdb *db, const ReadDesc *d_reads, uint32_t n, int rs, int levels, pgx_mm128 *d_slab,
                        const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags);

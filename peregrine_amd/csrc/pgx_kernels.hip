@@ -11,28 +11,9 @@
 #include <algorithm>
 
 #include "pgx_internal.h"
+#include "pgx_sketch_win.h"
 
 namespace pgx {
-
-// =========================================================================================================
-// minimizer hash (src/mm_sketch.c:23-32), 64-bit form for any k <= 28
-// =========================================================================================================
-__device__ __forceinline__ uint64_t mix64(uint64_t key, uint64_t mask) {
-  key = (~key + (key << 21)) & mask;
-  key = key ^ key >> 24;
-  key = ((key + (key << 3)) + (key << 8)) & mask;
-  key = key ^ key >> 14;
-  key = ((key + (key << 2)) + (key << 4)) & mask;
-  key = key ^ key >> 28;
-  key = (key + (key << 31)) & mask;
-  return key;
-}
-
-__device__ __forceinline__ int code_of_nibble(uint32_t b) {
-  // seqdb low nibble is one-hot A=1 C=2 G=4 T=8 (src/shmr_utils.c:18-30); anything else decodes to 'N'
-  b &= 0xF;
-  return (b == 1) ? 0 : (b == 2) ? 1 : (b == 4) ? 2 : (b == 8) ? 3 : 4;
-}
 
 // =========================================================================================================
 // mm_reduce (src/shmr_reduce.c:53-90), data-parallel restatement:
@@ -172,38 +153,6 @@ __global__ void k_need_of_list(const uint32_t *__restrict__ need, const uint32_t
   if (i < n) out[i] = need[list[i]];
 }
 
-// Running extremum within blocks of w consecutive elements (block b = [b w, (b+1) w)), the whole wavefront walking the array 64
-// elements at a time with coalesced accesses: a segmented Hillis-Steele scan (segment heads at multiples of w) plus a carry
-// between the 64-element slices.  FWD: dst[i] = op(src[block start .. i]);  !FWD: dst[i] = op(src[i .. block end]).
-template <bool MIN, bool FWD>
-__device__ __forceinline__ void block_running_extremum(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, int count, int w,
-                                                       int lane) {
-  const uint64_t neutral = MIN ? ~0ULL : 0ULL;
-  auto op = [](uint64_t a, uint64_t b) { return MIN ? (a < b ? a : b) : (a > b ? a : b); };
-  const int nslice = (count + 63) / 64;
-  uint64_t carry = neutral;
-  for (int sl = 0; sl < nslice; ++sl) {
-    const int c0 = (FWD ? sl : nslice - 1 - sl) * 64;
-    const int i = c0 + (FWD ? lane : 63 - lane);  // scan order: ascending i when FWD, descending otherwise
-    uint64_t v = i < count ? src[i] : neutral;
-    // a segment starts at this lane (in scan order) when i is the first (FWD) / last (!FWD) element of its block
-    int f = i < count && (FWD ? (i % w == 0) : (i % w == w - 1 || i == count - 1)) ? 1 : 0;
-    const int head = f;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t vu = (uint64_t)__shfl_up((int)(v >> 32), d, 64) << 32 | (uint32_t)__shfl_up((int)v, d, 64);
-      const int fu = __shfl_up(f, d, 64);
-      if (lane >= d) {
-        if (!f) v = op(v, vu);
-        f |= fu;
-      }
-    }
-    if (!f) v = op(v, carry);  // no segment head at or before this lane inside the slice: the open segment continues
-    if (i < count) dst[i] = v;
-    (void)head;
-    carry = (uint64_t)__shfl((int)(v >> 32), 63, 64) << 32 | (uint32_t)__shfl((int)v, 63, 64);
-  }
-}
-
 // =========================================================================================================
 // k_sketch_general: the closed form of pgx_sketch_fast.hip (see its header) for ANY window and k-mer size
 // (0 < w < 256, 0 < k <= 28; pg_run.py exposes both as --shimmer-w / --shimmer-k), one wavefront per read, three
@@ -288,73 +237,10 @@ __global__ __launch_bounds__(64) void k_sketch_general(const uint8_t *__restrict
       continue;
     }
     __syncthreads();  // (one wavefront per block: orders this wave's global writes before its reads below)
-    // ---- pass 2: window minima in O(1) per entry (van Herk / Gil-Werman over blocks of w entries) ---------------------
-    // T1 = running minimum from the start of the entry's block, T2 = running minimum from the end of its block;
-    // the window [s, s+w) is the tail of block(s) plus the head of the next block: WM[s] = min(T2[s], T1[s+w-1]).
-    const int nwin = n - w + 1;  // number of full windows (<= 0: short read)
-    if (nwin > 0) {
-      block_running_extremum<true, true>(H, T1, n, w, lane);
-      block_running_extremum<true, false>(H, T2, n, w, lane);
-      __syncthreads();
-      for (int v0 = 0; v0 < nwin; v0 += 64) {
-        const int v = v0 + lane;
-        if (v < nwin) WM[v] = (v % w == 0) ? T1[v + w - 1] : min(T2[v], T1[v + w - 1]);
-      }
-      __syncthreads();
-      // the same over WM with maxima: GX(p) = max of WM over the (up to w) windows that contain entry p
-      block_running_extremum<false, true>(WM, T1, nwin, w, lane);
-      block_running_extremum<false, false>(WM, T2, nwin, w, lane);
-    }
-    // rightmost smallest of the first min(n, w - 1) entries (all n entries for a short read)
-    const int lim = nwin > 0 ? w - 1 : n;
-    uint64_t bh = ~0ULL;
-    int bi = -1;
-    for (int v = lane; v < lim; v += 64) {
-      const uint64_t x = H[v];
-      if (x <= bh) bh = x, bi = v;  // ascending v per lane: <= keeps the rightmost
-    }
-    for (int d = 32; d; d >>= 1) {
-      const uint64_t oh = (uint64_t)__shfl_xor((int)(bh >> 32), d, 64) << 32 | (uint32_t)__shfl_xor((int)bh, d, 64);
-      const int oi = __shfl_xor(bi, d, 64);
-      if (oi >= 0 && (bi < 0 || oh < bh || (oh == bh && oi > bi))) bh = oh, bi = oi;
-    }
-    const int m_idx = bi;
-    const uint64_t m_h = bh;
-    const uint64_t h_last = nwin > 0 ? H[w - 1] : 0;
-    __syncthreads();
-    // ---- pass 3 ----------------------------------------------------------------------------------------------
+    // ---- passes 2 and 3: the window passes (pgx_sketch_win.h) -------------------------------------------------------
     const uint64_t cap = slab_off[slot + 1] - slab_off[slot];
-    pgx_mm128 *dst = slab + slab_off[slot];
-    uint32_t nout = 0;
     bool over = false;
-    for (int p0 = 0; p0 < n; p0 += 64) {
-      const int p = p0 + lane;
-      bool emit = false;
-      uint64_t hp = 0;
-      if (p < n) {
-        hp = H[p];
-        if (nwin > 0) {
-          const int s0 = p - w + 1 > 0 ? p - w + 1 : 0, s1 = p < nwin - 1 ? p : nwin - 1;
-          uint64_t gx = 0;
-          if (s1 - s0 + 1 == w) {  // all w windows exist: tail of block(s0) + head of the next block
-            gx = (s0 % w == 0) ? T1[s1] : max(T2[s0], T1[s1]);
-          } else {  // the first / last w-1 entries of the read: fewer windows, scanned directly
-            for (int sidx = s0; sidx <= s1; ++sidx) gx = max(gx, WM[sidx]);
-          }
-          emit = gx == hp;  // (a window that contains p has minimum <= hash(p))
-          if (p <= w - 2 && hp == m_h) emit = p != m_idx ? true : h_last > m_h;
-        } else {
-          emit = p == m_idx;
-        }
-      }
-      const uint64_t em = __ballot(emit);
-      if (emit) {
-        const uint32_t r = nout + (uint32_t)__builtin_popcountll(em & ((1ULL << lane) - 1));
-        if (r < cap) dst[r] = pgx_mm128{hp << 8 | (uint64_t)k, (uint64_t)rd.rid << 32 | PY[p]};
-        else over = true;
-      }
-      nout += (uint32_t)__builtin_popcountll(em);
-    }
+    const uint32_t nout = sketch_windows<false>(H, PY, WM, T1, T2, n, w, k, lane, (uint64_t)rd.rid << 32, slab + slab_off[slot], cap, 0u, over);
     const bool anyover = __ballot(over) != 0;
     if (lane == 0) {
       counts[slot] = anyover ? 0u : nout;
@@ -402,13 +288,50 @@ void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const s
   }
 }
 
+// dev_sketch's hpc form: every read through k_sketch_hpc (pgx_sketch_hpc.hip), which takes ambiguous bases itself; the reads that outgrow
+// their slabs once more into slabs of exactly the size the first pass reported (exact / exact_off, named in src_of).  Returns how many.
+static uint32_t sketch_hpc_reads(const pgx_seqdb *db, const std::vector<uint32_t> &lens, int w, int k, uint64_t bases, const ReadDesc *d_reads,
+                                 pgx_mm128 *slab, const uint64_t *d_slab_off, uint32_t *counts, uint32_t *d_flags, uint32_t *d_list,
+                                 const pgx_mm128 **d_src_of, DevBuf<pgx_mm128> &exact, DevBuf<uint64_t> &exact_off) {
+  hipStream_t st = ctx().stream;
+  const uint32_t n = (uint32_t)lens.size();
+  DevBuf<uint32_t> need(n);
+  {
+    KernelTimer tm("sketch_hpc", bases);
+    launch_sketch_hpc(db, d_reads, lens, nullptr, w, k, slab, d_slab_off, 0, counts, d_flags, need.p);
+  }
+  const uint32_t n_redo = select_flagged(d_flags, n, d_list);
+  if (!n_redo) return 0;
+  KernelTimer tm("sketch_hpc_redo", 0);
+  std::vector<uint32_t> redo(n_redo), redo_lens(n_redo);
+  PGX_HIP(hipMemcpyAsync(redo.data(), d_list, (size_t)n_redo * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  sync();
+  for (uint32_t i = 0; i < n_redo; ++i) redo_lens[i] = lens[redo[i]];
+  exact_off.alloc((size_t)n_redo + 1);
+  hipLaunchKernelGGL(k_need_of_list, dim3(cdiv(n_redo, 256)), dim3(256), 0, st, need.p, d_list, n_redo, exact_off.p + 1);
+  const uint64_t total = scan_to_total(exact_off.p + 1, exact_off.p, n_redo);
+  exact.alloc(total ? total : 1);
+  PGX_HIP(hipMemsetAsync(d_flags, 0, (size_t)n * sizeof(uint32_t), st));
+  launch_sketch_hpc(db, d_reads, redo_lens, d_list, w, k, exact.p, exact_off.p, 1, counts, d_flags, need.p);
+  uint32_t *d_anybad = ws<uint32_t>("sk.hpc_bad", 1);
+  PGX_HIP(hipMemsetAsync(d_anybad, 0, sizeof(uint32_t), st));
+  reduce_max(d_flags, d_anybad, n);
+  uint32_t anybad = 0;
+  PGX_HIP(hipMemcpyAsync(&anybad, d_anybad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  sync();
+  PGX_REQUIRE(!anybad, PGX_EARG, "a read outgrew a slab of exactly the size its first pass reported");
+  set_sources(d_src_of, d_list, n_redo, exact.p, exact_off.p);
+  return n_redo;
+}
+
 // Level-0 minimizers of `reads`, one contiguous list in `reads` order.  Every read goes through the closed-form kernel of the
 // (w, k) -- k_sketch_wave for k = 16 and w in {64, 80, 96, 128}, k_sketch_general otherwise -- single pass into per-read slabs, then
 // an ordered gather; the reads it flags (an ambiguous base, a slab outgrown by low-complexity sequence) are cut into runs of
 // unambiguous bases that the same kernels sketch (pgx_sketch_n.hip: dev_sketch_nreads).  n_literal (name kept from the C-ABI's
 // reads_literal): how many reads took that second path.
+// hpc: mm_sketch's is_hpc = 1 (sketch_hpc_reads above; n_literal counts the reads sketched a second time).
 void dev_sketch(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, int k, DevBuf<pgx_mm128> &out,
-                size_t &n_out, uint32_t *n_literal) {
+                size_t &n_out, uint32_t *n_literal, bool hpc) {
   n_out = 0;
   if (n_literal) *n_literal = 0;
   const uint32_t n = (uint32_t)reads.size();
@@ -432,26 +355,31 @@ void dev_sketch(const pgx_seqdb *db, const std::vector<ReadDesc> &reads, int w, 
   PGX_HIP(hipMemsetAsync(counts.p, 0, n * sizeof(uint32_t), st));
   PGX_HIP(hipMemsetAsync(d_flags.p, 0, n * sizeof(uint32_t), st));
   PGX_HIP(hipMemsetAsync(d_src_of.p, 0, n * sizeof(pgx_mm128 *), st));
-  // (w, k) outside the specialised kernel's set: the general closed-form kernel takes the wave kernel's place
-  if (k == 16 && (w == 64 || w == 80 || w == 96 || w == 128)) {
-    KernelTimer tm("sketch", bases);
-    launch_sketch_wave(db, d_reads.p, nullptr, n, w, k, slab.p, d_slab_off.p, counts.p, d_flags.p);
-  } else {
-    KernelTimer tm("sketch_general", bases);
-    launch_sketch_general(db, d_reads.p, lens, nullptr, w, k, slab.p, d_slab_off.p, counts.p, d_flags.p);
-  }
-  // the flagged reads: segments of unambiguous bases through the same kernels, exact slabs on demand
-  const uint32_t n_second = select_flagged(d_flags.p, n, d_list.p);
   DevBuf<pgx_mm128> nl0;
   DevBuf<uint64_t> nl0_off;
-  if (n_second) {
-    KernelTimer tm("sketch_nreads", 0);
-    uint64_t tot2 = 0;
-    dev_sketch_nreads(db, d_reads.p, d_list.p, n_second, w, k, nl0, nl0_off, &tot2);
-    dev_scatter_counts(counts.p, d_list.p, n_second, nl0_off.p, nullptr);
-    set_sources(d_src_of.p, d_list.p, n_second, nl0.p, nl0_off.p);
+  if (hpc) {
+    const uint32_t n_redo = sketch_hpc_reads(db, lens, w, k, bases, d_reads.p, slab.p, d_slab_off.p, counts.p, d_flags.p, d_list.p, d_src_of.p, nl0, nl0_off);
+    if (n_literal) *n_literal = n_redo;
+  } else {
+    // (w, k) outside the specialised kernel's set: the general closed-form kernel takes the wave kernel's place
+    if (k == 16 && (w == 64 || w == 80 || w == 96 || w == 128)) {
+      KernelTimer tm("sketch", bases);
+      launch_sketch_wave(db, d_reads.p, nullptr, n, w, k, slab.p, d_slab_off.p, counts.p, d_flags.p);
+    } else {
+      KernelTimer tm("sketch_general", bases);
+      launch_sketch_general(db, d_reads.p, lens, nullptr, w, k, slab.p, d_slab_off.p, counts.p, d_flags.p);
+    }
+    // the flagged reads: segments of unambiguous bases through the same kernels, exact slabs on demand
+    const uint32_t n_second = select_flagged(d_flags.p, n, d_list.p);
+    if (n_second) {
+      KernelTimer tm("sketch_nreads", 0);
+      uint64_t tot2 = 0;
+      dev_sketch_nreads(db, d_reads.p, d_list.p, n_second, w, k, nl0, nl0_off, &tot2);
+      dev_scatter_counts(counts.p, d_list.p, n_second, nl0_off.p, nullptr);
+      set_sources(d_src_of.p, d_list.p, n_second, nl0.p, nl0_off.p);
+    }
+    if (n_literal) *n_literal = n_second;
   }
-  if (n_literal) *n_literal = n_second;
   n_out = (size_t)scan_to_total(counts.p, offs.p, n);
   out.alloc(n_out);
   if (n_out == 0) return;

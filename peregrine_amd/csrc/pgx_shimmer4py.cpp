@@ -65,11 +65,6 @@ void decode_biseq(uint8_t *src, char *seq, size_t len, uint8_t strand) {
 
 void mm_sketch(void *km, const char *str, int len, int w, int k, uint32_t rid, int is_hpc, mm128_v *p) {
   (void)km;
-  if (is_hpc) {
-    set_error("mm_sketch: is_hpc=1 is not on the index path and is not implemented");
-    complain("mm_sketch", PGX_EARG);
-    return;
-  }
   if (len <= 0 || !p) return;
   if (!ctx().ready && pgx_init(0)) return complain("mm_sketch", PGX_EHIP);
   std::vector<uint8_t> enc((size_t)len);
@@ -83,7 +78,7 @@ void mm_sketch(void *km, const char *str, int len, int w, int k, uint32_t rid, i
   int rc = pgx_seqdb_upload(enc.data(), enc.size(), &rid, &l, &off, 1, &db);
   pgx_mm128 *out = nullptr;
   size_t n = 0;
-  if (!rc) rc = pgx_sketch_batch(db, &slot, 1, w, k, &out, &n);
+  if (!rc) rc = is_hpc ? pgx_sketch_batch_hpc(db, &slot, 1, w, k, &out, &n) : pgx_sketch_batch(db, &slot, 1, w, k, &out, &n);
   if (rc) complain("mm_sketch", rc);
   else append(p, out, n);
   free(out);

@@ -185,9 +185,10 @@ class ResidentDB:
         _lib.check(self._lib.pgx_seqdb_save(self.h, self._names, len(self._names), os.fsencode(prefix)), "pgx_seqdb_save")
 
     # ---- multi-GPU hand-over on device pointers (include/pgx.h) ------------------------------------------
-    def index_dev(self, total_chunk=1, mychunk=1, levels=2, reduction=6, window=80, kmer=16):
-        """index stage; returns (IndexOut without arrays, d_top, n_top, d_mc, n_mc): list and counts stay in HBM (library-owned)"""
-        p = _lib.IndexParams(total_chunk, mychunk, levels, reduction, window, kmer, 0)
+    def index_dev(self, total_chunk=1, mychunk=1, levels=2, reduction=6, window=80, kmer=16, hpc=False):
+        """index stage; returns (IndexOut without arrays, d_top, n_top, d_mc, n_mc): list and counts stay in HBM (library-owned).
+        hpc: homopolymer-compressed shimmers (see index)"""
+        p = _lib.IndexParams(total_chunk, mychunk, levels, reduction, window, kmer, _lib.want_l0_word(0, hpc))
         r = _lib.IndexResult()
         d_top, n_top, d_mc, n_mc = C.c_void_p(), C.c_size_t(0), C.c_void_p(), C.c_size_t(0)
         _lib.check(self._lib.pgx_index_resident_dev(self.h, C.byref(p), C.byref(r), C.byref(d_top), C.byref(n_top), C.byref(d_mc),
@@ -277,8 +278,10 @@ class ResidentDB:
             pass
 
     # ---- stages ------------------------------------------------------------------------------------------
-    def index(self, total_chunk=1, mychunk=1, levels=2, reduction=6, window=80, kmer=16, want_l0=False) -> IndexOut:
-        p = _lib.IndexParams(total_chunk, mychunk, levels, reduction, window, kmer, 1 if want_l0 else 0)
+    def index(self, total_chunk=1, mychunk=1, levels=2, reduction=6, window=80, kmer=16, want_l0=False, hpc=False) -> IndexOut:
+        """index stage of one chunk.  hpc: homopolymer-compressed shimmers (mm_sketch's is_hpc = 1, minimap2's -H): minimizers of the read with
+        every run of equal bases taken as one base, positions and spans in raw coordinates; needs the database's bytes."""
+        p = _lib.IndexParams(total_chunk, mychunk, levels, reduction, window, kmer, _lib.want_l0_word(1 if want_l0 else 0, hpc))
         r = _lib.IndexResult()
         _lib.check(self._lib.pgx_index_resident(self.h, C.byref(p), C.byref(r)), "pgx_index_resident")
         return IndexOut(
@@ -298,10 +301,10 @@ class ResidentDB:
         return _lib.take(out.value, n.value, OVLP_DTYPE), st.asdict()
 
     def index_overlap(self, want_index_arrays=False, levels=2, reduction=6, window=80, kmer=16, bestn=4, mc_lower=2,
-                      mc_upper=240, align_bandwidth=100, ovlp_upper=120):
+                      mc_upper=240, align_bandwidth=100, ovlp_upper=120, hpc=False):
         """single-chunk index + overlap in one call; the shimmer list and its counts never leave HBM between the stages.
-        Returns (IndexOut — arrays None unless want_index_arrays —, ovlp records, stats)."""
-        ip = _lib.IndexParams(1, 1, levels, reduction, window, kmer, 0)
+        Returns (IndexOut — arrays None unless want_index_arrays —, ovlp records, stats).  hpc: see index."""
+        ip = _lib.IndexParams(1, 1, levels, reduction, window, kmer, _lib.want_l0_word(0, hpc))
         op = _lib.OverlapParams(1, 1, bestn, mc_lower, mc_upper, align_bandwidth, ovlp_upper)
         r, out, n, st = _lib.IndexResult(), C.c_void_p(), C.c_size_t(0), _lib.OverlapStats()
         _lib.check(self._lib.pgx_index_overlap_resident(self.h, C.byref(ip), C.byref(op), 1 if want_index_arrays else 0,
@@ -313,11 +316,12 @@ class ResidentDB:
         return ix, _lib.take(out.value, n.value, OVLP_DTYPE), st.asdict()
 
     # ---- batch level -------------------------------------------------------------------------------------
-    def sketch(self, read_slots, w=80, k=16) -> np.ndarray:
+    def sketch(self, read_slots, w=80, k=16, hpc=False) -> np.ndarray:
+        """level-0 minimizers of the listed reads (any 0 < k <= 28, 0 < w < 256); hpc: mm_sketch's is_hpc = 1 (pgx_sketch_batch_hpc)"""
         slots = np.ascontiguousarray(read_slots, np.uint32)
         out, n = C.c_void_p(), C.c_size_t(0)
-        _lib.check(self._lib.pgx_sketch_batch(self.h, _ptr(slots), len(slots), w, k, C.byref(out), C.byref(n)),
-                   "pgx_sketch_batch")
+        name = "pgx_sketch_batch_hpc" if hpc else "pgx_sketch_batch"
+        _lib.check(getattr(self._lib, name)(self.h, _ptr(slots), len(slots), w, k, C.byref(out), C.byref(n)), name)
         return _lib.take(out.value, n.value, MM_DTYPE)
 
     def align(self, keys: np.ndarray, band=100) -> np.ndarray:
@@ -429,10 +433,11 @@ def get_shimmer_alns(shimmers0, shimmers1, direction=0, max_diff=100, max_dist=1
 
 # ---- file-level stages: drop-ins for the two executables -------------------------------------------------------
 def shmr_index(seqdb_prefix: str, out_prefix: str = "shimmer", total_chunk=1, mychunk=1, levels=2, reduction=6,
-               write_l0=1, window=80, kmer=16, device=None) -> dict:
-    """shmr_index -p -o -t -c -l -r -m -w -k   (defaults of src/shmr_index.c:21-23,49-55)."""
+               write_l0=1, window=80, kmer=16, device=None, hpc=False) -> dict:
+    """shmr_index -p -o -t -c -l -r -m -w -k   (defaults of src/shmr_index.c:21-23,49-55), and -H (hpc): homopolymer-compressed shimmers
+    under the same file names."""
     _lib.init(device)
-    p = _lib.IndexParams(total_chunk, mychunk, levels, reduction, window, kmer, write_l0)
+    p = _lib.IndexParams(total_chunk, mychunk, levels, reduction, window, kmer, _lib.want_l0_word(write_l0, hpc))
     r = _lib.IndexResult()
     _lib.check(_lib.load().pgx_index_chunk(seqdb_prefix.encode(), out_prefix.encode(), C.byref(p), C.byref(r)),
                "pgx_index_chunk")
@@ -1317,12 +1322,13 @@ def consensus_branch(read_prefix: str, read_index_prefix: str, ctg_prefix: str, 
 
 
 def polish(rdb: "ResidentDB", read_top, read_counts, contig_fasta, mapping_nchunk: int, cns_nchunk: int, levels=2, reduction=6, window=80, kmer=16,
-           mc_lower=1, mc_upper=240, out: str | None = None, stats: dict | None = None):
+           mc_lower=1, mc_upper=240, out: str | None = None, stats: dict | None = None, hpc=False):
     """The consensus branch of pg_run.py (:401-545) on a read database that is resident already, with its top-level shimmer list and
     counts (all index chunks, concatenated in chunk order), and the contigs as FASTA text (bytes, or a torch uint8 device tensor): the
     contig database straight from the text (ResidentDB.from_fasta), its index with -t 1 -c 1, map_rows_of for the chunks
     1 .. mapping_nchunk, map_merge, cns_job_resident for my = 1 .. cns_nchunk in consensus_branch's order.  No contig file, index file
-    or map text is formed.  The concatenated FASTA is returned, or written to `out` (its length returned)."""
+    or map text is formed.  The concatenated FASTA is returned, or written to `out` (its length returned).
+    hpc: the reads' list holds homopolymer-compressed shimmers, so the contigs' index is made of them too."""
     import time
     if rdb.rlen_by_rid is None:
         raise _lib.PgxError("polish: the read database carries no read lengths on the host (a from_fasta database)")
@@ -1330,7 +1336,7 @@ def polish(rdb: "ResidentDB", read_top, read_counts, contig_fasta, mapping_nchun
     cdb = ResidentDB.from_fasta(contig_fasta)
     try:
         t.append(time.perf_counter())
-        ix = cdb.index(1, 1, levels, reduction, window, kmer)
+        ix = cdb.index(1, 1, levels, reduction, window, kmer, hpc=hpc)
         t.append(time.perf_counter())
         parts = [map_rows_of(ix.top, read_top, read_counts, rdb.rlen_by_rid, mapping_nchunk, c, mc_lower, mc_upper) for c in range(1, int(mapping_nchunk) + 1)]
         t.append(time.perf_counter())
@@ -1352,7 +1358,7 @@ def polish(rdb: "ResidentDB", read_top, read_counts, contig_fasta, mapping_nchun
 
 def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: int = 0, cns_nchunk: int = 0, min_len: int = 4000,
              min_idt: float = 96.0, with_alt: bool = False, levels=2, reduction=6, window=80, kmer=16, bestn=4, mc_lower=2, mc_upper=240,
-             align_bandwidth=100, ovlp_upper=120, chimer_ordered: bool = True, out_dir: str | None = None, device=None) -> dict:
+             align_bandwidth=100, ovlp_upper=120, chimer_ordered: bool = True, out_dir: str | None = None, device=None, hpc=False) -> dict:
     """pg_run.py from the read database on (:227-386 and, with cns_nchunk > 0, :389-565) in one process, on one ResidentDB loaded once:
     every index chunk; every overlap chunk on the concatenated lists and counts; the chunks' records through one graph-mode
     DedupStream in chunk order; the string graph (chimer_ordered: the chimer bridge step, which pg_run.py leaves on, under the stated
@@ -1361,7 +1367,7 @@ def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: 
     seqdb_prefix may be a ResidentDB that carries its read lengths (ResidentDB.from_reads): it is used as it is and left open.
     Returns dict(p_ctg, a_ctg, p_ctg_cns, stats): FASTA bytes (a_ctg / p_ctg_cns None when not asked for) and the stages' statistics
     with their wall times.  With out_dir, p_ctg.fa, a_ctg.fa and p_ctg_cns.fa are written there.  Every handle is closed, also when
-    a stage raises."""
+    a stage raises.  hpc: every index (reads and contigs) holds homopolymer-compressed shimmers (ResidentDB.index)."""
     import contextlib
     import time
     from .formats import read_seqdb
@@ -1387,7 +1393,7 @@ def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: 
             rdb = ResidentDB(read_seqdb(seqdb_prefix), device)
             es.callback(rdb.close)
         lap("load")
-        ixs = [rdb.index(index_nchunk, c, levels, reduction, window, kmer) for c in range(1, int(index_nchunk) + 1)]
+        ixs = [rdb.index(index_nchunk, c, levels, reduction, window, kmer, hpc=hpc) for c in range(1, int(index_nchunk) + 1)]
         top = np.concatenate([ix.top for ix in ixs]) if ixs else np.zeros(0, MM_DTYPE)
         counts = np.concatenate([ix.top_mc for ix in ixs]) if ixs else np.zeros(0, MC_DTYPE)
         stats["index"] = [dict(bases=ix.bases, reads=ix.reads, shimmers=len(ix.top)) for ix in ixs]
@@ -1412,7 +1418,7 @@ def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: 
         cns = None
         if int(cns_nchunk) > 0:
             stats["polish"] = {}
-            cns = b"" if not p_ctg else polish(rdb, top, counts, p_ctg, mapping_nchunk, cns_nchunk, levels, reduction, window, kmer, mc_lower, mc_upper, stats=stats["polish"])
+            cns = b"" if not p_ctg else polish(rdb, top, counts, p_ctg, mapping_nchunk, cns_nchunk, levels, reduction, window, kmer, mc_lower, mc_upper, stats=stats["polish"], hpc=hpc)
             lap("polish")
     stats["ms"] = ms
     if out_dir is not None:
