@@ -58,6 +58,10 @@ void pgx_shutdown(void);
 const char *pgx_last_error(void);
 int pgx_device_count(void);
 const char *pgx_version(void);
+/* the grid a persistent kernel gets for n_items at per_cu workgroups per CU: min(n_items, CUs * per_cu), and under the test hook
+ * PGX_GRID_CAP=c (read at every launch) at most c.  For tests: to see that the hook holds, and to size inputs from the device's CU count.
+ * Call pgx_init first: the CU count is the selected device's (before that, the answer assumes 256 CUs). */
+uint32_t pgx_stride_grid(uint64_t n_items, uint32_t per_cu);
 void pgx_free(void *p);              /* releases any host array returned by this library */
 
 /* per-kernel device time (HIP events on the library's stream), accumulated since the last reset.

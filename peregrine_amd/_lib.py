@@ -144,7 +144,7 @@ SHMR_ALN_PAIR_DTYPE = np.dtype([("list0", "<u4"), ("list1", "<u4")])
 
 # every symbol include/pgx.h declares (checked by tests/test_abi.py)
 EXPORTS = [
-    "pgx_init", "pgx_shutdown", "pgx_last_error", "pgx_device_count", "pgx_version", "pgx_free",
+    "pgx_init", "pgx_shutdown", "pgx_last_error", "pgx_device_count", "pgx_version", "pgx_stride_grid", "pgx_free",
     "pgx_timing_get", "pgx_timing_reset", "pgx_mem_ledger", "pgx_results_async", "pgx_results_wait",
     "pgx_seqdb_upload", "pgx_seqdb_load", "pgx_seqdb_free", "pgx_seqdb_bases", "pgx_seqdb_reads", "pgx_seqdb_release_bytes", "pgx_seqdb_has_bytes",
     "pgx_seqdb_compact_bytes", "pgx_seqdb_side_bytes", "pgx_seqdb_read_bytes", "pgx_seqdb_from_fasta", "pgx_seqdb_save",
@@ -192,6 +192,8 @@ def load():
         lib.pgx_last_error.restype = C.c_char_p
         lib.pgx_version.restype = C.c_char_p
         lib.pgx_free.argtypes = [C.c_void_p]
+        lib.pgx_stride_grid.restype = C.c_uint32
+        lib.pgx_stride_grid.argtypes = [C.c_uint64, C.c_uint32]
         lib.pgx_seqdb_free.argtypes = [C.c_void_p]
         lib.pgx_seqdb_bases.restype = C.c_uint64
         lib.pgx_seqdb_bases.argtypes = [C.c_void_p]

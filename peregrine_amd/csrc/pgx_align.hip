@@ -825,7 +825,7 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
     if (nh) {
       ByteView view;
       side_view_of_keys(db, d_keys, hand + 4, nh, view);
-      hipLaunchKernelGGL(k_align1_list<false>, dim3(std::min<unsigned>(nh, (unsigned)ctx().num_cu * 32)), dim3(64), ring * sizeof(int32_t), st, view.seq,
+      hipLaunchKernelGGL(k_align1_list<false>, dim3(stride_grid(nh, 32)), dim3(64), ring * sizeof(int32_t), st, view.seq,
                          view.off, db->d_rlen.p, d_keys, hand, hand + 4, band, ring, d_out);
       PGX_HIP(hipGetLastError());
     }
@@ -939,7 +939,7 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
         hipLaunchKernelGGL(ph_bytes, dim3((unsigned)std::min<size_t>(nf / (64 * NW) + 8, n_wg)), dim3(64 * NW), lds, st, view.seq, view.off,
                            db->d_rlen.p, d_keys, (uint32_t)n, band, ring_ph, d_out, esc + 2, esc + 1, esc + 4 + n, esc2, esc2 + 4, (const uint32_t *)nullptr,
                            segment(nf / 16 + 1), iter_limit);
-        hipLaunchKernelGGL(k_align1_list<false>, dim3(std::min<unsigned>(nf, (unsigned)ctx().num_cu * 32)), dim3(64), ring * sizeof(int32_t), st, view.seq,
+        hipLaunchKernelGGL(k_align1_list<false>, dim3(stride_grid(nf, 32)), dim3(64), ring * sizeof(int32_t), st, view.seq,
                            view.off, db->d_rlen.p, d_keys, esc2, esc2 + 4, band, ring, d_out);
       }
     } else if (db->n_flagged_reads)
@@ -947,7 +947,7 @@ void dev_align(const pgx_seqdb *db, const pgx_align_key *d_keys, size_t n, int b
                 db->d_rlen.p, d_keys, (uint32_t)n, band, ring_ph, d_out, esc + 2, esc + 1, esc + 4 + n, esc, esc + 4, nullptr, segment(n / 16 + 1),
                 iter_limit);
     // the stragglers of either launch, a wavefront per candidate, from the list
-    const dim3 g1((unsigned)std::min<size_t>(std::max<size_t>(n / 256, 256), (size_t)ctx().num_cu * 32));
+    const dim3 g1(stride_grid(std::max<size_t>(n / 256, 256), 32));
     launch_on(src.one, k_align1_list<true>, k_align1_list<false>, g1, dim3(64), ring * sizeof(int32_t), db->d_rlen.p, d_keys, esc, esc + 4, band,
               ring, d_out);
   }

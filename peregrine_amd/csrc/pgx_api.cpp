@@ -589,6 +589,8 @@ int pgx_device_count(void) {
   return n;
 }
 
+uint32_t pgx_stride_grid(uint64_t n_items, uint32_t per_cu) { return pgx::stride_grid(n_items, per_cu); }
+
 int pgx_init(int device) {
   return guarded([&]() -> int {
     Context &c = ctx();

@@ -93,6 +93,20 @@ struct Context {
 };
 Context &ctx();
 void require_ready();
+// The grid of a persistent kernel (a workgroup strides over the items: `for (i = blockIdx.x; i < n; i += gridDim.x)`).
+// PGX_GRID_CAP: a test hook, read at every launch, that caps such a grid so that small inputs give a workgroup several items one
+// after the other (1: one workgroup takes them all, in order).  Without it (or when it holds no positive integer) a grid is what it was.
+inline uint32_t grid_cap(uint64_t grid) {
+  const char *v = getenv("PGX_GRID_CAP");
+  const long long c = v ? atoll(v) : 0;
+  if (c > 0 && (uint64_t)c < grid) grid = (uint64_t)c;
+  return (uint32_t)grid;
+}
+// min(n_items, per_cu workgroups for every CU), under the cap
+inline uint32_t stride_grid(uint64_t n_items, uint32_t per_cu) {
+  const uint64_t full = (uint64_t)ctx().num_cu * per_cu;
+  return grid_cap(n_items < full ? n_items : full);
+}
 // Per-context device state that outlives a call (buffers handed out as library-owned views, side streams, pinned pools) registers a
 // reset function: pgx_shutdown() runs them all BEFORE it returns the cached blocks to the driver, so nothing survives into the next
 // pgx_init() (which may choose another device).  Use: static pgx::ShutdownHook h_([] { ... });
@@ -409,6 +423,13 @@ void dev_count(const pgx_mm128 *d_in, size_t n, int kmer_bits, DevBuf<pgx_mm_cou
 bool sketch_wave_eligible(const ReadDesc &rd, int w, int k);
 void launch_sketch_wave(const pgx_seqdb *db, const ReadDesc *d_reads, const uint32_t *d_list, uint32_t n_list, int w, int k,
                         pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags, const uint8_t *bytes = nullptr);
+// the bases of one batch of launch_sketch_general / launch_sketch_hpc (a longer read is a batch of its own).  PGX_SKETCH_BATCH: a test
+// hook that shrinks it so that small inputs take several batches.
+inline uint64_t sketch_batch_bases() {
+  const char *v = getenv("PGX_SKETCH_BATCH");
+  const long long b = v ? atoll(v) : (long long)(256ull << 20);
+  return (uint64_t)(b < 1 ? 1 : b);
+}
 void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const std::vector<uint32_t> &lens, const uint32_t *d_list, int w,
                            int k, pgx_mm128 *d_slab, const uint64_t *d_slab_off, uint32_t *d_counts, uint32_t *d_flags,
                            const uint8_t *bytes = nullptr);

@@ -258,7 +258,7 @@ void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const s
                            const uint8_t *bytes) {
   hipStream_t st = ctx().stream;
   if (!bytes) bytes = db->d_seq.p;
-  const uint64_t batch_bases = 256ull << 20;
+  const uint64_t batch_bases = sketch_batch_bases();
   DevBuf<uint32_t> iota;
   if (!d_list) {   // the kernel walks a list: the identity
     std::vector<uint32_t> id(lens.size());
@@ -278,7 +278,7 @@ void launch_sketch_general(const pgx_seqdb *db, const ReadDesc *d_reads, const s
     uint64_t *T1 = ws<uint64_t>("sk.gen_t1", acc), *T2 = ws<uint64_t>("sk.gen_t2", acc);
     uint32_t *PY = ws<uint32_t>("sk.gen_py", acc);
     PGX_HIP(hipMemcpyAsync(d_so, so.data(), so.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    const unsigned grid = (unsigned)std::min<size_t>(b1 - b0, (size_t)ctx().num_cu * 16);
+    const unsigned grid = stride_grid(b1 - b0, 16);
     PGX_REQUIRE(bytes, PGX_ESTATE, "the seqdb's bytes were released (pgx_seqdb_release_bytes): the general sketch kernel (other w / k, L0 output) needs them");
     hipLaunchKernelGGL(k_sketch_general, dim3(grid), dim3(64), 0, st, bytes, d_reads, d_list + b0, (uint32_t)(b1 - b0), w, k,
                        d_so, H, PY, WMv, T1, T2, d_slab, d_slab_off, d_counts, d_flags);

@@ -171,7 +171,7 @@ const uint32_t *seq_packs(const pgx_seqdb *db) {
     hipLaunchKernelGGL(k_words_of, dim3((n + 255) / 256), dim3(256), 0, st, n, ord.p, db->d_rlen.p, words.p);
     exclusive_sum(words.p, start.p, n, &tmp);
     hipLaunchKernelGGL(k_scatter_layout, dim3((n + 255) / 256), dim3(256), 0, st, n, ord.p, start.p, db->d_poff.p, db->d_prank.p);
-    hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)std::min<size_t>(nr, (size_t)ctx().num_cu * 64)), dim3(256), 0, st, db->d_seq.p, ord.p, n, db->d_roff.p,
+    hipLaunchKernelGGL(k_pack_reads, dim3(stride_grid(nr, 64)), dim3(256), 0, st, db->d_seq.p, ord.p, n, db->d_roff.p,
                        db->d_rlen.p, db->d_poff.p, db->d_pack.p, db->d_nflag.p);
     PGX_HIP(hipGetLastError());
     {   // how many reads hold a byte without a 2-bit code (0 for everything the reference's encoder wrote from ACGT reads): the alignment

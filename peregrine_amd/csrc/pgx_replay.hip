@@ -387,7 +387,7 @@ struct Walk {
     if (list == DEV_LIST_WIN) count(lo, hi);
     const uint32_t a = list ? 0u : lo, b = list ? (uint32_t)nb : hi;   // (a list's entries are buckets of [0, nb))
     const uint32_t big_a = list == DEV_LIST_WIN ? LIST_CAP : list == DEV_LIST ? groups : lo;   // (list mode: the list entries this pass covers)
-    const dim3 big_grid(std::min<uint32_t>(BIG_WG, groups)), big_block(64 * BIG_NW), grid(cdiv256((size_t)groups * GL));
+    const dim3 big_grid(grid_cap(std::min<uint32_t>(BIG_WG, groups))), big_block(64 * BIG_NW), grid(cdiv256((size_t)groups * GL));
     const bool side = use_big && list && !timed && !deep;
     if (side) {
       PGX_HIP(hipEventRecord(rs.side_ev[0], s));

@@ -718,11 +718,11 @@ void chimer_pass(pgx_sgraph *g, uint32_t n_nodes, uint32_t n_e, uint32_t max_deg
   const ChGraph G{out_off, out_w, in_off, in_e, node_of, krank.p, by_rank.p};
   DevBuf<uint8_t> res(n_cand);
   DevBuf<uint32_t> list(n_cand);
-  hipLaunchKernelGGL(k_sg_chimer_lds, dim3(std::min<uint32_t>(n_cand, (uint32_t)ctx().num_cu * 32u)), dim3(64), 0, st, cand.p, n_cand, chimer_lds(), G, res.p);
+  hipLaunchKernelGGL(k_sg_chimer_lds, dim3(stride_grid(n_cand, 32)), dim3(64), 0, st, cand.p, n_cand, chimer_lds(), G, res.p);
   LAUNCH(k_sg_chimer_flags, n_cand, res.p, n_cand, (uint8_t)CH_OVER, flag.p, d_past1);
   const uint32_t n_over = select_indices(flag.p, n_cand, list.p, tmp);
   if (n_over) {   // a table with an entry per node for each workgroup: as many workgroups as 1 GiB of tables allows
-    const uint32_t wgs = (uint32_t)std::min<uint64_t>({(uint64_t)n_over, 64, std::max<uint64_t>(1, (1ULL << 27) / n_nodes)});
+    const uint32_t wgs = grid_cap(std::min<uint64_t>({(uint64_t)n_over, 64, std::max<uint64_t>(1, (1ULL << 27) / n_nodes)}));   // (the slices below and the launch: this one value)
     const uint32_t pool_size = 4 * max_deg + 1;
     DevBuf<uint64_t> tabs((size_t)wgs * n_nodes);
     DevBuf<uint32_t> pools((size_t)wgs * pool_size);
@@ -821,14 +821,14 @@ void build_graph(const Row *d_rows, uint32_t n_rows, int64_t min_len, double min
   part.reset(), part.reset(new KernelTimer("sgraph_tr", n_e));
   DevBuf<uint8_t> type(n_e), best(n_e), nflag(n_nodes);
   PGX_HIP(hipMemsetAsync(type.p, 0, n_e, st));
-  hipLaunchKernelGGL(k_sg_tr_lds, dim3(std::min<uint32_t>(n_nodes, (uint32_t)ctx().num_cu * 32u)), dim3(64), 0, st, n_nodes, cap, out_off.p, out_e.p, out_w.p,
+  hipLaunchKernelGGL(k_sg_tr_lds, dim3(stride_grid(n_nodes, 32)), dim3(64), 0, st, n_nodes, cap, out_off.p, out_e.p, out_w.p,
                      out_len.p, type.p);
   if (max_deg > cap) {
     DevBuf<uint32_t> big(n_nodes), marks(n_e);
     LAUNCH(k_sg_big_flags, n_nodes, out_off.p, n_nodes, cap, nflag.p);
     const uint32_t n_big = select_indices(nflag.p, n_nodes, big.p, &tmp);
     PGX_HIP(hipMemsetAsync(marks.p, 0, (size_t)n_e * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_sg_tr_global, dim3(std::min<uint32_t>(n_big, (uint32_t)ctx().num_cu * 32u)), dim3(64), 0, st, big.p, n_big, out_off.p, out_e.p, out_w.p,
+    hipLaunchKernelGGL(k_sg_tr_global, dim3(stride_grid(n_big, 32)), dim3(64), 0, st, big.p, n_big, out_off.p, out_e.p, out_w.p,
                        out_len.p, vw_key.p, vw_pos.p, n_e, marks.p, type.p);
     PGX_HIP(hipGetLastError());
     pgx::sync();   // (big and marks go back to the block cache behind the kernel anyway: one stream)

@@ -253,8 +253,6 @@ uint32_t lds_chains() {   // PGX_SHMR_ALN_LDS: a test hook that shrinks the LDS 
   return (uint32_t)std::min<long>(std::max<long>(c, 0), (long)ALN_LDS_CHAINS);
 }
 
-uint32_t wave_grid(size_t n_pairs) { return (uint32_t)std::min<size_t>(n_pairs, (size_t)ctx().num_cu * 8); }
-
 // the four arrays for the caller; after a failure none is left
 struct AlnOut {
   uint64_t *pair_off = nullptr, *chain_off = nullptr;
@@ -274,7 +272,7 @@ void shmr_aln_dev(const char *who, const pgx_mm128 *mm0, const uint64_t *off0, s
                   AlnOut &out, pgx_shmr_aln_stats &stats) {
   hipStream_t st = ctx().stream;
   const uint64_t n0 = off0[n_lists0], n1 = off1[n_lists1];
-  const uint32_t np = (uint32_t)n_pairs, grid = wave_grid(n_pairs);
+  const uint32_t np = (uint32_t)n_pairs, grid = stride_grid(n_pairs, 8);   // one grid for the four persistent kernels
   PrimWs ws;
   const double t0 = wall_ms();
   DevBuf<pgx_mm128> d_mm0(n0 ? n0 : 1), d_mm1(n1 ? n1 : 1);

@@ -236,7 +236,7 @@ void launch_sketch_hpc(const pgx_seqdb *db, const ReadDesc *d_reads, const std::
   if (lens.empty()) return;
   // every batch's scratch offsets (they restart at 0 with a batch) in one upload, the scratch sized for the largest batch: the launches
   // follow each other on the stream, which orders their use of the scratch, and the host waits once, at the end
-  const uint64_t batch_bases = 256ull << 20;
+  const uint64_t batch_bases = sketch_batch_bases();
   std::vector<uint64_t> so(lens.size());
   std::vector<size_t> first{0};
   uint64_t acc = 0, most = 0;
@@ -254,7 +254,7 @@ void launch_sketch_hpc(const pgx_seqdb *db, const ReadDesc *d_reads, const std::
   PGX_HIP(hipMemcpyAsync(d_so, so.data(), so.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   for (size_t b = 0; b + 1 < first.size(); ++b) {
     const size_t b0 = first[b], b1 = first[b + 1];
-    const unsigned grid = (unsigned)std::min<size_t>(b1 - b0, (size_t)ctx().num_cu * 16);
+    const unsigned grid = stride_grid(b1 - b0, 16);
     hipLaunchKernelGGL(k_sketch_hpc, dim3(grid), dim3(64), 0, st, db->d_seq.p, d_reads, d_list ? d_list + b0 : nullptr, (uint32_t)b0,
                        (uint32_t)(b1 - b0), w, k, d_so + b0, X, PY, WMv, T1, T2, d_slab, off_by_list ? d_slab_off + b0 : d_slab_off, off_by_list,
                        d_counts, d_flags, d_need);

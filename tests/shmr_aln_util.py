@@ -142,6 +142,24 @@ def random_pairs(seed, n_pairs=300, max_len=400):
     return lists0, lists1, pairs
 
 
+_batch = None
+
+
+def seeded_batch():
+    """about 300 seeded pairs, sizes 0 .. 400, several pairs to a list 0, and the restatement's chains of each pair alone per max_repeat:
+    (lists0, lists1, pairs, {max_repeat: [chains of pair p]}), made once and left alone"""
+    global _batch
+    if _batch is None:
+        lists0, lists1, pairs = random_pairs(20261121)
+        want = {mr: [shmr_aln(lists0[a], lists1[b], max_repeat=mr)[0] for a, b in pairs.tolist()] for mr in (1, 2, 5)}
+        shared = np.bincount(pairs[:, 0])
+        assert len(pairs) == 300 and shared.max() >= 3 and min(len(l) for l in lists1) == 0 and max(len(l) for l in lists1) == 400
+        for mr in (1, 2, 5):   # repeats and ties are common: chains longer than one element, several chains to a pair, in many pairs
+            assert sum(len(ch) > 1 for ch in want[mr]) > 50 and sum(any(len(a) > 1 for a, _ in ch) for ch in want[mr]) > 50, mr
+        _batch = (lists0, lists1, pairs, want)
+    return _batch
+
+
 RC = bytes.maketrans(b"ACGT", b"TGCA")
 
 

@@ -223,6 +223,24 @@ def test_containment(family8, monkeypatch):
     _run(family8, monkeypatch, ALL_BIG, kw, 5000)
 
 
+BIG_WG = 512   # workgroups of a k_eval_big launch at the most (pgx_replay.h; no CU term), striding over the pass's list of big buckets
+
+
+def test_a_workgroup_walks_many_buckets(family8, monkeypatch):
+    """Every bucket of 3 .. 128 entries is dirty in the first pass, and under PGX_REPLAY_BIG=2 every one of them is on that pass's big
+    list: more than two grids of them, so in every test of this file that uses ALL_BIG on family8 a workgroup of k_eval_big walks bucket
+    after bucket on the same LDS (s_fact, s_vis / s_ins, the pair set).  Here the same under PGX_GRID_CAP = 3: three workgroups take
+    them all."""
+    kw = dict(WIDE, bestn=8)
+    sh = family8.shapes(kw)
+    walked = int(((sh.size > 2) & (sh.size <= kw["ovlp_upper"])).sum())
+    print("buckets of 3 ..", kw["ovlp_upper"], "entries:", walked)
+    assert walked > 2 * BIG_WG
+    monkeypatch.setenv("PGX_GRID_CAP", "3")
+    assert _lib.load().pgx_stride_grid(2**40, 32) == 3
+    _run(family8, monkeypatch, ALL_BIG, kw, 5000)
+
+
 def test_re_evaluation_with_default_thresholds(tandem, monkeypatch):
     """default thresholds, several sweeps: the walk runs over facts from settled and from pending memo entries"""
     st = _run(tandem, monkeypatch, dict(), dict(bestn=4), 5000)

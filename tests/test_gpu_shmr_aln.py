@@ -73,13 +73,7 @@ def test_fixture_on_the_second_path(lds):
 @pytest.fixture(scope="module")
 def batch():
     """about 300 seeded pairs, sizes 0 .. 400, several pairs to a list 0, and the restatement's chains of each pair alone per max_repeat"""
-    lists0, lists1, pairs = A.random_pairs(20261121)
-    want = {mr: [A.shmr_aln(lists0[a], lists1[b], max_repeat=mr)[0] for a, b in pairs.tolist()] for mr in (1, 2, 5)}
-    shared = np.bincount(pairs[:, 0])
-    assert len(pairs) == 300 and shared.max() >= 3 and min(len(l) for l in lists1) == 0 and max(len(l) for l in lists1) == 400
-    for mr in (1, 2, 5):   # repeats and ties are common: chains longer than one element, several chains to a pair, in many pairs
-        assert sum(len(ch) > 1 for ch in want[mr]) > 50 and sum(any(len(a) > 1 for a, _ in ch) for ch in want[mr]) > 50, mr
-    return lists0, lists1, pairs, want
+    return A.seeded_batch()   # (shared with test_gpu_wave_reuse.py)
 
 
 @pytest.mark.parametrize("max_repeat", [1, 2, 5])
