@@ -1,7 +1,9 @@
 """klib-khash's slot layout as the overlap stage computes it for its OUTER table (pgx_khash.h: DistinctSlotTable -- one packed word
 per slot, a skip count per home slot instead of re-walking probe chains, the kick-out rehash of khash.h:258-284) against the
 oracle's literal put-by-put emulation (oracle/: otab_put, restating /root/reference/src/khash.h:232-336).  (The inner tables are
-replayed on the device, pgx_visit.hip: tests/test_gpu_parity.py::test_device_visit_order_equals_oracle_and_host_visit.)"""
+replayed on the device, pgx_visit.hip: tests/test_gpu_parity.py::test_device_visit_order_equals_oracle_and_host_visit on simulated reads,
+and tests/test_gpu_designed_lists.py on designed lists -- a group of every size at the lane / wavefront boundary, the wavefront limit and every
+resize boundary, with and without a trailing put.)"""
 import ctypes as C
 
 import numpy as np
