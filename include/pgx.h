@@ -68,7 +68,8 @@ void pgx_free(void *p);              /* releases any host array returned by this
  * names: "sketch", "sketch_general", "sketch_redo", "sketch_nreads", "sketch_gather", "pack", "reduce", "count", "pairs", "replay_dense" / "replay_rows" / "replay_update" (k_eval, k_eval_rows, k_update of the device replay; only with PGX_REPLAY_TIMING=1), "align" (k_align_ph), "align1" (k_align1: launches of
  * at most 13 k alignments), "align1t" (k_align1t: alignments with a target offset), "tile_geom", "stitch" (the contig layout), "encode", "dedup", "map", "sgraph" (the string graph: build and text; its parts also as "sgraph_edges", "sgraph_adj", "sgraph_tr", "sgraph_chimer", "sgraph_spur",
  * "sgraph_best", "sgraph_text"), "unitigs" (its parts: "unitigs_links", "unitigs_rank", "unitigs_paths", "unitigs_text"), "ctg_paths" (its parts:
- * "ctg_paths_graph", "ctg_paths_clean", "ctg_paths_walk", "ctg_paths_text"). */
+ * "ctg_paths_graph", "ctg_paths_clean", "ctg_paths_walk", "ctg_paths_text"), "gfa" (the build with the layout of the segments; its own parts:
+ * "gfa_dual", "gfa_rows", "gfa_links", "gfa_text"). */
 int pgx_timing_get(const char *kernel, double *total_ms, uint64_t *launches, uint64_t *units);
 void pgx_timing_reset(void);
 /* HBM ledger: JSON text of the library's device memory -- live bytes, bytes held in the block cache, and the live bytes BY OWNER (seqdb,
@@ -637,6 +638,52 @@ int pgx_tiling_text(pgx_tiling *t, int which, uint64_t max_lines, char **text, s
 int pgx_tiling_contigs(const pgx_tiling *t, int which, const char *seqdb_prefix, const char *out_path, uint64_t *n_ctg, uint64_t *n_bases);
 int pgx_tiling_free(pgx_tiling *t);
 int pgx_tiling_chunk(const char *sg_edges_list_fn, const char *utg_data_fn, const char *ctg_paths_fn, const char *p_out, const char *a_out, pgx_tiling_stats_t *stats);
+
+/* ---- assembly graph as GFA 1.0 (no counterpart in the reference workflow): the phase-1 unitigs (above: every directed G
+ * edge lies in exactly one unitig, a path and its reverse are two) as segments with sequences, and the links between them.  The rule:
+ *   dual      dual(u) is the unitig that holds the reverse of u's first edge: edge e ^ 1 in a built graph, the edge (rev w, rev v) among
+ *             host records.  dual(dual(u)) == u and dual(u) != u follow from what pgx_unitigs checks; violations are counted on the device
+ *             and any is PGX_ESTATE: no wrong file is written.
+ *   segments  u is canonical iff u < dual(u); every canonical unitig is one segment, numbered densely in ascending unitig index and named
+ *             "utg%06u" of the unitig's index -- the 0-based number of its line in pgx_unitigs_text.  A directed unitig x prints as the name
+ *             of min(x, dual(x)) and '+' if x is canonical, else '-'.
+ *   rows      segment j of canonical unitig u has one pgx_tile_row per edge of u's path, in path order (a ring's closing edge included: the
+ *             first read's bases come again at the end): ctg = j, rid0 = v_rid, rid1 = w_rid, s = sp, e = tp, strand0 = 1 - v_end,
+ *             strand1 = 1 - w_end.
+ *   sequences (only with a database) a segment's bases are what the contig layout (above, "contig layout") makes of its rows; a row the
+ *             layout refuses is PGX_EARG, the message names the segment, the position in its path and the edge index.
+ *   links     for every ordered pair of directed unitigs (a, b) with t(a) == s(b), a == b included, there is a directed link; a's links
+ *             are the G out-edges of node t(a), each the first edge of a unitig.  The dual of (a, b) is (dual b, dual a), never the same
+ *             pair; of the two the lexicographically smaller pair of unitig indices is written.  Links ascend by (a, b).
+ *   text      "H\tVN:Z:1.0\n"; per segment "S\t<name>\t<bases>\tLN:i:<number of bases>\n", or "S\t<name>\t*\n" without a database (no
+ *             length is invented: a unitig's `length` excludes its first read); per link "L\t<name a>\t<+|->\t<name b>\t<+|->\t*\n" -- the
+ *             overlap is '*' on purpose: the end of a and the start of b come from one read through different stitching alignments.
+ *             No G edge: the header line alone.
+ *   pgx_gfa_build : u, and the edge records u was built from: a live graph g, or n_edges host records in creation order -- exactly one of
+ *                   the two (else PGX_EARG); db: a resident read database in any state (bytes, released, compacted), or NULL for the
+ *                   topology-only file.  PGX_EARG: the records' G count differs from u's g_edges, a path index lies beyond the records,
+ *                   a path's edge is not the G edge the unitigs saw there.  PGX_ENOMEM: the inputs stay usable.  The result owns its
+ *                   arrays: u, g and db may be freed first.
+ *   pgx_gfa_build_files : the file level -- the same with the sequences from <seqdb_prefix>.idx / .seqdb (NULL: the topology-only file):
+ *                   only the reads the rows name are uploaded, in pgx_contigs_chunk's batches of whole segments that fit HBM.
+ *   pgx_gfa_stats / _segments / _links / _rows : the counts, and n table entries from entry `first` on.
+ *   pgx_gfa_text  : the whole file, malloc'd (pgx_free).      pgx_gfa_write : to a file (NULL: stdout).
+ *   pgx_gfa_free  : releases it (NULL is accepted).
+ * After pgx_shutdown every call but pgx_gfa_free answers PGX_ESTATE.  Device memory is booked as "gfa", time as "gfa" with the parts
+ * "gfa_dual", "gfa_rows", "gfa_links", "gfa_text" (the layout's parts keep their names). */
+typedef struct { uint32_t unitig, dual; uint32_t n_rows; uint8_t circular, pad[3]; uint64_t first_row, seq_off, seq_len; } pgx_gfa_segment; /* 40 bytes */
+typedef struct { uint32_t from_seg, to_seg; uint8_t from_rev, to_rev, pad[2]; } pgx_gfa_link;                                         /* 12 bytes */
+typedef struct { uint64_t unitigs, segments, rows, links_directed, links, bases; } pgx_gfa_stats_t;
+typedef struct pgx_gfa pgx_gfa;
+int pgx_gfa_build(pgx_unitigs *u, pgx_sgraph *g, const pgx_sgraph_edge *edges, uint64_t n_edges, pgx_seqdb *db, pgx_gfa **out);
+int pgx_gfa_build_files(pgx_unitigs *u, pgx_sgraph *g, const pgx_sgraph_edge *edges, uint64_t n_edges, const char *seqdb_prefix, pgx_gfa **out);
+int pgx_gfa_stats(const pgx_gfa *f, pgx_gfa_stats_t *out);
+int pgx_gfa_segments(const pgx_gfa *f, uint64_t first, uint64_t n, pgx_gfa_segment *out);
+int pgx_gfa_links(const pgx_gfa *f, uint64_t first, uint64_t n, pgx_gfa_link *out);
+int pgx_gfa_rows(const pgx_gfa *f, uint64_t first, uint64_t n, pgx_tile_row *out);
+int pgx_gfa_text(pgx_gfa *f, char **text, size_t *len);
+int pgx_gfa_write(pgx_gfa *f, const char *path);
+int pgx_gfa_free(pgx_gfa *f);
 
 /* ---- consensus call: the second half of pg_asm_cns.py's inner loop (py/scripts/pg_asm_cns.py:149-242), get_align_tags and
  * get_cns_from_align_tags of falcon/falcon.c:67-122,277-397, for a batch of pieces at once.  An alignment is what falcon.align answers for

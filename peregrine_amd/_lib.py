@@ -156,6 +156,7 @@ EXPORTS = [
     "pgx_sgraph_build", "pgx_sgraph_stats", "pgx_sgraph_edges", "pgx_sgraph_text", "pgx_sgraph_free", "pgx_sgraph_chimer_stats", "pgx_sgraph_chimer_nodes",
     "pgx_sgraph_unitigs", "pgx_unitigs_build", "pgx_unitigs_stats", "pgx_unitigs_table", "pgx_unitigs_paths", "pgx_unitigs_text", "pgx_unitigs_free",
     "pgx_unitigs_contig_paths", "pgx_ctg_paths_build", "pgx_ctg_paths_stats", "pgx_ctg_paths_table", "pgx_ctg_paths_rows", "pgx_ctg_paths_utg_text", "pgx_ctg_paths_ctg_text", "pgx_ctg_paths_free",
+    "pgx_gfa_build", "pgx_gfa_build_files", "pgx_gfa_stats", "pgx_gfa_segments", "pgx_gfa_links", "pgx_gfa_rows", "pgx_gfa_text", "pgx_gfa_write", "pgx_gfa_free",
     "pgx_sgraph_parse", "pgx_tiling_build", "pgx_tiling_stats", "pgx_tiling_rows", "pgx_tiling_names", "pgx_tiling_text", "pgx_tiling_contigs", "pgx_tiling_free", "pgx_tiling_chunk",
     "pgx_sketch_batch", "pgx_sketch_batch_hpc", "pgx_reduce_batch", "pgx_count_batch", "pgx_align_batch",
     "decode_biseq", "encode_biseq", "mm_sketch", "mm_reduce", "ovlp_match", "free_ovlp_match", "read_mmlist", "write_mmlist",
@@ -265,6 +266,14 @@ def load():
         lib.pgx_ctg_paths_utg_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_ctg_paths_ctg_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_ctg_paths_free.argtypes = [C.c_void_p]
+        lib.pgx_gfa_build.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.pgx_gfa_build_files.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p]
+        lib.pgx_gfa_stats.argtypes = [C.c_void_p, C.c_void_p]
+        for fn in (lib.pgx_gfa_segments, lib.pgx_gfa_links, lib.pgx_gfa_rows):
+            fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.pgx_gfa_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgx_gfa_write.argtypes = [C.c_void_p, C.c_char_p]
+        lib.pgx_gfa_free.argtypes = [C.c_void_p]
         lib.pgx_sgraph_parse.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pgx_tiling_build.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p]
         lib.pgx_tiling_stats.argtypes = [C.c_void_p, C.c_void_p]

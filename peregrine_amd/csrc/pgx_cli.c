@@ -399,6 +399,7 @@ struct sgraph_opts {
   const char *utg_data, *ctg_paths;   /* --utg-data FILE, --ctg-paths FILE: the final utg_data and ctg_paths (NULL: not written) */
   int chimer_ordered;                 /* --chimer_bridge_ordered: PGX_SGRAPH_CHIMER_ORDERED */
   const char *chimers_nodes;          /* --chimers-nodes FILE: the chimers_nodes file (NULL: not written) */
+  const char *gfa, *gfa_seqdb;        /* --gfa FILE: the unitig graph as GFA; --gfa-seqdb PREFIX: with the sequences from that database */
 };
 /* What every hand-out of text ends with: the status of the call `what` reported, or its text written to f (named fname in the
  * complaint); the text is freed either way.  Returns the exit code so far. */
@@ -444,6 +445,12 @@ static int write_unitigs(const char *tool, pgx_sgraph *g, const struct sgraph_op
   pgx_ctg_paths *c = NULL;
   int rc = 0;
   if (pgx_sgraph_unitigs(g, &u)) rc = fail(tool, "pgx_sgraph_unitigs");
+  if (!rc && sg->gfa) {   /* nothing is written unless the whole graph was built */
+    pgx_gfa *f = NULL;
+    if (pgx_gfa_build_files(u, g, NULL, 0, sg->gfa_seqdb, &f)) rc = fail(tool, "pgx_gfa_build_files");
+    else if (pgx_gfa_write(f, sg->gfa)) rc = fail(tool, "pgx_gfa_write");
+    pgx_gfa_free(f);
+  }
   if (!rc && sg->utg) rc = write_text_file(tool, "pgx_unitigs_text", next_unitigs_text, u, piece, sg->utg);
   if (!rc && (sg->utg_data || sg->ctg_paths) && pgx_unitigs_contig_paths(u, &c)) rc = fail(tool, "pgx_unitigs_contig_paths");
   if (!rc && sg->utg_data) rc = write_text_file(tool, "pgx_ctg_paths_utg_text", next_ctg_utg_text, c, piece, sg->utg_data);
@@ -512,7 +519,7 @@ static int dedup_stdin(const char *tool, int graph, const struct sgraph_opts *sg
   if (sg && ds && !rc && pgx_sgraph_build(ds, sg->min_len, sg->min_idt, sg->chimer_ordered ? PGX_SGRAPH_CHIMER_ORDERED : 0, &g)) rc = fail(tool, "pgx_sgraph_build");
   if (g) rc = write_pieces(tool, "pgx_sgraph_text", next_sgraph_text, g, piece, stdout, "stdout");
   if (g && sg->chimers_nodes && !rc) rc = write_chimers_nodes(tool, g, sg->chimers_nodes);
-  if (g && (sg->utg || sg->utg_data || sg->ctg_paths) && !rc) rc = write_unitigs(tool, g, sg, piece);
+  if (g && (sg->utg || sg->utg_data || sg->ctg_paths || sg->gfa) && !rc) rc = write_unitigs(tool, g, sg, piece);
   pgx_sgraph_free(g);
   if (graph && !sg && ds && !rc) rc = write_pieces(tool, "pgx_dedup_drain", next_drain_text, ds, piece, stdout, "stdout");
   if (ds) pgx_dedup_close(ds, NULL, NULL);
@@ -526,11 +533,11 @@ static int main_dedup(int argc, char **argv) {
   return dedup_stdin("shmr_dedup", graph, NULL);
 }
 
-/* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
+/* cat ovlp*.dat | shmr_sgraph [--min_len N] [--min_idt X] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] [--gfa FILE [--gfa-seqdb PREFIX]] > sg_edges_list: the first half of ovlp_to_graph.py (its defaults), with
  * --disable_chimer_bridge_removal and without --lfc; --chimer_bridge_ordered [--chimers-nodes FILE] runs the chimer bridge step too, under the
  * stated pop order (pgx.h, PGX_SGRAPH_CHIMER_ORDERED) */
 static int main_sgraph(int argc, char **argv) {
-  struct sgraph_opts o = {4000, 96.0, NULL, NULL, NULL, 0, NULL};
+  struct sgraph_opts o = {4000, 96.0, NULL, NULL, NULL, 0, NULL, NULL, NULL};
   for (int i = 1; i < argc; ++i) {
     const char *a = argv[i], *v = NULL;
     const int len_opt = strncmp(a, "--min_len", 9) == 0 && (a[9] == 0 || a[9] == '='), idt_opt = strncmp(a, "--min_idt", 9) == 0 && (a[9] == 0 || a[9] == '=');
@@ -557,6 +564,14 @@ static int main_sgraph(int argc, char **argv) {
         fprintf(stderr, "shmr_sgraph: %.*s needs a file name\n", (int)nl, a);
         return 2;
       }
+    } else if ((strncmp(a, "--gfa-seqdb", 11) == 0 && (a[11] == 0 || a[11] == '=')) || (strncmp(a, "--gfa", 5) == 0 && (a[5] == 0 || a[5] == '='))) {
+      const size_t nl = a[5] == '-' ? 11 : 5;
+      const char **dst = nl == 11 ? &o.gfa_seqdb : &o.gfa;
+      *dst = a[nl] ? a + nl + 1 : (i + 1 < argc ? argv[++i] : NULL);
+      if (!*dst || !**dst) {
+        fprintf(stderr, "shmr_sgraph: %.*s needs a %s\n", (int)nl, a, nl == 11 ? "seqdb prefix" : "file name");
+        return 2;
+      }
     } else if (strcmp(a, "--chimer_bridge_ordered") == 0) {
       o.chimer_ordered = 1;
     } else if (strncmp(a, "--chimers-nodes", 15) == 0 && (a[15] == 0 || a[15] == '=')) {
@@ -575,12 +590,16 @@ static int main_sgraph(int argc, char **argv) {
                       "with the hash seed); --chimer_bridge_ordered runs it under a stated pop order, or compare with ovlp_to_graph.py --disable_chimer_bridge_removal\n");
       return 2;
     } else {
-      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal | --chimer_bridge_ordered [--chimers-nodes FILE]] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] < ovlp.dat > sg_edges_list\n");
+      fprintf(stderr, "usage: shmr_sgraph [--min_len N] [--min_idt X] [--disable_chimer_bridge_removal | --chimer_bridge_ordered [--chimers-nodes FILE]] [--utg FILE] [--utg-data FILE] [--ctg-paths FILE] [--gfa FILE [--gfa-seqdb PREFIX]] < ovlp.dat > sg_edges_list\n");
       return 2;
     }
   }
   if (o.chimers_nodes && !o.chimer_ordered) {
     fprintf(stderr, "shmr_sgraph: --chimers-nodes needs --chimer_bridge_ordered\n");
+    return 2;
+  }
+  if (o.gfa_seqdb && !o.gfa) {
+    fprintf(stderr, "shmr_sgraph: --gfa-seqdb needs --gfa\n");
     return 2;
   }
   return dedup_stdin("shmr_sgraph", 1, &o);

@@ -192,20 +192,20 @@ void check_rows(const pgx_seqdb *db, std::vector<pgx_tile_row> &rows, size_t n_c
   for (size_t i = 0; i < n; ++i) {
     pgx_tile_row &r = rows[i];
     const unsigned long long nm = name_of(row_name, i);
-    PGX_REQUIRE(r.ctg < n_ctg && (i == 0 ? r.ctg == 0 : r.ctg == rows[i - 1].ctg || r.ctg == rows[i - 1].ctg + 1), PGX_EARG,
+    PGX_REQUIRE_PIECE(r.ctg < n_ctg && (i == 0 ? r.ctg == 0 : r.ctg == rows[i - 1].ctg || r.ctg == rows[i - 1].ctg + 1), PGX_EARG, nm,
                 "tiling path row %llu: contig number %u (the rows of a contig must be consecutive, the contigs numbered 0 .. %zu in order)", nm, r.ctg,
                 n_ctg - 1);
     if (i == 0 || r.ctg != rows[i - 1].ctg) first_row[r.ctg] = (uint32_t)i;
-    PGX_REQUIRE(r.rid0 < nr && db->rlen_by_rid[r.rid0] && r.rid1 < nr && db->rlen_by_rid[r.rid1], PGX_EARG,
+    PGX_REQUIRE_PIECE(r.rid0 < nr && db->rlen_by_rid[r.rid0] && r.rid1 < nr && db->rlen_by_rid[r.rid1], PGX_EARG, nm,
                 "tiling path row %llu: read %u is not in the database", nm, r.rid0 < nr && db->rlen_by_rid[r.rid0] ? r.rid1 : r.rid0);
     const int64_t l0 = db->rlen_by_rid[r.rid0], l1 = db->rlen_by_rid[r.rid1];
-    PGX_REQUIRE(l0 >= OVERHANG, PGX_EARG, "tiling path row %llu: read %u has %lld bases, fewer than the overhang of %d", nm, r.rid0, (long long)l0, OVERHANG);
+    PGX_REQUIRE_PIECE(l0 >= OVERHANG, PGX_EARG, nm, "tiling path row %llu: read %u has %lld bases, fewer than the overhang of %d", nm, r.rid0, (long long)l0, OVERHANG);
     const int64_t span = std::llabs((int64_t)r.e - (int64_t)r.s);
-    PGX_REQUIRE(span + OVERHANG <= l1, PGX_EARG, "tiling path row %llu: |e - s| + %d = %lld exceeds the %lld bases of read %u", nm, OVERHANG,
+    PGX_REQUIRE_PIECE(span + OVERHANG <= l1, PGX_EARG, nm, "tiling path row %llu: |e - s| + %d = %lld exceeds the %lld bases of read %u", nm, OVERHANG,
                 (long long)(span + OVERHANG), (long long)l1, r.rid1);
     int64_t s = r.s, e = r.e;
     if (r.strand1) s = l1 - s, e = l1 - e;
-    PGX_REQUIRE(e > s, PGX_EARG, "tiling path row %llu: e <= s (%lld <= %lld%s)", nm, (long long)e, (long long)s, r.strand1 ? ", after the strand transform" : "");
+    PGX_REQUIRE_PIECE(e > s, PGX_EARG, nm, "tiling path row %llu: e <= s (%lld <= %lld%s)", nm, (long long)e, (long long)s, r.strand1 ? ", after the strand transform" : "");
     r.s = (int32_t)s, r.e = (int32_t)e;   // (|s|, |e| <= 2 l1 < 2^31 for the reads the alignment kernels take; checked by the caller)
     r.strand0 = r.strand0 ? 1 : 0, r.strand1 = r.strand1 ? 1 : 0;
   }
@@ -264,7 +264,7 @@ void contigs_layout(pgx_seqdb *db, const std::vector<pgx_tile_row> &rows, const 
   if (bad != NO_BAD) {
     const size_t i = (size_t)(bad >> 2);
     const unsigned kind = (unsigned)(bad & 3u);
-    PGX_REQUIRE(false, PGX_EARG, "tiling path row %llu: %s", (unsigned long long)name_of(row_name, i),
+    PGX_REQUIRE_PIECE(false, PGX_EARG, name_of(row_name, i), "tiling path row %llu: %s", (unsigned long long)name_of(row_name, i),
                 kind == BAD_SOURCE  ? "the segment the alignment cuts starts before read w's first base (e - seg < 0)"
                 : kind == BAD_START ? "the segment would start before its contig's first base"
                                     : "a segment ends beyond the end of its contig (a later row pulled the contig's length back)");
@@ -340,6 +340,15 @@ struct PathRow {
 };
 
 }  // namespace
+
+// the layout of rows over a resident database, whoever made the rows (pgx_contigs_resident; the GFA segments of pgx_gfa.hip): the checks
+// that need no alignment, then contigs_layout.  A refusal of a row throws a Fail that carries the row's index.
+void contigs_resident_rows(const char *who, pgx_seqdb *db, std::vector<pgx_tile_row> &rows, size_t n_ctg, char **text, uint64_t *ctg_off, uint64_t *text_len) {
+  PGX_REQUIRE(db->max_rlen < (1u << 30), PGX_EARG, "%s: a read of %u bases", who, db->max_rlen);
+  std::vector<uint32_t> first_row;
+  check_rows(db, rows, n_ctg, nullptr, first_row);
+  contigs_layout(db, rows, first_row, nullptr, text, ctg_off, text_len);
+}
 }  // namespace pgx
 
 namespace pgx {
@@ -375,16 +384,17 @@ void feed_path_text(const char *tiling_path, const TileRowFn &add) {
 }
 }  // namespace
 
-// The layout behind pgx_contigs_chunk and pgx_tiling_contigs: feed hands over the rows in order (contig name, the two reads' ids as the idx
-// names them, s, e, strands, the row's number for messages); every check runs in that order, then the batching, the layout, the FASTA.
-int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFeed &feed, const char *out_path, uint64_t *n_ctg_out, uint64_t *n_bases_out) {
-  struct Piece {   // a batch's contig bytes, kept until every batch is through: an error in a later batch must leave nothing written
-    char *text = nullptr;
-    std::vector<uint64_t> off;
-    size_t ctg0 = 0;
-  };
-  std::vector<Piece> pieces;
-  const int rc = guarded([&]() -> int {
+ContigPieces::~ContigPieces() {
+  for (auto &pc : pieces) out_free(pc.text);
+}
+
+// The layout behind pgx_contigs_chunk, pgx_tiling_contigs and the GFA's file level: feed hands over the rows in order (contig name, the two
+// reads' ids as the idx names them, s, e, strands, the row's number for messages); every check runs in that order, then the batching and
+// the layout: the batches' contig bytes as pieces (throws; the Fail of a refused row carries the row's number)
+void contig_pieces_from_rows(const char *who, const char *seqdb_prefix, const TileRowFeed &feed, ContigPieces &out) {
+  std::vector<ContigPieces::Piece> &pieces = out.pieces;
+  std::vector<std::string> &ctg_names = out.names;
+  {
     require_ready();
     PGX_REQUIRE(seqdb_prefix, PGX_EARG, "%s: null argument", who);
     const std::string prefix(seqdb_prefix);
@@ -400,12 +410,11 @@ int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFe
       slot_of[rid[i]] = (uint32_t)i;
     }
     // ---- the tiling path: rows by contig, contigs in order of first appearance (path_to_contig.py:32-39), every check in FILE order
-    std::vector<std::string> ctg_names;
     std::unordered_map<std::string, uint32_t> ctg_of;
     std::vector<std::vector<PathRow>> by_ctg;
     feed([&](const std::string &ctg, int64_t r0, int64_t r1, int64_t s, int64_t e, uint8_t st0, uint8_t st1, uint64_t line) {
       const auto i0 = slot_of.find((uint32_t)r0), i1 = slot_of.find((uint32_t)r1);
-      PGX_REQUIRE(i0 != slot_of.end() && i1 != slot_of.end(), PGX_EARG, "tiling path row %llu: read %lld is not in %s.idx", (unsigned long long)line,
+      PGX_REQUIRE_PIECE(i0 != slot_of.end() && i1 != slot_of.end(), PGX_EARG, line, "tiling path row %llu: read %lld is not in %s.idx", (unsigned long long)line,
                   (long long)(i0 == slot_of.end() ? r0 : r1), seqdb_prefix);
       auto it = ctg_of.find(ctg);
       if (it == ctg_of.end()) {
@@ -415,11 +424,11 @@ int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFe
       by_ctg[it->second].push_back(PathRow{it->second, i0->second, i1->second, (int32_t)s, (int32_t)e, st0, st1, line});
       // the checks of the row itself, here so that the FIRST bad row of the file is the one reported
       const int64_t l0 = rlen[i0->second], l1 = rlen[i1->second];
-      PGX_REQUIRE(l0 >= OVERHANG, PGX_EARG, "tiling path row %llu: read %lld has %lld bases, fewer than the overhang of %d", (unsigned long long)line,
-                  (long long)r0, (long long)l0, OVERHANG);
-      PGX_REQUIRE(l1 < (1LL << 30) && std::llabs(e - s) + OVERHANG <= l1, PGX_EARG, "tiling path row %llu: |e - s| + %d = %lld exceeds the %lld bases of read %lld",
-                  (unsigned long long)line, OVERHANG, (long long)(std::llabs(e - s) + OVERHANG), (long long)l1, (long long)r1);
-      PGX_REQUIRE(st1 ? l1 - e > l1 - s : e > s, PGX_EARG, "tiling path row %llu: e <= s%s", (unsigned long long)line, st1 ? " after the strand transform" : "");
+      PGX_REQUIRE_PIECE(l0 >= OVERHANG, PGX_EARG, line, "tiling path row %llu: read %lld has %lld bases, fewer than the overhang of %d", (unsigned long long)line,
+                        (long long)r0, (long long)l0, OVERHANG);
+      PGX_REQUIRE_PIECE(l1 < (1LL << 30) && std::llabs(e - s) + OVERHANG <= l1, PGX_EARG, line, "tiling path row %llu: |e - s| + %d = %lld exceeds the %lld bases of read %lld",
+                        (unsigned long long)line, OVERHANG, (long long)(std::llabs(e - s) + OVERHANG), (long long)l1, (long long)r1);
+      PGX_REQUIRE_PIECE(st1 ? l1 - e > l1 - s : e > s, PGX_EARG, line, "tiling path row %llu: e <= s%s", (unsigned long long)line, st1 ? " after the strand transform" : "");
     });
     // ---- batches of whole contigs: the reads a batch names gathered into a sub-database of their own, rids remapped to 0 .. m - 1
     size_t free_b = 0, total_b = 0;
@@ -470,13 +479,13 @@ int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFe
       }
       pgx_seqdb *sdb = nullptr;
       const int urc = pgx_seqdb_upload(sub.p, sub_bytes, srid.data(), srlen.data(), sroff.data(), (uint32_t)slots.size(), &sdb);
-      if (urc) return urc;
+      if (urc) throw Fail{urc};   // (its message stands)
       std::unique_ptr<pgx_seqdb, void (*)(pgx_seqdb *)> hold(sdb, pgx_seqdb_free);
       sub.clear();
       std::vector<uint32_t> first_row;
       check_rows(sdb, rows, c1 - c0, names.data(), first_row);
       pieces.emplace_back();
-      Piece &pc = pieces.back();
+      ContigPieces::Piece &pc = pieces.back();
       pc.ctg0 = c0, pc.off.assign(c1 - c0 + 1, 0);
       uint64_t len = 0;
       contigs_layout(sdb, rows, first_row, names.data(), &pc.text, pc.off.data(), &len);
@@ -486,11 +495,22 @@ int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFe
                 slots.size(), sub_bytes / 1e6, len / 1e6);
       c0 = c1;
     }
+    out.bases = bases;
+  }
+}
+
+// The layout behind pgx_contigs_chunk and pgx_tiling_contigs: the pieces, then the FASTA -- written only when every batch is through, so
+// that an error in a later batch leaves nothing written
+int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFeed &feed, const char *out_path, uint64_t *n_ctg_out, uint64_t *n_bases_out) {
+  ContigPieces cp;
+  return guarded([&]() -> int {
+    contig_pieces_from_rows(who, seqdb_prefix, feed, cp);
+    const std::vector<std::string> &ctg_names = cp.names;
     // ---- the FASTA (path_to_contig.py:109,115)
     FILE *f = out_path ? fopen(out_path, "wb") : stdout;
     PGX_REQUIRE(f, PGX_EIO, "cannot write %s", out_path);
     bool ok = true;
-    for (const Piece &pc : pieces)
+    for (const ContigPieces::Piece &pc : cp.pieces)
       for (size_t c = 0; c + 1 < pc.off.size() && ok; ++c) {
         const std::string &nm = ctg_names[pc.ctg0 + c];
         const uint64_t len = pc.off[c + 1] - pc.off[c];
@@ -499,12 +519,10 @@ int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFe
       }
     ok = (out_path ? fclose(f) == 0 : fflush(f) == 0) && ok;
     PGX_REQUIRE(ok, PGX_EIO, "writing %s failed", out_path ? out_path : "stdout");
-    if (n_ctg_out) *n_ctg_out = by_ctg.size();
-    if (n_bases_out) *n_bases_out = bases;
+    if (n_ctg_out) *n_ctg_out = ctg_names.size();
+    if (n_bases_out) *n_bases_out = cp.bases;
     return PGX_OK;
   });
-  for (auto &pc : pieces) out_free(pc.text);
-  return rc;
 }
 
 }  // namespace pgx
@@ -544,11 +562,8 @@ int pgx_contigs_resident(pgx_seqdb *db, const pgx_tile_row *rows, size_t n_rows,
   return guarded([&]() -> int {
     require_ready();
     PGX_REQUIRE(db && text && ctg_off && text_len && (n_rows == 0 || rows), PGX_EARG, "pgx_contigs_resident: null argument");
-    PGX_REQUIRE(db->max_rlen < (1u << 30), PGX_EARG, "pgx_contigs_resident: a read of %u bases", db->max_rlen);
     std::vector<pgx_tile_row> r(rows, rows + n_rows);
-    std::vector<uint32_t> first_row;
-    check_rows(db, r, n_ctg, nullptr, first_row);
-    contigs_layout(db, r, first_row, nullptr, text, ctg_off, text_len);
+    contigs_resident_rows("pgx_contigs_resident", db, r, n_ctg, text, ctg_off, text_len);
     return PGX_OK;
   });
 }

@@ -753,6 +753,27 @@ void drain_deferred();  // waits until every queued job has run (pgx_shutdown)
 using TileRowFn = std::function<void(const std::string &ctg, int64_t rid0, int64_t rid1, int64_t s, int64_t e, uint8_t strand0, uint8_t strand1, uint64_t line)>;
 using TileRowFeed = std::function<void(const TileRowFn &add)>;
 int contigs_from_rows(const char *who, const char *seqdb_prefix, const TileRowFeed &feed, const char *out_path, uint64_t *n_ctg, uint64_t *n_bases);
+// ... up to the FASTA: the batches' contig bytes, kept until every batch is through (an error in a later batch must leave nothing
+// written).  Batch b holds the contigs ctg0 .. ctg0 + off.size() - 2, contig ctg0 + c at text[off[c] .. off[c + 1]); names: the contigs'
+// in order of first appearance.
+struct ContigPieces {
+  struct Piece {
+    char *text = nullptr;   // out_alloc'd
+    std::vector<uint64_t> off;
+    size_t ctg0 = 0;
+  };
+  std::vector<Piece> pieces;
+  std::vector<std::string> names;
+  uint64_t bases = 0;
+  ContigPieces() = default;
+  ContigPieces(const ContigPieces &) = delete;
+  ContigPieces &operator=(const ContigPieces &) = delete;
+  ~ContigPieces();
+};
+void contig_pieces_from_rows(const char *who, const char *seqdb_prefix, const TileRowFeed &feed, ContigPieces &out);   // throws
+// ... over a resident database in any state: pgx_contigs_resident's body (rows: s, e as the tiling path gives them, transformed in place;
+// *text out_alloc'd, NUL-terminated; ctg_off: n_ctg + 1 entries).  Throws; the Fail of a refused row carries the row's index (Fail::piece).
+void contigs_resident_rows(const char *who, pgx_seqdb *db, std::vector<pgx_tile_row> &rows, size_t n_ctg, char **text, uint64_t *ctg_off, uint64_t *text_len);
 
 // host helpers (pgx_api.cpp)
 int load_idx(const char *path, std::vector<uint32_t> &rid, std::vector<uint32_t> &rlen, std::vector<uint64_t> &roff);

@@ -698,6 +698,25 @@ class Unitigs(_DeviceText):
         _lib.check(self._lib.pgx_unitigs_paths(self._handle("pgx_unitigs_paths"), int(first), int(n), _ptr(out)), "pgx_unitigs_paths")
         return out
 
+    def gfa(self, graph_or_edges, db: "ResidentDB | str | None" = None) -> "Gfa":
+        """The assembly graph of these unitigs as GFA 1.0 (pgx_gfa_build): graph_or_edges is what they were built from, a live
+        StringGraph or the edge records (SGRAPH_EDGE_DTYPE) in creation order; db: the resident reads for the segments' sequences (any
+        state), a seqdb prefix (pgx_gfa_build_files: only the reads the segments name are uploaded), or None for the topology-only
+        file.  The result owns its arrays."""
+        g, e, n = None, None, 0
+        if isinstance(graph_or_edges, StringGraph):
+            g = graph_or_edges._handle("pgx_gfa_build")
+        else:
+            e = np.ascontiguousarray(graph_or_edges, SGRAPH_EDGE_DTYPE)
+            n = len(e)
+            e = e if n else np.zeros(1, SGRAPH_EDGE_DTYPE)       # (no records is still "records": a pointer that is not null)
+        f = C.c_void_p()
+        if isinstance(db, (str, bytes, os.PathLike)):
+            name, src = "pgx_gfa_build_files", os.fsencode(db)
+        else:
+            name, src = "pgx_gfa_build", db.h if db is not None else None
+        _lib.check(getattr(self._lib, name)(self._handle(name), g, None if e is None else _ptr(e), n, src, C.byref(f)), name)
+        return Gfa(f)
 
     def contig_paths(self) -> "ContigPaths":
         """the final utg_data and ctg_paths of these unitigs (pgx_unitigs_contig_paths); utg_text() reads these unitigs' paths: keep them
@@ -705,6 +724,72 @@ class Unitigs(_DeviceText):
         c = C.c_void_p()
         _lib.check(self._lib.pgx_unitigs_contig_paths(self._handle("pgx_unitigs_contig_paths"), C.byref(c)), "pgx_unitigs_contig_paths")
         return ContigPaths(c, keep=self)
+
+
+GFA_SEGMENT_DTYPE = np.dtype([("unitig", "<u4"), ("dual", "<u4"), ("n_rows", "<u4"), ("circular", "u1"), ("pad", "u1", (3,)), ("first_row", "<u8"),
+                              ("seq_off", "<u8"), ("seq_len", "<u8")])   # pgx_gfa_segment
+GFA_LINK_DTYPE = np.dtype([("from_seg", "<u4"), ("to_seg", "<u4"), ("from_rev", "u1"), ("to_rev", "u1"), ("pad", "u1", (2,))])   # pgx_gfa_link
+_GFA_STATS = ("unitigs", "segments", "rows", "links_directed", "links", "bases")   # pgx_gfa_stats_t
+assert GFA_SEGMENT_DTYPE.itemsize == 40 and GFA_LINK_DTYPE.itemsize == 12
+
+
+class Gfa:
+    """The assembly graph as GFA 1.0 (Unitigs.gfa): every unitig that is smaller than its dual is a segment `utg%06u` of
+    its index, with the bases the contig layout makes of its rows when a read database was given; the links join the directed unitigs
+    a, b with t(a) == s(b), one of each link and its dual.  stats: the counts; segments() / links() / rows(): the tables
+    (GFA_SEGMENT_DTYPE, GFA_LINK_DTYPE, _lib.TILE_ROW_DTYPE); text(): the whole file; write(path): to a file, returns the bytes."""
+
+    def __init__(self, handle):
+        self._lib = _lib.load()
+        self.h = handle
+        st = (C.c_uint64 * len(_GFA_STATS))()
+        _lib.check(self._lib.pgx_gfa_stats(self.h, st), "pgx_gfa_stats")
+        self.stats = dict(zip(_GFA_STATS, (int(v) for v in st)))
+
+    def _handle(self, who):
+        if not self.h:
+            raise _lib.PgxError(f"{who}: the GFA is closed")
+        return self.h
+
+    def _table(self, name, count, dtype, first, n):
+        n = self.stats[count] - first if n is None else n
+        out = np.zeros(n, dtype)
+        _lib.check(getattr(self._lib, name)(self._handle(name), int(first), int(n), _ptr(out)), name)
+        return out
+
+    def segments(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        return self._table("pgx_gfa_segments", "segments", GFA_SEGMENT_DTYPE, first, n)
+
+    def links(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        return self._table("pgx_gfa_links", "links", GFA_LINK_DTYPE, first, n)
+
+    def rows(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        return self._table("pgx_gfa_rows", "rows", _lib.TILE_ROW_DTYPE, first, n)
+
+    def text(self) -> bytes:
+        return _take_text("pgx_gfa_text", lambda text, tl: self._lib.pgx_gfa_text(self._handle("pgx_gfa_text"), text, tl))
+
+    def write(self, path: str) -> int:
+        _lib.check(self._lib.pgx_gfa_write(self._handle("pgx_gfa_write"), str(path).encode()), "pgx_gfa_write")
+        return os.path.getsize(path)
+
+    def close(self):
+        h, self.h = self.h, C.c_void_p()
+        if h:
+            _lib.check(self._lib.pgx_gfa_free(h), "pgx_gfa_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 CTG_UNITIG_DTYPE = np.dtype([("type", "<u4"), ("dual", "<u4")])   # pgx_ctg_unitig
@@ -970,13 +1055,17 @@ def graph_to_path(sg, utg_data: str, ctg_paths: str, p_out: str | None = None, a
 
 
 def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float = 96.0, device=None, utg_path: str | None = None, utg_data_path: str | None = None,
-                ctg_paths_path: str | None = None, chimer_ordered: bool = False, chimers_nodes_path: str | None = None) -> dict:
+                ctg_paths_path: str | None = None, chimer_ordered: bool = False, chimers_nodes_path: str | None = None, gfa_path: str | None = None,
+                gfa_seqdb: str | None = None) -> dict:
     """cat ovlp*.dat | shmr_sgraph > sg_edges_list: the files through a graph-mode DedupStream piece by piece, the graph, its text to
     out_path (and, with utg_path, its unitigs' lines to that file; with utg_data_path / ctg_paths_path the final utg_data / ctg_paths).
     chimer_ordered: with the chimer bridge step under the stated pop order (DedupStream.string_graph); chimers_nodes_path, valid only with
-    it, takes the chimers_nodes file.  Returns the graph's statistics."""
+    it, takes the chimers_nodes file.  gfa_path: the unitig graph as GFA 1.0 to that file (Unitigs.gfa), with the segments' sequences
+    from the seqdb prefix gfa_seqdb, topology only without one.  Returns the graph's statistics."""
     if chimers_nodes_path is not None and not chimer_ordered:
         raise ValueError("chimers_nodes_path needs chimer_ordered")
+    if gfa_seqdb is not None and gfa_path is None:
+        raise ValueError("gfa_seqdb needs gfa_path")
     _lib.init(device)
     if isinstance(ovlp_paths, (str, bytes)):
         ovlp_paths = [ovlp_paths]
@@ -995,8 +1084,11 @@ def shmr_sgraph(ovlp_paths, out_path: str, min_len: int = 4000, min_idt: float =
             if chimers_nodes_path is not None:
                 with open(chimers_nodes_path, "wb") as f:
                     f.write(g.chimers_nodes())
-            if utg_path is not None or utg_data_path is not None or ctg_paths_path is not None:
+            if utg_path is not None or utg_data_path is not None or ctg_paths_path is not None or gfa_path is not None:
                 with g.unitigs() as u:
+                    if gfa_path is not None:
+                        with u.gfa(g, gfa_seqdb) as f:
+                            f.write(gfa_path)
                     if utg_path is not None:
                         u.write(utg_path)
                     if utg_data_path is not None or ctg_paths_path is not None:
@@ -1358,7 +1450,8 @@ def polish(rdb: "ResidentDB", read_top, read_counts, contig_fasta, mapping_nchun
 
 def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: int = 0, cns_nchunk: int = 0, min_len: int = 4000,
              min_idt: float = 96.0, with_alt: bool = False, levels=2, reduction=6, window=80, kmer=16, bestn=4, mc_lower=2, mc_upper=240,
-             align_bandwidth=100, ovlp_upper=120, chimer_ordered: bool = True, out_dir: str | None = None, device=None, hpc=False) -> dict:
+             align_bandwidth=100, ovlp_upper=120, chimer_ordered: bool = True, out_dir: str | None = None, device=None, hpc=False,
+             gfa: bool = False) -> dict:
     """pg_run.py from the read database on (:227-386 and, with cns_nchunk > 0, :389-565) in one process, on one ResidentDB loaded once:
     every index chunk; every overlap chunk on the concatenated lists and counts; the chunks' records through one graph-mode
     DedupStream in chunk order; the string graph (chimer_ordered: the chimer bridge step, which pg_run.py leaves on, under the stated
@@ -1367,7 +1460,9 @@ def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: 
     seqdb_prefix may be a ResidentDB that carries its read lengths (ResidentDB.from_reads): it is used as it is and left open.
     Returns dict(p_ctg, a_ctg, p_ctg_cns, stats): FASTA bytes (a_ctg / p_ctg_cns None when not asked for) and the stages' statistics
     with their wall times.  With out_dir, p_ctg.fa, a_ctg.fa and p_ctg_cns.fa are written there.  Every handle is closed, also when
-    a stage raises.  hpc: every index (reads and contigs) holds homopolymer-compressed shimmers (ResidentDB.index)."""
+    a stage raises.  hpc: every index (reads and contigs) holds homopolymer-compressed shimmers (ResidentDB.index).
+    gfa: the result also carries `gfa`, the assembly graph of the phase-1 unitigs with sequences (Unitigs.gfa on the graph and the
+    resident reads) as GFA bytes, out_dir gets asm.gfa and stats["ms"] the key "gfa"; without it nothing of that is there."""
     import contextlib
     import time
     from .formats import read_seqdb
@@ -1415,6 +1510,11 @@ def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: 
         p_ctg = fasta_of(t, 0)
         a_ctg = fasta_of(t, 1) if with_alt else None
         lap("contigs")
+        gfa_text = None
+        if gfa:
+            with u.gfa(g, rdb) as f:
+                gfa_text, stats["gfa"] = f.text(), f.stats
+            lap("gfa")
         cns = None
         if int(cns_nchunk) > 0:
             stats["polish"] = {}
@@ -1423,11 +1523,14 @@ def assemble(seqdb_prefix, index_nchunk: int, ovlp_nchunk: int, mapping_nchunk: 
     stats["ms"] = ms
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
-        for name, data in (("p_ctg.fa", p_ctg), ("a_ctg.fa", a_ctg), ("p_ctg_cns.fa", cns)):
+        for name, data in (("p_ctg.fa", p_ctg), ("a_ctg.fa", a_ctg), ("p_ctg_cns.fa", cns), ("asm.gfa", gfa_text)):
             if data is not None:
                 with open(os.path.join(out_dir, name), "wb") as f:
                     f.write(data)
-    return dict(p_ctg=p_ctg, a_ctg=a_ctg, p_ctg_cns=cns, stats=stats)
+    out = dict(p_ctg=p_ctg, a_ctg=a_ctg, p_ctg_cns=cns, stats=stats)
+    if gfa:
+        out["gfa"] = gfa_text
+    return out
 
 
 def map_reads_to_ref(ref_mmers, mmers, counts, rlen_by_rid, total_chunk=1, mychunk=1, mc_lower=1, mc_upper=240, device=None):
