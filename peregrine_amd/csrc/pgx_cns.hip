@@ -128,14 +128,6 @@ __global__ void k_cns_piece_check(const uint32_t *naln, uint32_t n_piece, uint32
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p < n_piece && naln[p] > MAX_ALNS_PER_PIECE) atomicMin(&err[E_MANY], p);
 }
-__global__ void k_cns_iota(uint32_t *v, uint32_t n) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = i;
-}
-__global__ void k_cns_gather(const uint64_t *in, const uint32_t *idx, uint64_t *out, uint32_t n) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[idx[i]];
-}
 // hi, lo: the keys of the sorted tags.  An edge starts where either changes.
 __global__ void k_cns_edge_heads(const uint64_t *hi, const uint64_t *lo, uint32_t n, uint8_t *flag) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -393,16 +385,13 @@ void cns_call_dev(const char *who, const pgx_cns_aln *d_alns, size_t n_aln, cons
   DevBuf<uint32_t> estart, nfirst, e_nid;
   DevBuf<uint64_t> node_key;
   {
-    DevBuf<uint64_t> tmp(n_tag);
-    DevBuf<uint32_t> idx0(n_tag), idx1(n_tag);
+    DevBuf<uint32_t> order(n_tag);
     DevBuf<uint8_t> flag(n_tag);
     int piece_bits = 1;
     while ((1u << piece_bits) < np) ++piece_bits;
-    if (n_tag) LAUNCH(k_cns_iota, n_tag, idx0.p, n_tag);
-    sort_pairs(lo.p, tmp.p, idx0.p, idx1.p, n_tag, 0, 44, &ws);
-    if (n_tag) LAUNCH(k_cns_gather, n_tag, hi.p, idx1.p, tmp.p, n_tag);
-    sort_pairs(tmp.p, hi.p, idx1.p, idx0.p, n_tag, 0, PIECE_SHIFT + piece_bits, &ws);
-    if (n_tag) LAUNCH(k_cns_gather, n_tag, lo.p, idx0.p, tmp.p, n_tag);
+    sort_order({{hi.p, PIECE_SHIFT + piece_bits}, {lo.p, 44}}, n_tag, nullptr, order.p, hi.p, &ws);
+    DevBuf<uint64_t> tmp(n_tag);
+    gather(lo.p, order.p, n_tag, tmp.p, &ws);
     lo = std::move(tmp);   // hi, lo: the sorted tags' keys
     if (n_tag) LAUNCH(k_cns_edge_heads, n_tag, hi.p, lo.p, n_tag, flag.p);
     estart.alloc(n_tag);

@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <string>
 
-#include "pgx_internal.h"
+#include "pgx_text.h"
 
 namespace pgx {
 namespace {
@@ -358,7 +358,6 @@ const char *const P_TEXT[] = {"", "does not have nine fields", "has a field that
                               "has a byte that is not ASCII"};
 
 __host__ __device__ inline uint64_t pad16(uint64_t n) { return (n + 15) & ~15ull; }
-__host__ __device__ inline bool is_blank(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31); }   // Python's split()
 
 struct Item {   // one sequence of a batch's pool
   uint64_t dst, src;
@@ -548,19 +547,6 @@ __global__ void k_par_newlines(const char *text, uint32_t n, uint8_t *flag) {   
   if (i < n) flag[i] = text[i] == '\n';
 }
 namespace {
-// an optional '-' and 1 .. 18 digits
-__device__ inline bool parse_int(const char *p, uint32_t n, int64_t *out) {
-  const bool neg = n && p[0] == '-';
-  uint32_t i = neg;
-  if (i >= n || n - i > 18) return false;
-  int64_t v = 0;
-  for (; i < n; ++i) {
-    if (p[i] < '0' || p[i] > '9') return false;
-    v = v * 10 + (p[i] - '0');
-  }
-  *out = neg ? -v : v;
-  return true;
-}
 // A thread per line: line k is text[nlpos[k - 1] + 1, nlpos[k]).  rows[k]: its nine numbers; keep[k]: it belongs to the chunk; a line the
 // script dies on: code[k], and err[0] = min(err[0], k)
 __global__ void k_par_lines(const char *__restrict__ text, const uint32_t *__restrict__ nlpos, uint32_t nl, uint32_t total, uint32_t my, int64_t *__restrict__ rows,

@@ -23,32 +23,12 @@
 #include <unordered_map>
 #include <unordered_set>
 
-#include "pgx_dedup_rows.h"
+#include "pgx_gedges.h"
 
 namespace pgx {
 namespace {
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint64_t NA = ~0ULL;   // the via of a compound unitig
 enum : uint32_t { T_SIMPLE, T_SPUR2, T_DUP, T_CONTAINED, T_BRIDGE, T_COMPOUND, N_TYPES };
-
-__device__ inline uint32_t lower_bound(const uint64_t *__restrict__ a, uint32_t n, uint64_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-__device__ inline uint32_t lower_bound(const uint32_t *__restrict__ a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // the unitig graph

@@ -8,7 +8,7 @@
 //   by_v   (vkey, gi) ascending                (a stable sort: within a node the edges ascend by creation index, and so do the unitigs they
 //                                               start -- the links come out in ascending (a, b) without a sort of their own)
 // and, for host records only, the reverse of an edge is looked up in
-//   by_vw  (vkey, wkey, gi) ascending          (the two-key binary search of k_ut_links)
+//   by_vw  (vkey, wkey, gi) ascending          (pgx_gedges.h: GEdges, find_vw)
 // No launch and no host round trip per unitig or per link.  No result depends on the order in which atomics land: they count.
 // The text: the bases come to the host once, from the layout; the heads and tails of the S lines and the L lines are formatted on the
 // device with the piece scheme of pgx_text.h and the file is put together on the host, as contigs_from_rows writes its FASTA -- one copy
@@ -16,45 +16,18 @@
 
 #include <atomic>
 
-#include "pgx_dedup_rows.h"
+#include "pgx_gedges.h"
 
 typedef pgx_sgraph_edge Edge;
 
 namespace pgx {
 namespace {
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 // the counters of a build
 enum : uint32_t { C_BEYOND = 0, C_FOREIGN = 1, C_DUAL = 2, C_LINK = 3, C_N = 4 };
-
-__device__ inline uint64_t vkey(const Edge &e) { return (uint64_t)e.v_rid << 1 | (e.v_end & 1u); }
-__device__ inline uint64_t wkey(const Edge &e) { return (uint64_t)e.w_rid << 1 | (e.w_end & 1u); }
-__device__ inline uint32_t lower_bound(const uint64_t *__restrict__ a, uint32_t n, uint64_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-// the last i < n with a[i] <= x (a ascending, a[0] <= x)
-__device__ inline uint32_t last_le(const uint64_t *__restrict__ a, uint32_t n, uint64_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo ? lo - 1 : 0;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // the records against the unitigs, the edge -> unitig map
 // ---------------------------------------------------------------------------------------------------------
-__global__ void k_gf_flags(const Edge *__restrict__ edges, uint32_t n, uint8_t *__restrict__ flag) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) flag[e] = edges[e].type == PGX_SGRAPH_G;
-}
 // A thread per path slot k.  cnt[C_BEYOND] counts the path indices beyond the records, cnt[C_FOREIGN] the slots whose record is not the G
 // edge the unitigs saw there (another node entered, another start node at a unitig's first slot).  unitig_of[] is written for the rest.
 __global__ void k_gf_map(const uint32_t *__restrict__ paths, const uint32_t *__restrict__ slot_u, const uint64_t *__restrict__ slot_w, const pgx_unitig *__restrict__ tab,
@@ -71,17 +44,6 @@ __global__ void k_gf_map(const uint32_t *__restrict__ paths, const uint32_t *__r
   if (ok && tab[u].first == k) ok = vkey(r) == ((uint64_t)tab[u].s_rid << 1 | tab[u].s_end);
   if (!ok) atomicAdd(&cnt[C_FOREIGN], 1u);
   else unitig_of[e] = u;
-}
-__global__ void k_gf_keys(const Edge *__restrict__ edges, const uint32_t *__restrict__ gsel, uint32_t m, uint64_t *__restrict__ vk, uint64_t *__restrict__ wk,
-                          uint32_t *__restrict__ iota) {
-  const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= m) return;
-  const Edge e = edges[gsel[gi]];
-  vk[gi] = vkey(e), wk[gi] = wkey(e), iota[gi] = gi;
-}
-__global__ void k_gf_gather(const uint64_t *__restrict__ key, const uint32_t *__restrict__ idx, uint32_t m, uint64_t *__restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) out[i] = key[idx[i]];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -101,13 +63,8 @@ __global__ void k_gf_dual(const pgx_unitig *__restrict__ tab, const uint32_t *__
       r = e ^ 1u;
     } else {
       const uint64_t rv = wkey(edges[e]) ^ 1u, rw = vkey(edges[e]) ^ 1u;
-      uint32_t lo = 0, hi = m;
-      while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (sv[mid] < rv || (sv[mid] == rv && sw[mid] < rw)) lo = mid + 1;
-        else hi = mid;
-      }
-      if (lo < m && sv[lo] == rv && sw[lo] == rw) r = gsel[se[lo]];
+      const uint32_t i = find_vw(sv, sw, m, rv, rw);
+      if (i != NONE) r = gsel[se[i]];
     }
   }
   dual[u] = r < n ? unitig_of[r] : NONE;
@@ -347,14 +304,9 @@ void build_gfa(const char *who, const UnitigsView &uv, const Edge *d_edges, uint
   f->poff.assign(1, 0), f->seq_off.assign(1, 0);
   // ---- the records against the unitigs, the edge -> unitig map, the sorted lists
   std::unique_ptr<KernelTimer> part(new KernelTimer("gfa_dual", n));
-  DevBuf<uint32_t> gsel(n);
-  uint32_t m_rec = 0;
-  if (n) {
-    DevBuf<uint8_t> flag(n);
-    LAUNCH(k_gf_flags, n, d_edges, n, flag.p);
-    m_rec = select_indices(flag.p, n, gsel.p, &tmp);
-  }
-  PGX_REQUIRE(m_rec == m, PGX_EARG, "pgx_gfa_build: the edge records hold %u G edges, the unitigs were built from %u", m_rec, m);
+  GEdges g;
+  g.select(d_edges, n, &tmp);
+  PGX_REQUIRE(g.m == m, PGX_EARG, "pgx_gfa_build: the edge records hold %u G edges, the unitigs were built from %u", g.m, m);
   if (m == 0) return;
   DevBuf<uint32_t> cnt(C_N), unitig_of(n);
   PGX_HIP(hipMemsetAsync(cnt.p, 0, C_N * sizeof(uint32_t), st));
@@ -367,23 +319,14 @@ void build_gfa(const char *who, const UnitigsView &uv, const Edge *d_edges, uint
   PGX_REQUIRE(h_cnt[C_BEYOND] == 0, PGX_EARG, "pgx_gfa_build: %u path indices lie beyond the %u edge records", h_cnt[C_BEYOND], n);
   PGX_REQUIRE(h_cnt[C_FOREIGN] == 0, PGX_EARG, "pgx_gfa_build: %u path edges are not the G edges the unitigs were built from (the records of another graph)",
               h_cnt[C_FOREIGN]);
-  DevBuf<uint64_t> vk(m), wk(m), ov(m);
-  DevBuf<uint32_t> iota(m), oe(m);
-  LAUNCH(k_gf_keys, m, d_edges, gsel.p, m, vk.p, wk.p, iota.p);
-  sort_pairs(vk.p, ov.p, iota.p, oe.p, m, 0, 33, &tmp);
+  DevBuf<uint64_t> ov(m);
+  DevBuf<uint32_t> oe(m);
+  g.keys(NoRule{}, nullptr);
+  sort_pairs(g.vk.p, ov.p, g.ids.p, oe.p, m, 0, 33, &tmp);
   DevBuf<uint32_t> dual(n_u);
-  {
-    DevBuf<uint64_t> swk, sv, sw, k2;
-    DevBuf<uint32_t> in_e, se;
-    if (!pairs) {   // by_vw: by w, then stably by v; sw gathered behind the second sort
-      swk.alloc(m), sv.alloc(m), sw.alloc(m), k2.alloc(m), in_e.alloc(m), se.alloc(m);
-      sort_pairs(wk.p, swk.p, iota.p, in_e.p, m, 0, 33, &tmp);
-      LAUNCH(k_gf_gather, m, vk.p, in_e.p, m, k2.p);
-      sort_pairs(k2.p, sv.p, in_e.p, se.p, m, 0, 33, &tmp);
-      LAUNCH(k_gf_gather, m, wk.p, se.p, m, sw.p);
-    }
-    LAUNCH(k_gf_dual, n_u, uv.tab, uv.paths, n_u, m, d_edges, n, unitig_of.p, gsel.p, sv.p, sw.p, se.p, dual.p);
-  }
+  if (!pairs) g.by_w(&tmp), g.by_vw(nullptr, &tmp);   // host records: the reverse of an edge is looked up in by_vw
+  LAUNCH(k_gf_dual, n_u, uv.tab, uv.paths, n_u, m, d_edges, n, unitig_of.p, g.gsel.p, g.sv.p, g.sw.p, g.out_e.p, dual.p);
+  g.vk.release(), g.wk.release(), g.release_lists();
   // ---- segments
   uint32_t n_seg = 0;
   DevBuf<uint32_t> seg_unitig(n_u), seg_of(n_u);
@@ -436,7 +379,7 @@ void build_gfa(const char *who, const UnitigsView &uv, const Edge *d_edges, uint
     if (n_dir) {
       DevBuf<uint32_t> la(n_dir), lb(n_dir), kept(n_dir);
       DevBuf<uint8_t> keep(n_dir);
-      hipLaunchKernelGGL(k_gf_link_fill, dim3(stride_grid(cdiv(n_dir, 256), 8)), dim3(256), 0, st, loff.p, lo_out.p, n_u, n_dir, oe.p, gsel.p, m, unitig_of.p, uv.tab,
+      hipLaunchKernelGGL(k_gf_link_fill, dim3(stride_grid(cdiv(n_dir, 256), 8)), dim3(256), 0, st, loff.p, lo_out.p, n_u, n_dir, oe.p, g.gsel.p, m, unitig_of.p, uv.tab,
                          uv.paths, dual.p, la.p, lb.p, keep.p, cnt.p);
       PGX_HIP(hipGetLastError());
       cnt.download(h_cnt, C_N);

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -248,6 +249,18 @@ void sort_pairs(const uint64_t *k_in, uint64_t *k_out, const uint32_t *v_in, uin
 void sort_pairs(const uint32_t *k_in, uint32_t *k_out, const uint32_t *v_in, uint32_t *v_out, size_t n, int begin_bit, int end_bit, PGX_PRIM_TAIL);
 void sort_pairs(const uint8_t *k_in, uint8_t *k_out, const uint32_t *v_in, uint32_t *v_out, size_t n, int begin_bit, int end_bit, PGX_PRIM_TAIL);
 void sort_keys(const uint64_t *k_in, uint64_t *k_out, size_t n, int begin_bit, int end_bit, PGX_PRIM_TAIL);
+// d[i] = i; out[i] = key[idx[i]]
+void iota(uint32_t *d, size_t n, PGX_PRIM_TAIL);
+void gather(const uint64_t *key, const uint32_t *idx, size_t n, uint64_t *out, PGX_PRIM_TAIL);
+// order_out = the stable order of 0 .. n-1 by (keys[0], keys[1], ..), each key by its low `bits` bits: a chain of sort_pairs from the last
+// key to the first, each key but the chain's first gathered behind the order so far.  first_out = keys[0] in that order (it may be
+// keys[0] itself where there are more keys).  order_in: the order the chain starts from (equal keys keep its order; not order_out),
+// nullptr: 0 .. n-1.  On ctx().stream only: the temporaries (an order, a key column or two) go back to the block cache on return.
+struct SortKey {
+  const uint64_t *key;
+  int bits;
+};
+void sort_order(std::initializer_list<SortKey> keys, size_t n, const uint32_t *order_in, uint32_t *order_out, uint64_t *first_out, PrimWs *tmp = nullptr);
 // list = the i < n, ascending, with flags[i] != 0; returns how many (_dev: leaves the number at d_num instead, no synchronisation)
 uint32_t select_indices(const uint8_t *d_flags, size_t n, uint32_t *d_list, PGX_PRIM_TAIL);
 uint32_t select_indices(const uint32_t *d_flags, size_t n, uint32_t *d_list, PGX_PRIM_TAIL);

@@ -235,15 +235,6 @@ __global__ void k_first_flag(const uint64_t *__restrict__ key0, uint32_t nr, con
   flag[i] = tseq[h] == i;
 }
 
-__global__ void k_iota(uint32_t *__restrict__ v, uint32_t n) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = i;
-}
-__global__ void k_gather_u64(const uint64_t *__restrict__ src, const uint32_t *__restrict__ perm, uint32_t n,
-                             uint64_t *__restrict__ dst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[perm[i]];
-}
 __global__ void k_gather_out(const uint64_t *__restrict__ y0, const uint8_t *__restrict__ dir,
                              const uint32_t *__restrict__ perm, uint32_t n, uint64_t *__restrict__ sy0,
                              uint8_t *__restrict__ sdir) {
@@ -570,7 +561,7 @@ void dev_pairs_scatter(const uint32_t *d_rlen, uint32_t T, int64_t start, const 
   hipLaunchKernelGGL(k_records_all<1>, dim3(cdiv(n, 256)), dim3(256), 0, st, g_scatter.mm, n, chain.p, T, d_rlen, (uint32_t *)nullptr,
                      off.p, rec.p, dest.p);
   // stable by destination: the records of a destination stay in scan order (= insertion order of the receiving chunk)
-  hipLaunchKernelGGL(k_iota, dim3(cdiv(nr, 256)), dim3(256), 0, st, idx.p, nr);
+  iota(idx.p, nr);
   sort_pairs(dest.p, dest_s.p, idx.p, perm.p, nr, 0, 8, &tmp);
   g_scatter.send.alloc(nr);
   hipLaunchKernelGGL(k_gather_rec, dim3(cdiv(nr, 256)), dim3(256), 0, st, rec.p, perm.p, nr, g_scatter.send.p);
@@ -668,7 +659,7 @@ static void early_groups(const PairRecs &R, PrimWs &tmp, const EarlyFn &early) {
   eg.n = nd;
   if (nd) {
     DevBuf<uint64_t> keys(nd);
-    hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nd, 256)), dim3(256), 0, st, R.key0.p, idx.p, nd, keys.p);
+    gather(R.key0.p, idx.p, nd, keys.p);
     eg.keys = to_host(keys, nd);
     PGX_HIP(hipMemcpyAsync(&eg.last_first, idx.p + nd - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     sync();
@@ -733,20 +724,20 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
   }
   {
     if (flags & PAIRS_INSERTION_ORDER) {  // buckets keep their records in insertion order (shmr_map never sorts them)
-      hipLaunchKernelGGL(k_iota, dim3(cdiv(nr, 256)), dim3(256), 0, st, perm_a.p, nr);
+      iota(perm_a.p, nr);
     } else {
-      hipLaunchKernelGGL(k_iota, dim3(cdiv(nr, 256)), dim3(256), 0, st, idx.p, nr);
+      iota(idx.p, nr);
       sort_pairs(npos.p, k32s.p, idx.p, perm_a.p, nr, 0, pbits, &tmp);
     }
-    hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nr, 256)), dim3(256), 0, st, key1.p, perm_a.p, nr, kg.p);
+    gather(key1.p, perm_a.p, nr, kg.p);
     sort_pairs(kg.p, kgs.p, perm_a.p, perm_b.p, nr, 0, kbits, &tmp);
-    hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nr, 256)), dim3(256), 0, st, key0.p, perm_b.p, nr, kg.p);
+    gather(key0.p, perm_b.p, nr, kg.p);
     sort_pairs(kg.p, kgs.p, perm_b.p, perm_a.p, nr, 0, kbits, &tmp);
   }
   // perm_a = final order; kgs = sorted key0
   DevBuf<uint64_t> sk1(nr), sy0(nr);
   DevBuf<uint8_t> sdir(nr), fb(nr), fg(nr);
-  hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nr, 256)), dim3(256), 0, st, key1.p, perm_a.p, nr, sk1.p);
+  gather(key1.p, perm_a.p, nr, sk1.p);
   hipLaunchKernelGGL(k_gather_out, dim3(cdiv(nr, 256)), dim3(256), 0, st, y0.p, dir.p, perm_a.p, nr, sy0.p, sdir.p);
   hipLaunchKernelGGL(k_flags, dim3(cdiv(nr, 256)), dim3(256), 0, st, kgs.p, sk1.p, nr, fb.p, fg.p);
   DevBuf<uint32_t> bstart(nr + 1), gstart(nr + 1), d_n(2);
@@ -776,9 +767,9 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
     int fbits = 1, gbits = 1;
     while (fbits < 32 && ((uint64_t)1 << fbits) < (uint64_t)nr) ++fbits;
     while (gbits < 32 && ((uint64_t)1 << gbits) < (uint64_t)ng) ++gbits;
-    hipLaunchKernelGGL(k_iota, dim3(cdiv(ng, 256)), dim3(256), 0, st, iota_g.p, ng);
+    iota(iota_g.p, ng);
     sort_pairs(gfirst.p, gf_sorted.p, iota_g.p, gord.p, ng, 0, fbits, &tmp);
-    hipLaunchKernelGGL(k_iota, dim3(cdiv(nbk, 256)), dim3(256), 0, st, iota_b.p, nbk);
+    iota(iota_b.p, nbk);
     hipLaunchKernelGGL(k_bucket_order_key, dim3(cdiv(nbk, 256)), dim3(256), 0, st, gbucket.p, ng, bfirst.p, nbk, fbits, bok.p);
     sort_pairs(bok.p, bok_sorted.p, iota_b.p, bord.p, nbk, 0, fbits + gbits, &tmp);
   }
@@ -798,7 +789,7 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
   }
   DevBuf<uint64_t> sy1((flags & PAIRS_Y1) ? nr : 0);
   if (flags & PAIRS_Y1) {
-    hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nr, 256)), dim3(256), 0, st, y1.p, perm_a.p, nr, sy1.p);
+    gather(y1.p, perm_a.p, nr, sy1.p);
     out.y1 = to_host(sy1, nr);
   }
   const bool dev_tables = (flags & PAIRS_DEV_TABLES) && (flags & PAIRS_ORD_TABLES) && keep_dev && lazy && !(flags & PAIRS_Y1);
@@ -807,7 +798,7 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
     out.bord = to_host(bord, nbk);
   }
   DevBuf<uint64_t> bkey1(nbk), gkey0(ng);
-  hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(ng, 256)), dim3(256), 0, st, kgs.p, gstart.p, ng, gkey0.p);
+  gather(kgs.p, gstart.p, ng, gkey0.p);
   DevBuf<uint32_t> bn_o((flags & PAIRS_ORD_TABLES) ? nbk : 0);
   DevBuf<uint8_t> gtrail((flags & PAIRS_ORD_TABLES) ? ng : 0);
   if (dev_tables) {
@@ -848,7 +839,7 @@ static void bucketize(PairRecs &R, unsigned flags, PairTables &out, DevicePairs 
     out.bn_ord = to_host(bn_o, nbk);
     out.gtrail = to_host(gtrail, ng);
   } else {
-    hipLaunchKernelGGL(k_gather_u64, dim3(cdiv(nbk, 256)), dim3(256), 0, st, sk1.p, bstart.p, nbk, bkey1.p);
+    gather(sk1.p, bstart.p, nbk, bkey1.p);
     out.bkey1 = to_host(bkey1, nbk);
     out.bfirst = to_host(bfirst, nbk);
   }

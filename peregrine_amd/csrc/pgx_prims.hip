@@ -62,6 +62,14 @@ void sort_pairs_of(const K *k_in, K *k_out, const uint32_t *v_in, uint32_t *v_ou
     return hipcub::DeviceRadixSort::SortPairs(work, bytes, k_in, k_out, v_in, v_out, ni, begin_bit, end_bit, st);
   });
 }
+__global__ void k_prim_iota(uint32_t *__restrict__ d, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = i;
+}
+__global__ void k_prim_gather(const uint64_t *__restrict__ key, const uint32_t *__restrict__ idx, uint32_t n, uint64_t *__restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = key[idx[i]];
+}
 template <typename FlagIt>
 uint32_t select_indices_of(FlagIt flags, size_t n, uint32_t *d_list, PrimWs *tmp, hipStream_t st) {
   return counted<uint32_t>("select", n, tmp, st, [&](void *work, size_t &bytes, int ni, uint32_t *d_num) {
@@ -102,6 +110,42 @@ void sort_pairs(const uint8_t *k_in, uint8_t *k_out, const uint32_t *v_in, uint3
 void sort_keys(const uint64_t *k_in, uint64_t *k_out, size_t n, int begin_bit, int end_bit, TAIL) {
   run("radix sort of keys", n, tmp,
       [&](void *work, size_t &bytes, int ni) { return hipcub::DeviceRadixSort::SortKeys(work, bytes, k_in, k_out, ni, begin_bit, end_bit, st); });
+}
+void iota(uint32_t *d, size_t n, TAIL) {
+  if (n == 0) return;
+  PGX_REQUIRE(n <= (size_t)INT_MAX, PGX_EARG, "too many records for one call");
+  LAUNCH(k_prim_iota, n, d, (uint32_t)n);
+  PGX_HIP(hipGetLastError());
+}
+void gather(const uint64_t *key, const uint32_t *idx, size_t n, uint64_t *out, TAIL) {
+  if (n == 0) return;
+  PGX_REQUIRE(n <= (size_t)INT_MAX, PGX_EARG, "too many records for one call");
+  LAUNCH(k_prim_gather, n, key, idx, (uint32_t)n, out);
+  PGX_HIP(hipGetLastError());
+}
+void sort_order(std::initializer_list<SortKey> keys, size_t n, const uint32_t *order_in, uint32_t *order_out, uint64_t *first_out, PrimWs *tmp) {
+  const int n_keys = (int)keys.size();
+  if (n == 0 || n_keys == 0) return;
+  hipStream_t st = ctx().stream;
+  DevBuf<uint32_t> other;      // the orders alternate between this and order_out, the last lands in order_out
+  DevBuf<uint64_t> col, junk;  // a key behind the order so far; the sorted keys nobody reads
+  if (n_keys > 1 || !order_in) other.alloc(n);
+  if (n_keys > 1 || order_in) col.alloc(n);
+  if (n_keys > 2 || (n_keys > 1 && order_in)) junk.alloc(n);
+  const uint32_t *cur = order_in;
+  if (!cur) {
+    uint32_t *first = n_keys & 1 ? other.p : order_out;
+    iota(first, n, tmp, st);
+    cur = first;
+  }
+  for (int k = n_keys - 1; k >= 0; --k) {
+    const uint64_t *k_in = keys.begin()[k].key;
+    if (order_in || k < n_keys - 1) gather(k_in, cur, n, col.p, tmp, st), k_in = col.p;
+    uint32_t *next = k & 1 ? other.p : order_out;
+    uint64_t *k_out = k == 0 ? first_out : k_in == col.p ? junk.p : col.p;
+    sort_pairs(k_in, k_out, cur, next, n, 0, keys.begin()[k].bits, tmp, st);
+    cur = next;
+  }
 }
 
 // ---- selects -------------------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-// pgx_text.h -- everything about device text, once: the pieces of a line as glibc prints them (LineOut), the stream-out of a tile of
+// pgx_text.h -- everything about device text, once: the fields of a line that is read (is_blank, parse_int), the pieces of a line as
+// glibc prints them (LineOut), the stream-out of a tile of
 // text from LDS (tile_out), the pinned staging that device text leaves through (TextStage), the host side of an entry point that hands
 // text out (text_call, text_hand_out), and the piece scheme whole (k_piece_len, k_piece_format, TextPlan, plan_text, text_next).
 // The stages that write their text on the device tile it in one of two ways:
@@ -13,6 +14,22 @@
 #include "pgx_internal.h"
 
 namespace pgx {
+// ---- reading text: the fields of a line as Python's split() cuts them ----------------------------------------------------------------------
+__host__ __device__ inline bool is_blank(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31); }
+// an optional '-' and 1 .. 18 digits
+__host__ __device__ inline bool parse_int(const char *p, uint32_t n, int64_t *out) {
+  const bool neg = n && p[0] == '-';
+  uint32_t i = neg;
+  if (i >= n || n - i > 18) return false;
+  int64_t v = 0;
+  for (; i < n; ++i) {
+    if (p[i] < '0' || p[i] > '9') return false;
+    v = v * 10 + (p[i] - '0');
+  }
+  *out = neg ? -v : v;
+  return true;
+}
+
 // ---- text: "%d", "%09d", "%u", "%0.1f" as glibc prints them -------------------------------------------------------------------------------
 __device__ inline uint32_t div10(uint32_t v) { return __umulhi(v, 0xCCCCCCCDu) >> 3; }
 __device__ inline uint64_t div10(uint64_t v) { return __umul64hi(v, 0xCCCCCCCCCCCCCCCDULL) >> 3; }

@@ -2,8 +2,9 @@
 // device), utg_data and ctg_paths to p_ctg_tiling_path and a_ctg_tiling_path, byte for byte, and to the same rows as pgx_tile_row.  The
 // rule is stated in DESIGN.md, "tiling paths".  Who does what:
 //   device  sg_edges_list text -> edge records (the hot path: the file goes up in pieces, a lane tokenises a line); the edge table
-//           as a list sorted by (v, w) with its duplicate and E/B checks; the unitig index (the three keys under three stable sorts, one
-//           binary search per name) and the dual-skip rule of ctg_paths (a sort by canonical key, the group's first row wins); every
+//           as a list sorted by (v, w) with its duplicate and E/B checks (by_vw of pgx_gedges.h, looked up by find_vw); the unitig
+//           index (the three keys under three stable sorts, one binary search per name) and the dual-skip rule of ctg_paths (a sort by
+//           canonical key, the group's first row wins); every
 //           node and edge of every path: path slots by binary search of the segments' offsets, the edge of every consecutive pair by
 //           binary search of the table, |s - t|, the running length of a contig, the rows, the lengths of the lines and the text
 //           (tiles of 8 KiB formatted in LDS, 16-byte stores).
@@ -18,13 +19,12 @@
 #include <tuple>
 #include <unordered_map>
 
-#include "pgx_dedup_rows.h"
+#include "pgx_gedges.h"
 
 typedef pgx_sgraph_edge Edge;
 
 namespace pgx {
 namespace {
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t SG_LINE_MAX = 256;    // bytes of a sg_edges_list line, its '\n' not counted
 constexpr uint32_t CTG_NAME_MAX = 96;     // bytes of a contig name in a tiling path line (an alternate's suffix included)
 constexpr uint64_t VIA_NA = ~0ULL;    // the `via` of a compound unitig ("NA")
@@ -34,9 +34,8 @@ const char *const PE_TEXT[] = {"", "is longer than 256 bytes", "does not have 8 
                                "has an identity that is not a decimal with at most two fraction digits", "has a byte that is not ASCII"};
 
 // ---------------------------------------------------------------------------------------------------------
-// fields (host and device): what Python's split() takes for a blank, and the numbers that print back as they were read
+// fields (host and device; is_blank and parse_int: pgx_text.h): the names and numbers that print back as they were read
 // ---------------------------------------------------------------------------------------------------------
-__host__ __device__ inline bool is_blank(unsigned char c) { return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31); }
 // the digits "%09d" prints for a value in [0, 2^31): nine, or ten without a leading zero
 __host__ __device__ inline bool parse_rid(const char *p, uint32_t n, uint32_t *rid) {
   if (n < 9 || n > 10 || (n > 9 && p[0] == '0')) return false;
@@ -54,19 +53,6 @@ __host__ __device__ inline bool parse_node(const char *p, uint32_t n, uint64_t *
   uint32_t rid;
   if (!parse_rid(p, n - 2, &rid)) return false;
   *key = (uint64_t)rid << 1 | (p[n - 1] == 'E');
-  return true;
-}
-// an optional sign and 1 .. 18 digits
-__host__ __device__ inline bool parse_int(const char *p, uint32_t n, int64_t *out) {
-  const bool neg = n && p[0] == '-';
-  uint32_t i = neg;
-  if (i >= n || n - i > 18) return false;
-  int64_t v = 0;
-  for (; i < n; ++i) {
-    if (p[i] < '0' || p[i] > '9') return false;
-    v = v * 10 + (p[i] - '0');
-  }
-  *out = neg ? -v : v;
   return true;
 }
 // an identity in hundredths: [-] up to 9 digits [. up to 2 digits], a digit at least; no exponent, no nan, no "-0" (which prints "-0.00")
@@ -183,58 +169,23 @@ __global__ void k_tl_from_graph(const Edge *__restrict__ rec, uint32_t n, int64_
 // ---------------------------------------------------------------------------------------------------------
 // the edge table: the G edges sorted by (v, w)
 // ---------------------------------------------------------------------------------------------------------
-__global__ void k_tl_flags(const Edge *__restrict__ edges, uint32_t n, uint8_t *__restrict__ flag) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) flag[e] = edges[e].type == PGX_SGRAPH_G;
-}
-// err[0] = min(err[0], record index of a G edge that breaks the script's assertion: w ends in E when s < t, else in B)
-__global__ void k_tl_keys(const Edge *__restrict__ edges, const uint32_t *__restrict__ gsel, uint32_t m, uint64_t *__restrict__ vk, uint64_t *__restrict__ wk,
-                          uint32_t *__restrict__ iota, uint32_t *__restrict__ err) {
-  const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= m) return;
-  const Edge e = edges[gsel[gi]];
-  vk[gi] = (uint64_t)e.v_rid << 1 | (e.v_end & 1u), wk[gi] = (uint64_t)e.w_rid << 1 | (e.w_end & 1u), iota[gi] = gi;
-  if ((e.sp < e.tp) != ((e.w_end & 1u) == 1u)) atomicMin(&err[0], gsel[gi]);
-}
-__global__ void k_tl_gather(const uint64_t *__restrict__ key, const uint32_t *__restrict__ idx, uint32_t m, uint64_t *__restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) out[i] = key[idx[i]];
-}
-// the second key and the record of every sorted entry; err[1] = min(err[1], record index of a G edge whose (v, w) an earlier one has)
-__global__ void k_tl_dups(const uint64_t *__restrict__ sv, const uint32_t *__restrict__ order, const uint64_t *__restrict__ wk, const uint32_t *__restrict__ gsel,
-                          uint32_t m, uint64_t *__restrict__ sw, uint32_t *__restrict__ se, uint32_t *__restrict__ err) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  const uint64_t w = wk[order[i]];
-  sw[i] = w, se[i] = gsel[order[i]];
-  if (i && sv[i] == sv[i - 1] && w == wk[order[i - 1]]) atomicMin(&err[1], gsel[order[i]]);   // (stable sorts: i is the later of the two)
-}
-// the record of edge (v, w), NONE: the table lacks it
-__device__ inline uint32_t find_edge(const uint64_t *__restrict__ sv, const uint64_t *__restrict__ sw, const uint32_t *__restrict__ se, uint32_t m, uint64_t v, uint64_t w) {
-  uint32_t lo = 0, hi = m;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (sv[mid] < v || (sv[mid] == v && sw[mid] < w)) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < m && sv[lo] == v && sw[lo] == w ? se[lo] : NONE;
-}
+// the script's assertion on a G edge: w ends in E when s < t, else in B
+struct EndRule {
+  __device__ bool operator()(const Edge &e) const { return (e.sp < e.tp) != ((e.w_end & 1u) == 1u); }
+};
 // the scores of n edges named by their two keys (the bundles' edges, all at once); found[i] = 0: the table lacks it
 __global__ void k_tl_scores(const uint64_t *__restrict__ v, const uint64_t *__restrict__ w, uint32_t n, const uint64_t *__restrict__ sv, const uint64_t *__restrict__ sw,
-                            const uint32_t *__restrict__ se, uint32_t m, const Edge *__restrict__ edges, int64_t *__restrict__ score, uint8_t *__restrict__ found) {
+                            const uint32_t *__restrict__ se, const uint32_t *__restrict__ gsel, uint32_t m, const Edge *__restrict__ edges, int64_t *__restrict__ score,
+                            uint8_t *__restrict__ found) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t r = find_edge(sv, sw, se, m, v[i], w[i]);
-  found[i] = r != NONE, score[i] = r != NONE ? edges[r].score : 0;
+  const uint32_t at = find_vw(sv, sw, m, v[i], w[i]);
+  found[i] = at != NONE, score[i] = at != NONE ? edges[gsel[se[at]]].score : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // the unitig index: the (s, via, t) keys sorted, looked up by binary search; the dual-skip rule of ctg_paths
 // ---------------------------------------------------------------------------------------------------------
-__global__ void k_tl_iota(uint32_t n, uint32_t *__restrict__ iota) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) iota[i] = i;
-}
 // err[0] = min(err[0], the unitig whose key an earlier one has) (stable sorts: i is the later of the two)
 __global__ void k_tl_u_dups(const uint64_t *__restrict__ ss, const uint64_t *__restrict__ sv, const uint64_t *__restrict__ st, const uint32_t *__restrict__ su, uint32_t n,
                             uint32_t *__restrict__ err) {
@@ -247,22 +198,16 @@ __global__ void k_tl_u_find(const uint64_t *__restrict__ rs, const uint64_t *__r
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_ref) return;
   const uint64_t a = rs[i], b = rv[i], c = rt[i];
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (ss[mid] < a || (ss[mid] == a && (sv[mid] < b || (sv[mid] == b && st[mid] < c)))) lo = mid + 1;
-    else hi = mid;
-  }
+  const uint32_t lo = bisect(0, n, [&](uint32_t k) { return ss[k] < a || (ss[k] == a && (sv[k] < b || (sv[k] == b && st[k] < c))); });
   out[i] = lo < n && ss[lo] == a && sv[lo] == b && st[lo] == c ? su[lo] : NONE;
 }
 // the canonical key of a row: the smaller of K = (s0, t0) and its dual (rev t0, rev s0)
-__global__ void k_tl_dual_keys(const uint64_t *__restrict__ s0, const uint64_t *__restrict__ t0, uint32_t n, uint64_t *__restrict__ c0, uint64_t *__restrict__ c1,
-                               uint32_t *__restrict__ iota) {
+__global__ void k_tl_dual_keys(const uint64_t *__restrict__ s0, const uint64_t *__restrict__ t0, uint32_t n, uint64_t *__restrict__ c0, uint64_t *__restrict__ c1) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t a = s0[i], b = t0[i], da = b ^ 1u, db = a ^ 1u;
   const bool dual_first = da < a || (da == a && db < b);
-  c0[i] = dual_first ? da : a, c1[i] = dual_first ? db : b, iota[i] = i;
+  c0[i] = dual_first ? da : a, c1[i] = dual_first ? db : b;
 }
 // The rows sorted by canonical key (stable: a group's first entry is its first row in the file).  The key of that row wins: every row of
 // the group with the winning key is kept, every row with the other is skipped; of a key that is its own dual only the first row is kept.
@@ -271,12 +216,7 @@ __global__ void k_tl_dual_keep(const uint64_t *__restrict__ sc0, const uint64_t 
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t a = sc0[i], b = sc1[i];
-  uint32_t lo = 0, hi = i;   // the group's first entry
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (sc0[mid] < a || (sc0[mid] == a && sc1[mid] < b)) lo = mid + 1;
-    else hi = mid;
-  }
+  const uint32_t lo = find_vw(sc0, sc1, i + 1, a, b);   // the group's first entry (at i at the latest)
   const uint32_t winner = order[lo], row = order[i];
   const bool same = s0[row] == s0[winner] && t0[row] == t0[winner], self_dual = s0[row] == (t0[row] ^ 1u);
   keep[row] = same && (!self_dual || row == winner);
@@ -292,23 +232,13 @@ struct alignas(16) RowInfo {   // what a line prints beside its pgx_tile_row
   int64_t score, hund;
   uint32_t label, dl, path, pad;
 };
-// the last i in [0, n) with a[i] <= x (a ascending, a[0] <= x)
-__device__ inline uint32_t last_le(const uint64_t *__restrict__ a, uint32_t n, uint64_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo ? lo - 1 : 0;
-}
 // A thread per row r: its path p by binary search of the paths' first rows, its two nodes -- slots r + p and r + p + 1 of the concatenated
 // paths, a path of k nodes has k - 1 rows -- by binary search of the segments' offsets, its edge by binary search of the table.
 // err[0] = min(err[0], r) where the table lacks the edge; err[1] counts indices out of range (never: they go into loads).
 __global__ void k_tl_rows(const uint64_t *__restrict__ path_row0, const uint32_t *__restrict__ path_ctg, uint32_t n_path, const Segment *__restrict__ seg,
                           const uint64_t *__restrict__ node_off, uint32_t n_seg, const uint64_t *__restrict__ pool, uint64_t pool_n, const uint64_t *__restrict__ sv,
-                          const uint64_t *__restrict__ sw, const uint32_t *__restrict__ se, uint32_t m, const Edge *__restrict__ edges, const int64_t *__restrict__ hund,
-                          uint32_t n_rows, pgx_tile_row *__restrict__ rows, RowInfo *__restrict__ info, uint32_t *__restrict__ dl, uint32_t *__restrict__ err) {
+                          const uint64_t *__restrict__ sw, const uint32_t *__restrict__ se, const uint32_t *__restrict__ gsel, uint32_t m, const Edge *__restrict__ edges,
+                          const int64_t *__restrict__ hund, uint32_t n_rows, pgx_tile_row *__restrict__ rows, RowInfo *__restrict__ info, uint32_t *__restrict__ dl, uint32_t *__restrict__ err) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_rows) return;
   const uint32_t p = last_le(path_row0, n_path, r);
@@ -327,10 +257,11 @@ __global__ void k_tl_rows(const uint64_t *__restrict__ path_row0, const uint32_t
   if (!ok) {
     atomicAdd(&err[1], 1u);
   } else {
-    const uint32_t ei = find_edge(sv, sw, se, m, key[0], key[1]);
-    if (ei == NONE) {
+    const uint32_t at = find_vw(sv, sw, m, key[0], key[1]);
+    if (at == NONE) {
       atomicMin(&err[0], r);
     } else {
+      const uint32_t ei = gsel[se[at]];
       const Edge e = edges[ei];
       const int64_t diff = (int64_t)e.sp - (int64_t)e.tp;
       d = (uint32_t)(diff < 0 ? -diff : diff);
@@ -400,11 +331,89 @@ struct File {
     if (f) fclose(f);
   }
 };
+struct Part {   // the records of one piece of the file
+  DevBuf<Edge> rec;
+  DevBuf<int64_t> hund;
+  DevBuf<uint32_t> line;
+  uint32_t n = 0, lines = 0;   // records; lines of the piece, the blank ones counted
+};
+struct PieceWs {   // what every piece is parsed through
+  DevBuf<char> text;
+  DevBuf<uint8_t> flag;
+  DevBuf<uint32_t> cnt;   // [0] newlines of the piece, [1] its first refused line
+  PrimWs tmp;
+  explicit PieceWs(uint64_t cap) : text(cap), flag(cap), cnt(2) {}
+};
+// One piece: the `used` bytes at p, whole lines, with four bytes of room behind them.  Its newlines, a lane per line, the first refused
+// line, the records of the kept lines.  line0, rec0: the lines and records of the pieces before it; meanwhile() runs on the host while
+// the lanes tokenise.  all: see k_tl_tokenise.
+template <class F>
+Part parse_piece(const char *path, bool all, char *p, uint64_t used, uint64_t line0, uint64_t rec0, PieceWs &ws, F &&meanwhile) {
+  hipStream_t st = ctx().stream;
+  const uint32_t n = (uint32_t)used, n4 = (n + 3) / 4;
+  char save[4];   // the last word's pad goes up as zeros; what stands there (the start of the next piece) comes back once the copy has run
+  memcpy(save, p + used, 4), memset(p + used, 0, 4);
+  PGX_HIP(hipMemcpyAsync(ws.text.p, p, (size_t)n4 * 4, hipMemcpyHostToDevice, st));
+  PGX_HIP(hipMemsetAsync(ws.cnt.p, 0, sizeof(uint32_t), st));
+  PGX_HIP(hipMemsetAsync(ws.cnt.p + 1, 0xFF, sizeof(uint32_t), st));
+  LAUNCH(k_tl_newlines, n4, (const uint32_t *)ws.text.p, n4, (uint32_t *)ws.flag.p, ws.cnt.p);
+  PGX_HIP(hipGetLastError());
+  uint32_t nl = 0;
+  ws.cnt.download(&nl, 1);
+  pgx::sync();
+  memcpy(p + used, save, 4);
+  PGX_REQUIRE(line0 + nl < NONE, PGX_EINVAL, "%s: more than 2^32 - 2 lines", path);
+  DevBuf<uint32_t> nlpos(nl), list(nl);
+  DevBuf<Edge> rec(nl);
+  DevBuf<int64_t> hund(nl);
+  DevBuf<uint8_t> keep(nl), code(nl);
+  const uint32_t got = select_indices(ws.flag.p, n, nlpos.p, &ws.tmp);
+  PGX_REQUIRE(got == nl, PGX_EHIP, "pgx_tiling: %u newlines counted, %u selected (a bug)", nl, got);
+  LAUNCH(k_tl_tokenise, nl, ws.text.p, nlpos.p, nl, all ? 1u : 0u, rec.p, hund.p, keep.p, code.p, ws.cnt.p + 1);
+  PGX_HIP(hipGetLastError());
+  meanwhile();
+  uint32_t bad = NONE;
+  PGX_HIP(hipMemcpyAsync(&bad, ws.cnt.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  pgx::sync();
+  if (bad != NONE) {
+    uint8_t why = PE_OK;
+    PGX_HIP(hipMemcpyAsync(&why, code.p + bad, 1, hipMemcpyDeviceToHost, st));
+    pgx::sync();
+    PGX_REQUIRE(false, PGX_EINVAL, "%s: line %llu %s", path, (unsigned long long)(line0 + bad), PE_TEXT[why < 8 ? why : 0]);
+  }
+  Part part;
+  part.lines = nl;
+  part.n = select_indices(keep.p, nl, list.p, &ws.tmp);
+  PGX_REQUIRE(rec0 + part.n <= (uint64_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 edge lines", path);
+  part.rec.alloc(part.n), part.hund.alloc(part.n), part.line.alloc(part.n);
+  if (part.n) LAUNCH(k_tl_compact, part.n, rec.p, hund.p, list.p, part.n, (uint32_t)line0, part.rec.p, part.hund.p, part.line.p);
+  PGX_HIP(hipGetLastError());
+  return part;
+}
+// the parts one behind the other (a single part as it is)
+void concat_parts(std::vector<Part> &parts, uint64_t records, DevEdges &out) {
+  hipStream_t st = ctx().stream;
+  out.n = (uint32_t)records;
+  if (parts.size() == 1) {
+    out.own = std::move(parts[0].rec), out.hund = std::move(parts[0].hund), out.line = std::move(parts[0].line);
+  } else {
+    out.own.alloc(records), out.hund.alloc(records), out.line.alloc(records);
+    uint64_t at = 0;
+    for (Part &p : parts) {
+      if (p.n) {
+        PGX_HIP(hipMemcpyAsync(out.own.p + at, p.rec.p, (size_t)p.n * sizeof(Edge), hipMemcpyDeviceToDevice, st));
+        PGX_HIP(hipMemcpyAsync(out.hund.p + at, p.hund.p, (size_t)p.n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        PGX_HIP(hipMemcpyAsync(out.line.p + at, p.line.p, (size_t)p.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+      }
+      at += p.n;
+      p.rec.release(), p.hund.release(), p.line.release();   // (stream-ordered: the copies come first)
+    }
+  }
+  out.rec = out.own.p;
+}
 // The file in pieces of piece_bytes(): each is cut at its last newline (what follows it opens the next piece), uploaded, and parsed; the
 // next piece is read while the lanes tokenise this one.  all: see k_tl_tokenise.
 void parse_sg_file(const char *path, bool all, DevEdges &out) {
-  hipStream_t st = ctx().stream;
-  PrimWs tmp;
   File in;
   in.f = fopen(path, "rb");
   PGX_REQUIRE(in.f, PGX_EINVAL, "%s: cannot be opened", path);
@@ -415,15 +424,7 @@ void parse_sg_file(const char *path, bool all, DevEdges &out) {
   const uint64_t piece = std::max<uint64_t>(std::min<uint64_t>(piece_bytes(), size + 1), 2 * SG_LINE_MAX), cap = SG_LINE_MAX + 1 + piece + 8;   // (size + 1: a small file is one short read)
   Pinned pin[2];
   for (int k = 0; k < 2; ++k) PGX_HIP(hipHostMalloc((void **)&pin[k].p, cap, hipHostMallocDefault));
-  DevBuf<char> d_text(cap);
-  DevBuf<uint8_t> flag(cap);
-  DevBuf<uint32_t> cnt(2);   // [0] newlines of the piece, [1] its first refused line
-  struct Part {
-    DevBuf<Edge> rec;
-    DevBuf<int64_t> hund;
-    DevBuf<uint32_t> line;
-    uint32_t n;
-  };
+  PieceWs ws(cap);
   std::vector<Part> parts;
   uint64_t lines = 0, records = 0;
   // fill(b, carry): the next piece behind the `carry` bytes already at the start of pin[b]; returns the bytes up to and with the last
@@ -453,111 +454,46 @@ void parse_sg_file(const char *path, bool all, DevEdges &out) {
   auto refuse_long = [&](uint64_t at) { PGX_REQUIRE(false, PGX_EINVAL, "%s: line %llu %s", path, (unsigned long long)at, PE_TEXT[PE_LONG]); };
   if (too_long != NONE && used == 0) refuse_long(too_long);
   while (used) {
-    const uint32_t n = (uint32_t)used, n4 = (n + 3) / 4;
-    char save[4];   // the last word's pad goes up as zeros; what stands there (the start of `rest`) comes back once the copy has run
-    memcpy(save, pin[b].p + used, 4), memset(pin[b].p + used, 0, 4);
-    PGX_HIP(hipMemcpyAsync(d_text.p, pin[b].p, (size_t)n4 * 4, hipMemcpyHostToDevice, st));
-    PGX_HIP(hipMemsetAsync(cnt.p, 0, sizeof(uint32_t), st));
-    PGX_HIP(hipMemsetAsync(cnt.p + 1, 0xFF, sizeof(uint32_t), st));
-    LAUNCH(k_tl_newlines, n4, (const uint32_t *)d_text.p, n4, (uint32_t *)flag.p, cnt.p);
-    PGX_HIP(hipGetLastError());
-    uint32_t nl = 0;
-    cnt.download(&nl, 1);
-    pgx::sync();
-    memcpy(pin[b].p + used, save, 4);
-    PGX_REQUIRE(lines + nl < NONE, PGX_EINVAL, "%s: more than 2^32 - 2 lines", path);
-    DevBuf<uint32_t> nlpos(nl), list(nl);
-    DevBuf<Edge> rec(nl);
-    DevBuf<int64_t> hund(nl);
-    DevBuf<uint8_t> keep(nl), code(nl);
-    const uint32_t got = select_indices(flag.p, n, nlpos.p, &tmp);
-    PGX_REQUIRE(got == nl, PGX_EHIP, "pgx_tiling: %u newlines counted, %u selected (a bug)", nl, got);
-    LAUNCH(k_tl_tokenise, nl, d_text.p, nlpos.p, nl, all ? 1u : 0u, rec.p, hund.p, keep.p, code.p, cnt.p + 1);
-    PGX_HIP(hipGetLastError());
-    // the next piece, while the lanes work
-    memmove(pin[b ^ 1].p, pin[b].p + used, rest);
     const uint64_t this_long = too_long;   // (of THIS piece's tail: lines + this_long is its line)
-    if (this_long != NONE) rest = 0;       // nothing more is read
-    uint64_t next_rest = 0, next_long = NONE;
-    const uint64_t next_used = this_long != NONE ? 0 : fill(b ^ 1, rest, &next_rest, &next_long);
-    uint32_t bad = NONE;
-    PGX_HIP(hipMemcpyAsync(&bad, cnt.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    pgx::sync();
-    if (bad != NONE) {
-      uint8_t why = PE_OK;
-      PGX_HIP(hipMemcpyAsync(&why, code.p + bad, 1, hipMemcpyDeviceToHost, st));
-      pgx::sync();
-      PGX_REQUIRE(false, PGX_EINVAL, "%s: line %llu %s", path, (unsigned long long)(lines + bad), PE_TEXT[why < 8 ? why : 0]);
-    }
-    Part part;
-    part.n = select_indices(keep.p, nl, list.p, &tmp);
-    PGX_REQUIRE(records + part.n <= (uint64_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 edge lines", path);
-    part.rec.alloc(part.n), part.hund.alloc(part.n), part.line.alloc(part.n);
-    if (part.n) LAUNCH(k_tl_compact, part.n, rec.p, hund.p, list.p, part.n, (uint32_t)lines, part.rec.p, part.hund.p, part.line.p);
-    PGX_HIP(hipGetLastError());
+    uint64_t next_used = 0, next_rest = 0, next_long = NONE;
+    Part part = parse_piece(path, all, pin[b].p, used, lines, records, ws, [&] {   // the next piece, while the lanes work
+      memmove(pin[b ^ 1].p, pin[b].p + used, rest);
+      if (this_long == NONE) next_used = fill(b ^ 1, rest, &next_rest, &next_long);   // (else nothing more is read)
+    });
     if (this_long != NONE) refuse_long(lines + this_long);
-    lines += nl, records += part.n;
+    lines += part.lines, records += part.n;
     parts.push_back(std::move(part));
     b ^= 1, used = next_used, rest = next_rest, too_long = next_long;
     if (too_long != NONE && used == 0) refuse_long(lines + too_long);
   }
-  out.n = (uint32_t)records;
-  if (parts.size() == 1) {
-    out.own = std::move(parts[0].rec), out.hund = std::move(parts[0].hund), out.line = std::move(parts[0].line);
-  } else {
-    out.own.alloc(records), out.hund.alloc(records), out.line.alloc(records);
-    uint64_t at = 0;
-    for (Part &p : parts) {
-      if (p.n) {
-        PGX_HIP(hipMemcpyAsync(out.own.p + at, p.rec.p, (size_t)p.n * sizeof(Edge), hipMemcpyDeviceToDevice, st));
-        PGX_HIP(hipMemcpyAsync(out.hund.p + at, p.hund.p, (size_t)p.n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        PGX_HIP(hipMemcpyAsync(out.line.p + at, p.line.p, (size_t)p.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-      }
-      at += p.n;
-      p.rec.release(), p.hund.release(), p.line.release();   // (stream-ordered: the copies come first)
-    }
-  }
-  out.rec = out.own.p;
+  concat_parts(parts, records, out);
   pgx::sync();   // the pinned buffers go
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // host: the edge table
 // ---------------------------------------------------------------------------------------------------------
-struct EdgeTable {
-  DevBuf<uint64_t> sv, sw;   // the G edges' keys, sorted by (v, w)
-  DevBuf<uint32_t> se;       // ... and their records
-  uint32_t m = 0;
-};
+typedef GEdges EdgeTable;   // of pgx_gedges.h, what is left of it: by_vw (sv, sw, out_e) and gsel
 uint32_t line_of(const DevEdges &e, uint32_t rec) {
   uint32_t l = 0;
   PGX_HIP(hipMemcpyAsync(&l, e.line.p + rec, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx().stream));
   pgx::sync();
   return l;
 }
+// the G edges' by_vw of pgx_gedges.h with its duplicate check, under the script's assertion
 void build_table(const DevEdges &e, const char *sg_name, EdgeTable &t) {
   hipStream_t st = ctx().stream;
   PrimWs tmp;
   if (e.n == 0) return;
-  DevBuf<uint32_t> gsel(e.n);
-  {
-    DevBuf<uint8_t> flag(e.n);
-    LAUNCH(k_tl_flags, e.n, e.rec, e.n, flag.p);
-    t.m = select_indices(flag.p, e.n, gsel.p, &tmp);
-  }
-  const uint32_t m = t.m;
-  if (m == 0) return;
+  t.select(e.rec, e.n, &tmp);
+  if (t.m == 0) return;
   DevBuf<uint32_t> err(2);
   PGX_HIP(hipMemsetAsync(err.p, 0xFF, 2 * sizeof(uint32_t), st));
-  DevBuf<uint64_t> vk(m), wk(m), swk(m), k2(m);
-  DevBuf<uint32_t> iota(m), by_w(m), order(m);
-  t.sv.alloc(m), t.sw.alloc(m), t.se.alloc(m);
-  LAUNCH(k_tl_keys, m, e.rec, gsel.p, m, vk.p, wk.p, iota.p, err.p);
-  sort_pairs(wk.p, swk.p, iota.p, by_w.p, m, 0, 33, &tmp);
-  LAUNCH(k_tl_gather, m, vk.p, by_w.p, m, k2.p);
-  sort_pairs(k2.p, t.sv.p, by_w.p, order.p, m, 0, 33, &tmp);
-  LAUNCH(k_tl_dups, m, t.sv.p, order.p, wk.p, gsel.p, m, t.sw.p, t.se.p, err.p);
+  t.keys(EndRule{}, err.p);
+  t.by_w(&tmp);
+  t.by_vw(err.p + 1, &tmp);
   PGX_HIP(hipGetLastError());
+  t.vk.release(), t.wk.release(), t.ids.release(), t.swk.release(), t.in_e.release();
   uint32_t h[2];
   err.download(h, 2);
   pgx::sync();
@@ -806,7 +742,7 @@ void build_set(const PathSet &ps, const DevBuf<uint64_t> &d_pool, uint64_t pool_
   PGX_HIP(hipMemsetAsync(err.p + 1, 0, sizeof(uint32_t), st));
   const uint64_t nodes = scan_to_total(seg_n.p, node_off.p, n_seg, &tmp);   // (synchronises: the host vectors above are read)
   PGX_REQUIRE(nodes == ps.nodes, PGX_EHIP, "pgx_tiling: the segments hold %llu of %llu nodes (a bug)", (unsigned long long)nodes, (unsigned long long)ps.nodes);
-  LAUNCH(k_tl_rows, n_rows, out.row0.p, path_ctg.p, n_path, seg.p, node_off.p, n_seg, d_pool.p, pool_n, t.sv.p, t.sw.p, t.se.p, t.m, e.rec, e.hund.p, (uint32_t)n_rows,
+  LAUNCH(k_tl_rows, n_rows, out.row0.p, path_ctg.p, n_path, seg.p, node_off.p, n_seg, d_pool.p, pool_n, t.sv.p, t.sw.p, t.out_e.p, t.gsel.p, t.m, e.rec, e.hund.p, (uint32_t)n_rows,
          out.rows.p, out.info.p, dl.p, err.p);
   PGX_HIP(hipGetLastError());
   uint32_t h[2];
@@ -839,36 +775,45 @@ struct Inputs {
   size_t utg_len, ctg_len;
   const char *utg_name, *ctg_name;
 };
+struct UtgData {   // utg_data, tokenised
+  std::vector<uint64_t> pool;   // the nodes of the simple and contained unitigs' paths; the alternates join it later
+  std::vector<Key3> subs;       // the sub-unitigs the compound lines name
+  std::vector<Utg> utgs;
+};
+struct CtgRow {
+  uint64_t line;
+  std::string name;
+  uint32_t ref0, n_ref;        // its unitigs: refs[ref0, ref0 + n_ref)
+  const char *defect;          // why the row is refused if it is kept
+};
+struct CtgRows {   // ctg_paths, tokenised
+  std::vector<CtgRow> rows;
+  std::vector<uint64_t> s0, t0;   // every row's key
+  std::vector<Key3> refs;         // the unitigs the rows name
+};
+struct KeptRow {
+  uint64_t line;
+  std::string name;
+  std::vector<uint32_t> utg;
+};
 
-void build_tiling(const Inputs &in, pgx_tiling *out) {
+// ---- the edge records: a file, or a live graph's
+void edge_records(const Inputs &in, DevEdges &e) {
   hipStream_t st = ctx().stream;
-  pgx_tiling_stats_t &S = out->st;
-  const char *sg_name = in.sg_fn ? in.sg_fn : "the string graph";
-  // ---- the edge records
-  std::unique_ptr<KernelTimer> part(new KernelTimer("tiling_parse", 0));
-  DevEdges e;
   if (in.sg_fn) {
     parse_sg_file(in.sg_fn, false, e);
-  } else {
-    uint64_t n = 0;
-    e.rec = sgraph_device_edges(in.g, "pgx_tiling_build", &n);
-    PGX_REQUIRE(n <= (uint64_t)INT32_MAX, PGX_EINVAL, "pgx_tiling_build: %llu edge records, more than 2^31 - 1", (unsigned long long)n);
-    e.n = (uint32_t)n, e.hund.alloc(n), e.line.alloc(n);
-    if (n) LAUNCH(k_tl_from_graph, n, e.rec, e.n, e.hund.p, e.line.p);
-    PGX_HIP(hipGetLastError());
+    return;
   }
-  S.sg_lines = e.n;
-  // ---- the edge table
-  part.reset(), part.reset(new KernelTimer("tiling_index", e.n));
-  EdgeTable t;
-  build_table(e, sg_name, t);
-  S.g_edges = t.m;
-  part.reset(), part.reset(new KernelTimer("tiling_paths", t.m));
-  // ---- utg_data
-  const double host0 = wall_ms();
-  std::vector<uint64_t> pool;
-  std::vector<Key3> subs;
-  std::vector<Utg> utgs;
+  uint64_t n = 0;
+  e.rec = sgraph_device_edges(in.g, "pgx_tiling_build", &n);
+  PGX_REQUIRE(n <= (uint64_t)INT32_MAX, PGX_EINVAL, "pgx_tiling_build: %llu edge records, more than 2^31 - 1", (unsigned long long)n);
+  e.n = (uint32_t)n, e.hund.alloc(n), e.line.alloc(n);
+  if (n) LAUNCH(k_tl_from_graph, n, e.rec, e.n, e.hund.p, e.line.p);
+  PGX_HIP(hipGetLastError());
+}
+
+// ---- utg_data: the pool, the subs and the unitigs
+void read_utg_data(const Inputs &in, pgx_tiling_stats_t &S, UtgData &U) {
   for (Lines ln(in.utg, in.utg_len); ln.next();) {
     if (ln.nf == 0) continue;
     PGX_REQUIRE(ln.nf == 7, PGX_EINVAL, "%s: line %llu does not have 7 fields", in.utg_name, (unsigned long long)ln.line);
@@ -889,35 +834,29 @@ void build_tiling(const Inputs &in, pgx_tiling *out) {
     Tok path = ln.f[6], piece;
     bool started = false;
     if (u.type == UT_COMPOUND) {
-      u.off = subs.size();
+      u.off = U.subs.size();
       while (split(path, '|', &piece, &started)) {
         Key3 sk;
         if (!parse_key3(piece, &sk)) u.bad = true;
-        else subs.push_back(sk);
+        else U.subs.push_back(sk);
       }
-      u.n = (uint32_t)(subs.size() - u.off);
+      u.n = (uint32_t)(U.subs.size() - u.off);
     } else {
-      u.off = pool.size();
+      u.off = U.pool.size();
       while (split(path, '~', &piece, &started)) {
         uint64_t key;
         if (!parse_node(piece.p, piece.n, &key)) u.bad = true;
-        else pool.push_back(key);
+        else U.pool.push_back(key);
       }
-      u.n = (uint32_t)(pool.size() - u.off);
+      u.n = (uint32_t)(U.pool.size() - u.off);
     }
-    utgs.push_back(u);
+    U.utgs.push_back(u);
   }
-  PGX_REQUIRE(utgs.size() <= (size_t)INT32_MAX && subs.size() <= (size_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 unitigs", in.utg_name);
-  // ---- ctg_paths, tokenised: every row's key and the unitigs it names; what the script reads of a kept row only is noted, not refused yet
-  struct CtgRow {
-    uint64_t line;
-    std::string name;
-    uint32_t ref0, n_ref;        // its unitigs: refs[ref0, ref0 + n_ref)
-    const char *defect;          // why the row is refused if it is kept
-  };
-  std::vector<CtgRow> rows;
-  std::vector<uint64_t> row_s0, row_t0;
-  std::vector<Key3> refs;
+  PGX_REQUIRE(U.utgs.size() <= (size_t)INT32_MAX && U.subs.size() <= (size_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 unitigs", in.utg_name);
+}
+
+// ---- ctg_paths, tokenised: every row's key and the unitigs it names; what the script reads of a kept row only is noted, not refused yet
+void read_ctg_paths(const Inputs &in, size_t n_subs, CtgRows &C) {
   for (Lines ln(in.ctg, in.ctg_len); ln.next();) {
     if (ln.nf == 0) continue;
     PGX_REQUIRE(ln.nf == 7, PGX_EINVAL, "%s: line %llu does not have 7 fields", in.ctg_name, (unsigned long long)ln.line);
@@ -927,7 +866,7 @@ void build_tiling(const Inputs &in, pgx_tiling *out) {
     uint64_t s0, t0;
     PGX_REQUIRE(parse_node(first.p, first.n, &s0) && parse_node(ln.f[3].p, ln.f[3].n, &t0), PGX_EINVAL,
                 "%s: line %llu: the first node of i_utig or t0 is not a node name ('%%09d:B' or '%%09d:E' of a read id below 2^31)", in.ctg_name, (unsigned long long)ln.line);
-    CtgRow row{ln.line, std::string(ln.f[0].p, ln.f[0].n), (uint32_t)refs.size(), 0, nullptr};
+    CtgRow row{ln.line, std::string(ln.f[0].p, ln.f[0].n), (uint32_t)C.refs.size(), 0, nullptr};
     int64_t number;
     if (!parse_int(ln.f[4].p, ln.f[4].n, &number)) row.defect = "length is not a decimal integer";
     else if (ln.f[0].n > CTG_NAME_MAX - 7) row.defect = "a contig name of more than 89 bytes";
@@ -936,81 +875,82 @@ void build_tiling(const Inputs &in, pgx_tiling *out) {
     while (!row.defect && split(list, '|', &piece, &started)) {
       Key3 k;
       if (!parse_key3(piece, &k)) row.defect = "a unitig that is not s~via~t of node names";
-      else refs.push_back(k);
+      else C.refs.push_back(k);
     }
-    row.n_ref = (uint32_t)refs.size() - row.ref0;
-    rows.push_back(std::move(row)), row_s0.push_back(s0), row_t0.push_back(t0);
+    row.n_ref = (uint32_t)C.refs.size() - row.ref0;
+    C.rows.push_back(std::move(row)), C.s0.push_back(s0), C.t0.push_back(t0);
   }
-  PGX_REQUIRE(rows.size() <= (size_t)INT32_MAX && refs.size() + subs.size() <= (size_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 rows or unitig names", in.ctg_name);
-  // ---- on the device: the dual rule (a sort by canonical key, the group's first row wins) and the unitig index (three stable sorts, then
-  // one binary search per name: the rows' unitigs and the compound lines' sub-unitigs in one launch)
-  const uint32_t n_row = (uint32_t)rows.size(), n_u = (uint32_t)utgs.size(), n_find = (uint32_t)(refs.size() + subs.size());
+  PGX_REQUIRE(C.rows.size() <= (size_t)INT32_MAX && C.refs.size() + n_subs <= (size_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 rows or unitig names", in.ctg_name);
+}
+
+// ---- the dual rule on the device: the rows sorted by canonical key, the group's first row wins.  keep[r]: row r is kept
+std::vector<uint8_t> dual_rule(const CtgRows &C) {
+  hipStream_t st = ctx().stream;
+  const uint32_t n_row = (uint32_t)C.rows.size();
   std::vector<uint8_t> keep(n_row, 0);
-  std::vector<uint32_t> found_utg(n_find, NONE);
-  {
-    PrimWs tmp;
-    if (n_row) {
-      DevBuf<uint64_t> s0(n_row), t0(n_row), c0(n_row), c1(n_row), k1(n_row), k2(n_row), sc0(n_row), sc1(n_row);
-      DevBuf<uint32_t> iota(n_row), o1(n_row), order(n_row);
-      DevBuf<uint8_t> d_keep(n_row);
-      s0.upload(row_s0.data(), n_row), t0.upload(row_t0.data(), n_row);
-      LAUNCH(k_tl_dual_keys, n_row, s0.p, t0.p, n_row, c0.p, c1.p, iota.p);
-      sort_pairs(c1.p, k1.p, iota.p, o1.p, n_row, 0, 33, &tmp);
-      LAUNCH(k_tl_gather, n_row, c0.p, o1.p, n_row, k2.p);
-      sort_pairs(k2.p, sc0.p, o1.p, order.p, n_row, 0, 33, &tmp);
-      LAUNCH(k_tl_gather, n_row, c1.p, order.p, n_row, sc1.p);
-      LAUNCH(k_tl_dual_keep, n_row, sc0.p, sc1.p, order.p, s0.p, t0.p, n_row, d_keep.p);
-      PGX_HIP(hipGetLastError());
-      d_keep.download(keep.data(), n_row);
-      pgx::sync();
-    }
-    if (n_u) {
-      std::vector<uint64_t> h[3];
-      for (const Utg &u : utgs) h[0].push_back(u.key.s), h[1].push_back(u.key.v), h[2].push_back(u.key.t);
-      DevBuf<uint64_t> ks(n_u), kv(n_u), kt(n_u), a(n_u), b(n_u), ss(n_u), sv(n_u), st_(n_u);
-      DevBuf<uint32_t> iota(n_u), o1(n_u), o2(n_u), su(n_u), err(1);
-      ks.upload(h[0].data(), n_u), kv.upload(h[1].data(), n_u), kt.upload(h[2].data(), n_u);
-      PGX_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(uint32_t), st));
-      LAUNCH(k_tl_iota, n_u, n_u, iota.p);
-      sort_pairs(kt.p, a.p, iota.p, o1.p, n_u, 0, 33, &tmp);
-      LAUNCH(k_tl_gather, n_u, kv.p, o1.p, n_u, b.p);
-      sort_pairs(b.p, a.p, o1.p, o2.p, n_u, 0, 64, &tmp);
-      LAUNCH(k_tl_gather, n_u, ks.p, o2.p, n_u, b.p);
-      sort_pairs(b.p, ss.p, o2.p, su.p, n_u, 0, 33, &tmp);
-      LAUNCH(k_tl_gather, n_u, kv.p, su.p, n_u, sv.p);
-      LAUNCH(k_tl_gather, n_u, kt.p, su.p, n_u, st_.p);
-      LAUNCH(k_tl_u_dups, n_u, ss.p, sv.p, st_.p, su.p, n_u, err.p);
-      PGX_HIP(hipGetLastError());
-      uint32_t dup = NONE;
-      err.download(&dup, 1);
-      pgx::sync();   // (also: the host vectors above are read)
-      PGX_REQUIRE(dup == NONE, PGX_EINVAL, "%s: line %llu repeats the (s, via, t) of an earlier line (the script would keep the later one; its own files never do)", in.utg_name,
-                  (unsigned long long)utgs[dup < n_u ? dup : 0].line);
-      if (n_find) {
-        for (int k = 0; k < 3; ++k) h[k].clear();
-        for (const std::vector<Key3> *list : {&refs, &subs})
-          for (const Key3 &k : *list) h[0].push_back(k.s), h[1].push_back(k.v), h[2].push_back(k.t);
-        DevBuf<uint64_t> rs(n_find), rv(n_find), rt(n_find);
-        DevBuf<uint32_t> out_u(n_find);
-        rs.upload(h[0].data(), n_find), rv.upload(h[1].data(), n_find), rt.upload(h[2].data(), n_find);
-        LAUNCH(k_tl_u_find, n_find, rs.p, rv.p, rt.p, n_find, ss.p, sv.p, st_.p, su.p, n_u, out_u.p);
-        PGX_HIP(hipGetLastError());
-        out_u.download(found_utg.data(), n_find);
-        pgx::sync();
-      }
-    }
-  }
-  const uint32_t *ref_utg = found_utg.data(), *sub_utg = found_utg.data() + refs.size();
-  // ---- the kept rows in file order: what the script would raise on, the compound unitigs in use
-  struct KeptRow {
-    uint64_t line;
-    std::string name;
-    std::vector<uint32_t> utg;
-  };
+  if (n_row == 0) return keep;
+  PrimWs tmp;
+  DevBuf<uint64_t> s0(n_row), t0(n_row), c0(n_row), c1(n_row), sc0(n_row), sc1(n_row);
+  DevBuf<uint32_t> order(n_row);
+  DevBuf<uint8_t> d_keep(n_row);
+  s0.upload(C.s0.data(), n_row), t0.upload(C.t0.data(), n_row);
+  LAUNCH(k_tl_dual_keys, n_row, s0.p, t0.p, n_row, c0.p, c1.p);
+  sort_order({{c0.p, 33}, {c1.p, 33}}, n_row, nullptr, order.p, sc0.p, &tmp);
+  gather(c1.p, order.p, n_row, sc1.p, &tmp);
+  LAUNCH(k_tl_dual_keep, n_row, sc0.p, sc1.p, order.p, s0.p, t0.p, n_row, d_keep.p);
+  PGX_HIP(hipGetLastError());
+  d_keep.download(keep.data(), n_row);
+  pgx::sync();
+  return keep;
+}
+
+// ---- the unitig index on the device (the three keys in one stable order, duplicates refused) and one binary search per name: the rows'
+// unitigs, then the compound lines' sub-unitigs, in one launch.  found[i]: the unitig of name i, NONE: the index lacks it
+std::vector<uint32_t> find_unitigs(const Inputs &in, const UtgData &U, const CtgRows &C) {
+  hipStream_t st = ctx().stream;
+  const uint32_t n_u = (uint32_t)U.utgs.size(), n_find = (uint32_t)(C.refs.size() + U.subs.size());
+  std::vector<uint32_t> found(n_find, NONE);
+  if (n_u == 0) return found;
+  PrimWs tmp;
+  std::vector<uint64_t> h[3];
+  for (const Utg &u : U.utgs) h[0].push_back(u.key.s), h[1].push_back(u.key.v), h[2].push_back(u.key.t);
+  DevBuf<uint64_t> ks(n_u), kv(n_u), kt(n_u), ss(n_u), sv(n_u), st_(n_u);
+  DevBuf<uint32_t> su(n_u), err(1);
+  ks.upload(h[0].data(), n_u), kv.upload(h[1].data(), n_u), kt.upload(h[2].data(), n_u);
+  PGX_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(uint32_t), st));
+  sort_order({{ks.p, 33}, {kv.p, 64}, {kt.p, 33}}, n_u, nullptr, su.p, ss.p, &tmp);   // (64: via may be VIA_NA)
+  gather(kv.p, su.p, n_u, sv.p, &tmp);
+  gather(kt.p, su.p, n_u, st_.p, &tmp);
+  LAUNCH(k_tl_u_dups, n_u, ss.p, sv.p, st_.p, su.p, n_u, err.p);
+  PGX_HIP(hipGetLastError());
+  uint32_t dup = NONE;
+  err.download(&dup, 1);
+  pgx::sync();   // (also: the host vectors above are read)
+  PGX_REQUIRE(dup == NONE, PGX_EINVAL, "%s: line %llu repeats the (s, via, t) of an earlier line (the script would keep the later one; its own files never do)", in.utg_name,
+              (unsigned long long)U.utgs[dup < n_u ? dup : 0].line);
+  if (n_find == 0) return found;
+  for (int k = 0; k < 3; ++k) h[k].clear();
+  for (const std::vector<Key3> *list : {&C.refs, &U.subs})
+    for (const Key3 &k : *list) h[0].push_back(k.s), h[1].push_back(k.v), h[2].push_back(k.t);
+  DevBuf<uint64_t> rs(n_find), rv(n_find), rt(n_find);
+  DevBuf<uint32_t> out_u(n_find);
+  rs.upload(h[0].data(), n_find), rv.upload(h[1].data(), n_find), rt.upload(h[2].data(), n_find);
+  LAUNCH(k_tl_u_find, n_find, rs.p, rv.p, rt.p, n_find, ss.p, sv.p, st_.p, su.p, n_u, out_u.p);
+  PGX_HIP(hipGetLastError());
+  out_u.download(found.data(), n_find);
+  pgx::sync();
+  return found;
+}
+
+// ---- the kept rows in file order: what the script would raise on, and the compound unitigs in use (bundles; bundle_of: per unitig, its
+// number among them)
+std::vector<KeptRow> kept_rows(const Inputs &in, pgx_tiling_stats_t &S, const UtgData &U, CtgRows &C, const std::vector<uint8_t> &keep, const uint32_t *ref_utg,
+                               std::vector<uint32_t> &bundle_of, std::vector<uint32_t> &bundles) {
+  const uint32_t n_u = (uint32_t)U.utgs.size();
   std::vector<KeptRow> kept;
-  std::vector<uint32_t> bundle_of(utgs.size(), NONE), bundles;   // per unitig: its number among the compound unitigs in use
-  for (uint32_t r = 0; r < n_row; ++r) {
-    CtgRow &row = rows[r];
+  bundle_of.assign(n_u, NONE);
+  for (size_t r = 0; r < C.rows.size(); ++r) {
+    CtgRow &row = C.rows[r];
     if (!keep[r]) {
       ++S.ctg_skipped;
       continue;
@@ -1020,7 +960,7 @@ void build_tiling(const Inputs &in, pgx_tiling *out) {
     for (uint32_t j = row.ref0; j < row.ref0 + row.n_ref; ++j) {
       const uint32_t ui = ref_utg[j];
       PGX_REQUIRE(ui < n_u, PGX_EINVAL, "%s: line %llu names a unitig that %s lacks (as simple, contained or compound)", in.ctg_name, (unsigned long long)row.line, in.utg_name);
-      const Utg &u = utgs[ui];
+      const Utg &u = U.utgs[ui];
       PGX_REQUIRE(!u.bad, PGX_EINVAL, "%s: line %llu names the unitig of %s line %llu, whose path does not parse", in.ctg_name, (unsigned long long)row.line, in.utg_name,
                   (unsigned long long)u.line);
       if (u.type == UT_COMPOUND && bundle_of[ui] == NONE) bundle_of[ui] = (uint32_t)bundles.size(), bundles.push_back(ui);
@@ -1028,76 +968,87 @@ void build_tiling(const Inputs &in, pgx_tiling *out) {
     }
     kept.push_back(std::move(k));
   }
-  // ---- the bundles: every edge of every sub-unitig of the compound unitigs in use, their scores in one lookup, the rounds
-  std::vector<std::vector<Alt>> alts(bundles.size());
-  {
-    std::vector<uint64_t> ev, ew;
-    for (uint32_t ui : bundles) {
-      const Utg &u = utgs[ui];
-      for (uint32_t j = 0; j < u.n; ++j) {
-        PGX_REQUIRE(sub_utg[u.off + j] < n_u, PGX_EINVAL, "%s: line %llu names a sub-unitig that the file lacks (as simple, contained or compound)", in.utg_name,
-                    (unsigned long long)u.line);
-        const Utg &sub = utgs[sub_utg[u.off + j]];
-        PGX_REQUIRE(sub.type != UT_COMPOUND, PGX_EINVAL, "%s: line %llu: a sub-unitig (line %llu) is itself compound", in.utg_name, (unsigned long long)u.line,
-                    (unsigned long long)sub.line);
-        PGX_REQUIRE(!sub.bad, PGX_EINVAL, "%s: line %llu names the sub-unitig of line %llu, whose path does not parse", in.utg_name, (unsigned long long)u.line,
-                    (unsigned long long)sub.line);
-        for (uint32_t k = 0; k + 1 < sub.n; ++k) ev.push_back(pool[sub.off + k]), ew.push_back(pool[sub.off + k + 1]);
-      }
-    }
-    const size_t ne = ev.size();
-    PGX_REQUIRE(ne <= (size_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 edges in compound unitigs", in.utg_name);
-    std::vector<int64_t> score(ne);
-    std::vector<uint8_t> found(ne);
-    if (ne) {
-      DevBuf<uint64_t> dv(ne), dw(ne);
-      DevBuf<int64_t> ds(ne);
-      DevBuf<uint8_t> df(ne);
-      dv.upload(ev.data(), ne), dw.upload(ew.data(), ne);
-      LAUNCH(k_tl_scores, ne, dv.p, dw.p, (uint32_t)ne, t.sv.p, t.sw.p, t.se.p, t.m, e.rec, ds.p, df.p);
-      PGX_HIP(hipGetLastError());
-      ds.download(score.data(), ne), df.download(found.data(), ne);
-      pgx::sync();
-    }
-    size_t at = 0;
-    for (size_t b = 0; b < bundles.size(); ++b) {
-      const Utg &u = utgs[bundles[b]];
-      const unsigned long long line = (unsigned long long)u.line;
-      Bundle g;
-      for (uint32_t j = 0; j < u.n; ++j) {
-        const Utg &sub = utgs[sub_utg[u.off + j]];
-        for (uint32_t k = 0; k + 1 < sub.n; ++k, ++at) {
-          PGX_REQUIRE(found[at], PGX_EINVAL, "%s: line %llu: an edge of the sub-unitig of line %llu is not a G edge of the edge table", in.utg_name, line,
-                      (unsigned long long)sub.line);
-          PGX_REQUIRE(score[at] > 0, PGX_EINVAL, "%s: line %llu: an edge of the sub-unitig of line %llu has aln_score <= 0 (the shortest-path rounds need weights > 0)",
-                      in.utg_name, line, (unsigned long long)sub.line);
-          PGX_REQUIRE(score[at] < (1LL << 40), PGX_EINVAL, "%s: line %llu: an edge of the sub-unitig of line %llu has aln_score >= 2^40 (the sums of a round stay exact)",
-                      in.utg_name, line, (unsigned long long)sub.line);
-          g.add_edge(ev[at], ew[at], score[at]);
-        }
-      }
-      const Key3 self = u.key;
-      auto si = g.id.find(self.s), ti = g.id.find(self.t);
-      PGX_REQUIRE(si != g.id.end() && ti != g.id.end(), PGX_EINVAL, "%s: line %llu: s or t is not a node of the compound unitig's graph", in.utg_name, line);
-      PGX_REQUIRE(self.s != self.t, PGX_EINVAL, "%s: line %llu: a compound unitig with s == t (the script's rounds would not end)", in.utg_name, line);
-      Alt a;
-      bool tie = false;
-      PGX_REQUIRE(g.search(si->second, ti->second, &a, &tie), PGX_EINVAL, "%s: line %llu: no path from s to t in the compound unitig's graph", in.utg_name, line);
-      do {
-        S.compound_tie_rounds += tie;
-        g.remove_path(a.path);
-        alts[b].push_back(a);
-      } while (g.search(si->second, ti->second, &a, &tie));
-      std::sort(alts[b].begin(), alts[b].end(), [](const Alt &x, const Alt &y) { return x.weight != y.weight ? x.weight > y.weight : names_above(x.path, y.path); });
+  return kept;
+}
+
+// ---- the bundles: every edge of every sub-unitig of the compound unitigs in use, their scores in one lookup; then the rounds: a bundle's
+// shortest paths one after the other, each removed before the next, sorted as the script sorts them
+std::vector<std::vector<Alt>> bundle_alts(const Inputs &in, pgx_tiling_stats_t &S, const UtgData &U, const uint32_t *sub_utg, const std::vector<uint32_t> &bundles,
+                                          const DevEdges &e, const EdgeTable &t) {
+  hipStream_t st = ctx().stream;
+  std::vector<uint64_t> ev, ew;
+  const uint32_t n_u = (uint32_t)U.utgs.size();
+  for (uint32_t ui : bundles) {
+    const Utg &u = U.utgs[ui];
+    for (uint32_t j = 0; j < u.n; ++j) {
+      PGX_REQUIRE(sub_utg[u.off + j] < n_u, PGX_EINVAL, "%s: line %llu names a sub-unitig that the file lacks (as simple, contained or compound)", in.utg_name,
+                  (unsigned long long)u.line);
+      const Utg &sub = U.utgs[sub_utg[u.off + j]];
+      PGX_REQUIRE(sub.type != UT_COMPOUND, PGX_EINVAL, "%s: line %llu: a sub-unitig (line %llu) is itself compound", in.utg_name, (unsigned long long)u.line,
+                  (unsigned long long)sub.line);
+      PGX_REQUIRE(!sub.bad, PGX_EINVAL, "%s: line %llu names the sub-unitig of line %llu, whose path does not parse", in.utg_name, (unsigned long long)u.line,
+                  (unsigned long long)sub.line);
+      for (uint32_t k = 0; k + 1 < sub.n; ++k) ev.push_back(U.pool[sub.off + k]), ew.push_back(U.pool[sub.off + k + 1]);
     }
   }
-  // the chosen paths join the pool
-  std::vector<std::vector<uint64_t>> alt_off(bundles.size());
-  for (size_t b = 0; b < bundles.size(); ++b)
+  const size_t ne = ev.size();
+  PGX_REQUIRE(ne <= (size_t)INT32_MAX, PGX_EINVAL, "%s: more than 2^31 - 1 edges in compound unitigs", in.utg_name);
+  std::vector<int64_t> score(ne);
+  std::vector<uint8_t> found(ne);
+  if (ne) {
+    DevBuf<uint64_t> dv(ne), dw(ne);
+    DevBuf<int64_t> ds(ne);
+    DevBuf<uint8_t> df(ne);
+    dv.upload(ev.data(), ne), dw.upload(ew.data(), ne);
+    LAUNCH(k_tl_scores, ne, dv.p, dw.p, (uint32_t)ne, t.sv.p, t.sw.p, t.out_e.p, t.gsel.p, t.m, e.rec, ds.p, df.p);
+    PGX_HIP(hipGetLastError());
+    ds.download(score.data(), ne), df.download(found.data(), ne);
+    pgx::sync();
+  }
+  std::vector<std::vector<Alt>> alts(bundles.size());
+  size_t at = 0;
+  for (size_t b = 0; b < bundles.size(); ++b) {
+    const Utg &u = U.utgs[bundles[b]];
+    const unsigned long long line = (unsigned long long)u.line;
+    Bundle g;
+    for (uint32_t j = 0; j < u.n; ++j) {
+      const Utg &sub = U.utgs[sub_utg[u.off + j]];
+      for (uint32_t k = 0; k + 1 < sub.n; ++k, ++at) {
+        PGX_REQUIRE(found[at], PGX_EINVAL, "%s: line %llu: an edge of the sub-unitig of line %llu is not a G edge of the edge table", in.utg_name, line,
+                    (unsigned long long)sub.line);
+        PGX_REQUIRE(score[at] > 0, PGX_EINVAL, "%s: line %llu: an edge of the sub-unitig of line %llu has aln_score <= 0 (the shortest-path rounds need weights > 0)",
+                    in.utg_name, line, (unsigned long long)sub.line);
+        PGX_REQUIRE(score[at] < (1LL << 40), PGX_EINVAL, "%s: line %llu: an edge of the sub-unitig of line %llu has aln_score >= 2^40 (the sums of a round stay exact)",
+                    in.utg_name, line, (unsigned long long)sub.line);
+        g.add_edge(ev[at], ew[at], score[at]);
+      }
+    }
+    const Key3 self = u.key;
+    auto si = g.id.find(self.s), ti = g.id.find(self.t);
+    PGX_REQUIRE(si != g.id.end() && ti != g.id.end(), PGX_EINVAL, "%s: line %llu: s or t is not a node of the compound unitig's graph", in.utg_name, line);
+    PGX_REQUIRE(self.s != self.t, PGX_EINVAL, "%s: line %llu: a compound unitig with s == t (the script's rounds would not end)", in.utg_name, line);
+    Alt a;
+    bool tie = false;
+    PGX_REQUIRE(g.search(si->second, ti->second, &a, &tie), PGX_EINVAL, "%s: line %llu: no path from s to t in the compound unitig's graph", in.utg_name, line);
+    do {
+      S.compound_tie_rounds += tie;
+      g.remove_path(a.path);
+      alts[b].push_back(a);
+    } while (g.search(si->second, ti->second, &a, &tie));
+    std::sort(alts[b].begin(), alts[b].end(), [](const Alt &x, const Alt &y) { return x.weight != y.weight ? x.weight > y.weight : names_above(x.path, y.path); });
+  }
+  return alts;
+}
+
+// ---- the chosen paths join the pool behind the file's nodes; ctg_paths, second pass: the kept rows as segments of the pool, the primary
+// paths in ps[0], the alternates in ps[1]
+void path_sets(const Inputs &in, pgx_tiling_stats_t &S, UtgData &U, const std::vector<KeptRow> &kept, const std::vector<uint32_t> &bundle_of,
+               const std::vector<std::vector<Alt>> &alts, PathSet ps[2]) {
+  std::vector<uint64_t> &pool = U.pool;
+  std::vector<std::vector<uint64_t>> alt_off(alts.size());
+  for (size_t b = 0; b < alts.size(); ++b)
     for (const Alt &a : alts[b]) alt_off[b].push_back(pool.size()), pool.insert(pool.end(), a.path.begin(), a.path.end());
   PGX_REQUIRE(pool.size() < NONE, PGX_EINVAL, "%s: more than 2^32 - 2 nodes in unitig paths", in.utg_name);
-  // ---- ctg_paths, second pass: the kept rows as segments
-  PathSet ps[2];
   for (const KeptRow &row : kept) {
     uint64_t len = 0;
     std::vector<std::pair<uint64_t, uint64_t>> segs;
@@ -1107,7 +1058,7 @@ void build_tiling(const Inputs &in, pgx_tiling *out) {
       segs.emplace_back(off + skip, n - skip), len += n - skip;
     };
     for (uint32_t ui : row.utg) {
-      const Utg &u = utgs[ui];
+      const Utg &u = U.utgs[ui];
       if (u.type == UT_SIMPLE) {
         extend(u.off, u.n);
       } else if (u.type == UT_COMPOUND) {
@@ -1143,11 +1094,39 @@ void build_tiling(const Inputs &in, pgx_tiling *out) {
       }
     }
   }
+}
+
+// the stage as its phases.  tiling_paths opens before utg_data is read and closes with the function; host_us: from there to the path
+// sets, the device sorts of the dual rule and the unitig index included
+void build_tiling(const Inputs &in, pgx_tiling *out) {
+  pgx_tiling_stats_t &S = out->st;
+  std::unique_ptr<KernelTimer> part(new KernelTimer("tiling_parse", 0));
+  DevEdges e;
+  edge_records(in, e);
+  S.sg_lines = e.n;
+  part.reset(), part.reset(new KernelTimer("tiling_index", e.n));
+  EdgeTable t;
+  build_table(e, in.sg_fn ? in.sg_fn : "the string graph", t);
+  S.g_edges = t.m;
+  part.reset(), part.reset(new KernelTimer("tiling_paths", t.m));
+  const double host0 = wall_ms();
+  UtgData U;
+  read_utg_data(in, S, U);
+  CtgRows C;
+  read_ctg_paths(in, U.subs.size(), C);
+  const std::vector<uint8_t> keep = dual_rule(C);
+  const std::vector<uint32_t> found = find_unitigs(in, U, C);
+  const uint32_t *ref_utg = found.data(), *sub_utg = found.data() + C.refs.size();
+  std::vector<uint32_t> bundle_of, bundles;
+  const std::vector<KeptRow> kept = kept_rows(in, S, U, C, keep, ref_utg, bundle_of, bundles);
+  const std::vector<std::vector<Alt>> alts = bundle_alts(in, S, U, sub_utg, bundles, e, t);
+  PathSet ps[2];
+  path_sets(in, S, U, kept, bundle_of, alts, ps);
   S.host_us = (uint64_t)((wall_ms() - host0) * 1000.0);
-  // ---- every node and edge of every path
-  DevBuf<uint64_t> d_pool(pool.size() + 1);
-  d_pool.upload(pool.data(), pool.size());
-  for (int w = 0; w < 2; ++w) build_set(ps[w], d_pool, pool.size(), e, t, pool, in.ctg_name, out->set[w]);
+  // every node and edge of every path
+  DevBuf<uint64_t> d_pool(U.pool.size() + 1);
+  d_pool.upload(U.pool.data(), U.pool.size());
+  for (int w = 0; w < 2; ++w) build_set(ps[w], d_pool, U.pool.size(), e, t, U.pool, in.ctg_name, out->set[w]);
   S.p_rows = out->set[0].n_rows, S.a_rows = out->set[1].n_rows;
   pgx::sync();
 }

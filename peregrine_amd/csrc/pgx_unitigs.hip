@@ -7,7 +7,8 @@
 //     smallest creation index;
 //   * unitigs are numbered by the creation index of their first edge; `via` is the path's second node.
 // Device layout.  G edges are numbered gi = 0 .. m-1 in creation order (gsel[gi]: the creation index).  A node is its key
-// (rid << 1) | end; there are no node ids: degrees and the single in- / out-edge of a node are ranges of two sorted edge lists
+// (rid << 1) | end; there are no node ids: degrees and the single in- / out-edge of a node are ranges of the two sorted edge lists
+// of pgx_gedges.h
 //   by_w   (wkey, gi) ascending                (in-lists)
 //   by_vw  (vkey, wkey, gi) ascending          (out-lists; equal neighbours are duplicates; the reverse of an edge is looked up here)
 // found by binary search.  pred[gi] / succ[gi]: the edge before / after gi on its path, where the node between them is simple.
@@ -19,52 +20,19 @@
 
 #include <atomic>
 
-#include "pgx_dedup_rows.h"
+#include "pgx_gedges.h"
 
 typedef pgx_sgraph_edge Edge;
 
 namespace pgx {
 namespace {
-constexpr uint32_t NONE = 0xFFFFFFFFu;
-
 // ---------------------------------------------------------------------------------------------------------
 // edges -> keys, sorted lists, checks, links
 // ---------------------------------------------------------------------------------------------------------
-__global__ void k_ut_flags(const Edge *__restrict__ edges, uint32_t n, uint8_t *__restrict__ flag) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) flag[e] = edges[e].type == PGX_SGRAPH_G;
-}
-// err[0] = min(err[0], creation index of an edge between the two ends of one read)
-__global__ void k_ut_keys(const Edge *__restrict__ edges, const uint32_t *__restrict__ gsel, uint32_t m, uint64_t *__restrict__ vk, uint64_t *__restrict__ wk,
-                          uint32_t *__restrict__ iota, uint32_t *__restrict__ err) {
-  const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= m) return;
-  const Edge e = edges[gsel[gi]];
-  vk[gi] = (uint64_t)e.v_rid << 1 | (e.v_end & 1u), wk[gi] = (uint64_t)e.w_rid << 1 | (e.w_end & 1u), iota[gi] = gi;
-  if (e.v_rid == e.w_rid) atomicMin(&err[0], gsel[gi]);
-}
-__global__ void k_ut_gather(const uint64_t *__restrict__ key, const uint32_t *__restrict__ idx, uint32_t m, uint64_t *__restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) out[i] = key[idx[i]];
-}
-// the out-lists' second key; err[1] = min(err[1], creation index of an edge whose (v, w) an earlier edge has)
-__global__ void k_ut_dups(const uint64_t *__restrict__ sv, const uint32_t *__restrict__ out_e, const uint64_t *__restrict__ wk, const uint32_t *__restrict__ gsel,
-                          uint32_t m, uint64_t *__restrict__ sw, uint32_t *__restrict__ err) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  const uint64_t w = wk[out_e[i]];
-  sw[i] = w;
-  if (i && sv[i] == sv[i - 1] && w == wk[out_e[i - 1]]) atomicMin(&err[1], gsel[out_e[i]]);   // (stable sorts: i is the later of the two)
-}
-__device__ inline uint32_t lower_bound(const uint64_t *__restrict__ a, uint32_t n, uint64_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
+// the unitigs' rule on a G edge: it joins two reads
+struct TwoReads {
+  __device__ bool operator()(const Edge &e) const { return e.v_rid == e.w_rid; }
+};
 // is a node simple; lo_out / lo_in: where its out-list / in-list starts
 __device__ inline bool node_simple(uint64_t x, const uint64_t *__restrict__ sv, const uint64_t *__restrict__ swk, uint32_t m, uint32_t &lo_out, uint32_t &lo_in) {
   lo_out = lower_bound(sv, m, x), lo_in = lower_bound(swk, m, x);
@@ -77,16 +45,7 @@ __global__ void k_ut_links(const uint64_t *__restrict__ vk, const uint64_t *__re
   const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
   if (gi >= m) return;
   const uint64_t v = vk[gi], w = wk[gi];
-  {   // the reverse (w ^ 1, v ^ 1), in the list sorted by (v, w)
-    const uint64_t rv = w ^ 1u, rw = v ^ 1u;
-    uint32_t lo = 0, hi = m;
-    while (lo < hi) {
-      const uint32_t mid = lo + ((hi - lo) >> 1);
-      if (sv[mid] < rv || (sv[mid] == rv && sw[mid] < rw)) lo = mid + 1;
-      else hi = mid;
-    }
-    if (!(lo < m && sv[lo] == rv && sw[lo] == rw)) atomicMin(&err[2], gsel[gi]);
-  }
+  if (find_vw(sv, sw, m, w ^ 1u, v ^ 1u) == NONE) atomicMin(&err[2], gsel[gi]);   // the reverse (w ^ 1, v ^ 1)
   uint32_t lo_out, lo_in;
   succ[gi] = node_simple(w, sv, swk, m, lo_out, lo_in) ? out_e[lo_out] : NONE;
   pred[gi] = node_simple(v, sv, swk, m, lo_out, lo_in) ? in_e[lo_in] : NONE;
@@ -282,30 +241,21 @@ void build_unitigs(const Edge *d_edges, uint64_t n64, pgx_unitigs *u) {
   if (n == 0) return;
   // ---- G edges, keys, the two sorted lists, the checks, pred / succ
   std::unique_ptr<KernelTimer> part(new KernelTimer("unitigs_links", n));
-  DevBuf<uint32_t> gsel(n);
-  uint32_t m = 0;
-  {
-    DevBuf<uint8_t> flag(n);
-    LAUNCH(k_ut_flags, n, d_edges, n, flag.p);
-    m = select_indices(flag.p, n, gsel.p, &tmp);
-  }
+  GEdges g;
+  g.select(d_edges, n, &tmp);
+  const uint32_t m = g.m;
   u->st.g_edges = m;
   if (m == 0) return;
   DevBuf<uint32_t> cnt(8);   // [0 .. 3) first offending edge of each rule, [4] edges with a pointer, [5] circular unitigs, [6] longest, [7] edges that found no place
   PGX_HIP(hipMemsetAsync(cnt.p, 0xFF, 4 * sizeof(uint32_t), st));
   PGX_HIP(hipMemsetAsync(cnt.p + 4, 0, 4 * sizeof(uint32_t), st));
-  DevBuf<uint64_t> vk(m), wk(m);
   DevBuf<uint32_t> pred(m), succ(m);
+  g.keys(TwoReads{}, cnt.p);
+  g.by_w(&tmp);
+  g.by_vw(cnt.p + 1, &tmp);
+  LAUNCH(k_ut_links, m, g.vk.p, g.wk.p, g.sv.p, g.sw.p, g.out_e.p, g.swk.p, g.in_e.p, g.gsel.p, m, pred.p, succ.p, cnt.p);
+  PGX_HIP(hipGetLastError());
   {
-    DevBuf<uint64_t> swk(m), sv(m), sw(m), k2(m);
-    DevBuf<uint32_t> iota(m), in_e(m), out_e(m);
-    LAUNCH(k_ut_keys, m, d_edges, gsel.p, m, vk.p, wk.p, iota.p, cnt.p);
-    sort_pairs(wk.p, swk.p, iota.p, in_e.p, m, 0, 33, &tmp);
-    LAUNCH(k_ut_gather, m, vk.p, in_e.p, m, k2.p);
-    sort_pairs(k2.p, sv.p, in_e.p, out_e.p, m, 0, 33, &tmp);
-    LAUNCH(k_ut_dups, m, sv.p, out_e.p, wk.p, gsel.p, m, sw.p, cnt.p);
-    LAUNCH(k_ut_links, m, vk.p, wk.p, sv.p, sw.p, out_e.p, swk.p, in_e.p, gsel.p, m, pred.p, succ.p, cnt.p);
-    PGX_HIP(hipGetLastError());
     uint32_t err[3];
     cnt.download(err, 3);
     pgx::sync();
@@ -313,6 +263,7 @@ void build_unitigs(const Edge *d_edges, uint64_t n64, pgx_unitigs *u) {
     PGX_REQUIRE(err[1] == NONE, PGX_EINVAL, "pgx_unitigs: G edge %u repeats the (v, w) of an earlier G edge", err[1]);
     PGX_REQUIRE(err[2] == NONE, PGX_EINVAL, "pgx_unitigs: G edge %u has no reverse (rev w, rev v) among the G edges", err[2]);
   }
+  g.release_lists();
   // ---- list ranking
   part.reset(), part.reset(new KernelTimer("unitigs_rank", m));
   DevBuf<Rank> ra(m), rb(m);
@@ -321,9 +272,9 @@ void build_unitigs(const Edge *d_edges, uint64_t n64, pgx_unitigs *u) {
   Rank *cur = ra.p, *other = rb.p;
   uint32_t full = 0;
   while (full < 31 && (1u << full) < m) ++full;   // 2^full >= m: no path is longer
-  if (rank_edges(d_edges, gsel.p, pred.p, m, full, &cur, &other, cnt.p + 4)) {
+  if (rank_edges(d_edges, g.gsel.p, pred.p, m, full, &cur, &other, cnt.p + 4)) {
     LAUNCH(k_ut_cut, m, cur, m, pred.p, circ.p);
-    const uint32_t left = rank_edges(d_edges, gsel.p, pred.p, m, full, &cur, &other, cnt.p + 4);
+    const uint32_t left = rank_edges(d_edges, g.gsel.p, pred.p, m, full, &cur, &other, cnt.p + 4);
     PGX_REQUIRE(left == 0, PGX_EHIP, "pgx_unitigs: %u edges are not ranked (a bug)", left);
   }
   // ---- assembly
@@ -341,13 +292,13 @@ void build_unitigs(const Edge *d_edges, uint64_t n64, pgx_unitigs *u) {
   PGX_HIP(hipMemsetAsync(n_edges.p, 0, (size_t)n_u * sizeof(uint32_t), st));
   DevBuf<uint64_t> off((size_t)n_u + 1);
   PGX_HIP(hipMemsetAsync(u->tab.p, 0, (size_t)n_u * sizeof(pgx_unitig), st));
-  LAUNCH(k_ut_heads, n_u, firsts.p, n_u, vk.p, wk.p, circ.p, uid_of.p, u->tab.p, cnt.p + 5);
-  LAUNCH(k_ut_tails, m, cur, succ.p, circ.p, wk.p, uid_of.p, m, n_u, u->tab.p, n_edges.p, cnt.p + 7);
+  LAUNCH(k_ut_heads, n_u, firsts.p, n_u, g.vk.p, g.wk.p, circ.p, uid_of.p, u->tab.p, cnt.p + 5);
+  LAUNCH(k_ut_tails, m, cur, succ.p, circ.p, g.wk.p, uid_of.p, m, n_u, u->tab.p, n_edges.p, cnt.p + 7);
   reduce_max(n_edges.p, cnt.p + 6, n_u, &tmp);
   const uint64_t total_edges = scan_to_total(n_edges.p, off.p, n_u, &tmp);
   PGX_REQUIRE(total_edges == m, PGX_EHIP, "pgx_unitigs: the unitigs hold %llu of %u edges (a bug)", (unsigned long long)total_edges, m);
   LAUNCH(k_ut_firsts, n_u, off.p, n_u, u->tab.p);
-  LAUNCH(k_ut_scatter, m, cur, uid_of.p, off.p, gsel.p, wk.p, m, n_u, u->paths.p, u->slot_u.p, u->slot_w.p, cnt.p + 7);
+  LAUNCH(k_ut_scatter, m, cur, uid_of.p, off.p, g.gsel.p, g.wk.p, m, n_u, u->paths.p, u->slot_u.p, u->slot_w.p, cnt.p + 7);
   // ---- where the text of every piece and line starts
   part.reset(), part.reset(new KernelTimer("unitigs_text", m));
   plan_text(slot_pieces(u), off.p, n_u, &u->text, &tmp);

@@ -394,6 +394,20 @@ def test_refused_inputs_name_the_line_and_write_nothing(name, tmp_path):
     assert st["p_rows"] > 0 and st["alternates"] == 1
 
 
+def test_the_assertion_is_refused_before_a_repeated_edge(tmp_path):
+    """the order of the refusals: an input with both damages gets the assertion's, on its own line"""
+    b = _base()
+    b.sg.append(b.sg[1])                                                                          # vw_twice
+    _edit(b.sg, 1, lambda ln: _field(4, ln.split()[3])(_field(3, ln.split()[4])(ln)))             # assertion
+    inputs = put(str(tmp_path), *b.files())
+    with pytest.raises(_lib.PgxError) as ei:
+        shimmer.graph_to_path(*inputs, str(tmp_path / "p"), str(tmp_path / "a"))
+    msg = str(ei.value)
+    assert "code %d" % _lib.PGX_EINVAL in msg and os.path.join(str(tmp_path), "sg_edges_list") + ": line 1:" in msg, msg
+    assert "the script asserts it" in msg and "repeats" not in msg, msg
+    assert not (tmp_path / "p").exists() and not (tmp_path / "a").exists()
+
+
 def test_lines_the_script_only_counts_are_not_parsed(tmp_path):
     """a TR line with fields that are no numbers, a dropped unitig type with a path of anything: the script reads neither"""
     b = _base()

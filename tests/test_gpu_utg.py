@@ -229,6 +229,21 @@ def test_error_paths_leave_everything_usable(fixture):
         assert lib.pgx_timing_get(part, None, None, C.byref(units)) == 0 and units.value > 0, part
 
 
+def test_a_doubly_damaged_input_gets_the_first_refusal(fixture):
+    """the order of the refusals: v_rid == w_rid, then a repeated (v, w), then a missing reverse"""
+    _, edges, _, _, _ = fixture["forks"]
+    _lib.init()
+    g = [int(e) for e in np.flatnonzero(edges["type"] == SG.G)]
+    bad = edges.copy()
+    bad["w_rid"][g[7]] = bad["v_rid"][g[7]]
+    rc, u, msg = raw_build(np.concatenate([bad, bad[g[3]:g[3] + 1]]))
+    assert rc == _lib.PGX_EINVAL and not u.value and b"v_rid == w_rid" in msg and (b"G edge %d " % g[7]) in msg and b"repeats" not in msg, msg
+    bad = edges.copy()
+    bad["type"][g[5]] = SG.TR                                    # its reverse is left without a reverse
+    rc, u, msg = raw_build(np.concatenate([bad, bad[g[3]:g[3] + 1]]))
+    assert rc == _lib.PGX_EINVAL and not u.value and b"repeats" in msg and (b"G edge %d " % len(edges)) in msg and b"reverse" not in msg, msg
+
+
 def test_after_shutdown_every_call_but_free_answers_estate(fixture, tmp_path):
     """in a process of its own: one context per process"""
     np.save(tmp_path / "edges.npy", fixture["forks"][1])
